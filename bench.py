@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — encrypted DB vectors matched/sec (HyDia, CKKS N = 2^15) on N MI355X of one node.
 
-A "step" is ONE query through DiagonalSender::indexScenario (/root/reference/src/sender/sender_diag.cpp:52-63: 511 hoisted
+A "step" is ONE query through DiagonalSender::indexScenario (the reference's src/sender/sender_diag.cpp:52-63: 511 hoisted
 rotations, per block 512 tensor products + 1 relinearise + 1 rescale, degree-59 Chebyshev o f4 comparator) over the
 encrypted database resident in HBM.
   N = 1   the 2^20-vector database (64 blocks, 142.5 GiB resident) on one GPU — the configuration BASELINE.json quotes its target on.
@@ -17,6 +17,7 @@ matches in {1,2,3}); the database is REAL ciphertexts produced by the on-GPU enr
 decrypts the gathered index result and checks it against the planted matches (global indices).
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR   # also DIR/*.npy: what the last timed step returned
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -32,17 +33,12 @@ import time
 
 import numpy as np
 
-# The engine runs two comparator lanes (HIP streams); torch and RCCL bring their own.  With ROCm's default of 4 hardware queues
-# the lanes end up sharing a queue with RCCL's streams and serialise (+4 ms per query, measured with tools/probe_dist.py), so ask
-# for 8 before the HIP runtime starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 SEED = 20250725
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
-PUBLISHED_2P20_INDEX_VPS = (1 << 20) / 96.52172  # /root/reference/tools/figures/approach5.csv:12 (Xeon Gold 5412U, 48 threads)
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E: 8.0 TB/s spec
+PUBLISHED_2P20_INDEX_VPS = (1 << 20) / 96.52172  # the reference's tools/figures/approach5.csv:12 (Xeon Gold 5412U, 48 threads)
 
 
 def synth_rows(lo, hi, dim, planted):
@@ -60,6 +56,27 @@ def synth_rows(lo, hi, dim, planted):
         a, z = max(lo, b * S), min(hi, (b + 1) * S)
         out[a - lo:z - lo] = blk[a - b * S:z - b * S]
     return out
+
+
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: the .npy payloads together stay under 64 MB
+
+
+def dump_outputs(d, cc, res):
+    """--dump-outputs: what the last timed indexScenario returned to its caller — one result ciphertext per 16384-vector block —
+    as float64 .npy files in `d`: the residues [blocks][2][limbs][N] split into their high and low 32 bits (both exact in float64)
+    and the decrypted slots [blocks][16384] (the comparator's ~1 for a match, ~0 otherwise).  An array larger than its share of
+    DUMP_BYTES is replaced by the same seeded sample of its flattened elements on every run with the same arguments."""
+    ct = res.export()
+    arrays = {"index_ct_hi": (ct >> np.uint64(32)).astype(np.float64),
+              "index_ct_lo": (ct & np.uint64(0xFFFFFFFF)).astype(np.float64),
+              "index_slots": cc.decrypt(res)}
+    del ct
+    cap = DUMP_BYTES // 8 // len(arrays)
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        if a.size > cap:
+            a = a.ravel()[np.sort(np.random.default_rng(SEED).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def cpu_model():
@@ -326,6 +343,8 @@ def main():
     ap.add_argument("--no-secondary-weak", action="store_true", help="N > 1: skip the weak-scaling figure of config.secondary")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--random-db", action="store_true", help="fill the DB with random residues instead of enrolling")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0: the gathered result) as DIR/<name>.npy")
     ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -333,6 +352,8 @@ def main():
     # (torch.distributed.run) its world size has to be the N that was asked for — a mismatch would silently measure another job
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         if not args.selftest_launcher and os.environ.get("HYDIA_BENCH_REHEARSE") != "1":
             import torch  # (counting devices does not initialise the GPU)
@@ -467,6 +488,9 @@ def main():
     elapsed = timed(sender, qc, args.steps)
 
     ms_tensor, launches = cc.kernel_time("hydia_tensor")
+    # (before anything below replaces `res`: the N > 1 phase timing runs further steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cc, res)
     # N > 1: where a step goes, per rank (outside the timed region: the phases are fenced, which the timed steps are not)
     split_report = None
     if multi:

@@ -87,3 +87,52 @@ def test_straggler_after_rank0_is_stopped(tmp_path):
     """rank 0 finishes, another rank hangs: the launcher stops it after the grace period and the run fails"""
     r = run(["--gpus", "2", "--selftest-launcher"], HYDIA_BENCH_SELFTEST_HANG_RANK="1", HYDIA_BENCH_STRAGGLER_S="3")
     assert r.returncode == 5 and "still run" in r.stderr
+
+
+def test_steps_below_one_is_refused():
+    r = run(["--gpus", "1", "--steps", "0", "--no-cpu-baseline"])
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs_writes_exact_residues_and_a_fixed_sample(tmp_path):
+    """--dump-outputs on stand-in result ciphertexts: the residues come back exactly from their float64 halves, the decrypted slots
+    are written as given, and an output too large for the budget is cut to the same seeded sample every time"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Res:
+        def __init__(self, ct):
+            self.ct = ct
+
+        def export(self):
+            return self.ct
+
+    class Ctx:
+        def decrypt(self, res):
+            return np.arange(res.ct.shape[0] * 4096, dtype=np.float64).reshape(res.ct.shape[0], 4096) / 7
+
+    rng = np.random.default_rng(1)
+    ct = rng.integers(0, 1 << 60, size=(3, 2, 1, 64), dtype=np.uint64)
+    bench.dump_outputs(str(tmp_path / "small"), Ctx(), Res(ct))
+    hi, lo, sl = (np.load(tmp_path / "small" / (n + ".npy")) for n in ("index_ct_hi", "index_ct_lo", "index_slots"))
+    assert hi.dtype == lo.dtype == sl.dtype == np.float64 and hi.shape == ct.shape and sl.shape == (3, 4096)
+    assert np.array_equal(hi.astype(np.uint64) << np.uint64(32) | lo.astype(np.uint64), ct)
+    assert np.array_equal(sl, Ctx().decrypt(Res(ct)))
+
+    big = rng.integers(0, 1 << 60, size=(16, 2, 1, 1 << 16), dtype=np.uint64)
+    old = bench.DUMP_BYTES
+    bench.DUMP_BYTES = 3 * 8 * 1000
+    try:
+        for d in ("a", "b"):
+            bench.dump_outputs(str(tmp_path / d), Ctx(), Res(big))
+    finally:
+        bench.DUMP_BYTES = old
+    total = 0
+    for n in ("index_ct_hi", "index_ct_lo", "index_slots"):
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.shape == (1000,) and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 3 * 8 * 1000
+    hi, lo = (np.load(tmp_path / "a" / (n + ".npy")).astype(np.uint64) for n in ("index_ct_hi", "index_ct_lo"))
+    assert np.isin(hi << np.uint64(32) | lo, big).all()

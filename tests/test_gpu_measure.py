@@ -105,3 +105,30 @@ def test_bench_gpus_flag_runs_two_real_ranks_on_this_gpu():
     assert abs(sp["rank0_sum_ms"] - sp["instrumented_ms_per_step"]) <= 0.10 * sp["instrumented_ms_per_step"], sp
     assert "model" in out  # (2^15 in all is not a modelled configuration: null; tests/test_bench_launcher.py checks the model itself)
     assert rf["stream_ceiling"]["source"].startswith("profiles/") and rf["vs_measured_stream_ceiling"] > 0
+
+
+def test_bench_steps_and_dump_outputs(tmp_path):
+    """`bench.py --steps K` times K steps (K loop-B launches inside the timed window), and --dump-outputs writes what the last timed
+    step returned: the same arrays for the same arguments whatever K is, decrypting to the planted matches."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    lines, dumps = {}, {}
+    for steps in (1, 3):
+        d = tmp_path / ("steps%d" % steps)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--log2n", "14", "--steps", str(steps),
+                            "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[steps] = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+        dumps[steps] = {n: np.load(d / (n + ".npy")) for n in ("index_ct_hi", "index_ct_lo", "index_slots")}
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 * 10 ** 6
+    assert lines[1]["steps"] == 1 and lines[3]["steps"] == 3
+    assert lines[1]["roofline"]["launches"] >= 1 and lines[3]["roofline"]["launches"] == 3 * lines[1]["roofline"]["launches"]
+    for n, a in dumps[1].items():
+        assert a.dtype == np.float64 and np.array_equal(a, dumps[3][n]), n
+    hi, lo, slots = dumps[1]["index_ct_hi"], dumps[1]["index_ct_lo"], dumps[1]["index_slots"]
+    assert hi.ndim == 4 and hi.shape[:2] == (1, 2) and lo.max() < 2 ** 32 and slots.shape == (1, 16384)
+    assert np.flatnonzero(slots.ravel() >= 1.0).tolist() == [0, 8192, 16383]  # bench.py's planted matches at 2^14
