@@ -94,8 +94,9 @@ struct CfSum {
     u64 L, H;
     DEV u128 wide() const { return (u128)L + ((u128)H << 60); }
 };
-// (NS = 5, round 5: five sources BELOW 2^48 — yh < 2^18 — keep every bound: ll < 5 2^60 < 2^63, mid < 5 (2^60 + 2^48) < 2^63, hh < 5 2^48, so
-// L < 2^63 and H < 2^51; the launcher refuses five sources with a wider modulus)
+// (NS = 5, round 5: five sources BELOW 2^48 — yh < 2^18 — keep every partial sum in one word: ll < 5 2^60, mid < 5 (2^60 + 2^48) < 2^63,
+// hh < 5 2^48, so L < 5 2^60 + 2^62 = 9 2^60 (not 2^63: every reduction of the sum takes any 64-bit L) and H < 2^51; the launcher
+// refuses five sources with a wider modulus)
 template <int NS>
 DEV CfSum cf_macN(const u64 (&y)[NS], const CfConstN<NS> &f) {
     u64 pll = 0, pmid = 0, phh = 0;

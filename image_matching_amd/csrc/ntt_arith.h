@@ -8,7 +8,12 @@
 //         h = a*w; l = fma(a,w,-h); c = rint(a*(w/q)); r = fma(-c,q,h) + l — six FP64 instructions, no compares, no carries.
 // Between two passes FpA limbs travel as raw doubles in the (uint64) buffer; every limb leaves a transform as canonical uint64.
 #pragma once
-#include "kernels.h"
+#include "devmath.h"
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#else
+#include "host_shim.h"  // host builds of the structs (tests/csrc/ntt_arith_check.cpp)
+#endif
 
 namespace {
 
@@ -76,7 +81,8 @@ struct IntP {
     // Wide sums without a Barrett reduction (round 4): with 2^60 = c and 2^64 = 16c (mod q) a two-word sum folds to a lazy
     // representative in four carry-free multiply-adds — the transforms take lazy operands anyway (forward: up to 12q before a
     // stage; inverse: below 4q where two stages run to the next fold).
-    // L + H 2^60, H < 2^63 (the conversion sums of colfuse.hip: L < 2^63, H < 2^62 + 2^33): result below 2.07 2^60.
+    // L + H 2^60, any L, H < 2^63 (the conversion sums of colfuse.hip: L < 2^63 and H < 2^62 + 2^33 with four sources, L < 9 2^60
+    // and H < 2^51 with five below 2^48): result below 2.07 2^60.
     DEV u64 fold_lh(u64 L, u64 H) const {
         const u64 m1 = (u64)(unsigned)(H >> 32) * c;  // < 2^55; m1 2^32 = (m1 >> 28) 2^60 + (m1 mod 2^28) 2^32
         u64 acc = (L & ((1ull << 60) - 1)) + (u64)(unsigned)(L >> 60) * c;
@@ -153,7 +159,10 @@ struct FpA {
     DEV T from_canon(u64 x) const { return u2d(x); }  // x < 2^47: exact
     DEV static T from_bits(u64 x) { return __longlong_as_double((long long)x); }
     DEV static u64 to_bits(T x) { return (u64)__double_as_longlong(x); }
-    DEV double mulmod(const double v, const TW W) const {  // exact v*w - c*q with |result| <= 0.75 q
+    // exact v*w - c*q.  c is within |v| (w/q) 2^-52 of v w / q (1.5 times that with tw8), so |result| <= q/2 + |v| (w/q) 2^-52 q:
+    // <= 0.75 q (1.3 q with tw8) for the lean primes up to |v| = 32 q; a 47-bit prime's forward magnitudes (up to ~14 q) allow ~0.8 q
+    // (~1 q), which the headroom below 2^52 absorbs (tests/csrc/ntt_arith_check.cpp)
+    DEV double mulmod(const double v, const TW W) const {
         const double h = v * W.x;
         const double l = __fma_rn(v, W.x, -h);
         const double c = rint(v * W.y);
@@ -176,7 +185,7 @@ struct FpA {
         b = mulmod(d, W);
         a = s;
     }
-    DEV void recentre(T &x) const { x = __fma_rn(-rint(x * qinv), q, x); }  // -> [-q/2, q/2]
+    DEV void recentre(T &x) const { x = __fma_rn(-rint(x * qinv), q, x); }  // |x| < 2^52 -> [-(q+1)/2, (q+1)/2]
     // The inverse transform doubles magnitudes on its sum path; a reduction every 3-4 stages keeps 47-bit primes below 2^52.  For
     // the lean primes two of the four reductions of the two-pass inverse can go: runs of 5 and 6 stages reach 32 q < 2^50.1, where
     // products and quotient estimates are still exact enough (|quotient error| <= 1, results exact).  Final residues are unchanged.

@@ -24,3 +24,23 @@ def test_database_address_map_is_a_bijection(tmp_path):
     subprocess.run(["g++", "-O2", "-std=c++17", "-I", inc, src, "-o", str(exe)], check=True)
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "db layout ok" in out.stdout, out.stdout + out.stderr
+
+
+def test_ntt_arith_against_int128(tmp_path):
+    """image_matching_amd/csrc/ntt_arith.h on the host (tests/csrc/ntt_arith_check.cpp): the IntA, IntP and FpA butterfly arithmetics
+    against exact integer arithmetic at the edges of their prime classes — every IntP prime at N = 2^15 and the extreme ones at
+    N = 2^11, FP64 primes at the lean threshold and at 47 bits, 48- to 60-bit Harvey primes — and on the default chain.  Compiled
+    without FMA contraction so the doubles round as the device's do; prints each modulus and the worst bound observed per class."""
+    import oracle_lib as O
+    exe = tmp_path / "ntt_arith_check"
+    src = os.path.join(ROOT, "tests", "csrc", "ntt_arith_check.cpp")
+    inc = os.path.join(ROOT, "image_matching_amd", "csrc")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", inc, src, "-o", str(exe)], check=True)
+    P = O.Params()
+    chain = sorted({int(q) for q in P.moduli})
+    P.close()
+    out = subprocess.run([str(exe)] + [str(q) for q in chain], capture_output=True, text=True, timeout=600)
+    print(out.stdout)
+    assert out.returncode == 0 and "ntt_arith ok" in out.stdout, out.stdout + out.stderr
+    for cls in ("IntA", "IntP", "FpA"):
+        assert "worst " + cls in out.stdout
