@@ -3,6 +3,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include <sys/random.h>
 
@@ -614,6 +615,33 @@ int hydia_compute_similarity_rotated(hydia_ctx *ctx, const hydia_ct *query, hydi
 int hydia_index_scenario_rotated(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.index_scenario_rot(query->c)) }
 int hydia_index_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.index_scenario(query->c)) }
 int hydia_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.membership_scenario(query->c)) }
+// a batch of queries in one pass over the database: out[q] = the single-query result for queries[q]; on any error every out[q] is NULL
+static int scenario_multi_call(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out, int what) {
+    if (out)
+        for (uint32_t q = 0; q < n_queries; q++) out[q] = nullptr;
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && queries && out, "null argument");
+    REQUIRE(n_queries >= 1, "a batch of queries needs at least one query");
+    std::vector<const Ct *> qs(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) {
+        REQUIRE(queries[q], "null query in the batch");
+        qs[q] = &queries[q]->c;
+    }
+    std::vector<Ct> r = ctx->cx.scenario_multi(qs, what);
+    for (uint32_t q = 0; q < n_queries; q++) out[q] = wrap(ctx, std::move(r[q]));  // compact and owning: no copy, cannot fail
+    return HYDIA_OK;
+    API_END
+}
+int hydia_compute_similarity_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out) {
+    return scenario_multi_call(ctx, queries, n_queries, out, 0);
+}
+int hydia_index_scenario_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out) {
+    return scenario_multi_call(ctx, queries, n_queries, out, 1);
+}
+int hydia_membership_scenario_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out) {
+    return scenario_multi_call(ctx, queries, n_queries, out, 2);
+}
 int hydia_chebyshev_compare(hydia_ctx *ctx, const hydia_ct *query, double delta, size_t sign_depth, hydia_ct **out) {
     SENDER_CALL(ctx->cx.chebyshev_compare(query->c, delta, (int)sign_depth))
 }

@@ -1497,6 +1497,122 @@ Ct Context::sum_and_evalsum(const Ct &s) {
     }
     return m;
 }
+// ------------------------------------------------------------------ a batch of queries in one pass over the database (an extension:
+// the reference serves one query per call).  Loop A runs per query into one [Q][R][2][nQ][N] rotation buffer; loop B is ONE multi-query
+// launch set (ceil(Q / QW) passes over the database); the per-block tails run once on the [Q G] batch.  Every ciphertext is what the
+// single-query call returns for its query, bit for bit: each step computes every ciphertext of a batch as it would alone.
+void Context::check_multi(const std::vector<const Ct *> &qs) const {
+    if (qs.empty()) throw std::runtime_error("hydia: a batch of queries needs at least one query");
+    for (const Ct *q : qs)
+        if (!q || q->X != 1 || q->npoly != 2 || q->nl != nQ || !q->compact() || q->scale != qs[0]->scale)
+            throw std::runtime_error("hydia: every query of a batch must be one fresh 2-component ciphertext at full level");
+    if (!d_db || db_cts == 0 || (db_kind != 5 && db_kind != 6)) throw StateError("hydia: no database resident (diagonal packing)");
+}
+// queries one batch takes: what free HBM (plus the pool's cache) holds of a query's rotation set, accumulators and comparator
+// temporaries (48 full-level ciphertexts per block: at 2^20 vectors a batch of 8 with 24 per block ran out of HBM inside the comparator
+// and the allocator's trim-and-retry made it 7x slower than 8 single calls), never fewer than one — a batch of one needs what a
+// single-query call needs
+int Context::multi_batch(int Q) {
+    const int dim = prm.dim, R = db_kind == 6 ? db_babies : dim, NG = db_kind == 6 ? dim / db_babies : 1, G = (int)(db_cts / dim);
+    const double lp = (double)nQ * N * 8;
+    const double per_query = (double)R * 2 * lp + (double)G * NG * 3 * lp + (double)G * 48 * 2 * lp;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 1;
+    const double avail = 0.85 * ((double)free_b + (double)pool.bytes_cached);
+    return (int)std::max(1.0, std::min((double)Q, std::floor(avail / per_query)));
+}
+// loop A + loop B (+ for BSGS the relinearisation and the giant steps) of queries q0 .. q0+Qb-1: kind 5 the [Qb G][3][nQ]
+// accumulators, kind 6 the relinearised [Qb G][2][nQ] sums (what similarity_accumulate / similarity_bsgs_sum return, query-major)
+Ct Context::loop_b_multi(const std::vector<const Ct *> &qs, int q0, int Qb) {
+    const int dim = prm.dim, nl = nQ, nE = nl + nP, nd = (nl + alpha - 1) / alpha;
+    const int B = db_kind == 6 ? db_babies : dim, NG = (dim + B - 1) / B, G = (int)(db_cts / dim);
+    if (db_kind == 6 && (B < 1 || dim % B)) throw StateError("hydia: the resident database carries no valid baby count");
+    if (db_kind == 6) build_giants(Qb * G);  // one table entry per (giant step, query, block)
+    const double scale = qs[q0]->scale;
+    Ct acc(this, Qb * G * NG, 3, nl, scale * delta);
+    {
+        Ct rot(this, Qb * B, 2, nl, scale);
+        const size_t rqs = (size_t)B * rot.ct_elems();
+        for (int q = 0; q < Qb; q++) rotate_query_range(*qs[q0 + q], 0, B, rot.d + (size_t)q * rqs);
+        const int passes = (Qb + hk::hydia_tensor_mq_width(db_lay) - 1) / hk::hydia_tensor_mq_width(db_lay);
+        op_bytes("op:loop_b_multi", N, 0, (double)passes * db_cts * (double)db_lay.ct_bytes + ((double)Qb * B * 2 + (double)Qb * G * NG * 3) * nl * N * 8);
+        timer_begin("hydia_tensor_multi");
+        hk::hydia_tensor_accumulate_multi(stream, d_mod, N, rot.d, rqs, d_db, acc.d, Qb, G * NG, B, nl, db_lay, db_kind == 6 ? NG : 0);
+        timer_end("hydia_tensor_multi");
+    }
+    if (db_kind == 5) return acc;
+    // BSGS: slot (giant g, query q, block) = (g Qb + q) G + block; the giant steps g >= 1 of all queries and blocks in one key switch
+    const int X0 = Qb * G;
+    relinearize(acc);
+    Ct out(this, X0, 2, nl, acc.scale);
+    if (NG > 1) {
+        const int X = (NG - 1) * X0;
+        const size_t ce = acc.ct_elems();
+        op_bytes("op:rotate", N, (double)X * (nd * nE + 2 * nP + 2 * nl), (double)(NG - 1) * nd * 2 * nE * N * 8 + 4.0 * X * nl * N * 8);
+        Ct rotd(this, X, 2, nl, acc.scale);
+        const u64 *c = acc.d + (size_t)X0 * ce;
+        if (ks_fused_ok()) {
+            ks_fused(c + acc.poly_elems(), ce, X, nl, nullptr, nullptr, d_giant_keys, c, ce, acc.poly_elems(), 1, d_giant_ginv, 0, false, rotd.d);
+        } else {
+            u64 *dig = pool.get((size_t)X * nd * nE * N * sizeof(u64));
+            modup_digits(c + acc.poly_elems(), ce, X, nl, dig);
+            ks_apply(dig, (size_t)nd * nE * N, X, nl, d_giant_keys, 0, c, ce, acc.poly_elems(), 1, d_giant_gal, d_giant_ginv, 0, false, rotd.d);
+            pool.put(dig);
+        }
+        HIP_CHECK(hipMemcpyAsync(acc.d + (size_t)X0 * ce, rotd.d, (size_t)X * ce * sizeof(u64), hipMemcpyDeviceToDevice, stream));
+    }
+    op_bytes("op:add", N, 0, (double)(NG + 1) * X0 * 2 * nl * N * 8);
+    hk::batch_sum(stream, d_mod, N, acc.d, out.d, NG, 2, nl, X0, X0);
+    return out;
+}
+// ciphertexts q*per .. q*per+per-1 of a batch, compact and owning
+Ct Context::batch_slice(const Ct &b, int q, int per) {
+    Ct o(this, per, b.npoly, b.nl, b.scale);
+    hk::copy_limbs(stream, N, b.d + (size_t)q * per * b.ct_elems(), o.d, b.poly_elems(), o.poly_elems(), per * b.npoly, b.nl);
+    return o;
+}
+// 0 similarity, 1 index scenario, 2 membership scenario
+std::vector<Ct> Context::scenario_multi(const std::vector<const Ct *> &qs, int what) {
+    check_multi(qs);
+    const int Q = (int)qs.size(), G = (int)(db_cts / prm.dim);
+    std::vector<Ct> res;
+    res.reserve(Q);
+    for (int q0 = 0; q0 < Q;) {
+        const int Qb = multi_batch(Q - q0);
+        Ct acc = loop_b_multi(qs, q0, Qb);  // [Qb G]: 3 components (hoisted) : 2 (BSGS, relinearised)
+        Ct r;
+        if (what == 0) {
+            if (acc.npoly == 3) relin_rescale(acc);
+            else rescale(acc);
+            r = std::move(acc);
+        } else {
+            r = relin_compare_lanes(acc, 0.44 /* MATCH_THRESHOLD */, 10 /* COMP_DEPTH */);
+            acc = Ct();
+        }
+        if (what == 2) {  // EvalAddMany per query (segmented over the batch), then ONE EvalSum over the Qb sums
+            Ct m;
+            for (int q = 0; q < Qb; q++) {
+                Ct v = r.alias(r.nl);
+                v.X = G;
+                v.d = r.d + (size_t)q * G * r.ct_elems();
+                Ct s = add_many(v);
+                if (q == 0) m = Ct(this, Qb, s.npoly, s.nl, s.scale);
+                hk::copy_limbs(stream, N, s.d, m.d + (size_t)q * m.ct_elems(), s.poly_elems(), m.poly_elems(), s.npoly, s.nl);
+            }
+            r = Ct();
+            for (int rr = 1; rr < slots; rr <<= 1) {
+                Ct t = rotate(m, rr);
+                add_inplace(m, t);
+            }
+            for (int q = 0; q < Qb; q++) res.push_back(batch_slice(m, q, 1));
+        } else {
+            for (int q = 0; q < Qb; q++) res.push_back(batch_slice(r, q, G));
+        }
+        q0 += Qb;
+    }
+    return res;
+}
+
 // Cross-shard membership reduction: partial sums of the shards are added as plain 64-bit integers (what an RCCL
 // all-reduce(SUM) on int64 does: at most 16 residues below 2^60 cannot overflow) and reduced once.
 void Context::add_raw_inplace(Ct &a, const u64 *other) {

@@ -349,6 +349,14 @@ struct Context : HostParams {
     Ct eval_sum(const Ct &a);         // EvalSum alone
     void add_raw_inplace(Ct &a, const u64 *other /* compact, same shape, this device */);  // integer sum, no reduction
     void mod_reduce_inplace(Ct &a);   // every 64-bit value -> canonical residue of its limb
+    // ---- a batch of queries in one pass over the database (an extension; evaluator.cpp): one result per query, each exactly what
+    // the single-query call returns.  what: 0 similarity, 1 index scenario, 2 membership scenario.  The batch is split where free HBM
+    // does not hold it (multi_batch); the split changes no result
+    std::vector<Ct> scenario_multi(const std::vector<const Ct *> &qs, int what);
+    void check_multi(const std::vector<const Ct *> &qs) const;  // runtime_error: a query is not fresh; StateError: no diagonal database
+    int multi_batch(int Q);
+    Ct loop_b_multi(const std::vector<const Ct *> &qs, int q0, int Qb);
+    Ct batch_slice(const Ct &b, int q, int per);
     // ---- HERS sender (approach 4, src/sender/sender_hers.cpp): q = dim query ciphertexts
     Ct hers_similarity(const Ct &q);
     Ct hers_index_scenario(const Ct &q);

@@ -387,6 +387,12 @@ void rescale_combine(hipStream_t st, const ModC *mod, int N, const u64 *in, cons
 void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, const void *db, u64 *acc, int G,
                              int dim, int nl, int bpp, int nw, const DbLayout &L, int ng = 0);
 const char *hydia_tensor_kernel_name();
+// the same sums for Q queries in ceil(Q / QW) passes over the database (QW = hydia_tensor_mq_width): rot holds the queries' rotation
+// sets rqs elements apart; acc slot of (query q, block gi) is q * G + gi, and with ng > 0 giant-major over the whole batch:
+// ((gi % ng) * Q + q) * (G / ng) + gi / ng.  Every accumulator equals the single-query launch's for that query, bit for bit.
+void hydia_tensor_accumulate_multi(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q,
+                                   int G, int dim, int nl, const DbLayout &L, int ng = 0);
+int hydia_tensor_mq_width(const DbLayout &L);  // queries one pass over the database serves
 
 // ---- misc
 void fill_uniform_hash(hipStream_t st, const ModC *mod, int N, u64 *dst, size_t n_limbpolys, int nl,

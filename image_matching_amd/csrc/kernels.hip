@@ -914,6 +914,277 @@ __global__ __launch_bounds__(64 * KS) void k_hydia_tensor_sk(const ModC *__restr
     }
 }
 
+// ------------------------------------------------------------------------------------------------ loop B for a batch of queries
+// The sums of the three kernels above for QW queries in one pass over the database: a wave loads a database operand ONCE per
+// diagonal and multiply-accumulates it against the rotation operands of QW queries (rot: the queries' rotation sets, rqs elements
+// apart).  Same products, same lazy sums, one reduction per output: the residues are the single-query kernels' bit for bit (a sum
+// modulo q does not depend on how it is split).  Registers: the accumulators of QW queries take the place of the
+// single-query kernels' BPP blocks, so a wave serves ONE database block and a workgroup of NWM waves walks the blocks a single-query
+// workgroup walks — in the group-sequential layout NWM = the layout's group size, and the workgroup still reads one contiguous run.
+// Output slot of (query q of the batch of Qt, block gi): ng == 0: q G + gi; ng > 0 (BSGS): giant-major over the WHOLE batch,
+// (g Qt + q) nblk + block — one giant step's partial sums over every query and block are one contiguous batch.
+DEV size_t mq_slot(int q, int gi, int G, int ng, int nblk, int Qt) {
+    return ng > 0 ? ((size_t)(gi % ng) * Qt + q) * nblk + gi / ng : (size_t)q * G + gi;
+}
+// 128-bit lazy sums (k_hydia_tensor's arithmetic): limb 0 of every layout, the 48-bit packed limbs of the ciphertext-major layout
+// (PK), the unpacked layout.  grid (N/128 * Gq, limbs), the XCD-aware tile map of k_hydia_tensor.
+template <int QW, int NWM, bool PK>
+__global__ __launch_bounds__(64 * NWM) void k_hydia_tensor_mq(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs,
+                                                              const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                              int Gq, int xcd_map, DbLayout L, int j0, int G, int ng, int nblk, int q0, int Qt) {
+    const int j = blockIdx.y + j0;
+    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
+    const int gq = xcd_map ? k % Gq : blockIdx.x % Gq;
+    const int tile = xcd_map ? xcd + 8 * (k / Gq) : blockIdx.x / Gq;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const ModC M = mod[j];
+    const size_t c = (size_t)tile * 128 + lane * 2;
+    const size_t ps = (size_t)nl * N, cs = 2 * ps;
+    const int g = gq * NWM + wv;
+    const u64 *ra = rot + (size_t)q0 * rqs + (size_t)j * N + c;
+    const DbWalk dw = db_walk(L, N, dim, j, tile, lane, g, gq, wv);
+    const unsigned char *da = db + dw.base;
+    const size_t db_cs = dw.si, db_ps = dw.sp;
+    const int kbits = M.ks + 2;
+    const int chunk = (125 - 2 * kbits >= 30) ? dim : (1 << (125 - 2 * kbits));
+    u128 d0x[QW], d0y[QW], dkx[QW], dky[QW], d2x[QW], d2y[QW];
+#pragma unroll
+    for (int q = 0; q < QW; q++) d0x[q] = d0y[q] = dkx[q] = dky[q] = d2x[q] = d2y[q] = 0;
+    struct Operands {
+        ulonglong2 a0[QW], a1[QW];
+        DbRaw<PK> b0, b1;
+    };
+    auto fetch = [&](Operands &o, int i) {
+#pragma unroll
+        for (int q = 0; q < QW; q++) {
+            o.a0[q] = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs);
+            o.a1[q] = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs + ps);
+        }
+        o.b0.template load<true>(da + (size_t)i * db_cs);
+        o.b1.template load<true>(da + (size_t)i * db_cs + db_ps);
+    };
+    auto accumulate = [&](const Operands &o) {
+        const ulonglong2 b0 = o.b0.get(), b1 = o.b1.get();
+        const u64 sbx = b0.x + b1.x, sby = b0.y + b1.y;
+#pragma unroll
+        for (int q = 0; q < QW; q++) {
+            d0x[q] += (u128)o.a0[q].x * b0.x;
+            d0y[q] += (u128)o.a0[q].y * b0.y;
+            d2x[q] += (u128)o.a1[q].x * b1.x;
+            d2y[q] += (u128)o.a1[q].y * b1.y;
+            dkx[q] += (u128)(o.a0[q].x + o.a1[q].x) * sbx;
+            dky[q] += (u128)(o.a0[q].y + o.a1[q].y) * sby;
+        }
+    };
+    Operands cur, nxt;
+    fetch(cur, 0);
+    for (int i0 = 0; i0 < dim; i0 += chunk) {
+        const int i1 = i0 + chunk < dim ? i0 + chunk : dim;
+        for (int i = i0; i < i1; i += 2) {  // branch-free (see k_hydia_tensor)
+            fetch(nxt, i + 1);
+            accumulate(cur);
+            if (NWM > 1) __builtin_amdgcn_s_barrier();
+            fetch(cur, i + 2 < dim ? i + 2 : i + 1);
+            accumulate(nxt);
+            if (NWM > 1) __builtin_amdgcn_s_barrier();
+        }
+        if (i1 < dim) {
+#pragma unroll
+            for (int q = 0; q < QW; q++) {
+                d0x[q] = reduce128(d0x[q], M); d0y[q] = reduce128(d0y[q], M);
+                dkx[q] = reduce128(dkx[q], M); dky[q] = reduce128(dky[q], M);
+                d2x[q] = reduce128(d2x[q], M); d2y[q] = reduce128(d2y[q], M);
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < QW; q++) {
+        ulonglong2 r0, r1, r2;
+        r0.x = reduce128(d0x[q], M); r0.y = reduce128(d0y[q], M);
+        r2.x = reduce128(d2x[q], M); r2.y = reduce128(d2y[q], M);
+        r1.x = submod(submod(reduce128(dkx[q], M), r0.x, M.q), r2.x, M.q);
+        r1.y = submod(submod(reduce128(dky[q], M), r0.y, M.q), r2.y, M.q);
+        u64 *o = acc + (mq_slot(q0 + q, g, G, ng, nblk, Qt) * 3 * nl + j) * N + c;
+        *reinterpret_cast<ulonglong2 *>(o) = r0;
+        *reinterpret_cast<ulonglong2 *>(o + ps) = r1;
+        *reinterpret_cast<ulonglong2 *>(o + 2 * ps) = r2;
+    }
+}
+// 24-bit halves (k_hydia_tensor24's arithmetic, hide24 included) on the 46-bit limbs of a group-sequential database; the database
+// operands run two diagonals ahead, the rotation lines one.  The halves of the database residues are cut once per diagonal and
+// serve all QW queries.
+template <int QW, int NWM>
+__global__ __launch_bounds__(64 * NWM) void k_hydia_tensor24_mq(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs,
+                                                                const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                                int Gq, int xcd_map, DbLayout L, int j0, int G, int ng, int nblk, int q0, int Qt) {
+    const int j = blockIdx.y + j0;
+    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
+    const int gq = xcd_map ? k % Gq : blockIdx.x % Gq;
+    const int tile = xcd_map ? xcd + 8 * (k / Gq) : blockIdx.x / Gq;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const ModC M = mod[j];
+    const size_t c = (size_t)tile * 128 + lane * 2;
+    const size_t ps = (size_t)nl * N, cs = 2 * ps;
+    const int g = gq * NWM + wv;
+    const u64 *ra = rot + (size_t)q0 * rqs + (size_t)j * N + c;
+    const DbWalk dw = db_walk(L, N, dim, j, tile, lane, g, gq, wv);
+    const unsigned char *da = db + dw.base;
+    const size_t db_cs = dw.si, db_ps = dw.sp;
+    Acc24 d0[QW][2], dk[QW][2], d2[QW][2];  // [query][coefficient of the lane's pair]
+#pragma unroll
+    for (int q = 0; q < QW; q++)
+#pragma unroll
+        for (int e = 0; e < 2; e++) d0[q][e] = dk[q][e] = d2[q][e] = Acc24{0, 0, 0};
+    const unsigned s46 = (unsigned)(lane * 92) & 31u;
+    struct Operands {
+        ulonglong2 a0[QW], a1[QW];
+        DbRaw46 b0, b1;
+    };
+    auto fetch = [&](Operands &o, int i) {
+#pragma unroll
+        for (int q = 0; q < QW; q++) {
+            o.a0[q] = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs);
+            o.a1[q] = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs + ps);
+        }
+        o.b0.template load<true>(da + (size_t)i * db_cs);
+        o.b1.template load<true>(da + (size_t)i * db_cs + db_ps);
+    };
+    auto accumulate = [&](const Operands &o) {
+        unsigned bl[2][2], bh[2][2];  // database residues: halves of 24 and 22 bits, cut as in k_hydia_tensor24
+#pragma unroll
+        for (int p = 0; p < 2; p++) {
+            const auto w = p == 0 ? o.b0.w : o.b1.w;
+            const unsigned t0 = __builtin_amdgcn_alignbit(w[1], w[0], s46), t1 = __builtin_amdgcn_alignbit(w[2], w[1], s46),
+                           t2 = __builtin_amdgcn_alignbit(w[3], w[2], s46);
+            bl[p][0] = hide24(t0 & 0xFFFFFFu);
+            bh[p][0] = hide24(__builtin_amdgcn_alignbit(t1, t0, 24) & 0x3FFFFFu);
+            bl[p][1] = hide24(__builtin_amdgcn_alignbit(t2, t1, 14) & 0xFFFFFFu);
+            bh[p][1] = hide24((t2 >> 6) & 0x3FFFFFu);
+        }
+        unsigned sbl[2], sbh[2];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            sbl[e] = bl[0][e] + bl[1][e];
+            sbh[e] = bh[0][e] + bh[1][e];
+        }
+#pragma unroll
+        for (int q = 0; q < QW; q++) {
+            const u64 av[2][2] = {{o.a0[q].x, o.a0[q].y}, {o.a1[q].x, o.a1[q].y}};
+            unsigned al[2][2], ah[2][2];
+#pragma unroll
+            for (int p = 0; p < 2; p++)
+#pragma unroll
+                for (int e = 0; e < 2; e++) {
+                    al[p][e] = hide24((unsigned)av[p][e] & 0xFFFFFFu);
+                    ah[p][e] = __builtin_amdgcn_alignbit((unsigned)(av[p][e] >> 32), (unsigned)av[p][e], 24);
+                }
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                d0[q][e].mac(al[0][e], ah[0][e], bl[0][e], bh[0][e]);
+                d2[q][e].mac(al[1][e], ah[1][e], bl[1][e], bh[1][e]);
+                dk[q][e].mac(al[0][e] + al[1][e], ah[0][e] + ah[1][e], sbl[e], sbh[e]);
+            }
+        }
+    };
+    Operands A, B, C;
+    fetch(A, 0);
+    fetch(B, dim > 1 ? 1 : 0);
+    int i = 0;
+    for (; i + 2 < dim; i += 3) {  // branch-free inside: clamped re-fetches of the last diagonal are never accumulated
+        fetch(C, i + 2);
+        accumulate(A);
+        if (NWM > 1) __builtin_amdgcn_s_barrier();
+        fetch(A, i + 3 < dim ? i + 3 : dim - 1);
+        accumulate(B);
+        if (NWM > 1) __builtin_amdgcn_s_barrier();
+        fetch(B, i + 4 < dim ? i + 4 : dim - 1);
+        accumulate(C);
+        if (NWM > 1) __builtin_amdgcn_s_barrier();
+    }
+    if (i < dim) accumulate(A);
+    if (i + 1 < dim) accumulate(B);
+#pragma unroll
+    for (int q = 0; q < QW; q++) {
+        ulonglong2 r0, r1, r2;
+        r0.x = reduce128(d0[q][0].wide(), M); r0.y = reduce128(d0[q][1].wide(), M);
+        r2.x = reduce128(d2[q][0].wide(), M); r2.y = reduce128(d2[q][1].wide(), M);
+        r1.x = submod(submod(reduce128(dk[q][0].wide(), M), r0.x, M.q), r2.x, M.q);
+        r1.y = submod(submod(reduce128(dk[q][1].wide(), M), r0.y, M.q), r2.y, M.q);
+        u64 *o = acc + (mq_slot(q0 + q, g, G, ng, nblk, Qt) * 3 * nl + j) * N + c;
+        *reinterpret_cast<ulonglong2 *>(o) = r0;
+        *reinterpret_cast<ulonglong2 *>(o + ps) = r1;
+        *reinterpret_cast<ulonglong2 *>(o + 2 * ps) = r2;
+    }
+}
+// limb 0 of a small ciphertext-major database (k_hydia_tensor_sk's split: KS waves of a workgroup share one (block, tile) and take
+// every KS-th diagonal) for QW queries; the partial sums go through LDS one query at a time.  grid (N/128 * G, 1)
+template <int KS, int QW>
+__global__ __launch_bounds__(64 * KS) void k_hydia_tensor_sk_mq(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs,
+                                                                const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                                DbLayout L, int G, int ng, int nblk, int q0, int Qt) {
+    __shared__ u64 part[KS][6][64];
+    const int j = 0, tiles = N / 128;
+    const int tile = blockIdx.x % tiles, g = blockIdx.x / tiles;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const ModC M = mod[j];
+    const size_t c = (size_t)tile * 128 + lane * 2;
+    const size_t ps = (size_t)nl * N, cs = 2 * ps;
+    const u64 *ra = rot + (size_t)q0 * rqs + c;
+    const unsigned char *da = db + (size_t)g * dim * L.ct_bytes + c * 8;
+    const int kbits = M.ks + 2;
+    const int chunk = (125 - 2 * kbits >= 30) ? dim : (1 << (125 - 2 * kbits));
+    u128 d0x[QW], d0y[QW], dkx[QW], dky[QW], d2x[QW], d2y[QW];
+#pragma unroll
+    for (int q = 0; q < QW; q++) d0x[q] = d0y[q] = dkx[q] = dky[q] = d2x[q] = d2y[q] = 0;
+    int since = 0;
+    for (int i = wv; i < dim; i += KS) {
+        const ulonglong2 b0 = db_load2<false, true>(da + (size_t)i * L.ct_bytes);
+        const ulonglong2 b1 = db_load2<false, true>(da + (size_t)i * L.ct_bytes + L.poly_bytes);
+        const u64 sbx = b0.x + b1.x, sby = b0.y + b1.y;
+#pragma unroll
+        for (int q = 0; q < QW; q++) {
+            const ulonglong2 a0 = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs);
+            const ulonglong2 a1 = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs + ps);
+            d0x[q] += (u128)a0.x * b0.x;
+            d0y[q] += (u128)a0.y * b0.y;
+            d2x[q] += (u128)a1.x * b1.x;
+            d2y[q] += (u128)a1.y * b1.y;
+            dkx[q] += (u128)(a0.x + a1.x) * sbx;
+            dky[q] += (u128)(a0.y + a1.y) * sby;
+        }
+        if (++since == chunk) {
+            since = 0;
+#pragma unroll
+            for (int q = 0; q < QW; q++) {
+                d0x[q] = reduce128(d0x[q], M); d0y[q] = reduce128(d0y[q], M);
+                dkx[q] = reduce128(dkx[q], M); dky[q] = reduce128(dky[q], M);
+                d2x[q] = reduce128(d2x[q], M); d2y[q] = reduce128(d2y[q], M);
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < QW; q++) {
+        part[wv][0][lane] = reduce128(d0x[q], M); part[wv][1][lane] = reduce128(d0y[q], M);
+        part[wv][2][lane] = reduce128(dkx[q], M); part[wv][3][lane] = reduce128(dky[q], M);
+        part[wv][4][lane] = reduce128(d2x[q], M); part[wv][5][lane] = reduce128(d2y[q], M);
+        __syncthreads();
+        if (wv == 0) {
+            u64 r[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                u64 t = part[0][k][lane];
+                for (int w = 1; w < KS; w++) t = addmod(t, part[w][k][lane], M.q);
+                r[k] = t;
+            }
+            u64 *o = acc + (mq_slot(q0 + q, g, G, ng, nblk, Qt) * 3 * nl + j) * N + c;
+            *reinterpret_cast<ulonglong2 *>(o) = make_ulonglong2(r[0], r[1]);
+            *reinterpret_cast<ulonglong2 *>(o + ps) = make_ulonglong2(submod(submod(r[2], r[0], M.q), r[4], M.q), submod(submod(r[3], r[1], M.q), r[5], M.q));
+            *reinterpret_cast<ulonglong2 *>(o + 2 * ps) = make_ulonglong2(r[4], r[5]);
+        }
+        __syncthreads();
+    }
+}
+
 
 // unpacked [X][2][nQ][N] u64  <->  database layout.  grid (N/512, nQ, X*2)
 template <bool PACK>
@@ -1255,6 +1526,75 @@ void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *
     HY_TENSOR_CASE(1, 4) HY_TENSOR_CASE(1, 2) HY_TENSOR_CASE(1, 1)
 #undef HY_TENSOR_CASE
     throw std::logic_error("hydia: no loop B kernel for this split");
+}
+// ---- loop B for a batch of queries.  QW = 2: at QW = 4 every instantiation takes 256 VGPRs (one wave per SIMD) and the 512-thread
+// ones spill; at QW = 2 the kernels keep 152 / 165 VGPRs (three waves per SIMD), what the single-query kernels take
+constexpr int MQ_QW = 2;
+template <int QW>
+static void launch_tensor_mq(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const unsigned char *db, u64 *acc, int G,
+                             int dim, int nl, const DbLayout &L, int ng, int q0, int Qt) {
+    const int nblk = ng > 0 ? G / ng : 0;
+    const int xm = (N / 128) % 8 == 0 ? 1 : 0;
+    // blocks per workgroup (one per wave): the group of a group-sequential layout, else the largest of 4, 2, 1 dividing G
+    const int nwm = L.seq ? L.seq : (G % 4 == 0 ? 4 : G % 2 == 0 ? 2 : 1);
+    const int Gq = G / nwm;
+    const bool b46 = L.packed && L.seq && L.bits46, sk0 = L.packed && !L.seq && G <= 8;
+    const double per_lp8 = LP_BYTES(N), per_lp6 = (double)N * (b46 ? 5.75 : 6.0);
+    const double rot_acc = (double)QW * ((double)dim * 2 * per_lp8 + (double)G * 3 * per_lp8);  // QW rotation sets in, QW x G accumulators out
+    char n0[64], n1[64];
+    if (sk0) snprintf(n0, sizeof n0, "k_hydia_tensor_sk_mq<%d, %d>", G <= 2 ? 8 : 4, QW);
+    else snprintf(n0, sizeof n0, "k_hydia_tensor_mq<%d, %d, false>", QW, nwm);
+    snprintf(n1, sizeof n1, b46 ? "k_hydia_tensor24_mq<%d, %d>" : "k_hydia_tensor_mq<%d, %d, true>", QW, nwm);
+#define HY_MQ(K, ...)                                                                                                   \
+    switch (nwm) {                                                                                                      \
+    case 1: hipLaunchKernelGGL((K<QW, 1, ##__VA_ARGS__>), grid, dim3(64), 0, st, mod, N, rot, rqs, db, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Qt); break; \
+    case 2: hipLaunchKernelGGL((K<QW, 2, ##__VA_ARGS__>), grid, dim3(128), 0, st, mod, N, rot, rqs, db, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Qt); break; \
+    case 4: hipLaunchKernelGGL((K<QW, 4, ##__VA_ARGS__>), grid, dim3(256), 0, st, mod, N, rot, rqs, db, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Qt); break; \
+    case 8: hipLaunchKernelGGL((K<QW, 8, ##__VA_ARGS__>), grid, dim3(512), 0, st, mod, N, rot, rqs, db, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Qt); break; \
+    default: throw std::logic_error("hydia: no multi-query loop B kernel for this group size");                        \
+    }
+    if (!L.packed) {  // 8-byte residues everywhere: one launch over all limbs
+        ledger_add(n0, nl * ((double)G * dim * 2 * per_lp8) + nl * rot_acc);
+        const dim3 grid((N / 128) * Gq, nl);
+        const int j0 = 0;
+        HY_MQ(k_hydia_tensor_mq, false)
+        return;
+    }
+    ledger_add(n0, (double)G * dim * 2 * per_lp8 + rot_acc);
+    if (nl > 1) ledger_add(n1, (nl - 1) * ((double)G * dim * 2 * per_lp6 + rot_acc));
+    if (sk0) {
+        if (G <= 2)
+            hipLaunchKernelGGL((k_hydia_tensor_sk_mq<8, QW>), dim3((N / 128) * G, 1), dim3(64 * 8), 0, st, mod, N, rot, rqs, db, acc, dim, nl, L, G, ng, nblk, q0, Qt);
+        else
+            hipLaunchKernelGGL((k_hydia_tensor_sk_mq<4, QW>), dim3((N / 128) * G, 1), dim3(64 * 4), 0, st, mod, N, rot, rqs, db, acc, dim, nl, L, G, ng, nblk, q0, Qt);
+    } else {
+        const dim3 grid((N / 128) * Gq, 1);
+        const int j0 = 0;
+        HY_MQ(k_hydia_tensor_mq, false)
+    }
+    if (nl > 1) {
+        const dim3 grid((N / 128) * Gq, nl - 1);
+        const int j0 = 1;
+        if (b46) {
+            HY_MQ(k_hydia_tensor24_mq)
+        } else {
+            HY_MQ(k_hydia_tensor_mq, true)
+        }
+    }
+#undef HY_MQ
+}
+int hydia_tensor_mq_width(const DbLayout &) { return MQ_QW; }
+void hydia_tensor_accumulate_multi(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q,
+                                   int G, int dim, int nl, const DbLayout &L, int ng) {
+    if (Q < 1 || G < 1 || dim < 2 || (ng > 0 && G % ng)) throw std::logic_error("hydia: multi-query loop B with a bad shape");
+    if (L.seq && (G != L.blocks || dim != L.bd || G % L.seq || G <= 8 || (L.seq & (L.seq - 1)) || L.seq > 8))
+        throw std::logic_error("hydia: loop B launched against a group-sequential database with another shape");
+    if (L.bits46 && !(L.packed && L.seq && dim <= 4096)) throw std::logic_error("hydia: 46-bit database outside the 24-bit-halves loop B");
+    const unsigned char *dbb = (const unsigned char *)db;
+    for (int q0 = 0; q0 < Q; q0 += MQ_QW) {  // one pass over the database per QW queries (an odd last one alone)
+        if (Q - q0 >= MQ_QW) launch_tensor_mq<MQ_QW>(st, mod, N, rot, rqs, dbb, acc, G, dim, nl, L, ng, q0, Q);
+        else launch_tensor_mq<1>(st, mod, N, rot, rqs, dbb, acc, G, dim, nl, L, ng, q0, Q);
+    }
 }
 DbLayout db_layout(int N, int nQ, int packed) {
     DbLayout L{};

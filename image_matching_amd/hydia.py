@@ -106,6 +106,9 @@ def load_library():
         "hydia_compute_similarity": (i32, [vp, vp, pp]),
         "hydia_index_scenario": (i32, [vp, vp, pp]),
         "hydia_membership_scenario": (i32, [vp, vp, pp]),
+        "hydia_compute_similarity_multi": (i32, [vp, vp, u32, vp]),
+        "hydia_index_scenario_multi": (i32, [vp, vp, u32, vp]),
+        "hydia_membership_scenario_multi": (i32, [vp, vp, u32, vp]),
         "hydia_chebyshev_compare": (i32, [vp, vp, dbl, sz, pp]),
         "hydia_sum_and_evalsum": (i32, [vp, vp, pp]),
         "hydia_add_many": (i32, [vp, vp, pp]),
@@ -595,6 +598,25 @@ class DiagonalSender:
 
     def indexScenario(self, query_cipher):
         return self.cc._out(self.cc.L.hydia_index_scenario, query_cipher.h)
+
+    # ---- several queries in one pass over the database (an extension: the reference serves one query per call).  A list of query
+    # ciphertexts in, a list out: per query exactly what the single-query method returns
+    def _multi(self, fn, query_ciphers):
+        qs = list(query_ciphers)
+        n = len(qs)
+        hs = (C.c_void_p * max(n, 1))(*[q.h for q in qs])
+        out = (C.c_void_p * max(n, 1))()
+        _chk(fn(self.cc.h, hs, n, out))
+        return [Ciphertext(self.cc, C.c_void_p(out[i])) for i in range(n)]
+
+    def computeSimilarityMulti(self, query_ciphers):
+        return self._multi(self.cc.L.hydia_compute_similarity_multi, query_ciphers)
+
+    def indexScenarioMulti(self, query_ciphers):
+        return self._multi(self.cc.L.hydia_index_scenario_multi, query_ciphers)
+
+    def membershipScenarioMulti(self, query_ciphers):
+        return self._multi(self.cc.L.hydia_membership_scenario_multi, query_ciphers)
 
     # ---- loop A split over the GPUs of a node (sender_diag.cpp:23-26 cut into ranges; image_matching_amd.sharding)
     def rotateQueryRange(self, query_cipher, first, count):

@@ -218,6 +218,12 @@ int hydia_compute_similarity_rotated(hydia_ctx *ctx, const hydia_ct *rotations, 
 int hydia_index_scenario_rotated(hydia_ctx *ctx, const hydia_ct *rotations, hydia_ct **out);
 /* Sender::membershipScenario (:35-50) */
 int hydia_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out);
+/* Q independent queries against the resident database in one pass (an extension: the reference serves one query per
+ * call).  queries[q] as hydia_encrypt_query returns it; out[q] receives exactly what the single-query entry returns for
+ * queries[q], bit for bit, and is freed on its own.  On any error every out[q] is NULL. */
+int hydia_compute_similarity_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out);
+int hydia_index_scenario_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out);
+int hydia_membership_scenario_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out);
 /* OpenFHEWrapper::chebyshevCompare (src/openFHE_wrapper.cpp:143-185) on every ciphertext of the batch */
 int hydia_chebyshev_compare(hydia_ctx *ctx, const hydia_ct *in, double delta, size_t sign_depth, hydia_ct **out);
 /* multi-GPU membership tail: sum the batch into one ciphertext, then EvalSum over all slots (:46-47) */
@@ -288,7 +294,7 @@ int hydia_eval_add(hydia_ctx *ctx, hydia_ct *a, const hydia_ct *b);
 int hydia_level_reduce(hydia_ctx *ctx, hydia_ct *ct, uint32_t n_limbs);
 
 /* ---- measurement: HIP-event time of named kernels on the context's stream since the last reset
- * ("hydia_tensor" = loop B's tensor-accumulate kernel, "ks_inner_product") ---- */
+ * ("hydia_tensor" = loop B's tensor-accumulate kernel, "hydia_tensor_multi" = its multi-query form, "ks_inner_product") ---- */
 int hydia_kernel_time(hydia_ctx *ctx, const char *name, double *total_ms, uint64_t *launches);
 int hydia_kernel_time_reset(hydia_ctx *ctx);
 /* Byte ledger (process-wide): while enabled every kernel launcher records the bytes its launch has to move, by kernel name.

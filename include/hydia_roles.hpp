@@ -222,8 +222,43 @@ class DiagonalSender : public Sender {
         hydia_ct *out = run(queryCipher, hydia_index_scenario, hydia_group_index_scenario, "indexScenario");
         return out ? split_batch(cc, out) : std::vector<Ciphertext>{};
     }
+    // Several queries in one pass over the resident database (an extension: the reference serves one query per call).  One
+    // queryCipher per query in; per query exactly what the single-query method returns.  Not on a sharded context: an error, empty.
+    std::vector<std::vector<Ciphertext>> computeSimilarityMulti(std::vector<std::vector<Ciphertext>> &queryCiphers) {
+        std::vector<std::vector<Ciphertext>> r;
+        for (hydia_ct *h : run_multi(queryCiphers, hydia_compute_similarity_multi, "computeSimilarityMulti")) r.push_back(split_batch(cc, h));
+        return r;
+    }
+    std::vector<Ciphertext> membershipScenarioMulti(std::vector<std::vector<Ciphertext>> &queryCiphers) {
+        std::vector<Ciphertext> r;
+        for (hydia_ct *h : run_multi(queryCiphers, hydia_membership_scenario_multi, "membershipScenarioMulti")) r.push_back(split_batch(cc, h)[0]);
+        return r;
+    }
+    std::vector<std::vector<Ciphertext>> indexScenarioMulti(std::vector<std::vector<Ciphertext>> &queryCiphers) {
+        std::vector<std::vector<Ciphertext>> r;
+        for (hydia_ct *h : run_multi(queryCiphers, hydia_index_scenario_multi, "indexScenarioMulti")) r.push_back(split_batch(cc, h));
+        return r;
+    }
 
   private:
+    std::vector<hydia_ct *> run_multi(std::vector<std::vector<Ciphertext>> &qs,
+                                      int (*multi)(hydia_ctx *, const hydia_ct *const *, uint32_t, hydia_ct **), const char *what) {
+        if (cc->group) {
+            std::cerr << "Error: " << what << " is not available on a sharded context" << std::endl;
+            return {};
+        }
+        std::vector<const hydia_ct *> in;
+        for (auto &q : qs) {
+            if (q.empty() || !q[0]) {
+                std::cerr << "Error: empty query ciphertext" << std::endl;
+                return {};
+            }
+            in.push_back(q[0].batch->h);
+        }
+        std::vector<hydia_ct *> out(in.size(), nullptr);
+        if (!cc->check(multi(cc->h, in.data(), (uint32_t)in.size(), out.data()), what)) return {};
+        return out;
+    }
     hydia_ct *run(std::vector<Ciphertext> &q, int (*one)(hydia_ctx *, const hydia_ct *, hydia_ct **),
                   int (*sharded)(hydia_group *, const hydia_ct *, hydia_ct **), const char *what) {
         if (q.empty() || !q[0]) {
