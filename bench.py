@@ -11,12 +11,19 @@ encrypted database resident in HBM.
           is broadcast, loop A's rotations are either shared out over the ranks and all-gathered over xGMI (SURVEY 8e option B) or
           recomputed by every rank (option A) — whichever the warm-up measures faster on this node —, every rank runs an independent
           mat-vec + comparator on its own blocks, and the result ciphertexts are gathered over RCCL to rank 0 in global block order.
-          `--weak` keeps 2^log2n vectors PER GPU instead; its figure also rides in config.secondary of a default run.
+          `--weak` keeps 2^log2n vectors PER GPU instead; its figure also rides in config.secondary of a --full run.
 Data is synthetic with the distribution of the reference's tools/gen_dataset.sh (query = ones, random rows in [-99,99], planted
 matches in {1,2,3}); the database is REAL ciphertexts produced by the on-GPU enroller, and after the timed region rank 0
 decrypts the gathered index result and checks it against the planted matches (global indices).
 
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the result check and the JSON
+line, whose `roofline` comes from the kernel timers of the timed steps.  `--full` adds everything that takes work of its own after
+the timed steps: the CPU oracle baseline (`cpu_baseline`), computeSimilarity / membershipScenario beside indexScenario
+(`config.secondary`), one more query with the byte ledger on (`roofline.step`), and at N > 1 the per-phase split of three fenced
+steps (`step_split`, `comm_ms`, `compute_ms`, `loop_a_mode`, `model`) and the weak-scaling figure.
+
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full            # + CPU baseline, secondary figures, roofline.step
     python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR   # also DIR/*.npy: what the last timed step returned
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -340,8 +347,11 @@ def main():
     ap.add_argument("--loop-a", choices=["auto", "split", "replicated"], default="auto",
                     help="N > 1: loop A's 511 rotations shared out over the ranks and all-gathered (split), recomputed by every rank "
                          "(replicated), or whichever the warm-up measures faster (auto)")
-    ap.add_argument("--no-secondary-weak", action="store_true", help="N > 1: skip the weak-scaling figure of config.secondary")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the CPU baseline, the secondary figures, "
+                         "roofline.step (one more query with the byte ledger on) and, at N > 1, the per-phase split and the weak-scaling figure")
+    ap.add_argument("--no-secondary-weak", action="store_true", help="with --full, N > 1: skip the weak-scaling figure of config.secondary")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--random-db", action="store_true", help="fill the DB with random residues instead of enrolling")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one returned (rank 0: the gathered result) as DIR/<name>.npy")
@@ -491,9 +501,9 @@ def main():
     # (before anything below replaces `res`: the N > 1 phase timing runs further steps)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, cc, res)
-    # N > 1: where a step goes, per rank (outside the timed region: the phases are fenced, which the timed steps are not)
+    # N > 1, --full: where a step goes, per rank (outside the timed region: the phases are fenced, which the timed steps are not)
     split_report = None
-    if multi:
+    if multi and args.full:
         k_i = 3
         sender.timing = {}
         dt_i = timed(sender, qc, k_i)
@@ -515,9 +525,9 @@ def main():
                 "phases_ms": {k: {"max": round(max(d.get(k, 0.0) for d in per_rank), 3), "min": round(min(d.get(k, 0.0) for d in per_rank), 3)} for k in names},
                 "rank0_sum_ms": round(comm[0] + comp[0], 3),
                 "per_rank_ms": [{k: round(v, 3) for k, v in d.items()} for d in per_rank]}
-    # secondary figure of SURVEY 8d (outside the timed region): computeSimilarity alone = loop A + loop B + relin + rescale
+    # --full: secondary figure of SURVEY 8d (outside the timed region): computeSimilarity alone = loop A + loop B + relin + rescale
     ms_similarity = None
-    if not multi:
+    if not multi and args.full:
         cc.sync()
         t1 = time.time()
         for _ in range(3):
@@ -545,9 +555,9 @@ def main():
     backend = dist.get_backend() if multi else None
     # inherent bytes of the whole step (outside the timed region): one more query with the byte ledger on; the evaluator records what
     # each OPERATION has to move as SURVEY 8d prices it ("op:*" entries: loop B's resident bytes, loop A's keys in + rotations out,
-    # 2 N 8 B per limb-transform of every relinearisation / rescale / rotation, each evaluation key once per launch, ct x ct operands)
+    # 2 N 8 B per limb-transform of every relinearisation / rescale / rotation, each evaluation key once per launch, ct x ct operands); --full
     step_ops = None
-    if rank == 0 or multi:
+    if args.full and (rank == 0 or multi):
         im.byte_ledger(1)
         _r = sender.indexScenario(qc)
         cc.sync()
@@ -558,9 +568,9 @@ def main():
         flag = [bool(correct)]
         dist.broadcast_object_list(flag, src=0)
         correct = flag[0]
-    # N > 1, default run: the weak-scaling figure (2^log2n vectors PER GPU) beside the strong one, outside the timed region
+    # N > 1, --full: the weak-scaling figure (2^log2n vectors PER GPU) beside the strong one, outside the timed region
     weak = None
-    if multi and world > 1 and strong and not args.no_secondary_weak and not args.random_db and correct:
+    if args.full and multi and world > 1 and strong and not args.no_secondary_weak and not args.random_db and correct:
         try:
             n_w = world * (1 << args.log2n)
             f_w, l_w = im.shard_vectors(n_w, S, world, rank)
@@ -670,8 +680,8 @@ def main():
                                  "per residue (196608 B per DB vector): it exceeds `achieved` by the 46-bit storage and can pass 1.0 — a byte-saving "
                                  "figure, not a utilisation.  vs_measured_stream_ceiling: against stream_ceiling.GBs, what this GPU gives a read-once sequential "
                                  "stream in this access pattern (tools/ubench/stream_rate.hip, read from stream_ceiling.source; the guide's copy ceiling is 6.29).  traffic = PMC HBM bytes per launch "
-                                 "(profiles/tensor_traffic.json), quoted only while the kernel source it was profiled on is unchanged.  step = the whole "
-                                 "indexScenario: inherent bytes of every operation (byte ledger, op:* entries) / ms_per_step"},
+                                 "(profiles/tensor_traffic.json), quoted only while the kernel source it was profiled on is unchanged.  step (--full, else null) = "
+                                 "the whole indexScenario: inherent bytes of every operation (byte ledger, op:* entries) / ms_per_step"},
         }
         if split_report is not None:
             mode = "local" if (loop_a and loop_a["mode"] == "local") else ("split" if getattr(sender, "rotation_split", False) else "replicated")
@@ -688,7 +698,7 @@ def main():
                                           "computeSimilarity_vectors_per_s": round(n_local / ms_similarity * 1e3),
                                           "membershipScenario_ms_per_query": round(ms_membership, 3),
                                           "membershipScenario_result": membership_ok}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())

@@ -86,7 +86,7 @@ def test_bench_gpus_flag_runs_two_real_ranks_on_this_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["HYDIA_BENCH_REHEARSE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--total-log2n", "15", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-secondary-weak"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-secondary-weak"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -132,3 +132,31 @@ def test_bench_steps_and_dump_outputs(tmp_path):
     hi, lo, slots = dumps[1]["index_ct_hi"], dumps[1]["index_ct_lo"], dumps[1]["index_slots"]
     assert hi.ndim == 4 and hi.shape[:2] == (1, 2) and lo.max() < 2 ** 32 and slots.shape == (1, 16384)
     assert np.flatnonzero(slots.ravel() >= 1.0).tolist() == [0, 8192, 16383]  # bench.py's planted matches at 2^14
+
+
+def test_bench_plain_run_leaves_the_extras_to_full():
+    """a plain `bench.py` run stops at what its headline needs; `--full` adds the secondary figures and roofline.step (the CPU
+    baseline too, unless --no-cpu-baseline): same headline fields in both, and the same result"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = {}
+    for extra in ([], ["--full", "--no-cpu-baseline"]):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--log2n", "10", "--steps", "2", "--warmup", "1"]
+                           + extra, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        out[bool(extra)] = json.loads(lines[0])
+    for o in out.values():
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(o) and o["value"] > 0
+        assert o["config"]["result_correct"] is True and o["roofline"]["launches"] == 2
+        assert "cpu_baseline" not in o
+    plain, full = out[False], out[True]
+    assert "secondary" not in plain["config"] and plain["roofline"]["step"] is None
+    sec = full["config"]["secondary"]
+    assert sec["computeSimilarity_ms_per_query"] > 0 and sec["membershipScenario_result"] is True
+    assert full["roofline"]["step"]["inherent_bytes"] > full["roofline"]["bytes_per_launch"]
