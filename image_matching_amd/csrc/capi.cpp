@@ -78,6 +78,30 @@ size_t hydia_compute_required_depth(size_t approach) {
         default: return 0;
     }
 }
+/* src/main.cpp:169-173: HEStd_128_classic picks the smallest ring whose bound holds log2(QP) of the chain the depth implies */
+int hydia_params_for_approach(size_t approach, hydia_params *out) {
+    API_BEGIN
+    REQUIRE(out, "null argument");
+    const size_t depth = hydia_compute_required_depth(approach);
+    REQUIRE(depth > 0, "approach must be from 1 to 5");
+    hydia_params p;
+    hydia_default_params(&p);
+    p.mult_depth = (uint32_t)depth;
+    static const struct { uint32_t log_n; double bits; } bound[] = {{11, 54}, {12, 109}, {13, 218}, {14, 438}, {15, 881}, {16, 1772}};
+    for (const auto &b : bound) {
+        p.log_n = b.log_n;
+        if ((1u << b.log_n) / 2 < p.vector_dim) continue;  // a vector must fit the slots
+        const HostParams h(hydia_to_params(&p));
+        double bits = 0;
+        for (u64 m : h.q) bits += std::log2((double)m);
+        if (bits <= b.bits) {
+            *out = p;
+            return HYDIA_OK;
+        }
+    }
+    return fail(HYDIA_ERR_ARG, "hydia: no ring up to 2^16 holds this modulus chain at 128-bit classic security");
+    API_END
+}
 int hydia_params_describe(const hydia_params *p, hydia_info *info, uint64_t *moduli, uint64_t *roots) {
     API_BEGIN
     REQUIRE(p, "null params");
@@ -163,6 +187,21 @@ int hydia_keygen(hydia_ctx *ctx, const uint8_t seed[32]) {
     use_device(ctx);
     REQUIRE(ctx && seed, "null argument");
     client_keygen(ctx->cx, seed);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_keygen_rotations(hydia_ctx *ctx, const uint8_t seed[32], const int32_t *rots, uint32_t n) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && seed && (rots || n == 0), "null argument");
+    const long S = ctx->cx.slots;
+    std::vector<int> set;
+    for (uint32_t i = 0; i < n; i++) {
+        const int r = (int)((((long)rots[i] % S) + S) % S);  // HY_STREAM carries the key id as an unsigned field: never negative
+        REQUIRE(r != 0, "a rotation of 0 mod slots has no key");
+        if (std::find(set.begin(), set.end(), r) == set.end()) set.push_back(r);
+    }
+    client_keygen_rotations(ctx->cx, seed, set);
     return HYDIA_OK;
     API_END
 }
@@ -737,6 +776,27 @@ int hydia_level_reduce(hydia_ctx *ctx, hydia_ct *ct, uint32_t n_limbs) {
         Ct v = ct->c.alias((int)n_limbs);
         ct->c = ctx->cx.clone(v);
     }
+    return HYDIA_OK;
+    API_END
+}
+
+int hydia_eval_mult_plain(hydia_ctx *ctx, const hydia_ct *ct, const double *slots, hydia_ct **out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && ct && slots && out, "null argument");
+    REQUIRE(ct->c.npoly == 2 && ct->c.nl >= 2, "a plaintext multiply needs a 2-component ciphertext with a limb to rescale");
+    Context &cx = ctx->cx;
+    Ct pt(&cx, 1, 2, ct->c.nl, cx.delta);  // residues, Shoup companions
+    client_encode_plain(cx, slots, ct->c.nl, pt.d);
+    *out = wrap(ctx, cx.mult_plain_rescale(ct->c, pt.d));
+    return HYDIA_OK;
+    API_END
+}
+int hydia_binary_rotate(hydia_ctx *ctx, const hydia_ct *ct, int32_t factor, hydia_ct **out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && ct && out, "null argument");
+    *out = wrap(ctx, ctx->cx.binary_rotate(ct->c, factor));
     return HYDIA_OK;
     API_END
 }

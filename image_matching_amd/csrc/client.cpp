@@ -75,7 +75,33 @@ static void gen_evk(Context &cx, const ChaChaKey &key, int key_id, const u64 *s_
     cx.pool.put((u64 *)e32);
 }
 
+static void keygen_impl(Context &cx, const uint8_t seed[32], const std::vector<int> &rots);
 void client_keygen(Context &cx, const uint8_t seed[32]) {
+    // rotation keys {1..dim-1} u {dim, 2 dim, ... < slots}
+    std::vector<int> rots;
+    for (int i = 1; i < cx.prm.dim; i++) rots.push_back(i);
+    for (int i = cx.prm.dim; i < cx.slots; i <<= 1) rots.push_back(i);
+    keygen_impl(cx, seed, rots);
+}
+void client_keygen_rotations(Context &cx, const uint8_t seed[32], const std::vector<int> &rots) {
+    for (int r : rots)
+        if (r < 1 || r >= cx.slots) throw std::runtime_error("hydia: rotation keys are indexed by r mod slots in [1, slots)");
+    if (cx.keys_borrowed) throw StateError("hydia: this context borrows its keys from another context (re-key the owner)");
+    // keys outside the new set would belong to the previous secret: release them (and every table that points at rotation keys)
+    cx.sync_all();
+    for (auto it = cx.rot_keys.begin(); it != cx.rot_keys.end();) {
+        if (std::find(rots.begin(), rots.end(), it->first) != rots.end()) {
+            ++it;
+            continue;
+        }
+        for (void *p : {(void *)it->second.d, (void *)it->second.d_cell, (void *)it->second.d_gal})
+            if (p) HIP_CHECK(hipFree(p));
+        it = cx.rot_keys.erase(it);
+    }
+    cx.rotptrs_valid = cx.giants_valid = false;
+    keygen_impl(cx, seed, rots);
+}
+static void keygen_impl(Context &cx, const uint8_t seed[32], const std::vector<int> &rots) {
     const int N = cx.N, nT = cx.nT, nQ = cx.nQ;
     const ChaChaKey key = make_key(seed);
     const LimbSel all = cx.sel_range(0, nT), qsel = cx.sel_q(nQ);
@@ -98,11 +124,8 @@ void client_keygen(Context &cx, const uint8_t seed[32]) {
     u64 *tmp = cx.pool.get(sizeof(u64) * (size_t)nT * N);
     hc::mul(cx.stream, cx.d_mod, N, cx.d_sk, cx.d_sk, tmp, qsel);
     gen_evk(cx, key, 0, cx.d_sk, tmp);
-    // rotation keys {1..dim-1} u {dim, 2 dim, ... < slots}: key r switches s -> sigma_g^{-1}(s), g = 5^r, so
-    // EvalFastRotation needs a single automorphism at the very end (see evaluator.cpp, rotate_query)
-    std::vector<int> rots;
-    for (int i = 1; i < cx.prm.dim; i++) rots.push_back(i);
-    for (int i = cx.prm.dim; i < cx.slots; i <<= 1) rots.push_back(i);
+    // rotation keys: key r switches s -> sigma_g^{-1}(s), g = 5^r, so EvalFastRotation needs a single automorphism at the very end
+    // (see evaluator.cpp, rotate_query); the sampler streams are addressed by r, whatever set r belongs to
     const u64 M = 2ull * N;
     for (int r : rots) {
         const u64 ginv = inv_mod_pow2(cx.galois_elt(r), M);
@@ -151,6 +174,35 @@ Ct client_encrypt(Context &cx, const double *slots, int count, const uint8_t see
     cx.pool.put((u64 *)d_slots);
     cx.sync();  // `slots` is caller memory
     return out;
+}
+
+// the plaintext of EvalMult(ct, MakeCKKSPackedPlaintext(v)) under FIXEDMANUAL: v encoded at scale 2^scale_bits (the encoder of
+// encrypt_device) and reduced onto limbs 0..nl-1 of the ciphertext it multiplies, then transformed; the Shoup companions
+// floor(m 2^64 / q_j) are formed on the host once per plaintext
+void client_encode_plain(Context &cx, const double *slots, int nl, u64 *pt) {
+    if (nl < 1 || nl > cx.nQ) throw std::runtime_error("hydia: plaintext limb count outside 1 .. n_q");
+    ensure_embedding_tables(cx);
+    const int N = cx.N, Nh = cx.slots;
+    const LimbSel qsel = cx.sel_q(nl);
+    double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)Nh);
+    double2 *work = (double2 *)cx.pool.get(sizeof(double2) * (size_t)Nh);
+    long long *coeffs = (long long *)cx.pool.get(sizeof(long long) * (size_t)N);
+    HIP_CHECK(hipMemcpyAsync(d_slots, slots, sizeof(double) * (size_t)Nh, hipMemcpyHostToDevice, cx.stream));
+    hc::encode(cx.stream, d_slots, work, coeffs, N, 1, cx.delta, cx.d_rot_group, (const double2 *)cx.d_ksi);
+    hc::small_to_limbs(cx.stream, cx.d_mod, N, nullptr, coeffs, pt, 0, 1, qsel);
+    cx.ntt_fwd(pt, 0, 1, qsel);
+    std::vector<u64> m((size_t)nl * N);
+    HIP_CHECK(hipMemcpyAsync(m.data(), pt, sizeof(u64) * m.size(), hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();  // `slots` is caller memory, m is read below
+    for (int j = 0; j < nl; j++)
+        for (int c = 0; c < N; c++) {
+            u64 &v = m[(size_t)j * N + c];
+            v = (u64)(((unsigned __int128)v << 64) / cx.q[j]);
+        }
+    HIP_CHECK(hipMemcpy(pt + (size_t)nl * N, m.data(), sizeof(u64) * m.size(), hipMemcpyHostToDevice));  // the stream is idle
+    cx.pool.put((u64 *)coeffs);
+    cx.pool.put((u64 *)work);
+    cx.pool.put((u64 *)d_slots);
 }
 
 // VectorUtils::plaintextNormalize (vector_utils.cpp:42-51): divide by the L2 norm, zero vector passes through

@@ -5,6 +5,12 @@
 
 namespace hydia {
 void client_keygen(Context &cx, const uint8_t seed[32]);
+// sk, pk and relinearisation key exactly as client_keygen, rotation keys for exactly `rots` (each in [1, slots)); every other
+// rotation key is released.  A key that client_keygen also makes comes out bit-identical (same sampler streams).
+void client_keygen_rotations(Context &cx, const uint8_t seed[32], const std::vector<int> &rots);
+// MakeCKKSPackedPlaintext(slots) at scale 2^scale_bits on limbs 0..nl-1 in evaluation form, with the Shoup companion of every
+// residue for hk::mul_plain: pt [2][nl][N] (row 0 residues, row 1 companions)
+void client_encode_plain(Context &cx, const double *slots, int nl, u64 *pt);
 Ct client_encrypt(Context &cx, const double *slots, int count, const uint8_t seed[32], uint64_t nonce0);
 Ct client_encrypt_query(Context &cx, const double *query, const uint8_t seed[32], uint64_t nonce);
 void client_decrypt(Context &cx, const Ct &ct, double *out);

@@ -957,6 +957,36 @@ Ct Context::rotate(const Ct &a, int rot) {
     return out;
 }
 
+// ------------------------------------------------------------------ helpers of approach 1 (openFHE_wrapper.cpp)
+// binaryRotate (:103-128): round(log2 |f|), largest first, the signed power of two subtracted; steps that are multiples of the slot
+// count are skipped.  The order of the steps is the order of the key switches, and with it the noise: kept as the reference has it.
+std::vector<int> Context::binary_rotations(long factor) const {
+    std::vector<int> r;
+    while (factor != 0) {
+        const long sign = factor < 0 ? -1 : 1;
+        const long bc = (long)std::pow(2.0, std::round(std::log2((double)(factor * sign))));
+        if ((bc * sign) % slots != 0) r.push_back((int)((((bc * sign) % slots) + slots) % slots));
+        factor -= bc * sign;
+    }
+    return r;
+}
+Ct Context::binary_rotate(const Ct &a, long factor) {
+    Ct c = clone(a);
+    for (int r : binary_rotations(factor)) c = rotate(c, r);
+    return c;
+}
+// EvalMult(ct, MakeCKKSPackedPlaintext(v)) under FIXEDMANUAL, then RescaleInPlace (mergeSingleCipher, :235-237; the Relinearize between
+// them is a no-op on a product with a plaintext): residue-wise product with v encoded at scale 2^scale_bits on the ciphertext's limbs,
+// scale ct.scale * 2^scale_bits before the rescale
+Ct Context::mult_plain_rescale(const Ct &a, const u64 *pt) {
+    if (a.npoly != 2) throw std::runtime_error("hydia: a plaintext multiplies a 2-component ciphertext");
+    Ct o(this, a.X, 2, a.nl, a.scale * delta);
+    op_bytes("op:mult_plain", N, 0, (2.0 * a.X * 2 + 2.0) * a.nl * N * 8);
+    hk::mul_plain(stream, d_mod, N, a.d, a.lstride, pt, pt + (size_t)a.nl * N, o.d, a.X * 2, a.nl);
+    rescale(o);
+    return o;
+}
+
 // ------------------------------------------------------------------ HyDia sender
 // loop A (sender_diag.cpp:20-26): ONE ModUp of the query's c1, then dim-1 hoisted rotations as one batched
 // inner-product + ModDown + automorphism sequence.  Output: rot[0] = q, rot[i] = Rot_i(q).

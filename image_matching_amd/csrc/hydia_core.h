@@ -329,6 +329,12 @@ struct Context : HostParams {
     Ct mult_norelin_sub(const Ct &a, const Ct &b, const Ct &c);
     Ct mult(const Ct &a, const Ct &b);  // align, tensor, relin, rescale
     Ct rotate(const Ct &a, int rot);    // X = any; full key switch
+    // ---- helpers of approach 1 (the literature baseline, src/openFHE_wrapper.cpp)
+    // OpenFHEWrapper::binaryRotate's greedy signed decomposition of `factor` (:111-121), each step as r mod slots in [1, slots), in order
+    std::vector<int> binary_rotations(long factor) const;
+    Ct binary_rotate(const Ct &a, long factor);  // every ciphertext of the batch through those rotations
+    // EvalMult(ct, MakeCKKSPackedPlaintext(pt)) + RescaleInPlace; pt [2][nl][N] from client_encode_plain (residues, Shoup companions)
+    Ct mult_plain_rescale(const Ct &a, const u64 *pt);
 
     // ---- HyDia sender (src/sender/sender_diag.cpp)
     Ct rotate_query(const Ct &q);                   // -> [dim][2][nQ][N]

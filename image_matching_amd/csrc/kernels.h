@@ -394,6 +394,10 @@ void hydia_tensor_accumulate_multi(hipStream_t st, const ModC *mod, int N, const
                                    int G, int dim, int nl, const DbLayout &L, int ng = 0);
 int hydia_tensor_mq_width(const DbLayout &L);  // queries one pass over the database serves
 
+// EvalMult(ct, plaintext) residue-wise (approach 1's merge masks): o[xp][j] = a[xp][j] * m[j] mod q_j with the Shoup companions ms;
+// XP polynomials of nl limbs (a at limb stride a_ls, o compact), m / ms [nl][N]
+void mul_plain(hipStream_t st, const ModC *mod, int N, const u64 *a, int a_ls, const u64 *m, const u64 *ms, u64 *o, int XP, int nl);
+
 // ---- misc
 void fill_uniform_hash(hipStream_t st, const ModC *mod, int N, u64 *dst, size_t n_limbpolys, int nl,
                        unsigned long long seed);  // bench filler: residues < q_limb from a counter hash

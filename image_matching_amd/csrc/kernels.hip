@@ -1633,6 +1633,20 @@ void db_unpack(hipStream_t st, int N, int nQ, u64 *plain, const void *db, size_t
     hipLaunchKernelGGL(k_db_repack<false>, dim3(N / 512, b46 ? 1 : nQ, X * 2), dim3(256), 0, st, N, nQ, plain, (unsigned char *)db, L, t0);
     if (b46) hipLaunchKernelGGL(k_db_repack46<false>, dim3((N / 16 + 255) / 256, nQ - 1, X * 2), dim3(256), 0, st, N, nQ, plain, (unsigned char *)db, L, t0);
 }
+// grid (N/512, nl, XP): two coefficients per thread, the plaintext's residues and Shoup companions read beside the operand's
+__global__ __launch_bounds__(256) void k_mul_plain(const ModC *__restrict__ mod, int N, const u64 *__restrict__ a, int a_ls,
+                                                   const u64 *__restrict__ m, const u64 *__restrict__ ms, u64 *__restrict__ o, int nl) {
+    const int j = blockIdx.y, xp = blockIdx.z;
+    const u64 q = mod[j].q;
+    const size_t c = (size_t)(blockIdx.x * 256 + threadIdx.x) * 2, i = (size_t)j * N + c;
+    const ulonglong2 va = *reinterpret_cast<const ulonglong2 *>(a + (size_t)xp * a_ls * N + i);
+    const ulonglong2 w = *reinterpret_cast<const ulonglong2 *>(m + i), ws = *reinterpret_cast<const ulonglong2 *>(ms + i);
+    *reinterpret_cast<ulonglong2 *>(o + (size_t)xp * nl * N + i) = make_ulonglong2(mulmod_shoup(va.x, w.x, ws.x, q), mulmod_shoup(va.y, w.y, ws.y, q));
+}
+void mul_plain(hipStream_t st, const ModC *mod, int N, const u64 *a, int a_ls, const u64 *m, const u64 *ms, u64 *o, int XP, int nl) {
+    ledger_add("k_mul_plain", (2.0 * XP + 2.0) * nl * LP_BYTES(N));
+    hipLaunchKernelGGL(k_mul_plain, dim3(N / 512, nl, XP), dim3(256), 0, st, mod, N, a, a_ls, m, ms, o, nl);
+}
 const char *hydia_tensor_kernel_name() { return "k_hydia_tensor"; }
 void fill_uniform_hash(hipStream_t st, const ModC *mod, int N, u64 *dst, size_t n_limbpolys, int nl,
                        unsigned long long seed) {

@@ -149,6 +149,10 @@ def load_library():
         "hydia_rescale": (i32, [vp, vp]),
         "hydia_eval_add": (i32, [vp, vp, vp]),
         "hydia_level_reduce": (i32, [vp, vp, u32]),
+        "hydia_params_for_approach": (i32, [sz, vp]),
+        "hydia_keygen_rotations": (i32, [vp, vp, vp, u32]),
+        "hydia_eval_mult_plain": (i32, [vp, vp, vp, pp]),
+        "hydia_binary_rotate": (i32, [vp, vp, i32, pp]),
         "hydia_kernel_time": (i32, [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(u64)]),
         "hydia_kernel_time_reset": (i32, [vp]),
         "hydia_byte_ledger": (i32, [i32, C.c_char_p, sz, C.POINTER(sz)]),
@@ -209,6 +213,14 @@ def default_params(**over):
 def compute_required_depth(approach):
     """OpenFHEWrapper::computeRequiredDepth (src/openFHE_wrapper.cpp:6-44)."""
     return int(load_library().hydia_compute_required_depth(approach))
+
+
+def params_for_approach(approach):
+    """Host-only: the context ./ImageMatching <file> <approach> needs — depth computeRequiredDepth(approach), the smallest ring whose
+    log2(QP) fits HEStd_128_classic (log_n 15 for approaches 4 and 5, 16 for approach 1; include/hydia.h)."""
+    p = _Params()
+    _chk(load_library().hydia_params_for_approach(approach, C.byref(p)))
+    return p
 
 
 def describe_params(params=None):
@@ -319,6 +331,11 @@ class Context:
     def keygen(self, seed=None):
         _chk(self.L.hydia_keygen(self.h, _p(_seed(seed))))
 
+    def keygen_rotations(self, rotations, seed=None):
+        """keygen with rotation keys for exactly `rotations` (each taken mod slots; include/hydia.h hydia_keygen_rotations)."""
+        rots = np.ascontiguousarray(list(rotations), dtype=np.int32)
+        _chk(self.L.hydia_keygen_rotations(self.h, _p(_seed(seed)), _p(rots) if rots.size else None, rots.size))
+
     def import_eval_key(self, rot, data):
         data = np.ascontiguousarray(data, dtype=np.uint64)
         assert data.size == self.dnum * 2 * self.nT * self.N
@@ -424,6 +441,16 @@ class Context:
 
     def level_reduce(self, ct, n_limbs):
         _chk(self.L.hydia_level_reduce(self.h, ct.h, n_limbs))
+
+    def eval_mult_plain(self, ct, slots):
+        """EvalMult(ct, MakeCKKSPackedPlaintext(slots)) + RescaleInPlace on every ciphertext of the batch."""
+        v = np.ascontiguousarray(slots, dtype=np.float64)
+        assert v.shape == (self.slots,)
+        return self._out(self.L.hydia_eval_mult_plain, ct.h, _p(v))
+
+    def binary_rotate(self, ct, factor):
+        """OpenFHEWrapper::binaryRotate (src/openFHE_wrapper.cpp:103-128)."""
+        return self._out(self.L.hydia_binary_rotate, ct.h, int(factor))
 
     def chebyshev_compare(self, ct, delta=0.44, depth=10):
         """OpenFHEWrapper::chebyshevCompare (src/openFHE_wrapper.cpp:143-185)."""

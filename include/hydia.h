@@ -65,6 +65,12 @@ void hydia_default_params(hydia_params *out);
 int hydia_params_describe(const hydia_params *p, hydia_info *info, uint64_t *moduli, uint64_t *roots);
 /* OpenFHEWrapper::computeRequiredDepth, src/openFHE_wrapper.cpp:6-44 */
 size_t hydia_compute_required_depth(size_t approach);
+/* Host-only: the context ./ImageMatching <file> <approach> needs (src/main.cpp:169-173 with SetMultiplicativeDepth(
+ * computeRequiredDepth(approach))): hydia_default_params with mult_depth = hydia_compute_required_depth(approach) and the smallest
+ * log_n whose log2(QP) of the derived chain fits the HEStd_128_classic bound (54, 109, 218, 438, 881, 1772 bits at 2^11 .. 2^16) —
+ * what OpenFHE selects.  Approaches 4 and 5 (depth 11, 795 bits): log_n 15 = hydia_default_params; approach 1 (depth 13: 14 Q limbs,
+ * 5 special primes, 945 bits): log_n 16.  An approach outside 1..5: HYDIA_ERR_ARG. */
+int hydia_params_for_approach(size_t approach, hydia_params *out);
 
 /* replaces GenCryptoContext + Enable(...) (src/main.cpp:169-179) for the sender/receiver on GPU `device`.  No HIP device, or a
  * device index beyond the ones visible: HYDIA_ERR_DEVICE (a negative index: HYDIA_ERR_ARG) — there is no CPU fallback. */
@@ -94,6 +100,11 @@ int hydia_random_seed(uint8_t out[32]);
 /* ---- keys: cc->KeyGen / EvalMultKeyGen / EvalRotateKeyGen (src/main.cpp:184-206) ---- */
 /* generate sk, pk, relin key and rotation keys {1..dim-1} u {dim, 2dim, .., slots/2} on the GPU from a 32-byte seed */
 int hydia_keygen(hydia_ctx *ctx, const uint8_t seed[32]);
+/* the same sk, pk and relinearisation key, and rotation keys for exactly the rotations rots[0 .. n-1] (EvalRotateKeyGen with a list of
+ * its own, src/main.cpp:195-206): each r is taken as r mod slots in [1, slots) — a negative rotation is the key of slots + r — and
+ * r = 0 mod slots is HYDIA_ERR_ARG.  Rotation keys outside the set are released.  A key hydia_keygen also makes comes out bit-identical
+ * to it.  Approach 1 needs {2^k} u {slots - 2^k} (29 keys at 2^16 where hydia_keygen's set would take ~30 GB). */
+int hydia_keygen_rotations(hydia_ctx *ctx, const uint8_t seed[32], const int32_t *rots, uint32_t n);
 /* or import keys produced elsewhere (the reference's serial/{multkey,rotkey}.bin contents after unmarshalling):
  * rot = 0 is the relinearisation key, rot >= 1 the key of EvalRotate(., rot); data [dnum][2][n_q+n_p][N] */
 int hydia_import_eval_key(hydia_ctx *ctx, int rot, const uint64_t *data);
@@ -292,6 +303,14 @@ int hydia_relinearize(hydia_ctx *ctx, hydia_ct *ct);
 int hydia_rescale(hydia_ctx *ctx, hydia_ct *ct);
 int hydia_eval_add(hydia_ctx *ctx, hydia_ct *a, const hydia_ct *b);
 int hydia_level_reduce(hydia_ctx *ctx, hydia_ct *ct, uint32_t n_limbs);
+/* helpers of approach 1 (src/openFHE_wrapper.cpp), on every ciphertext of the batch:
+ * EvalMult(ct, MakeCKKSPackedPlaintext(slots)) + RescaleInPlace under FIXEDMANUAL (:235-237): `slots` (slots doubles) encoded at scale
+ * 2^scale_bits on the ciphertext's current limbs, multiplied residue-wise in evaluation form (scale ct.scale * 2^scale_bits), then
+ * rescaled — out has one limb less */
+int hydia_eval_mult_plain(hydia_ctx *ctx, const hydia_ct *ct, const double *slots, hydia_ct **out);
+/* OpenFHEWrapper::binaryRotate (:103-128): the greedy signed power-of-two decomposition of `factor` (round(log2 |f|), largest first),
+ * applied in that order; every step needs the key of its rotation mod slots */
+int hydia_binary_rotate(hydia_ctx *ctx, const hydia_ct *ct, int32_t factor, hydia_ct **out);
 
 /* ---- measurement: HIP-event time of named kernels on the context's stream since the last reset
  * ("hydia_tensor" = loop B's tensor-accumulate kernel, "hydia_tensor_multi" = its multi-query form, "ks_inner_product") ---- */
