@@ -379,7 +379,7 @@ Context::Context(const Params &p, int dev) : HostParams(p), device(dev) {
     if (!getenv("HYDIA_NTT_INT") && !getenv("HYDIA_NTT_NO_PM"))
         for (int m = 0; m < nT; m++)
             if (!((tabs.fp_mask >> m) & 1u) && mod[m].q < (1ull << 60) && (1ull << 60) - mod[m].q < (1ull << 24)) tabs.pm_mask |= 1u << m;
-    if (const char *e = getenv("HYDIA_TENSOR_BPP")) tensor_bpp = atoi(e);
+    if (const char *e = getenv("HYDIA_TENSOR_BPP")) tensor_bpp = std::max(1, atoi(e));  // (bpp 0 marks a batch launch)
     if (const char *e = getenv("HYDIA_TENSOR_NW")) tensor_nw = atoi(e);
     merge_rescale = getenv("HYDIA_NO_MERGE_RESCALE") == nullptr;
     fuse_ip = getenv("HYDIA_NO_FUSE_IP") == nullptr;

@@ -1086,7 +1086,7 @@ Ct Context::similarity_bsgs_sum(const Ct &qc) {
     if (qc.nl != nQ) throw StateError("hydia: query must be a fresh (level 0) ciphertext");
     const int dim = prm.dim, B = db_babies, NG = (dim + B - 1) / B;
     if (B < 1 || dim % B) throw StateError("hydia: the resident database carries no valid baby count");
-    const int G = (int)(db_cts / dim), nl = nQ, nE = nl + nP, nd = (nl + alpha - 1) / alpha;
+    const int G = (int)(db_cts / dim), nl = nQ;
     build_giants(G);
     // babies: rotations 0 .. B-1 of the query (loop A on B - 1 keys)
     Ct rot(this, B, 2, nl, qc.scale);
@@ -1096,18 +1096,23 @@ Ct Context::similarity_bsgs_sum(const Ct &qc) {
     Ct acc(this, G * NG, 3, nl, qc.scale * delta);
     op_bytes("op:loop_b", N, 0, (double)db_cts * (double)db_layout().ct_bytes + ((double)B * 2 + (double)G * NG * 3) * nl * N * 8);
     timer_begin("hydia_tensor");
-    hk::hydia_tensor_accumulate(stream, d_mod, N, rot.d, d_db, acc.d, G * NG, B, nl, tensor_bpp, tensor_nw, db_lay, NG);
+    hk::hydia_tensor_accumulate(stream, d_mod, N, rot.d, 0, d_db, acc.d, 1, G * NG, B, nl, db_lay, NG, tensor_bpp, tensor_nw);
     timer_end("hydia_tensor");
-    relinearize(acc);  // [NG*G][2][nl]
-    // giant steps: the partial sums g >= 1 of ALL blocks go through one batched key switch, rotation key B g for slot (g, block)
-    // (the automorphism rides in the ModDown epilogue); then out[block] = sum over g of slot (g, block)
-    Ct out(this, G, 2, nl, acc.scale);
+    return giant_step_sum(acc, NG);
+}
+// the giant steps of the BSGS mat-vec on giant-major degree-2 accumulators [NG X0] (slot g X0 + x): relinearise, the partial sums
+// g >= 1 of ALL X0 through one batched key switch, rotation key B g for slot (g, x) (the automorphism rides in the ModDown
+// epilogue); then out[x] = sum over g of slot (g, x)
+Ct Context::giant_step_sum(Ct &acc, int NG) {
+    const int X0 = acc.X / NG, nl = acc.nl, nE = nl + nP, nd = (nl + alpha - 1) / alpha;
+    relinearize(acc);
+    Ct out(this, X0, 2, nl, acc.scale);
     if (NG > 1) {
-        const int X = (NG - 1) * G;
+        const int X = (NG - 1) * X0;
         const size_t ce = acc.ct_elems();
         op_bytes("op:rotate", N, (double)X * (nd * nE + 2 * nP + 2 * nl), (double)(NG - 1) * nd * 2 * nE * N * 8 + 4.0 * X * nl * N * 8);
         Ct rotd(this, X, 2, nl, acc.scale);
-        const u64 *c = acc.d + (size_t)G * ce;
+        const u64 *c = acc.d + (size_t)X0 * ce;
         if (ks_fused_ok()) {
             ks_fused(c + acc.poly_elems(), ce, X, nl, nullptr, nullptr, d_giant_keys, c, ce, acc.poly_elems(), 1, d_giant_ginv, 0, false, rotd.d);
         } else {
@@ -1116,10 +1121,10 @@ Ct Context::similarity_bsgs_sum(const Ct &qc) {
             ks_apply(dig, (size_t)nd * nE * N, X, nl, d_giant_keys, 0, c, ce, acc.poly_elems(), 1, d_giant_gal, d_giant_ginv, 0, false, rotd.d);
             pool.put(dig);
         }
-        HIP_CHECK(hipMemcpyAsync(acc.d + (size_t)G * ce, rotd.d, (size_t)X * ce * sizeof(u64), hipMemcpyDeviceToDevice, stream));
+        HIP_CHECK(hipMemcpyAsync(acc.d + (size_t)X0 * ce, rotd.d, (size_t)X * ce * sizeof(u64), hipMemcpyDeviceToDevice, stream));
     }
-    op_bytes("op:add", N, 0, (double)(NG + 1) * G * 2 * nl * N * 8);
-    hk::batch_sum(stream, d_mod, N, acc.d, out.d, NG, 2, nl, G, G);
+    op_bytes("op:add", N, 0, (double)(NG + 1) * X0 * 2 * nl * N * 8);
+    hk::batch_sum(stream, d_mod, N, acc.d, out.d, NG, 2, nl, X0, X0);
     return out;
 }
 
@@ -1468,7 +1473,7 @@ Ct Context::similarity_accumulate_rot(const Ct &rot) {
     Ct acc(this, G, 3, nQ, rot.scale * delta);
     op_bytes("op:loop_b", N, 0, (double)db_cts * (double)db_layout().ct_bytes + ((double)dim * 2 + (double)G * 3) * nQ * N * 8);
     timer_begin("hydia_tensor");
-    hk::hydia_tensor_accumulate(stream, d_mod, N, rot.d, d_db, acc.d, G, dim, nQ, tensor_bpp, tensor_nw, db_lay);
+    hk::hydia_tensor_accumulate(stream, d_mod, N, rot.d, 0, d_db, acc.d, 1, G, dim, nQ, db_lay, 0, tensor_bpp, tensor_nw);
     timer_end("hydia_tensor");
     return acc;
 }
@@ -1510,21 +1515,21 @@ Ct Context::add_many(const Ct &s) {
     }
     return m;
 }
-// EvalSum(ct, batchSize) (sender_diag.cpp:47): log2(slots) rotate-and-add steps
-Ct Context::eval_sum(const Ct &a) {
-    Ct m = clone(a);
+// EvalSum(ct, batchSize) (sender_diag.cpp:47): log2(slots) rotate-and-add steps, on every ciphertext of the batch
+void Context::eval_sum_inplace(Ct &m) {
     for (int r = 1; r < slots; r <<= 1) {
         Ct t = rotate(m, r);
         add_inplace(m, t);
     }
+}
+Ct Context::eval_sum(const Ct &a) {
+    Ct m = clone(a);
+    eval_sum_inplace(m);
     return m;
 }
 Ct Context::sum_and_evalsum(const Ct &s) {
     Ct m = add_many(s);
-    for (int r = 1; r < slots; r <<= 1) {
-        Ct t = rotate(m, r);
-        add_inplace(m, t);
-    }
+    eval_sum_inplace(m);
     return m;
 }
 // ------------------------------------------------------------------ a batch of queries in one pass over the database (an extension:
@@ -1554,7 +1559,7 @@ int Context::multi_batch(int Q) {
 // loop A + loop B (+ for BSGS the relinearisation and the giant steps) of queries q0 .. q0+Qb-1: kind 5 the [Qb G][3][nQ]
 // accumulators, kind 6 the relinearised [Qb G][2][nQ] sums (what similarity_accumulate / similarity_bsgs_sum return, query-major)
 Ct Context::loop_b_multi(const std::vector<const Ct *> &qs, int q0, int Qb) {
-    const int dim = prm.dim, nl = nQ, nE = nl + nP, nd = (nl + alpha - 1) / alpha;
+    const int dim = prm.dim, nl = nQ;
     const int B = db_kind == 6 ? db_babies : dim, NG = (dim + B - 1) / B, G = (int)(db_cts / dim);
     if (db_kind == 6 && (B < 1 || dim % B)) throw StateError("hydia: the resident database carries no valid baby count");
     if (db_kind == 6) build_giants(Qb * G);  // one table entry per (giant step, query, block)
@@ -1567,33 +1572,12 @@ Ct Context::loop_b_multi(const std::vector<const Ct *> &qs, int q0, int Qb) {
         const int passes = (Qb + hk::hydia_tensor_mq_width(db_lay) - 1) / hk::hydia_tensor_mq_width(db_lay);
         op_bytes("op:loop_b_multi", N, 0, (double)passes * db_cts * (double)db_lay.ct_bytes + ((double)Qb * B * 2 + (double)Qb * G * NG * 3) * nl * N * 8);
         timer_begin("hydia_tensor_multi");
-        hk::hydia_tensor_accumulate_multi(stream, d_mod, N, rot.d, rqs, d_db, acc.d, Qb, G * NG, B, nl, db_lay, db_kind == 6 ? NG : 0);
+        hk::hydia_tensor_accumulate(stream, d_mod, N, rot.d, rqs, d_db, acc.d, Qb, G * NG, B, nl, db_lay, db_kind == 6 ? NG : 0,
+                                    hk::TENSOR_BATCH, 0);
         timer_end("hydia_tensor_multi");
     }
     if (db_kind == 5) return acc;
-    // BSGS: slot (giant g, query q, block) = (g Qb + q) G + block; the giant steps g >= 1 of all queries and blocks in one key switch
-    const int X0 = Qb * G;
-    relinearize(acc);
-    Ct out(this, X0, 2, nl, acc.scale);
-    if (NG > 1) {
-        const int X = (NG - 1) * X0;
-        const size_t ce = acc.ct_elems();
-        op_bytes("op:rotate", N, (double)X * (nd * nE + 2 * nP + 2 * nl), (double)(NG - 1) * nd * 2 * nE * N * 8 + 4.0 * X * nl * N * 8);
-        Ct rotd(this, X, 2, nl, acc.scale);
-        const u64 *c = acc.d + (size_t)X0 * ce;
-        if (ks_fused_ok()) {
-            ks_fused(c + acc.poly_elems(), ce, X, nl, nullptr, nullptr, d_giant_keys, c, ce, acc.poly_elems(), 1, d_giant_ginv, 0, false, rotd.d);
-        } else {
-            u64 *dig = pool.get((size_t)X * nd * nE * N * sizeof(u64));
-            modup_digits(c + acc.poly_elems(), ce, X, nl, dig);
-            ks_apply(dig, (size_t)nd * nE * N, X, nl, d_giant_keys, 0, c, ce, acc.poly_elems(), 1, d_giant_gal, d_giant_ginv, 0, false, rotd.d);
-            pool.put(dig);
-        }
-        HIP_CHECK(hipMemcpyAsync(acc.d + (size_t)X0 * ce, rotd.d, (size_t)X * ce * sizeof(u64), hipMemcpyDeviceToDevice, stream));
-    }
-    op_bytes("op:add", N, 0, (double)(NG + 1) * X0 * 2 * nl * N * 8);
-    hk::batch_sum(stream, d_mod, N, acc.d, out.d, NG, 2, nl, X0, X0);
-    return out;
+    return giant_step_sum(acc, NG);  // slot (giant g, query q, block) = (g Qb + q) G + block
 }
 // ciphertexts q*per .. q*per+per-1 of a batch, compact and owning
 Ct Context::batch_slice(const Ct &b, int q, int per) {
@@ -1630,10 +1614,7 @@ std::vector<Ct> Context::scenario_multi(const std::vector<const Ct *> &qs, int w
                 hk::copy_limbs(stream, N, s.d, m.d + (size_t)q * m.ct_elems(), s.poly_elems(), m.poly_elems(), s.npoly, s.nl);
             }
             r = Ct();
-            for (int rr = 1; rr < slots; rr <<= 1) {
-                Ct t = rotate(m, rr);
-                add_inplace(m, t);
-            }
+            eval_sum_inplace(m);
             for (int q = 0; q < Qb; q++) res.push_back(batch_slice(m, q, 1));
         } else {
             for (int q = 0; q < Qb; q++) res.push_back(batch_slice(r, q, G));

@@ -310,7 +310,7 @@ struct Context : HostParams {
     Ct clone(const Ct &a);          // compact copy
     void drop_to(Ct &a, int nl);    // O(1): keeps the allocation, lstride unchanged
     int tensor_bpp = 2;             // DB blocks per wave in loop B (HYDIA_TENSOR_BPP; 4 spills past 168 VGPRs)
-    int tensor_nw = 4;              // max waves per workgroup in loop B (HYDIA_TENSOR_NW; 0 = up to 16)
+    int tensor_nw = 4;              // max waves per workgroup in loop B (HYDIA_TENSOR_NW; 0 = up to 4, larger values clamped to 4)
     // round-2 fusions, each with its off switch for the parity variants (read once per context)
     bool modup_per_digit = false, loop_a_separate_ip = false, loop_a_int_ip = false, relin_separate_intt = false, loop_a_limb_fastest = false;
     void add_inplace(Ct &a, const Ct &b);
@@ -353,6 +353,7 @@ struct Context : HostParams {
     Ct sum_and_evalsum(const Ct &s);  // EvalAddMany over the batch + EvalSum over all slots
     Ct add_many(const Ct &s);         // EvalAddManyInPlace alone (the per-shard part of a sharded membership query)
     Ct eval_sum(const Ct &a);         // EvalSum alone
+    void eval_sum_inplace(Ct &m);     // EvalSum on every ciphertext of the batch
     void add_raw_inplace(Ct &a, const u64 *other /* compact, same shape, this device */);  // integer sum, no reduction
     void mod_reduce_inplace(Ct &a);   // every 64-bit value -> canonical residue of its limb
     // ---- a batch of queries in one pass over the database (an extension; evaluator.cpp): one result per query, each exactly what
@@ -362,6 +363,7 @@ struct Context : HostParams {
     void check_multi(const std::vector<const Ct *> &qs) const;  // runtime_error: a query is not fresh; StateError: no diagonal database
     int multi_batch(int Q);
     Ct loop_b_multi(const std::vector<const Ct *> &qs, int q0, int Qb);
+    Ct giant_step_sum(Ct &acc, int NG);  // BSGS giant steps on [NG X0] giant-major accumulators -> [X0][2][nQ][N] (relinearises acc)
     Ct batch_slice(const Ct &b, int q, int per);
     // ---- HERS sender (approach 4, src/sender/sender_hers.cpp): q = dim query ciphertexts
     Ct hers_similarity(const Ct &q);

@@ -381,17 +381,15 @@ void rescale_spread(hipStream_t st, const ModC *mod, int N, const u64 *t, u64 *t
 void rescale_combine(hipStream_t st, const ModC *mod, int N, const u64 *in, const u64 *tmp, u64 *out, int X, int l,
                      const ScaleSel &qlinv, int in_ls);
 
-// ---- loop B of the HyDia sender: acc[g][3][nl][N] = sum_i rot[i] (x) db[g][i], fully reduced
-// ng > 0: the G "blocks" are (database block, giant step) pairs, block-major in the database; accumulator (block, g) is written to
-// slot g * (G / ng) + block (giant-major), so that one giant step's partial sums over all database blocks are one contiguous batch
-void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, const void *db, u64 *acc, int G,
-                             int dim, int nl, int bpp, int nw, const DbLayout &L, int ng = 0);
-const char *hydia_tensor_kernel_name();
-// the same sums for Q queries in ceil(Q / QW) passes over the database (QW = hydia_tensor_mq_width): rot holds the queries' rotation
-// sets rqs elements apart; acc slot of (query q, block gi) is q * G + gi, and with ng > 0 giant-major over the whole batch:
-// ((gi % ng) * Q + q) * (G / ng) + gi / ng.  Every accumulator equals the single-query launch's for that query, bit for bit.
-void hydia_tensor_accumulate_multi(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q,
-                                   int G, int dim, int nl, const DbLayout &L, int ng = 0);
+// ---- loop B of the HyDia sender: acc[q][g][3][nl][N] = sum_i rot[q][i] (x) db[g][i], fully reduced, for Q queries whose rotation sets
+// lie rqs elements apart.  bpp, nw: a single query's launch (Q = 1) with the context's split caps (tensor_split); bpp = TENSOR_BATCH:
+// a batch, ceil(Q / QW) passes over the database (QW = hydia_tensor_mq_width), one block per wave.  Every accumulator equals the
+// single-query launch's for that query, bit for bit.  Slot of (query q, block gi): q * G + gi; ng > 0: the G "blocks" are (database
+// block, giant step) pairs, block-major in the database, and the slots are giant-major over the whole batch,
+// ((gi % ng) * Q + q) * (G / ng) + gi / ng, so that one giant step's partial sums over all queries and blocks are one contiguous batch
+constexpr int TENSOR_BATCH = 0;
+void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G,
+                             int dim, int nl, const DbLayout &L, int ng, int bpp, int nw);
 int hydia_tensor_mq_width(const DbLayout &L);  // queries one pass over the database serves
 
 // EvalMult(ct, plaintext) residue-wise (approach 1's merge masks): o[xp][j] = a[xp][j] * m[j] mod q_j with the Shoup companions ms;

@@ -598,107 +598,17 @@ DEV DbWalk db_walk(const DbLayout &L, int N, int dim, int j, int tile, int lane,
     return w;
 }
 // One Karatsuba step per coefficient: d0 += a0 b0, d2 += a1 b1, dk += (a0+a1)(b0+b1); d1 = dk - d0 - d2 at the end.
-// Three 64x64->128 products per coefficient instead of four — loop B is co-bound by the integer multiplier, not only
-// by HBM (gfx950 builds a 128-bit product from four v_mad_u64_u32).
-template <int BPP, int NW, bool NT, bool PK>
-__global__ __launch_bounds__(64 * NW, 2) void k_hydia_tensor(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot,
-                                                             const unsigned char *__restrict__ db, u64 *__restrict__ acc,
-                                                             int dim, int nl, int Gq, int xcd_map, DbLayout L, int j0, int ng, int nblk) {
-    const int j = blockIdx.y + j0;
-    // consecutive workgroup ids are dealt round-robin over the 8 XCDs: give every XCD its own tiles and let the Gq block
-    // groups of one tile follow each other ON THAT XCD, so they find the tile's rot lines in its L2
-    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int gq = xcd_map ? k % Gq : blockIdx.x % Gq;
-    const int tile = xcd_map ? xcd + 8 * (k / Gq) : blockIdx.x / Gq;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const ModC M = mod[j];
-    const size_t c = (size_t)tile * 128 + lane * 2;
-    const size_t ps = (size_t)nl * N, cs = 2 * ps;  // rot / acc poly stride, ciphertext stride (elements)
-    const int g0 = (gq * NW + wv) * BPP;
-    const u64 *ra = rot + (size_t)j * N + c;
-    const DbWalk dw = db_walk(L, N, dim, j, tile, lane, g0, gq, wv * BPP);
-    const unsigned char *da = db + dw.base;
-    const size_t db_cs = dw.si, db_ps = dw.sp, db_bs = dw.su;
-    const int kbits = M.ks + 2;
-    const int chunk = (125 - 2 * kbits >= 30) ? dim : (1 << (125 - 2 * kbits));
-    u128 d0x[BPP], d0y[BPP], dkx[BPP], dky[BPP], d2x[BPP], d2y[BPP];
-#pragma unroll
-    for (int u = 0; u < BPP; u++) d0x[u] = d0y[u] = dkx[u] = dky[u] = d2x[u] = d2y[u] = 0;
-    // One diagonal's operands are fetched while the previous one's products run: a wave always has 2 + 4 BPP loads in flight instead
-    // of none during its ~230 multiply-accumulate instructions (188 registers, two waves per SIMD; 27.2 -> 26.65 ms at 64 blocks on the
-    // same GPU.  Forcing three waves per SIMD spills and loses it: 28.0 ms).
-    struct Operands {
-        ulonglong2 a0, a1;
-        DbRaw<PK> b0[BPP], b1[BPP];
-    };
-    auto fetch = [&](Operands &o, int i) {
-        o.a0 = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * cs);
-        o.a1 = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * cs + ps);
-#pragma unroll
-        for (int u = 0; u < BPP; u++) {
-            o.b0[u].template load<NT>(da + u * db_bs + (size_t)i * db_cs);
-            o.b1[u].template load<NT>(da + u * db_bs + (size_t)i * db_cs + db_ps);
-        }
-    };
-    auto accumulate = [&](const Operands &o) {
-        const u64 sax = o.a0.x + o.a1.x, say = o.a0.y + o.a1.y;
-#pragma unroll
-        for (int u = 0; u < BPP; u++) {
-            const ulonglong2 b0 = o.b0[u].get(), b1 = o.b1[u].get();
-            d0x[u] += (u128)o.a0.x * b0.x;
-            d0y[u] += (u128)o.a0.y * b0.y;
-            d2x[u] += (u128)o.a1.x * b1.x;
-            d2y[u] += (u128)o.a1.y * b1.y;
-            dkx[u] += (u128)sax * (b0.x + b1.x);
-            dky[u] += (u128)say * (b0.y + b1.y);
-        }
-    };
-    Operands cur, nxt;
-    fetch(cur, 0);
-    for (int i0 = 0; i0 < dim; i0 += chunk) {
-        const int i1 = i0 + chunk < dim ? i0 + chunk : dim;
-        // dim (>= 2, checked at context creation) and every chunk are powers of two: even.  No branch inside the loop: at a join the
-        // compiler waits for every outstanding load, the prefetched ones included
-        for (int i = i0; i < i1; i += 2) {
-            fetch(nxt, i + 1);
-            accumulate(cur);
-            if (NW > 1) __builtin_amdgcn_s_barrier();  // keep the waves on the same diagonal (no memory wait implied)
-            fetch(cur, i + 2 < dim ? i + 2 : i + 1);   // the last one re-reads a line that is in flight: never used
-            accumulate(nxt);
-            if (NW > 1) __builtin_amdgcn_s_barrier();
-        }
-        if (i1 < dim) {
-#pragma unroll
-            for (int u = 0; u < BPP; u++) {
-                d0x[u] = reduce128(d0x[u], M); d0y[u] = reduce128(d0y[u], M);
-                dkx[u] = reduce128(dkx[u], M); dky[u] = reduce128(dky[u], M);
-                d2x[u] = reduce128(d2x[u], M); d2y[u] = reduce128(d2y[u], M);
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < BPP; u++) {
-        ulonglong2 r0, r1, r2;
-        r0.x = reduce128(d0x[u], M); r0.y = reduce128(d0y[u], M);
-        r2.x = reduce128(d2x[u], M); r2.y = reduce128(d2y[u], M);
-        r1.x = submod(submod(reduce128(dkx[u], M), r0.x, M.q), r2.x, M.q);
-        r1.y = submod(submod(reduce128(dky[u], M), r0.y, M.q), r2.y, M.q);
-        // ng > 0 (baby-step / giant-step split): accumulator of "block" gi = (database block, giant g) goes to slot g * blocks + block,
-        // so that the partial sums of one giant step over all database blocks are one contiguous batch
-        const int gi = g0 + u, go = ng > 0 ? (gi % ng) * nblk + gi / ng : gi;
-        u64 *o = acc + ((size_t)go * 3 * nl + j) * N + c;
-        *reinterpret_cast<ulonglong2 *>(o) = r0;
-        *reinterpret_cast<ulonglong2 *>(o + ps) = r1;
-        *reinterpret_cast<ulonglong2 *>(o + 2 * ps) = r2;
-    }
-}
-
-// Loop B on the packed limbs of a group-sequential database (residues and rotated-query residues below 2^48).  There HBM delivers
-// 7 TB/s and the 128-bit multiply-accumulates above (94 % of the vector issue slots at 6 TB/s) would be the limit, so the products are
-// taken on 24-bit halves, a = ah 2^24 + al, b = bh 2^24 + bl: the partial sums  ll = sum al bl,  mid = sum (al bh + ah bl),
-// hh = sum ah bh  stay below 2^63 for up to 4096 diagonals (Karatsuba's operand sums included: halves below 2^25), so every
-// multiply-accumulate is ONE v_mad_u64_u32 with no carry — 12 per coefficient instead of three 128-bit ones of ~9 instructions each;
-// the 6-byte residues are cut into halves straight from the three loaded dwords.  Same sums, same final reduction.
+// Three products per coefficient instead of four — loop B is co-bound by the integer multiplier, not only by HBM.
+//
+// Two arithmetics (policies of k_hydia_tensor), same sums, one reduction per output:
+// - Sums128: 64x64->128 products in 128-bit lazy sums (gfx950 builds one from four v_mad_u64_u32).  45/46-bit limbs never
+//   overflow (dim * 2^93 < 2^128); the 60-bit limb folds its sums every 64 diagonals.
+// - Halves24, on the packed limbs of a group-sequential database (residues and rotated-query residues below 2^48).  There HBM
+//   delivers 7 TB/s and the 128-bit multiply-accumulates (94 % of the vector issue slots at 6 TB/s) would be the limit, so the
+//   products are taken on 24-bit halves, a = ah 2^24 + al, b = bh 2^24 + bl: the partial sums  ll = sum al bl,
+//   mid = sum (al bh + ah bl),  hh = sum ah bh  stay below 2^63 for up to 4096 diagonals (Karatsuba's operand sums included:
+//   halves below 2^25), so every multiply-accumulate is ONE v_mad_u64_u32 with no carry — 12 per coefficient instead of three
+//   128-bit ones of ~9 instructions each; the 6-byte (48-bit) or 46-bit residues are cut into halves straight from the loaded dwords.
 // (The halves pass through an empty asm statement: knowing an operand has 24 bits the compiler (ROCm 7.2) forms 24-bit multiplies,
 // drops the masks they make redundant, and then fuses some of them back into v_mad_u64_u32 on the UNMASKED registers — wrong
 // products; tools/ubench/tensor_check.cpp found it.)
@@ -725,320 +635,130 @@ struct DbRaw46 {
         w = NT ? __builtin_nontemporal_load(reinterpret_cast<const u4a *>(p)) : *reinterpret_cast<const u4a *>(p);
     }
 };
-template <int BPP, int NW, bool B46, bool D2 = B46>
-__global__ __launch_bounds__(64 * NW, 2) void k_hydia_tensor24(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot,
-                                                               const unsigned char *__restrict__ db, u64 *__restrict__ acc,
-                                                               int dim, int nl, int Gq, int xcd_map, DbLayout L, int j0, int ng, int nblk) {
-    const int j = blockIdx.y + j0;
-    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int gq = xcd_map ? k % Gq : blockIdx.x % Gq;
-    const int tile = xcd_map ? xcd + 8 * (k / Gq) : blockIdx.x / Gq;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const ModC M = mod[j];
-    const size_t c = (size_t)tile * 128 + lane * 2;
-    const size_t ps = (size_t)nl * N, cs = 2 * ps;
-    const int g0 = (gq * NW + wv) * BPP;
-    const u64 *ra = rot + (size_t)j * N + c;
-    const DbWalk dw = db_walk(L, N, dim, j, tile, lane, g0, gq, wv * BPP);
-    const unsigned char *da = db + dw.base;
-    const size_t db_cs = dw.si, db_ps = dw.sp, db_bs = dw.su;
-    Acc24 d0[BPP][2], dk[BPP][2], d2[BPP][2];  // [block][coefficient of the lane's pair]
-#pragma unroll
-    for (int u = 0; u < BPP; u++)
-#pragma unroll
-        for (int e = 0; e < 2; e++) d0[u][e] = dk[u][e] = d2[u][e] = Acc24{0, 0, 0};
+// A policy turns a rotated-query residue (rot) and a loaded database operand (cut: one polynomial's two residues) into operands of
+// type T, multiply-accumulates them into a Sum (mac) and reduces it (reduce; fold: mid-way, every `chunk` diagonals).
+template <bool PK>  // PK: 6-byte database residues
+struct Sums128 {
+    typedef u64 T;
+    typedef u128 Sum;
+    typedef DbRaw<PK> Raw;
+    static constexpr int depth = 2;  // operand sets in flight
+    static constexpr const char *name = PK ? "Sums128<true>" : "Sums128<false>";
+    int chunk;  // products a lazy 128-bit sum can take
+    DEV Sums128(const ModC &M, int dim, int) {
+        const int kbits = M.ks + 2;
+        chunk = (125 - 2 * kbits >= 30) ? dim : (1 << (125 - 2 * kbits));
+    }
+    DEV static T rot(u64 v) { return v; }
+    DEV void cut(const Raw &r, T (&b)[2]) const {
+        const ulonglong2 v = r.get();
+        b[0] = v.x;
+        b[1] = v.y;
+    }
+    DEV static void mac(Sum &s, T a, T b) { s += (u128)a * b; }
+    DEV static void fold(Sum &s, const ModC &M) { s = reduce128(s, M); }
+    DEV static u64 reduce(const Sum &s, const ModC &M) { return reduce128(s, M); }
+};
+struct Half24 {
+    unsigned l, h;
+    DEV Half24 operator+(Half24 o) const { return {l + o.l, h + o.h}; }
+};
+template <bool B46>  // B46: 46-bit residues in 736-byte units, else 6-byte residues
+struct Halves24 {
+    typedef Half24 T;
+    typedef Acc24 Sum;
     typedef typename std::conditional<B46, DbRaw46, DbRaw<true>>::type Raw;
-    const unsigned s46 = (unsigned)(lane * 92) & 31u;  // B46: bit of the lane's first residue inside its first dword
-    struct Operands {
-        ulonglong2 a0, a1;
-        Raw b0[BPP], b1[BPP];
-    };
-    auto fetch = [&](Operands &o, int i) {
-        o.a0 = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * cs);
-        o.a1 = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * cs + ps);
-#pragma unroll
-        for (int u = 0; u < BPP; u++) {
-            o.b0[u].template load<true>(da + u * db_bs + (size_t)i * db_cs);
-            o.b1[u].template load<true>(da + u * db_bs + (size_t)i * db_cs + db_ps);
-        }
-    };
-    auto accumulate = [&](const Operands &o) {
-        // rotated-query residues (8 bytes each, below 2^48): halves of both polynomials and of their sum, shared by the BPP blocks
-        const u64 av[2][2] = {{o.a0.x, o.a0.y}, {o.a1.x, o.a1.y}};
-        unsigned al[2][2], ah[2][2], sl[2], sh[2];
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                al[p][e] = hide24((unsigned)av[p][e] & 0xFFFFFFu);
-                ah[p][e] = __builtin_amdgcn_alignbit((unsigned)(av[p][e] >> 32), (unsigned)av[p][e], 24);
-            }
-#pragma unroll
-        for (int e = 0; e < 2; e++) {
-            sl[e] = al[0][e] + al[1][e];
-            sh[e] = ah[0][e] + ah[1][e];
-        }
-#pragma unroll
-        for (int u = 0; u < BPP; u++) {
-            // database residues: two 48-bit integers in three dwords -> four 24-bit halves per polynomial
-            unsigned bl[2][2], bh[2][2];
-#pragma unroll
-            for (int p = 0; p < 2; p++) {
-                const auto w = p == 0 ? o.b0[u].w : o.b1[u].w;
-                if constexpr (B46) {  // T = (w3:w2:w1:w0) >> s: residue 0 = T[0, 46), residue 1 = T[46, 92); halves of 24 and 22 bits
-                    const unsigned t0 = __builtin_amdgcn_alignbit(w[1], w[0], s46), t1 = __builtin_amdgcn_alignbit(w[2], w[1], s46),
-                                   t2 = __builtin_amdgcn_alignbit(w[3], w[2], s46);
-                    bl[p][0] = hide24(t0 & 0xFFFFFFu);
-                    bh[p][0] = hide24(__builtin_amdgcn_alignbit(t1, t0, 24) & 0x3FFFFFu);
-                    bl[p][1] = hide24(__builtin_amdgcn_alignbit(t2, t1, 14) & 0xFFFFFFu);
-                    bh[p][1] = hide24((t2 >> 6) & 0x3FFFFFu);
-                } else {
-                    bl[p][0] = hide24(w[0] & 0xFFFFFFu);
-                    bh[p][0] = hide24(__builtin_amdgcn_alignbit(w[1], w[0], 24) & 0xFFFFFFu);
-                    bl[p][1] = hide24(__builtin_amdgcn_alignbit(w[2], w[1], 16) & 0xFFFFFFu);
-                    bh[p][1] = hide24(w[2] >> 8);
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                d0[u][e].mac(al[0][e], ah[0][e], bl[0][e], bh[0][e]);
-                d2[u][e].mac(al[1][e], ah[1][e], bl[1][e], bh[1][e]);
-                dk[u][e].mac(sl[e], sh[e], bl[0][e] + bl[1][e], bh[0][e] + bh[1][e]);
-            }
-        }
-    };
-    if constexpr (D2) {
-        // 46-bit units: 4 % fewer bytes per diagonal, and with one diagonal in flight per wave the launch did not get shorter — it is
-        // bound by what a CU keeps in flight (3 workgroups x one diagonal = 35 KB; 1.4 us of latency), not by HBM.  So the database
-        // operands run TWO diagonals ahead here (three rotating sets), the rotated-query lines (L2) one ahead as before.
-        Operands A, B, C;
-        fetch(A, 0);
-        fetch(B, 1);
-        int i = 0;
-        for (; i + 2 < dim; i += 3) {  // branch-free inside: clamped re-fetches of the last diagonal are never accumulated
-            fetch(C, i + 2);
-            accumulate(A);
-            if (NW > 1) __builtin_amdgcn_s_barrier();
-            fetch(A, i + 3 < dim ? i + 3 : dim - 1);
-            accumulate(B);
-            if (NW > 1) __builtin_amdgcn_s_barrier();
-            fetch(B, i + 4 < dim ? i + 4 : dim - 1);
-            accumulate(C);
-            if (NW > 1) __builtin_amdgcn_s_barrier();
-        }
-        if (i < dim) accumulate(A);      // the one or two diagonals the groups of three leave over (workgroup-uniform)
-        if (i + 1 < dim) accumulate(B);
-    } else {
-        Operands cur, nxt;
-        fetch(cur, 0);
-        for (int i = 0; i < dim; i += 2) {  // dim is a power of two >= 2; no branch inside (see k_hydia_tensor)
-            fetch(nxt, i + 1);
-            accumulate(cur);
-            if (NW > 1) __builtin_amdgcn_s_barrier();
-            fetch(cur, i + 2 < dim ? i + 2 : i + 1);
-            accumulate(nxt);
-            if (NW > 1) __builtin_amdgcn_s_barrier();
+    // 46-bit units: 4 % fewer bytes per diagonal, and with one diagonal in flight per wave the launch did not get shorter — it is
+    // bound by what a CU keeps in flight (3 workgroups x one diagonal = 35 KB; 1.4 us of latency), not by HBM.  So the database
+    // operands run TWO diagonals ahead there (three rotating sets), the rotated-query lines (L2) one ahead as before.
+    static constexpr int depth = B46 ? 3 : 2;
+    static constexpr const char *name = B46 ? "Halves24<true>" : "Halves24<false>";
+    int chunk;  // = dim: the sums hold 4096 diagonals, the launcher's limit
+    unsigned s46;  // B46: bit of the lane's first residue inside its first dword
+    DEV Halves24(const ModC &, int dim, int lane) : chunk(dim), s46((unsigned)(lane * 92) & 31u) {}
+    DEV static T rot(u64 v) {  // below 2^48
+        return {hide24((unsigned)v & 0xFFFFFFu), __builtin_amdgcn_alignbit((unsigned)(v >> 32), (unsigned)v, 24)};
+    }
+    DEV void cut(const Raw &r, T (&b)[2]) const {
+        const auto w = r.w;
+        if constexpr (B46) {  // T = (w3:w2:w1:w0) >> s: residue 0 = T[0, 46), residue 1 = T[46, 92); halves of 24 and 22 bits
+            const unsigned t0 = __builtin_amdgcn_alignbit(w[1], w[0], s46), t1 = __builtin_amdgcn_alignbit(w[2], w[1], s46),
+                           t2 = __builtin_amdgcn_alignbit(w[3], w[2], s46);
+            b[0] = {hide24(t0 & 0xFFFFFFu), hide24(__builtin_amdgcn_alignbit(t1, t0, 24) & 0x3FFFFFu)};
+            b[1] = {hide24(__builtin_amdgcn_alignbit(t2, t1, 14) & 0xFFFFFFu), hide24((t2 >> 6) & 0x3FFFFFu)};
+        } else {  // two 48-bit integers in three dwords
+            b[0] = {hide24(w[0] & 0xFFFFFFu), hide24(__builtin_amdgcn_alignbit(w[1], w[0], 24) & 0xFFFFFFu)};
+            b[1] = {hide24(__builtin_amdgcn_alignbit(w[2], w[1], 16) & 0xFFFFFFu), hide24(w[2] >> 8)};
         }
     }
+    DEV static void mac(Sum &s, T a, T b) { s.mac(a.l, a.h, b.l, b.h); }
+    DEV static void fold(Sum &, const ModC &) {}  // never reached (chunk = dim)
+    DEV static u64 reduce(const Sum &s, const ModC &M) { return reduce128(s.wide(), M); }
+};
+// one Karatsuba step on a lane's coefficient pair: a, b = [polynomial][coefficient] operands of the query and the database;
+// s = [d0, d2, dk][coefficient].  (The operand sums are formed here: the compiler forms each once per diagonal)
+template <class A>
+DEV void kara_mac(typename A::Sum (&s)[3][2], const typename A::T (&a)[2][2], const typename A::T (&b)[2][2]) {
 #pragma unroll
-    for (int u = 0; u < BPP; u++) {
-        ulonglong2 r0, r1, r2;
-        r0.x = reduce128(d0[u][0].wide(), M); r0.y = reduce128(d0[u][1].wide(), M);
-        r2.x = reduce128(d2[u][0].wide(), M); r2.y = reduce128(d2[u][1].wide(), M);
-        r1.x = submod(submod(reduce128(dk[u][0].wide(), M), r0.x, M.q), r2.x, M.q);
-        r1.y = submod(submod(reduce128(dk[u][1].wide(), M), r0.y, M.q), r2.y, M.q);
-        const int gi = g0 + u, go = ng > 0 ? (gi % ng) * nblk + gi / ng : gi;
-        u64 *o = acc + ((size_t)go * 3 * nl + j) * N + c;
-        *reinterpret_cast<ulonglong2 *>(o) = r0;
-        *reinterpret_cast<ulonglong2 *>(o + ps) = r1;
-        *reinterpret_cast<ulonglong2 *>(o + 2 * ps) = r2;
-    }
+    for (int k = 0; k < 2; k++)
+#pragma unroll
+        for (int e = 0; e < 2; e++) A::mac(s[k][e], a[k][e], b[k][e]);
+#pragma unroll
+    for (int e = 0; e < 2; e++) A::mac(s[2][e], a[0][e] + a[1][e], b[0][e] + b[1][e]);
 }
-
-// Loop B for SMALL databases (at most 8 blocks on this GPU): the limb-0 launch of k_hydia_tensor has only 256 x G waves, each
-// walking all `dim` diagonals — latency-bound (0.6 ms at G = 1 for 0.5 GB).  Here KS waves of a workgroup share one
-// (block, tile) and take every KS-th diagonal; the partial sums are reduced modulo q_j through LDS.  Same residues as the
-// one-wave kernel (a sum modulo q does not depend on how it is split).
-template <int KS, bool PK>
-__global__ __launch_bounds__(64 * KS) void k_hydia_tensor_sk(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot,
-                                                             const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim,
-                                                             int nl, DbLayout L, int j0, int ng, int nblk) {
-    __shared__ u64 part[KS][6][64];
-    const int j = blockIdx.y + j0, tiles = N / 128;
-    const int tile = blockIdx.x % tiles, g = blockIdx.x / tiles;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const ModC M = mod[j];
-    const size_t c = (size_t)tile * 128 + lane * 2;
-    const size_t ps = (size_t)nl * N, cs = 2 * ps;
-    const u64 *ra = rot + (size_t)j * N + c;
-    const unsigned char *da = db + (size_t)g * dim * L.ct_bytes + db_limb_offset(L, N, j) + c * (PK ? 6 : 8);
-    const int kbits = M.ks + 2;
-    const int chunk = (125 - 2 * kbits >= 30) ? dim : (1 << (125 - 2 * kbits));  // products a lazy 128-bit sum can take
-    u128 d0x = 0, d0y = 0, dkx = 0, dky = 0, d2x = 0, d2y = 0;
-    int since = 0;
-    for (int i = wv; i < dim; i += KS) {
-        const ulonglong2 a0 = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * cs);
-        const ulonglong2 a1 = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * cs + ps);
-        const ulonglong2 b0 = db_load2<PK, true>(da + (size_t)i * L.ct_bytes);
-        const ulonglong2 b1 = db_load2<PK, true>(da + (size_t)i * L.ct_bytes + L.poly_bytes);
-        d0x += (u128)a0.x * b0.x;
-        d0y += (u128)a0.y * b0.y;
-        d2x += (u128)a1.x * b1.x;
-        d2y += (u128)a1.y * b1.y;
-        dkx += (u128)(a0.x + a1.x) * (b0.x + b1.x);
-        dky += (u128)(a0.y + a1.y) * (b0.y + b1.y);
-        if (++since == chunk) {
-            since = 0;
-            d0x = reduce128(d0x, M); d0y = reduce128(d0y, M);
-            dkx = reduce128(dkx, M); dky = reduce128(dky, M);
-            d2x = reduce128(d2x, M); d2y = reduce128(d2y, M);
-        }
-    }
-    part[wv][0][lane] = reduce128(d0x, M); part[wv][1][lane] = reduce128(d0y, M);
-    part[wv][2][lane] = reduce128(dkx, M); part[wv][3][lane] = reduce128(dky, M);
-    part[wv][4][lane] = reduce128(d2x, M); part[wv][5][lane] = reduce128(d2y, M);
-    __syncthreads();
-    if (wv == 0) {
-        u64 r[6];
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-            u64 t = part[0][k][lane];
-            for (int w = 1; w < KS; w++) t = addmod(t, part[w][k][lane], M.q);
-            r[k] = t;
-        }
-        const int go = ng > 0 ? (g % ng) * nblk + g / ng : g;  // giant-major order (see k_hydia_tensor)
-        u64 *o = acc + ((size_t)go * 3 * nl + j) * N + c;
-        *reinterpret_cast<ulonglong2 *>(o) = make_ulonglong2(r[0], r[1]);
-        *reinterpret_cast<ulonglong2 *>(o + ps) = make_ulonglong2(submod(submod(r[2], r[0], M.q), r[4], M.q), submod(submod(r[3], r[1], M.q), r[5], M.q));
-        *reinterpret_cast<ulonglong2 *>(o + 2 * ps) = make_ulonglong2(r[4], r[5]);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ loop B for a batch of queries
-// The sums of the three kernels above for QW queries in one pass over the database: a wave loads a database operand ONCE per
-// diagonal and multiply-accumulates it against the rotation operands of QW queries (rot: the queries' rotation sets, rqs elements
-// apart).  Same products, same lazy sums, one reduction per output: the residues are the single-query kernels' bit for bit (a sum
-// modulo q does not depend on how it is split).  Registers: the accumulators of QW queries take the place of the
-// single-query kernels' BPP blocks, so a wave serves ONE database block and a workgroup of NWM waves walks the blocks a single-query
-// workgroup walks — in the group-sequential layout NWM = the layout's group size, and the workgroup still reads one contiguous run.
-// Output slot of (query q of the batch of Qt, block gi): ng == 0: q G + gi; ng > 0 (BSGS): giant-major over the WHOLE batch,
-// (g Qt + q) nblk + block — one giant step's partial sums over every query and block are one contiguous batch.
+// Output slot of (query q of the batch of Qt, block gi): ng == 0: q G + gi; ng > 0 (baby-step / giant-step split, gi = (database
+// block, giant)): giant-major over the WHOLE batch, (g Qt + q) nblk + block — one giant step's partial sums over every query and
+// block are one contiguous batch.  A single query is q = 0 of Qt = 1.
 DEV size_t mq_slot(int q, int gi, int G, int ng, int nblk, int Qt) {
     return ng > 0 ? ((size_t)(gi % ng) * Qt + q) * nblk + gi / ng : (size_t)q * G + gi;
 }
-// 128-bit lazy sums (k_hydia_tensor's arithmetic): limb 0 of every layout, the 48-bit packed limbs of the ciphertext-major layout
-// (PK), the unpacked layout.  grid (N/128 * Gq, limbs), the XCD-aware tile map of k_hydia_tensor.
-template <int QW, int NWM, bool PK>
-__global__ __launch_bounds__(64 * NWM) void k_hydia_tensor_mq(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs,
-                                                              const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
-                                                              int Gq, int xcd_map, DbLayout L, int j0, int G, int ng, int nblk, int q0, int Qt) {
-    const int j = blockIdx.y + j0;
-    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int gq = xcd_map ? k % Gq : blockIdx.x % Gq;
-    const int tile = xcd_map ? xcd + 8 * (k / Gq) : blockIdx.x / Gq;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const ModC M = mod[j];
-    const size_t c = (size_t)tile * 128 + lane * 2;
-    const size_t ps = (size_t)nl * N, cs = 2 * ps;
-    const int g = gq * NWM + wv;
-    const u64 *ra = rot + (size_t)q0 * rqs + (size_t)j * N + c;
-    const DbWalk dw = db_walk(L, N, dim, j, tile, lane, g, gq, wv);
-    const unsigned char *da = db + dw.base;
-    const size_t db_cs = dw.si, db_ps = dw.sp;
-    const int kbits = M.ks + 2;
-    const int chunk = (125 - 2 * kbits >= 30) ? dim : (1 << (125 - 2 * kbits));
-    u128 d0x[QW], d0y[QW], dkx[QW], dky[QW], d2x[QW], d2y[QW];
-#pragma unroll
-    for (int q = 0; q < QW; q++) d0x[q] = d0y[q] = dkx[q] = dky[q] = d2x[q] = d2y[q] = 0;
-    struct Operands {
-        ulonglong2 a0[QW], a1[QW];
-        DbRaw<PK> b0, b1;
-    };
-    auto fetch = [&](Operands &o, int i) {
-#pragma unroll
-        for (int q = 0; q < QW; q++) {
-            o.a0[q] = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs);
-            o.a1[q] = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs + ps);
-        }
-        o.b0.template load<true>(da + (size_t)i * db_cs);
-        o.b1.template load<true>(da + (size_t)i * db_cs + db_ps);
-    };
-    auto accumulate = [&](const Operands &o) {
-        const ulonglong2 b0 = o.b0.get(), b1 = o.b1.get();
-        const u64 sbx = b0.x + b1.x, sby = b0.y + b1.y;
-#pragma unroll
-        for (int q = 0; q < QW; q++) {
-            d0x[q] += (u128)o.a0[q].x * b0.x;
-            d0y[q] += (u128)o.a0[q].y * b0.y;
-            d2x[q] += (u128)o.a1[q].x * b1.x;
-            d2y[q] += (u128)o.a1[q].y * b1.y;
-            dkx[q] += (u128)(o.a0[q].x + o.a1[q].x) * sbx;
-            dky[q] += (u128)(o.a0[q].y + o.a1[q].y) * sby;
-        }
-    };
-    Operands cur, nxt;
-    fetch(cur, 0);
-    for (int i0 = 0; i0 < dim; i0 += chunk) {
-        const int i1 = i0 + chunk < dim ? i0 + chunk : dim;
-        for (int i = i0; i < i1; i += 2) {  // branch-free (see k_hydia_tensor)
-            fetch(nxt, i + 1);
-            accumulate(cur);
-            if (NWM > 1) __builtin_amdgcn_s_barrier();
-            fetch(cur, i + 2 < dim ? i + 2 : i + 1);
-            accumulate(nxt);
-            if (NWM > 1) __builtin_amdgcn_s_barrier();
-        }
-        if (i1 < dim) {
-#pragma unroll
-            for (int q = 0; q < QW; q++) {
-                d0x[q] = reduce128(d0x[q], M); d0y[q] = reduce128(d0y[q], M);
-                dkx[q] = reduce128(dkx[q], M); dky[q] = reduce128(dky[q], M);
-                d2x[q] = reduce128(d2x[q], M); d2y[q] = reduce128(d2y[q], M);
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < QW; q++) {
-        ulonglong2 r0, r1, r2;
-        r0.x = reduce128(d0x[q], M); r0.y = reduce128(d0y[q], M);
-        r2.x = reduce128(d2x[q], M); r2.y = reduce128(d2y[q], M);
-        r1.x = submod(submod(reduce128(dkx[q], M), r0.x, M.q), r2.x, M.q);
-        r1.y = submod(submod(reduce128(dky[q], M), r0.y, M.q), r2.y, M.q);
-        u64 *o = acc + (mq_slot(q0 + q, g, G, ng, nblk, Qt) * 3 * nl + j) * N + c;
-        *reinterpret_cast<ulonglong2 *>(o) = r0;
-        *reinterpret_cast<ulonglong2 *>(o + ps) = r1;
-        *reinterpret_cast<ulonglong2 *>(o + 2 * ps) = r2;
-    }
+// the three reduced sums (d0, dk, d2 of the lane's two coefficients) -> components d0, d1 = dk - d0 - d2, d2 of the accumulator
+DEV void store_karatsuba(u64 *o, size_t ps, ulonglong2 r0, ulonglong2 rk, ulonglong2 r2, u64 q) {
+    *reinterpret_cast<ulonglong2 *>(o) = r0;
+    *reinterpret_cast<ulonglong2 *>(o + ps) = make_ulonglong2(submod(submod(rk.x, r0.x, q), r2.x, q), submod(submod(rk.y, r0.y, q), r2.y, q));
+    *reinterpret_cast<ulonglong2 *>(o + 2 * ps) = r2;
 }
-// 24-bit halves (k_hydia_tensor24's arithmetic, hide24 included) on the 46-bit limbs of a group-sequential database; the database
-// operands run two diagonals ahead, the rotation lines one.  The halves of the database residues are cut once per diagonal and
-// serve all QW queries.
-template <int QW, int NWM>
-__global__ __launch_bounds__(64 * NWM) void k_hydia_tensor24_mq(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs,
-                                                                const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
-                                                                int Gq, int xcd_map, DbLayout L, int j0, int G, int ng, int nblk, int q0, int Qt) {
+// acc[slot][{d0,d1,d2}][j][c] = sum_{i<dim} rot[q][i] (x) db[g][i] for BPP database blocks x QW queries per wave (rot: the queries'
+// rotation sets, rqs elements apart, from query q0 on).  One pass reads a database operand ONCE per diagonal for its QW queries.
+//
+// Work split (HBM must see the 3 GiB of rotated queries ONCE, not once per block): a workgroup owns one 128-coefficient tile of one
+// limb and NW*BPP database blocks — each of its NW waves serves BPP blocks with one register copy of the rot operands, and the NW
+// waves read the SAME rot addresses in step (one barrier per diagonal), so the per-CU vector cache serves NW-1 of them.  The
+// database operands are streamed with non-temporal loads so they do not evict rot.  In the group-sequential layout a workgroup
+// walks one group, one contiguous run.  grid (256 tiles * Gq, limbs j0..), Gq = G/(NW*BPP) block groups per tile.
+// Registers: a wave holds BPP x QW accumulator sets; single queries take BPP = 2, batches QW = 2 (QW = 4 spilled).
+// The operands of the next diagonal(s) are fetched while the current one's products run (A::depth sets: 2 + 4 BPP loads in flight
+// instead of none during the multiply-accumulates; 27.2 -> 26.65 ms at 64 blocks for the 128-bit sums).
+template <class A, int BPP, int QW, int NW>
+__global__ __launch_bounds__(64 * NW, 2) void k_hydia_tensor(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs,
+                                                             const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                             int Gq, int xcd_map, DbLayout L, int j0, int G, int ng, int nblk, int q0, int Qt) {
+    typedef typename A::T T;
     const int j = blockIdx.y + j0;
+    // consecutive workgroup ids are dealt round-robin over the 8 XCDs: give every XCD its own tiles and let the Gq block
+    // groups of one tile follow each other ON THAT XCD, so they find the tile's rot lines in its L2
     const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
     const int gq = xcd_map ? k % Gq : blockIdx.x % Gq;
     const int tile = xcd_map ? xcd + 8 * (k / Gq) : blockIdx.x / Gq;
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const ModC M = mod[j];
     const size_t c = (size_t)tile * 128 + lane * 2;
-    const size_t ps = (size_t)nl * N, cs = 2 * ps;
-    const int g = gq * NWM + wv;
+    const size_t ps = (size_t)nl * N, cs = 2 * ps;  // rot / acc poly stride, ciphertext stride (elements)
+    const int g0 = (gq * NW + wv) * BPP;
     const u64 *ra = rot + (size_t)q0 * rqs + (size_t)j * N + c;
-    const DbWalk dw = db_walk(L, N, dim, j, tile, lane, g, gq, wv);
+    const DbWalk dw = db_walk(L, N, dim, j, tile, lane, g0, gq, wv * BPP);
     const unsigned char *da = db + dw.base;
-    const size_t db_cs = dw.si, db_ps = dw.sp;
-    Acc24 d0[QW][2], dk[QW][2], d2[QW][2];  // [query][coefficient of the lane's pair]
+    const A ar(M, dim, lane);
+    typename A::Sum s[BPP][QW][3][2];  // [block][query][d0, d2, dk][coefficient of the lane's pair]
 #pragma unroll
-    for (int q = 0; q < QW; q++)
+    for (int u = 0; u < BPP; u++)
 #pragma unroll
-        for (int e = 0; e < 2; e++) d0[q][e] = dk[q][e] = d2[q][e] = Acc24{0, 0, 0};
-    const unsigned s46 = (unsigned)(lane * 92) & 31u;
+        for (int q = 0; q < QW; q++)
+#pragma unroll
+            for (int k3 = 0; k3 < 3; k3++) s[u][q][k3][0] = s[u][q][k3][1] = typename A::Sum{};
     struct Operands {
         ulonglong2 a0[QW], a1[QW];
-        DbRaw46 b0, b1;
+        typename A::Raw b0[BPP], b1[BPP];
     };
     auto fetch = [&](Operands &o, int i) {
 #pragma unroll
@@ -1046,127 +766,133 @@ __global__ __launch_bounds__(64 * NWM) void k_hydia_tensor24_mq(const ModC *__re
             o.a0[q] = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs);
             o.a1[q] = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs + ps);
         }
-        o.b0.template load<true>(da + (size_t)i * db_cs);
-        o.b1.template load<true>(da + (size_t)i * db_cs + db_ps);
+#pragma unroll
+        for (int u = 0; u < BPP; u++) {
+            o.b0[u].template load<true>(da + u * dw.su + (size_t)i * dw.si);
+            o.b1[u].template load<true>(da + u * dw.su + (size_t)i * dw.si + dw.sp);
+        }
     };
     auto accumulate = [&](const Operands &o) {
-        unsigned bl[2][2], bh[2][2];  // database residues: halves of 24 and 22 bits, cut as in k_hydia_tensor24
-#pragma unroll
-        for (int p = 0; p < 2; p++) {
-            const auto w = p == 0 ? o.b0.w : o.b1.w;
-            const unsigned t0 = __builtin_amdgcn_alignbit(w[1], w[0], s46), t1 = __builtin_amdgcn_alignbit(w[2], w[1], s46),
-                           t2 = __builtin_amdgcn_alignbit(w[3], w[2], s46);
-            bl[p][0] = hide24(t0 & 0xFFFFFFu);
-            bh[p][0] = hide24(__builtin_amdgcn_alignbit(t1, t0, 24) & 0x3FFFFFu);
-            bl[p][1] = hide24(__builtin_amdgcn_alignbit(t2, t1, 14) & 0xFFFFFFu);
-            bh[p][1] = hide24((t2 >> 6) & 0x3FFFFFu);
-        }
-        unsigned sbl[2], sbh[2];
-#pragma unroll
-        for (int e = 0; e < 2; e++) {
-            sbl[e] = bl[0][e] + bl[1][e];
-            sbh[e] = bh[0][e] + bh[1][e];
-        }
+        // each query's operands once per diagonal, shared by the BPP blocks; each block's once (with the first query), shared by the QW
+        // queries.  (This nesting keeps the 24-bit kernels at 164 VGPRs for BPP = 2 and for QW = 2; others took up to 206)
+        T b[BPP][2][2];
 #pragma unroll
         for (int q = 0; q < QW; q++) {
-            const u64 av[2][2] = {{o.a0[q].x, o.a0[q].y}, {o.a1[q].x, o.a1[q].y}};
-            unsigned al[2][2], ah[2][2];
+            const T a[2][2] = {{A::rot(o.a0[q].x), A::rot(o.a0[q].y)}, {A::rot(o.a1[q].x), A::rot(o.a1[q].y)}};
 #pragma unroll
-            for (int p = 0; p < 2; p++)
-#pragma unroll
-                for (int e = 0; e < 2; e++) {
-                    al[p][e] = hide24((unsigned)av[p][e] & 0xFFFFFFu);
-                    ah[p][e] = __builtin_amdgcn_alignbit((unsigned)(av[p][e] >> 32), (unsigned)av[p][e], 24);
+            for (int u = 0; u < BPP; u++) {
+                if (q == 0) {
+                    ar.cut(o.b0[u], b[u][0]);
+                    ar.cut(o.b1[u], b[u][1]);
                 }
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                d0[q][e].mac(al[0][e], ah[0][e], bl[0][e], bh[0][e]);
-                d2[q][e].mac(al[1][e], ah[1][e], bl[1][e], bh[1][e]);
-                dk[q][e].mac(al[0][e] + al[1][e], ah[0][e] + ah[1][e], sbl[e], sbh[e]);
+                kara_mac<A>(s[u][q], a, b[u]);
             }
         }
     };
-    Operands A, B, C;
-    fetch(A, 0);
-    fetch(B, dim > 1 ? 1 : 0);
-    int i = 0;
-    for (; i + 2 < dim; i += 3) {  // branch-free inside: clamped re-fetches of the last diagonal are never accumulated
-        fetch(C, i + 2);
-        accumulate(A);
-        if (NWM > 1) __builtin_amdgcn_s_barrier();
-        fetch(A, i + 3 < dim ? i + 3 : dim - 1);
-        accumulate(B);
-        if (NWM > 1) __builtin_amdgcn_s_barrier();
-        fetch(B, i + 4 < dim ? i + 4 : dim - 1);
-        accumulate(C);
-        if (NWM > 1) __builtin_amdgcn_s_barrier();
-    }
-    if (i < dim) accumulate(A);
-    if (i + 1 < dim) accumulate(B);
+    if constexpr (A::depth == 3) {
+        Operands S0, S1, S2;
+        fetch(S0, 0);
+        fetch(S1, 1);
+        int i = 0;
+        for (; i + 2 < dim; i += 3) {  // branch-free inside: clamped re-fetches of the last diagonal are never accumulated
+            fetch(S2, i + 2);
+            accumulate(S0);
+            if (NW > 1) __builtin_amdgcn_s_barrier();  // keep the waves on the same diagonal (no memory wait implied)
+            fetch(S0, i + 3 < dim ? i + 3 : dim - 1);
+            accumulate(S1);
+            if (NW > 1) __builtin_amdgcn_s_barrier();
+            fetch(S1, i + 4 < dim ? i + 4 : dim - 1);
+            accumulate(S2);
+            if (NW > 1) __builtin_amdgcn_s_barrier();
+        }
+        if (i < dim) accumulate(S0);  // the one or two diagonals the groups of three leave over (workgroup-uniform)
+        if (i + 1 < dim) accumulate(S1);
+    } else {
+        Operands cur, nxt;
+        fetch(cur, 0);
+        for (int i0 = 0; i0 < dim; i0 += ar.chunk) {
+            const int i1 = i0 + ar.chunk < dim ? i0 + ar.chunk : dim;
+            // dim (>= 2, checked at context creation) and every chunk are powers of two: even.  No branch inside the loop: at a join the
+            // compiler waits for every outstanding load, the prefetched ones included
+            for (int i = i0; i < i1; i += 2) {
+                fetch(nxt, i + 1);
+                accumulate(cur);
+                if (NW > 1) __builtin_amdgcn_s_barrier();
+                fetch(cur, i + 2 < dim ? i + 2 : i + 1);  // the last one re-reads a line that is in flight: never used
+                accumulate(nxt);
+                if (NW > 1) __builtin_amdgcn_s_barrier();
+            }
+            if (i1 < dim) {
 #pragma unroll
-    for (int q = 0; q < QW; q++) {
-        ulonglong2 r0, r1, r2;
-        r0.x = reduce128(d0[q][0].wide(), M); r0.y = reduce128(d0[q][1].wide(), M);
-        r2.x = reduce128(d2[q][0].wide(), M); r2.y = reduce128(d2[q][1].wide(), M);
-        r1.x = submod(submod(reduce128(dk[q][0].wide(), M), r0.x, M.q), r2.x, M.q);
-        r1.y = submod(submod(reduce128(dk[q][1].wide(), M), r0.y, M.q), r2.y, M.q);
-        u64 *o = acc + (mq_slot(q0 + q, g, G, ng, nblk, Qt) * 3 * nl + j) * N + c;
-        *reinterpret_cast<ulonglong2 *>(o) = r0;
-        *reinterpret_cast<ulonglong2 *>(o + ps) = r1;
-        *reinterpret_cast<ulonglong2 *>(o + 2 * ps) = r2;
+                for (int u = 0; u < BPP; u++)
+#pragma unroll
+                    for (int q = 0; q < QW; q++)
+#pragma unroll
+                        for (int k3 = 0; k3 < 3; k3++) {
+                            A::fold(s[u][q][k3][0], M);
+                            A::fold(s[u][q][k3][1], M);
+                        }
+            }
+        }
     }
+#pragma unroll
+    for (int u = 0; u < BPP; u++)
+#pragma unroll
+        for (int q = 0; q < QW; q++) {
+            ulonglong2 r[3];
+#pragma unroll
+            for (int k3 = 0; k3 < 3; k3++) r[k3] = make_ulonglong2(A::reduce(s[u][q][k3][0], M), A::reduce(s[u][q][k3][1], M));
+            store_karatsuba(acc + (mq_slot(q0 + q, g0 + u, G, ng, nblk, Qt) * 3 * nl + j) * N + c, ps, r[0], r[2], r[1], M.q);
+        }
 }
-// limb 0 of a small ciphertext-major database (k_hydia_tensor_sk's split: KS waves of a workgroup share one (block, tile) and take
-// every KS-th diagonal) for QW queries; the partial sums go through LDS one query at a time.  grid (N/128 * G, 1)
+
+// Limb 0 of SMALL ciphertext-major databases (at most 8 blocks on this GPU): k_hydia_tensor's limb-0 launch has only 256 x G waves, each
+// walking all `dim` diagonals — latency-bound (0.6 ms at G = 1 for 0.5 GB).  Here KS waves of a workgroup share one (block, tile)
+// and take every KS-th diagonal for QW queries; the partial sums are reduced modulo q_0 through LDS, one query at a time.  Same
+// residues as the one-wave kernel (a sum modulo q does not depend on how it is split).  grid (N/128 * G, 1)
 template <int KS, int QW>
-__global__ __launch_bounds__(64 * KS) void k_hydia_tensor_sk_mq(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs,
-                                                                const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
-                                                                DbLayout L, int G, int ng, int nblk, int q0, int Qt) {
+__global__ __launch_bounds__(64 * KS) void k_hydia_tensor_sk(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs,
+                                                             const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                             DbLayout L, int G, int ng, int nblk, int q0, int Qt) {
+    typedef Sums128<false> A;
     __shared__ u64 part[KS][6][64];
-    const int j = 0, tiles = N / 128;
+    const int tiles = N / 128;
     const int tile = blockIdx.x % tiles, g = blockIdx.x / tiles;
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const ModC M = mod[j];
+    const ModC M = mod[0];
     const size_t c = (size_t)tile * 128 + lane * 2;
     const size_t ps = (size_t)nl * N, cs = 2 * ps;
     const u64 *ra = rot + (size_t)q0 * rqs + c;
     const unsigned char *da = db + (size_t)g * dim * L.ct_bytes + c * 8;
-    const int kbits = M.ks + 2;
-    const int chunk = (125 - 2 * kbits >= 30) ? dim : (1 << (125 - 2 * kbits));
-    u128 d0x[QW], d0y[QW], dkx[QW], dky[QW], d2x[QW], d2y[QW];
-#pragma unroll
-    for (int q = 0; q < QW; q++) d0x[q] = d0y[q] = dkx[q] = dky[q] = d2x[q] = d2y[q] = 0;
+    const A ar(M, dim, lane);
+    u128 s[QW][3][2] = {};
     int since = 0;
     for (int i = wv; i < dim; i += KS) {
-        const ulonglong2 b0 = db_load2<false, true>(da + (size_t)i * L.ct_bytes);
-        const ulonglong2 b1 = db_load2<false, true>(da + (size_t)i * L.ct_bytes + L.poly_bytes);
-        const u64 sbx = b0.x + b1.x, sby = b0.y + b1.y;
+        A::Raw r0, r1;
+        r0.load<true>(da + (size_t)i * L.ct_bytes);
+        r1.load<true>(da + (size_t)i * L.ct_bytes + L.poly_bytes);
+        u64 b[2][2];
+        ar.cut(r0, b[0]);
+        ar.cut(r1, b[1]);
 #pragma unroll
         for (int q = 0; q < QW; q++) {
             const ulonglong2 a0 = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs);
             const ulonglong2 a1 = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs + ps);
-            d0x[q] += (u128)a0.x * b0.x;
-            d0y[q] += (u128)a0.y * b0.y;
-            d2x[q] += (u128)a1.x * b1.x;
-            d2y[q] += (u128)a1.y * b1.y;
-            dkx[q] += (u128)(a0.x + a1.x) * sbx;
-            dky[q] += (u128)(a0.y + a1.y) * sby;
+            const u64 a[2][2] = {{a0.x, a0.y}, {a1.x, a1.y}};
+            kara_mac<A>(s[q], a, b);
         }
-        if (++since == chunk) {
+        if (++since == ar.chunk) {
             since = 0;
 #pragma unroll
-            for (int q = 0; q < QW; q++) {
-                d0x[q] = reduce128(d0x[q], M); d0y[q] = reduce128(d0y[q], M);
-                dkx[q] = reduce128(dkx[q], M); dky[q] = reduce128(dky[q], M);
-                d2x[q] = reduce128(d2x[q], M); d2y[q] = reduce128(d2y[q], M);
-            }
+            for (int q = 0; q < QW; q++)
+#pragma unroll
+                for (int k = 0; k < 6; k++) A::fold(s[q][k / 2][k % 2], M);
         }
     }
 #pragma unroll
     for (int q = 0; q < QW; q++) {
-        part[wv][0][lane] = reduce128(d0x[q], M); part[wv][1][lane] = reduce128(d0y[q], M);
-        part[wv][2][lane] = reduce128(dkx[q], M); part[wv][3][lane] = reduce128(dky[q], M);
-        part[wv][4][lane] = reduce128(d2x[q], M); part[wv][5][lane] = reduce128(d2y[q], M);
+#pragma unroll
+        for (int k = 0; k < 6; k++) part[wv][k][lane] = A::reduce(s[q][k / 2][k % 2], M);
         __syncthreads();
         if (wv == 0) {
             u64 r[6];
@@ -1176,15 +902,12 @@ __global__ __launch_bounds__(64 * KS) void k_hydia_tensor_sk_mq(const ModC *__re
                 for (int w = 1; w < KS; w++) t = addmod(t, part[w][k][lane], M.q);
                 r[k] = t;
             }
-            u64 *o = acc + (mq_slot(q0 + q, g, G, ng, nblk, Qt) * 3 * nl + j) * N + c;
-            *reinterpret_cast<ulonglong2 *>(o) = make_ulonglong2(r[0], r[1]);
-            *reinterpret_cast<ulonglong2 *>(o + ps) = make_ulonglong2(submod(submod(r[2], r[0], M.q), r[4], M.q), submod(submod(r[3], r[1], M.q), r[5], M.q));
-            *reinterpret_cast<ulonglong2 *>(o + 2 * ps) = make_ulonglong2(r[4], r[5]);
+            store_karatsuba(acc + mq_slot(q0 + q, g, G, ng, nblk, Qt) * 3 * nl * N + c, ps, make_ulonglong2(r[0], r[1]),
+                            make_ulonglong2(r[4], r[5]), make_ulonglong2(r[2], r[3]), M.q);
         }
         __syncthreads();
     }
 }
-
 
 // unpacked [X][2][nQ][N] u64  <->  database layout.  grid (N/512, nQ, X*2)
 template <bool PACK>
@@ -1446,53 +1169,6 @@ void rescale_combine(hipStream_t st, const ModC *mod, int N, const u64 *in, cons
     ledger_add("k_rescale_combine", 3.0 * X * l * LP_BYTES(N));
     hipLaunchKernelGGL(k_rescale_combine, dim3(N / 256, l, X), dim3(256), 0, st, mod, N, in, tmp, out, l, qlinv, in_ls);
 }
-template <int BPP, int NW>
-static void launch_tensor(hipStream_t st, const ModC *mod, int N, const u64 *rot, const void *db, u64 *acc, int G, int dim,
-                          int nl, const DbLayout &L, int ng) {
-    const int nblk = ng > 0 ? G / ng : 0;
-    const int Gq = G / (BPP * NW);
-    const int xm = (N / 128) % 8 == 0 ? 1 : 0;  // XCD-aware tile -> workgroup map
-    const unsigned char *dbb = (const unsigned char *)db;
-    const dim3 blk(64 * NW);
-    const bool h24 = L.packed && L.seq && dim <= 4096;  // the 24-bit-halves kernel: its partial sums hold 4096 diagonals
-    {   // resident database (6- or 8-byte residues) + rotated queries once + accumulators, split limb 0 / other limbs like the launches
-        const double per_lp6 = (double)N * (L.bits46 ? 5.75 : 6.0), per_lp8 = LP_BYTES(N);
-        const double rot_acc = (double)dim * 2 * per_lp8 + (double)G * 3 * per_lp8;
-        char n0[64], n1[64];
-        snprintf(n0, sizeof n0, "k_hydia_tensor<%d, %d, true, false>", BPP, NW);
-        snprintf(n1, sizeof n1, h24 ? (L.bits46 ? "k_hydia_tensor24<%d, %d, true, true>" : "k_hydia_tensor24<%d, %d, false, false>") : "k_hydia_tensor<%d, %d, true, true>", BPP, NW);  // as rocprofv3 prints the instantiation
-        if (L.packed && G <= 8) snprintf(n0, sizeof n0, "k_hydia_tensor_sk<%d, false>", G <= 2 ? 8 : 4);
-        if (L.packed) {
-            ledger_add(n0, (double)G * dim * 2 * per_lp8 + rot_acc);
-            if (nl > 1) ledger_add(n1, (nl - 1) * ((double)G * dim * 2 * per_lp6 + rot_acc));
-        } else {
-            ledger_add(n0, nl * ((double)G * dim * 2 * per_lp8 + rot_acc));
-        }
-    }
-    if (L.packed) {  // limb 0 (8-byte residues) and limbs 1.. (6-byte residues) as two launches: no shared register budget
-        if (G <= 2)  // few blocks: 256 x G one-wave workgroups cannot hide the latency of 512 dependent steps -> split the diagonals
-            // (eight waves: sixteen hold a lane to 128 registers and the kernel spilled 69 of them — round 5)
-            hipLaunchKernelGGL((k_hydia_tensor_sk<8, false>), dim3((N / 128) * G, 1), dim3(64 * 8), 0, st, mod, N, rot, dbb, acc, dim, nl, L, 0, ng, nblk);
-        else if (G <= 8)
-            hipLaunchKernelGGL((k_hydia_tensor_sk<4, false>), dim3((N / 128) * G, 1), dim3(64 * 4), 0, st, mod, N, rot, dbb, acc, dim, nl, L, 0, ng, nblk);
-        else
-            hipLaunchKernelGGL((k_hydia_tensor<BPP, NW, true, false>), dim3((N / 128) * Gq, 1), blk, 0, st, mod, N, rot, dbb, acc, dim, nl,
-                               Gq, xm, L, 0, ng, nblk);
-        if (nl > 1 && h24)
-            if (L.bits46)
-                hipLaunchKernelGGL((k_hydia_tensor24<BPP, NW, true>), dim3((N / 128) * Gq, nl - 1), blk, 0, st, mod, N, rot, dbb, acc, dim, nl, Gq, xm, L,
-                                   1, ng, nblk);
-            else
-                hipLaunchKernelGGL((k_hydia_tensor24<BPP, NW, false>), dim3((N / 128) * Gq, nl - 1), blk, 0, st, mod, N, rot, dbb, acc, dim, nl, Gq, xm, L,
-                                   1, ng, nblk);
-        else if (nl > 1)
-            hipLaunchKernelGGL((k_hydia_tensor<BPP, NW, true, true>), dim3((N / 128) * Gq, nl - 1), blk, 0, st, mod, N, rot, dbb, acc,
-                               dim, nl, Gq, xm, L, 1, ng, nblk);
-    } else {
-        hipLaunchKernelGGL((k_hydia_tensor<BPP, NW, true, false>), dim3((N / 128) * Gq, nl), blk, 0, st, mod, N, rot, dbb, acc, dim, nl,
-                           Gq, xm, L, 0, ng, nblk);
-    }
-}
 // bpp = database blocks per wave (1 or 2), nw = max waves per workgroup (1, 2 or 4; 0 = 4); both must divide G.  Round 5: four blocks
 // per wave and eight / sixteen waves per workgroup are gone — they spilled (863 registers at <4,16>, 237 at <4,8>) and were never
 // faster (profiles/r04/experiments.txt: BPP=4 140.5 ms, NW=8 inside the run-to-run spread); larger values are clamped.
@@ -1509,91 +1185,91 @@ void tensor_split(int G, int bpp, int nw, int *Bo, int *Wo) {
     *Bo = B;
     *Wo = W;
 }
-void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, const void *db, u64 *acc, int G,
-                             int dim, int nl, int bpp, int nw, const DbLayout &L, int ng) {
-    int B, W;
-    tensor_split(G, bpp, nw, &B, &W);
-    if (L.seq) {  // the layout fixes the workgroup's share: a group of the database is what one workgroup walks
-        if (L.bits46 && !(L.packed && dim <= 4096)) throw std::logic_error("hydia: 46-bit database outside the 24-bit-halves loop B");
-        if (G != L.blocks || dim != L.bd || L.seq % L.seq_bpp || G % L.seq || G <= 8)
-            throw std::logic_error("hydia: loop B launched against a group-sequential database with another shape");
-        B = L.seq_bpp;
-        W = L.seq / L.seq_bpp;
-    }
-#define HY_TENSOR_CASE(b, w) \
-    if (B == b && W == w) return launch_tensor<b, w>(st, mod, N, rot, db, acc, G, dim, nl, L, ng);
-    HY_TENSOR_CASE(2, 4) HY_TENSOR_CASE(2, 2) HY_TENSOR_CASE(2, 1)
-    HY_TENSOR_CASE(1, 4) HY_TENSOR_CASE(1, 2) HY_TENSOR_CASE(1, 1)
-#undef HY_TENSOR_CASE
-    throw std::logic_error("hydia: no loop B kernel for this split");
-}
-// ---- loop B for a batch of queries.  QW = 2: at QW = 4 every instantiation takes 256 VGPRs (one wave per SIMD) and the 512-thread
-// ones spill; at QW = 2 the kernels keep 152 / 165 VGPRs (three waves per SIMD), what the single-query kernels take
+// ---- loop B.  Batches: QW = 2.  At QW = 4 every instantiation takes 256 VGPRs (one wave per SIMD) and the 512-thread ones spill; at
+// QW = 2 the kernels keep what the single-query kernels at BPP = 2 take (three waves per SIMD)
 constexpr int MQ_QW = 2;
-template <int QW>
-static void launch_tensor_mq(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const unsigned char *db, u64 *acc, int G,
-                             int dim, int nl, const DbLayout &L, int ng, int q0, int Qt) {
-    const int nblk = ng > 0 ? G / ng : 0;
-    const int xm = (N / 128) % 8 == 0 ? 1 : 0;
-    // blocks per workgroup (one per wave): the group of a group-sequential layout, else the largest of 4, 2, 1 dividing G
-    const int nwm = L.seq ? L.seq : (G % 4 == 0 ? 4 : G % 2 == 0 ? 2 : 1);
-    const int Gq = G / nwm;
-    const bool b46 = L.packed && L.seq && L.bits46, sk0 = L.packed && !L.seq && G <= 8;
-    const double per_lp8 = LP_BYTES(N), per_lp6 = (double)N * (b46 ? 5.75 : 6.0);
-    const double rot_acc = (double)QW * ((double)dim * 2 * per_lp8 + (double)G * 3 * per_lp8);  // QW rotation sets in, QW x G accumulators out
-    char n0[64], n1[64];
-    if (sk0) snprintf(n0, sizeof n0, "k_hydia_tensor_sk_mq<%d, %d>", G <= 2 ? 8 : 4, QW);
-    else snprintf(n0, sizeof n0, "k_hydia_tensor_mq<%d, %d, false>", QW, nwm);
-    snprintf(n1, sizeof n1, b46 ? "k_hydia_tensor24_mq<%d, %d>" : "k_hydia_tensor_mq<%d, %d, true>", QW, nwm);
-#define HY_MQ(K, ...)                                                                                                   \
-    switch (nwm) {                                                                                                      \
-    case 1: hipLaunchKernelGGL((K<QW, 1, ##__VA_ARGS__>), grid, dim3(64), 0, st, mod, N, rot, rqs, db, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Qt); break; \
-    case 2: hipLaunchKernelGGL((K<QW, 2, ##__VA_ARGS__>), grid, dim3(128), 0, st, mod, N, rot, rqs, db, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Qt); break; \
-    case 4: hipLaunchKernelGGL((K<QW, 4, ##__VA_ARGS__>), grid, dim3(256), 0, st, mod, N, rot, rqs, db, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Qt); break; \
-    case 8: hipLaunchKernelGGL((K<QW, 8, ##__VA_ARGS__>), grid, dim3(512), 0, st, mod, N, rot, rqs, db, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Qt); break; \
-    default: throw std::logic_error("hydia: no multi-query loop B kernel for this group size");                        \
-    }
-    if (!L.packed) {  // 8-byte residues everywhere: one launch over all limbs
-        ledger_add(n0, nl * ((double)G * dim * 2 * per_lp8) + nl * rot_acc);
-        const dim3 grid((N / 128) * Gq, nl);
-        const int j0 = 0;
-        HY_MQ(k_hydia_tensor_mq, false)
-        return;
-    }
-    ledger_add(n0, (double)G * dim * 2 * per_lp8 + rot_acc);
-    if (nl > 1) ledger_add(n1, (nl - 1) * ((double)G * dim * 2 * per_lp6 + rot_acc));
-    if (sk0) {
-        if (G <= 2)
-            hipLaunchKernelGGL((k_hydia_tensor_sk_mq<8, QW>), dim3((N / 128) * G, 1), dim3(64 * 8), 0, st, mod, N, rot, rqs, db, acc, dim, nl, L, G, ng, nblk, q0, Qt);
-        else
-            hipLaunchKernelGGL((k_hydia_tensor_sk_mq<4, QW>), dim3((N / 128) * G, 1), dim3(64 * 4), 0, st, mod, N, rot, rqs, db, acc, dim, nl, L, G, ng, nblk, q0, Qt);
-    } else {
-        const dim3 grid((N / 128) * Gq, 1);
-        const int j0 = 0;
-        HY_MQ(k_hydia_tensor_mq, false)
-    }
-    if (nl > 1) {
-        const dim3 grid((N / 128) * Gq, nl - 1);
-        const int j0 = 1;
-        if (b46) {
-            HY_MQ(k_hydia_tensor24_mq)
-        } else {
-            HY_MQ(k_hydia_tensor_mq, true)
+int hydia_tensor_mq_width(const DbLayout &) { return MQ_QW; }
+// a loop-B launch's ledger entry, under the instantiation's name as rocprofv3 prints it (namespaces dropped); policy = nullptr: the
+// split-diagonal kernel <x = KS, qw>, else the streaming kernel <policy, x = BPP, qw, nw>
+static void ledger_tensor(double bytes, const char *policy, int x, int qw, int nw) {
+    char n[96];
+    if (policy) snprintf(n, sizeof n, "k_hydia_tensor<%s, %d, %d, %d>", policy, x, qw, nw);
+    else snprintf(n, sizeof n, "k_hydia_tensor_sk<%d, %d>", x, qw);
+    ledger_add(n, bytes);
+}
+template <class A, int BPP, int QW, class... Args>
+static void launch_stream(hipStream_t st, int nw, dim3 grid, Args... args) {
+    switch (nw) {
+    case 1: hipLaunchKernelGGL((k_hydia_tensor<A, BPP, QW, 1>), grid, dim3(64), 0, st, args...); return;
+    case 2: hipLaunchKernelGGL((k_hydia_tensor<A, BPP, QW, 2>), grid, dim3(128), 0, st, args...); return;
+    case 4: hipLaunchKernelGGL((k_hydia_tensor<A, BPP, QW, 4>), grid, dim3(256), 0, st, args...); return;
+    case 8:  // a batch over a group-sequential layout of eight-block groups
+        if constexpr (BPP == 1) {
+            hipLaunchKernelGGL((k_hydia_tensor<A, BPP, QW, 8>), grid, dim3(512), 0, st, args...);
+            return;
         }
     }
-#undef HY_MQ
+    throw std::logic_error("hydia: no loop B kernel for this split");
 }
-int hydia_tensor_mq_width(const DbLayout &) { return MQ_QW; }
-void hydia_tensor_accumulate_multi(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q,
-                                   int G, int dim, int nl, const DbLayout &L, int ng) {
-    if (Q < 1 || G < 1 || dim < 2 || (ng > 0 && G % ng)) throw std::logic_error("hydia: multi-query loop B with a bad shape");
-    if (L.seq && (G != L.blocks || dim != L.bd || G % L.seq || G <= 8 || (L.seq & (L.seq - 1)) || L.seq > 8))
-        throw std::logic_error("hydia: loop B launched against a group-sequential database with another shape");
+template <class... Args>
+static void launch_sk(hipStream_t st, int ks, int qw, dim3 grid, Args... args) {
+    if (ks == 8 && qw == 2) hipLaunchKernelGGL((k_hydia_tensor_sk<8, 2>), grid, dim3(512), 0, st, args...);
+    else if (ks == 8) hipLaunchKernelGGL((k_hydia_tensor_sk<8, 1>), grid, dim3(512), 0, st, args...);
+    else if (qw == 2) hipLaunchKernelGGL((k_hydia_tensor_sk<4, 2>), grid, dim3(256), 0, st, args...);
+    else hipLaunchKernelGGL((k_hydia_tensor_sk<4, 1>), grid, dim3(256), 0, st, args...);
+}
+void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G,
+                             int dim, int nl, const DbLayout &L, int ng, int bpp, int nw) {
+    const bool batch = bpp == TENSOR_BATCH;
+    if (Q < 1 || (!batch && Q != 1) || G < 1 || dim < 2 || (ng > 0 && G % ng)) throw std::logic_error("hydia: loop B with a bad shape");
     if (L.bits46 && !(L.packed && L.seq && dim <= 4096)) throw std::logic_error("hydia: 46-bit database outside the 24-bit-halves loop B");
+    if (L.seq && (G != L.blocks || dim != L.bd || G % L.seq || G <= 8 || L.seq % L.seq_bpp || (L.seq & (L.seq - 1)) || L.seq > 8))
+        throw std::logic_error("hydia: loop B launched against a group-sequential database with another shape");
+    // B blocks per wave, W waves per workgroup.  The group-sequential layout fixes the workgroup's share: a group of the database is
+    // what one workgroup walks.  A batch takes one block per wave (its QW accumulator sets take the registers of BPP blocks)
+    int B = 1, W;
+    if (batch) {
+        W = L.seq ? L.seq : G % 4 == 0 ? 4 : G % 2 == 0 ? 2 : 1;
+    } else if (L.seq) {
+        B = L.seq_bpp;
+        W = L.seq / L.seq_bpp;
+    } else {
+        tensor_split(G, bpp, nw, &B, &W);
+    }
+    const int Gq = G / (B * W), nblk = ng > 0 ? G / ng : 0;
+    const int xm = (N / 128) % 8 == 0 ? 1 : 0;  // XCD-aware tile -> workgroup map
     const unsigned char *dbb = (const unsigned char *)db;
+    // ledger bytes: resident database (6- or 8-byte residues, 5.75 for 46-bit) + the QW rotation sets once + QW x G accumulators
+    const double per_lp8 = LP_BYTES(N), per_lp6 = (double)N * (L.bits46 ? 5.75 : 6.0);
     for (int q0 = 0; q0 < Q; q0 += MQ_QW) {  // one pass over the database per QW queries (an odd last one alone)
-        if (Q - q0 >= MQ_QW) launch_tensor_mq<MQ_QW>(st, mod, N, rot, rqs, dbb, acc, G, dim, nl, L, ng, q0, Q);
-        else launch_tensor_mq<1>(st, mod, N, rot, rqs, dbb, acc, G, dim, nl, L, ng, q0, Q);
+        const int QW = Q - q0 >= MQ_QW ? MQ_QW : 1;
+        const double rot_acc = QW * ((double)dim * 2 * per_lp8 + (double)G * 3 * per_lp8);
+        auto bytes = [&](int limbs, double per_lp) { return limbs * ((double)G * dim * 2 * per_lp + rot_acc); };
+        auto stream = [&](auto *policy, int j0, int limbs) {  // policy: a null pointer of the arithmetic's type
+            typedef typename std::remove_pointer<decltype(policy)>::type A;
+            const dim3 grid((N / 128) * Gq, limbs);
+            ledger_tensor(bytes(limbs, j0 ? per_lp6 : per_lp8), A::name, B, QW, W);
+            if (B == 2) launch_stream<A, 2, 1>(st, W, grid, mod, N, rot, rqs, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Q);
+            else if (QW == 2) launch_stream<A, 1, 2>(st, W, grid, mod, N, rot, rqs, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Q);
+            else launch_stream<A, 1, 1>(st, W, grid, mod, N, rot, rqs, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Q);
+        };
+        if (!L.packed) {  // 8-byte residues everywhere: one launch over all limbs
+            stream((Sums128<false> *)nullptr, 0, nl);
+            continue;
+        }
+        // limb 0 (8-byte residues) and limbs 1.. (6-byte or 46-bit residues) as two launches: no shared register budget
+        if (!L.seq && G <= 8) {  // few blocks: 256 x G one-wave workgroups cannot hide the latency of dim dependent steps -> split the
+            // diagonals (eight waves: sixteen hold a lane to 128 registers and the kernel spilled 69 of them — round 5)
+            const int ks = G <= 2 ? 8 : 4;
+            ledger_tensor(bytes(1, per_lp8), nullptr, ks, QW, 0);
+            launch_sk(st, ks, QW, dim3((N / 128) * G, 1), mod, N, rot, rqs, dbb, acc, dim, nl, L, G, ng, nblk, q0, Q);
+        } else {
+            stream((Sums128<false> *)nullptr, 0, 1);
+        }
+        if (nl == 1) continue;
+        if (L.bits46) stream((Halves24<true> *)nullptr, 1, nl - 1);
+        else if (!batch && L.seq && dim <= 4096) stream((Halves24<false> *)nullptr, 1, nl - 1);  // (a batch keeps the 128-bit sums here)
+        else stream((Sums128<true> *)nullptr, 1, nl - 1);
     }
 }
 DbLayout db_layout(int N, int nQ, int packed) {
@@ -1647,7 +1323,6 @@ void mul_plain(hipStream_t st, const ModC *mod, int N, const u64 *a, int a_ls, c
     ledger_add("k_mul_plain", (2.0 * XP + 2.0) * nl * LP_BYTES(N));
     hipLaunchKernelGGL(k_mul_plain, dim3(N / 512, nl, XP), dim3(256), 0, st, mod, N, a, a_ls, m, ms, o, nl);
 }
-const char *hydia_tensor_kernel_name() { return "k_hydia_tensor"; }
 void fill_uniform_hash(hipStream_t st, const ModC *mod, int N, u64 *dst, size_t n_limbpolys, int nl,
                        unsigned long long seed) {
     // slabs of at most 32768 limb-polys (grid.y limit), each starting on a limb-0 boundary

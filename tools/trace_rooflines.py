@@ -25,7 +25,7 @@ for r in rows:
     us = float(r["us"])
     if k.startswith("k_hydia_tensor"):
         # grid.x = 256 tiles * G/(BPP*NW) block groups, grid.y limbs; bytes from the resident layout: DB + rot + acc
-        packed = "true, true" in k
+        packed = "Halves24" in k or "Sums128<true>" in k
         G = g[0] // 256 * 8
         limbs = g[1]
         db = G * 512 * 2 * limbs * 32768 * (6 if packed else 8)

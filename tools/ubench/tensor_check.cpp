@@ -26,7 +26,7 @@ int main(int argc, char **argv) {
     hk::fill_uniform_hash(cx.stream, cx.d_mod, N, rot, (size_t)2 * nl * dim, nl, 11);
     hk::fill_uniform_hash(cx.stream, cx.d_mod, N, plain, (size_t)2 * nl * dim * G, nl, 12);
     hk::db_pack(cx.stream, N, nl, plain, db, 0, dim * G, L);
-    hk::hydia_tensor_accumulate(cx.stream, cx.d_mod, N, rot, db, acc, G, dim, nl, 2, 4, L, 0);
+    hk::hydia_tensor_accumulate(cx.stream, cx.d_mod, N, rot, 0, db, acc, 1, G, dim, nl, L, 0, 2, 4);
     hipStreamSynchronize(cx.stream);
     std::vector<u64> hr(ct * dim), hp(ct * dim * G), ha((size_t)G * 3 * nl * N);
     hipMemcpy(hr.data(), rot, hr.size() * 8, hipMemcpyDeviceToHost);
