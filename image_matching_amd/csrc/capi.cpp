@@ -467,7 +467,7 @@ int hydia_db_import_ct(hydia_ctx *ctx, size_t t, const uint64_t *data) {
     u64 *tmp = cx.pool.get(e * sizeof(u64));
     cx.sync();
     HIP_CHECK(hipMemcpy(tmp, data, e * sizeof(u64), hipMemcpyHostToDevice));
-    cx.db_store(t, tmp, 1);
+    cx.db_store(t, tmp, 1);  // (a row-packed database, kind 1, is addressed the same way: its layout is the unpacked ciphertext-major one)
     cx.sync();
     cx.pool.put(tmp);
     if (cx.db_kind == 0) {
@@ -588,6 +588,41 @@ int hydia_hers_encrypt_query(hydia_ctx *ctx, const double *query, const uint8_t 
     *out = wrap(ctx, client_hers_encrypt_query(ctx->cx, query, seed, nonce0));
     return HYDIA_OK;
     API_END
+}
+// ------------------------------------------------------------------ approach 1 (the literature baseline)
+size_t hydia_base_db_num_cts(const hydia_ctx *ctx, size_t n) {
+    if (!ctx) return 0;
+    const int dim = ctx->cx.prm.dim;
+    if (dim < 1 || dim > ctx->cx.slots || (dim & (dim - 1))) return 0;
+    return ctx->cx.base_db_cts(n);
+}
+int hydia_base_db_enroll(hydia_ctx *ctx, double *db, size_t n, const uint8_t seed[32]) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && db && seed && n >= 1, "bad argument");
+    Context &cx = ctx->cx;
+    const int dim = cx.prm.dim;
+    REQUIRE(dim >= 1 && dim <= cx.slots && (dim & (dim - 1)) == 0, "row packing needs vector_dim to be a power of two of at most `slots`");
+    cx.db_kind = 0;
+    cx.db_resize_rows(n, cx.base_db_cts(n));
+    client_base_enroll(cx, db, n, seed);
+    cx.db_kind = 1;
+    cx.db_babies = 0;
+    return HYDIA_OK;
+    API_END
+}
+int hydia_base_rotations(uint32_t slots, int32_t *rots, size_t cap, size_t *n_out) {
+    REQUIRE(n_out && slots >= 2 && (slots & (slots - 1)) == 0 && slots <= (1u << 30), "slots must be a power of two");
+    std::vector<int32_t> v;
+    for (uint32_t k = 1; k < slots; k <<= 1) {
+        v.push_back((int32_t)k);
+        v.push_back((int32_t)(slots - k));
+    }
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    for (size_t i = 0; i < v.size() && i < cap && rots; i++) rots[i] = v[i];
+    *n_out = v.size();
+    return HYDIA_OK;
 }
 int hydia_db_save(hydia_ctx *ctx, const char *path) {
     API_BEGIN
@@ -715,6 +750,13 @@ int hydia_ct_mod_reduce(hydia_ctx *ctx, hydia_ct *ct) {
 int hydia_hers_compute_similarity(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.hers_similarity(query->c)) }
 int hydia_hers_index_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.hers_index_scenario(query->c)) }
 int hydia_hers_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.hers_membership_scenario(query->c)) }
+int hydia_base_compute_similarity(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.base_similarity(query->c)) }
+int hydia_base_index_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.base_index_scenario(query->c)) }
+int hydia_base_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.base_membership_scenario(query->c)) }
+int hydia_merge_ciphers(hydia_ctx *ctx, const hydia_ct *query, size_t dimension, hydia_ct **out) {
+    if (dimension > (size_t)INT32_MAX) return fail(HYDIA_ERR_ARG, "hydia: the merge dimension must be a power of two in 2 .. slots");
+    SENDER_CALL(ctx->cx.merge_ciphers(query->c, (int)dimension))
+}
 
 // ------------------------------------------------------------------ primitives
 int hydia_ntt(hydia_ctx *ctx, uint64_t *data, uint32_t count, uint32_t m, int inverse) {
@@ -844,6 +886,7 @@ int hydia_kernel_time(hydia_ctx *ctx, const char *name, double *total_ms, uint64
     API_BEGIN
     use_device(ctx);
     REQUIRE(ctx && name, "null argument");
+    ctx->cx.base_phase_collect();
     ctx->cx.timer_collect();
     auto it = ctx->cx.timers.find(name);
     if (total_ms) *total_ms = it == ctx->cx.timers.end() ? 0.0 : it->second.total_ms;
@@ -855,6 +898,7 @@ int hydia_kernel_time_reset(hydia_ctx *ctx) {
     API_BEGIN
     use_device(ctx);
     REQUIRE(ctx, "null ctx");
+    ctx->cx.base_phase_collect();
     ctx->cx.timer_collect();
     ctx->cx.timers.clear();
     return HYDIA_OK;

@@ -8,7 +8,8 @@
 //
 //   HYDIA_DEVICES=0,1,2,3   shard the encrypted database over these GPUs (an index may repeat: several shards on one GPU)
 //   HYDIA_SEED=<integer>    reproducible key / encryption randomness (default: operating-system entropy)
-// Approaches 5 (HyDia) and 4 (HERS) exist on this stack; 1-3 are refused.
+// Approaches 5 (HyDia), 4 (HERS) and 1 (the literature baseline, on the N = 2^16 ring of hydia_params_for_approach) exist on this
+// stack; 2 and 3 are refused.
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -50,6 +51,11 @@ struct Approach {
     std::function<Roles(CryptoContext, size_t, const uint8_t *)> make_roles;
 };
 const Approach APPROACHES[] = {
+    {1, "Experimental approach: Literature baseline", "Baseline",  // src/main.cpp:85-88
+     [](CryptoContext cc, Dataset &d, const uint8_t *s) { hydia::BaseEnroller(cc, d.n, s).serializeDB(d.rows); },
+     [](CryptoContext cc, size_t n, const uint8_t *s) {
+         return Roles{std::make_unique<hydia::BaseReceiver>(cc, n, s), std::make_unique<hydia::BaseSender>(cc, n)};
+     }},
     {4, "Experimental approach: HERS paper", "HERS",
      [](CryptoContext cc, Dataset &d, const uint8_t *s) { hydia::HersEnroller(cc, d.n, s).serializeDB(d.rows); },
      [](CryptoContext cc, size_t n, const uint8_t *s) {
@@ -118,7 +124,7 @@ int main(int argc, char *argv[]) {
     for (const Approach &a : APPROACHES)
         if (a.id == wanted) approach = &a;
     if (!approach)
-        return usage_error("only approach 5 (novel diagonal transform, HyDia) and approach 4 (HERS) are built in hydia-mi355x");
+        return usage_error("only approach 5 (novel diagonal transform, HyDia), approach 4 (HERS) and approach 1 (literature baseline) are built in hydia-mi355x");
     std::ofstream csv("latency.csv" /* EXP_FILEPATH, include/config.h:36 */, std::ios::app);
     if (!csv.is_open()) return usage_error("experiment file not found");
 
@@ -128,12 +134,14 @@ int main(int argc, char *argv[]) {
 
     const Seeds seeds;
     const std::vector<int> devices = devices_from_env();
-    CryptoContext cc = devices.empty() ? hydia::GenCryptoContext(depth, 45, hydia::VECTOR_DIM)
+    if (!devices.empty() && approach->id != 5) return usage_error("HYDIA_DEVICES shards approach 5 only");
+    hydia_params prm;
+    if (hydia_params_for_approach(approach->id, &prm) != 0) return usage_error(hydia_last_error());  // depth and ring: 2^16 for approach 1
+    CryptoContext cc = devices.empty() ? hydia::GenCryptoContext(depth, prm.scale_bits, hydia::VECTOR_DIM, prm.log_n)
                                        : hydia::GenShardedCryptoContext(devices, depth, 45, hydia::VECTOR_DIM);
     if (!cc->h) return 2;
-    if (!devices.empty() && approach->id != 5) return usage_error("HYDIA_DEVICES shards approach 5 only");
     std::cout << "Generating key pair, mult keys, sum keys and rotation keys on the GPU... " << std::endl;
-    if (!cc->KeyGen(seeds.get(seeds.keygen))) return 2;
+    if (!(approach->id == 1 ? cc->KeyGenBaseline(seeds.get(seeds.keygen)) : cc->KeyGen(seeds.get(seeds.keygen)))) return 2;
     std::cout << "CKKS scheme set up (depth = " << depth << ", batch size = " << cc->GetBatchSize() << ")" << std::endl;
     csv << data.n << "," << std::flush;
 

@@ -296,6 +296,32 @@ void client_hers_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32
     cx.pool.put((u64 *)d_slots);
     cx.pool.put((u64 *)d_rows);
 }
+#define HY_BASE_NONCE_BASE (3ull << 36)
+// BaseEnroller::serializeDB (/root/reference/src/enroller/enroller_base.cpp:13-56): normalise in place, then database ciphertext t =
+// vectors t vpc .. t vpc + vpc - 1 back to back, encrypted with nonce HY_BASE_NONCE_BASE + t straight into the resident kind-1 layout
+void client_base_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32]) {
+    const int dim = cx.prm.dim, Nh = cx.slots;
+    for (size_t v = 0; v < n; v++) normalize(db + v * dim, dim);
+    const ChaChaKey key = make_key(seed);
+    const size_t cts = cx.db_cts, ct_elems = (size_t)2 * cx.nQ * cx.N, elems = n * (size_t)dim;
+    if (cts > HY_NONCE_LIMIT - HY_BASE_NONCE_BASE) throw std::runtime_error("hydia: the database exceeds the 2^40 nonce space of the encryption sampler");
+    const size_t B = std::min<size_t>(cts, 16);  // ciphertexts encoded and encrypted per pass
+    double *d_rows = (double *)cx.pool.get(sizeof(double) * B * Nh);
+    double *d_slots = (double *)cx.pool.get(sizeof(double) * B * Nh);
+    u64 *d_cts = cx.pool.get(sizeof(u64) * B * ct_elems);
+    for (size_t t0 = 0; t0 < cts; t0 += B) {
+        const size_t X = std::min(B, cts - t0), first = t0 * (size_t)Nh;
+        const size_t have = elems > first ? std::min(X * (size_t)Nh, elems - first) : 0;
+        if (have) HIP_CHECK(hipMemcpyAsync(d_rows, db + first, sizeof(double) * have, hipMemcpyHostToDevice, cx.stream));
+        hc::row_pack(cx.stream, d_rows, (long long)have, Nh, d_slots, (int)X);
+        encrypt_device(cx, d_slots, (int)X, key, HY_BASE_NONCE_BASE + t0, d_cts);
+        cx.db_store(t0, d_cts, (int)X);
+    }
+    cx.sync();
+    cx.pool.put(d_cts);
+    cx.pool.put((u64 *)d_slots);
+    cx.pool.put((u64 *)d_rows);
+}
 // HersReceiver::encryptQuery (/root/reference/src/receiver/receiver_hers.cpp:13-24): vector_dim ciphertexts
 Ct client_hers_encrypt_query(Context &cx, const double *query, const uint8_t seed[32], uint64_t nonce0) {
     const int dim = cx.prm.dim, Nh = cx.slots;

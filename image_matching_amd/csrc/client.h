@@ -22,4 +22,6 @@ void client_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32], si
 // HERS (approach 4): column-packed enrolment and the vector_dim broadcast query ciphertexts
 void client_hers_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32]);
 Ct client_hers_encrypt_query(Context &cx, const double *query, const uint8_t seed[32], uint64_t nonce0);
+// BaseEnroller (approach 1, the literature baseline): row-packed enrolment into database kind 1; ciphertext t takes nonce base + t
+void client_base_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32]);
 }  // namespace hydia

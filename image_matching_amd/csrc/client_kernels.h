@@ -38,5 +38,7 @@ void decode(hipStream_t st, const ModC *mod, const u64 *t, int nu, int N, int X,
 void diag_pack(hipStream_t st, const double *dbg, long long rows_left, int dim, int Nh, double *slots, int babies = 0);
 // HERS (approach 4): slots[j][k] = dbg[k][j] (column packing); query coordinate i broadcast to every slot of vector i
 void hers_pack(hipStream_t st, const double *dbg, long long rows_left, int dim, int Nh, double *slots);
+// BaseEnroller (approach 1): slot vector x = rows x vpc .. x vpc + vpc - 1 back to back (vpc = Nh / dim), zeros past the last row
+void row_pack(hipStream_t st, const double *dbg, long long elems_left, int Nh, double *slots, int X);
 void broadcast_rows(hipStream_t st, const double *vals, int dim, int Nh, double *slots);
 }  // namespace hc

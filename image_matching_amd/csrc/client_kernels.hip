@@ -273,6 +273,14 @@ __global__ __launch_bounds__(256) void k_hers_pack(const double *__restrict__ db
     const int k = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
     slots[(size_t)j * Nh + k] = k < rows_left ? dbg[(size_t)k * dim + j] : 0.0;
 }
+// BaseEnroller::serializeDB's packing (/root/reference/src/enroller/enroller_base.cpp:28-44): database ciphertext x holds vectors
+// x vpc .. x vpc + vpc - 1 back to back, i.e. slot s of vector x is element x Nh + s of the row-major normalised rows; zeros past the
+// last row.  grid (Nh/256, X)
+__global__ __launch_bounds__(256) void k_row_pack(const double *__restrict__ dbg, long long elems_left, int Nh, double *__restrict__ slots) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    const long long e = (long long)blockIdx.y * Nh + s;
+    slots[e] = e < elems_left ? dbg[e] : 0.0;
+}
 // HersReceiver::encryptQueryThread (/root/reference/src/receiver/receiver_hers.cpp:58-63): every slot = coordinate i
 __global__ __launch_bounds__(256) void k_broadcast_rows(const double *__restrict__ vals, int Nh, double *__restrict__ slots) {
     slots[(size_t)blockIdx.y * Nh + blockIdx.x * 256 + threadIdx.x] = vals[blockIdx.y];
@@ -341,6 +349,9 @@ void decode(hipStream_t st, const ModC *mod, const u64 *t, int nu, int N, int X,
 }
 void hers_pack(hipStream_t st, const double *dbg, long long rows_left, int dim, int Nh, double *slots) {
     hipLaunchKernelGGL(k_hers_pack, dim3(Nh / 256, dim), dim3(256), 0, st, dbg, rows_left, dim, Nh, slots);
+}
+void row_pack(hipStream_t st, const double *dbg, long long elems_left, int Nh, double *slots, int X) {
+    hipLaunchKernelGGL(k_row_pack, dim3(Nh / 256, X), dim3(256), 0, st, dbg, elems_left, Nh, slots);
 }
 void broadcast_rows(hipStream_t st, const double *vals, int dim, int Nh, double *slots) {
     hipLaunchKernelGGL(k_broadcast_rows, dim3(Nh / 256, dim), dim3(256), 0, st, vals, Nh, slots);

@@ -285,6 +285,9 @@ Context::Context(const Params &p, int dev) : HostParams(p), device(dev) {
     if (getenv("HYDIA_NO_CSUB_FUSE")) prod_fuse_csub = false;
     if (getenv("HYDIA_NO_KS_FUSE")) ks_fuse = false;
     if (getenv("HYDIA_NO_RESCALE_CF")) rescale_cf = false;
+    if (getenv("HYDIA_BASE_NO_ROTADD")) base_rotadd = false;
+    if (getenv("HYDIA_BASE_NO_BCAST")) base_bcast = false;
+    if (const char *e = getenv("HYDIA_BASE_CHUNK")) base_chunk_env = std::max(0, atoi(e));
     for (int k = 1; k < nlanes; k++) {
         hipStream_t st;
         HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -417,6 +420,12 @@ Context::~Context() {
         if (kv.second.d_tabs) (void)hipFree(kv.second.d_tabs);
     for (auto &kv : cf_plans)
         if (kv.second.dev) (void)hipFree(kv.second.dev);
+    for (auto &kv : merge_masks)
+        if (kv.second) (void)hipFree(kv.second);
+    for (auto &e : base_phase_pending) {
+        (void)hipEventDestroy(e.a);
+        (void)hipEventDestroy(e.b);
+    }
     rot_keys[0] = relin_key;
     for (auto &kv : rot_keys)
         if (!kv.second.borrowed)
@@ -568,6 +577,17 @@ void Context::db_resize(size_t n_vectors, size_t cts, int form) {
     // database, whose blocks are the (database block, giant step) pairs)
     db_lay = want;
 }
+// kind 1 (approach 1's rows): plain 8-byte residues, ciphertext-major, whatever the context packs — the query-broadcast product
+// reads the ciphertexts where they lie
+void Context::db_resize_rows(size_t n_vectors, size_t cts) {
+    const bool keep = db_packed;
+    db_packed = false;
+    struct Restore {
+        bool &b, v;
+        ~Restore() { b = v; }
+    } restore{db_packed, keep};
+    db_resize(n_vectors, cts, -1);
+}
 // An imported database whose form is declared after the fact (hydia_db_set_babies): same ciphertexts, the order loop B wants for
 // that form.  Needs room for a second copy while it runs — the databases the split is meant for (a few dozen blocks) have it; when
 // the second buffer does not fit (a 148 GiB database on a 288 GB GPU) the call fails with a DeviceError BEFORE anything is touched:
@@ -650,6 +670,7 @@ struct DbConv {
 }  // namespace
 void Context::db_save(const char *path) {
     if (!d_db || db_cts == 0) throw StateError("hydia: no database resident");
+    if (db_kind == 1) throw StateError("hydia: a row-packed database (approach 1) is not saved: the file format describes the context's packing, not kind 1's plain residues");
     sync_all();
     FileCloser fc{fopen(path, "wb")};
     if (!fc.f) throw std::runtime_error(std::string("hydia: cannot open ") + path + " for writing");

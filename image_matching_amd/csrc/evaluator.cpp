@@ -23,7 +23,7 @@ static u64 shoup_h(u64 w, u64 q) { return (u64)(((u128)w << 64) / q); }
 // evaluation key once per launch, operands of coefficient-wise work once — recorded in the byte ledger under "op:<name>" next to
 // the per-kernel entries (which count what the launches really move: a two-pass transform twice that).  bench.py's roofline.step
 // sums them over one indexScenario.  Costs nothing while the ledger is off.
-static void op_bytes(const char *op, size_t N, double transforms, double other_bytes) {
+void op_bytes(const char *op, size_t N, double transforms, double other_bytes) {
     hk::ledger_add(op, transforms * 2.0 * (double)N * 8.0 + other_bytes);
 }
 
@@ -297,8 +297,10 @@ void Context::modup_digits(const u64 *c, size_t c_outer, int X, int nl, u64 *dig
 // automorphism (EvalFastRotation's tail).  out: [X][2][nl][N].
 void Context::ks_apply(const u64 *dig, size_t dig_x_stride, int X, int nl, const u64 *const *d_keys, int same_key,
                        const u64 *addend, size_t add_x_stride, size_t add_poly_stride, int add_polys,
-                       const unsigned *d_galois, const unsigned *d_ginv, int same_galois, bool dbl, u64 *out, int keys_packed_nQ) {
+                       const unsigned *d_galois, const unsigned *d_ginv, int same_galois, bool dbl, u64 *out, int keys_packed_nQ, const u64 *self,
+                       size_t self_x_stride, size_t self_poly_stride) {
     const int nE = nl + nP, nd = (nl + alpha - 1) / alpha;
+    if (self && prm.logN == 15) throw std::logic_error("hydia: the rotate-and-accumulate store exists in the generic pipeline only");
     const LimbSel esel = sel_ext(nl);
     const LimbSel qsel = sel_q(nl);
     const LimbSel psel = sel_range(nQ, nT);
@@ -439,7 +441,7 @@ void Context::ks_apply(const u64 *dig, size_t dig_x_stride, int X, int nl, const
         hk::base_convert(stream, d_mod, N, y, (size_t)nP * N, conv, (size_t)nl * N, X * 2, tab, qsel);
         ntt_fwd(conv, (size_t)nl * N, X * 2, qsel);
         hk::moddown_combine(stream, d_mod, prm.logN, acc, nE, conv, addend, add_x_stride, add_poly_stride, add_polys, out, X, nl,
-                            scale_of(qsel, pinv, false), d_galois, same_galois);
+                            scale_of(qsel, pinv, false), d_galois, same_galois, self, self_x_stride, self_poly_stride);
         if (dbl) hk::add(stream, d_mod, N, out, out, out, X * 2, qsel, nl, nl, nl);
     }
     pool.put(conv);
@@ -953,6 +955,28 @@ Ct Context::rotate(const Ct &a, int rot) {
     Ct out(this, X, 2, nl, a.scale);
     ks_apply(dig, (size_t)nd * nE * N, X, nl, it->second.d_cell, 1, a.d, a.ct_elems(), a.poly_elems(), 1, it->second.d_gal,
              it->second.d_gal + 1, 1, false, out.d);
+    pool.put(dig);
+    return out;
+}
+// self + Rot_rot(t) on every ciphertext of the batch: EvalAdd(self, EvalRotate(t, rot)).  Generic rings: the sum leaves in the key
+// switch's last kernel (k_moddown_combine reads self at the output index), one read of self instead of a read-modify-write pass over
+// the rotated batch.  The 2^15 pipeline, and HYDIA_BASE_NO_ROTADD, rotate and then add: the same residues (modular addition is exact)
+Ct Context::rotate_acc(const Ct &t, int rot, const Ct &self) {
+    check_same(t, self, "rotate-and-accumulate");
+    if (!base_rotadd || prm.logN == 15 || t.npoly != 2) {
+        Ct r = rotate(t, rot);
+        add_inplace(r, self);
+        return r;
+    }
+    auto it = rot_keys.find(rot);
+    if (it == rot_keys.end()) throw StateError("hydia: rotation key " + std::to_string(rot) + " not loaded");
+    const int nl = t.nl, nE = nl + nP, nd = (nl + alpha - 1) / alpha, X = t.X;
+    op_bytes("op:rotate_acc", N, (double)X * (nd * nE + 2 * nP + 2 * nl), (double)nd * 2 * nE * N * 8 + 6.0 * X * nl * N * 8);
+    u64 *dig = pool.get((size_t)X * nd * nE * N * sizeof(u64));
+    modup_digits(t.d + t.poly_elems(), t.ct_elems(), X, nl, dig);
+    Ct out(this, X, 2, nl, t.scale);
+    ks_apply(dig, (size_t)nd * nE * N, X, nl, it->second.d_cell, 1, t.d, t.ct_elems(), t.poly_elems(), 1, it->second.d_gal, it->second.d_gal + 1, 1,
+             false, out.d, 0, self.d, self.ct_elems(), self.poly_elems());
     pool.put(dig);
     return out;
 }
@@ -1518,6 +1542,10 @@ Ct Context::add_many(const Ct &s) {
 // EvalSum(ct, batchSize) (sender_diag.cpp:47): log2(slots) rotate-and-add steps, on every ciphertext of the batch
 void Context::eval_sum_inplace(Ct &m) {
     for (int r = 1; r < slots; r <<= 1) {
+        if (prm.logN != 15) {  // generic rings: the sum leaves in the key switch's last kernel (the same residues)
+            m = rotate_acc(m, r, m);
+            continue;
+        }
         Ct t = rotate(m, r);
         add_inplace(m, t);
     }

@@ -160,7 +160,7 @@ struct Context : HostParams {
     // 48-bit residues when every scaling prime is below 2^48; HYDIA_DB_UNPACKED keeps plain [2][nQ][N] u64)
     unsigned char *d_db = nullptr;
     size_t db_vectors = 0, db_cts = 0;
-    int db_kind = 0;   // 0 none, 5 diagonal packing (HyDia, approach 5), 6 the same with pre-rotated diagonals (BSGS mat-vec), 4 column packing (HERS)
+    int db_kind = 0;   // 0 none, 1 row packing (approach 1, the literature baseline: plain 8-byte residues, ciphertext-major), 5 diagonal packing (HyDia, approach 5), 6 the same with pre-rotated diagonals (BSGS mat-vec), 4 column packing (HERS)
     int db_babies = 0; // kind 5 / 6: hoisted (baby) rotations the resident database was enrolled for; == vector_dim for kind 5
     // Which form of the diagonal mat-vec a database enrolled on this context gets (HYDIA_MATVEC=auto|hoisted|bsgs|<B>, hydia_set_matvec).
     // With i = b + B g: B - 1 hoisted rotations of the query per QUERY, dim / B relinearisations + dim / B - 1 giant rotations per BLOCK.
@@ -207,6 +207,7 @@ struct Context : HostParams {
     // for (vector_dim = the reference's form, or the baby count): loop B walks blocks of `form` ciphertexts, and more than 8 of them
     // take the group-sequential layout; -1 (HERS' column packing) stays ciphertext-major
     void db_resize(size_t n_vectors, size_t cts, int form);
+    void db_resize_rows(size_t n_vectors, size_t cts);  // kind 1: `cts` ciphertexts as plain [ct][2][nQ][N] residues
     void db_relayout(int form);  // the same ciphertexts laid out for another form (a second buffer for the duration)
     // persistence of the resident database (own streaming format: header + the ciphertext-major layout verbatim, so a restart does
     // not re-enrol from plaintext; the reference keeps serial/db_diagonal/index<t>.bin, enroller_diag.cpp:158-166)
@@ -277,7 +278,8 @@ struct Context : HostParams {
     // keys_packed_nQ > 0: d_keys point at packed keys (hk::key_pack)
     void ks_apply(const u64 *dig, size_t dig_x_stride, int X, int nl, const u64 *const *d_keys, int same_key,
                   const u64 *addend, size_t add_x_stride, size_t add_poly_stride, int add_polys, const unsigned *d_galois,
-                  const unsigned *d_ginv, int same_galois, bool dbl, u64 *out, int keys_packed_nQ = 0);
+                  const unsigned *d_ginv, int same_galois, bool dbl, u64 *out, int keys_packed_nQ = 0, const u64 *self = nullptr,
+                  size_t self_x_stride = 0, size_t self_poly_stride = 0);  // self (generic rings only): out += self, un-permuted
     void build_rotptrs();
     void relinearize(Ct &c, bool dbl = false);  // [X][3][nl] -> [X][2][nl]; dbl: result doubled (2ab of a Chebyshev step)
     // drop the last limb; optionally fused: result -= sub (a view at the new level), result += addc (constant, poly 0)
@@ -335,6 +337,40 @@ struct Context : HostParams {
     Ct binary_rotate(const Ct &a, long factor);  // every ciphertext of the batch through those rotations
     // EvalMult(ct, MakeCKKSPackedPlaintext(pt)) + RescaleInPlace; pt [2][nl][N] from client_encode_plain (residues, Shoup companions)
     Ct mult_plain_rescale(const Ct &a, const u64 *pt);
+
+    // ---- approach 1, the literature baseline (src/sender/sender_base.cpp, OpenFHEWrapper::mergeCiphers); base.cpp
+    // self + Rot_rot(t), every ciphertext of the batch (t and self of one shape; self may be t: EvalSum's c += Rot(c)).  On generic rings the
+    // key switch's last kernel writes the sum (HYDIA_BASE_NO_ROTADD: rotate, then add); the same residues either way
+    Ct rotate_acc(const Ct &t, int rot, const Ct &self);
+    bool base_rotadd = true;   // HYDIA_BASE_NO_ROTADD
+    bool base_bcast = true;    // HYDIA_BASE_NO_BCAST: the query replicated per database ciphertext, the database staged, k_tensor
+    int base_chunk_env = 0;    // HYDIA_BASE_CHUNK: database ciphertexts per pass (0 = from free memory)
+    size_t base_db_cts(size_t n_vectors) const { return (n_vectors + (size_t)(slots / prm.dim) - 1) / (size_t)(slots / prm.dim); }
+    int base_chunk(size_t cts);
+    void base_check_query(const Ct &q) const;
+    void base_check_keys(const std::vector<int> &rots) const;  // StateError naming the first missing rotation (or the relinearisation key)
+    std::vector<int> merge_rotations(size_t n_cts, int dimension) const;  // every key-switch rotation of mergeCiphers on n_cts ciphertexts
+    // HIP-event time of a query's phases ("base_similarity", "base_merge", "base_compare"), kept apart from `timers` because a phase
+    // encloses timed launches: only completed pairs are ever stored; base_phase_collect adds them to timers[name] (hydia_kernel_time)
+    struct PhaseEv {
+        const char *name;
+        hipEvent_t a, b;
+    };
+    std::vector<PhaseEv> base_phase_pending;
+    void base_phase_collect();
+    // generateMergeMask(dimension, seg) encoded on nl limbs, in k_mul_plain's form (residues, Shoup companions); made once per
+    // (dimension, segment, level) and kept — at most HY_MERGE_MASKS of them (2 nl N 8 bytes each): one more empties the cache first
+    std::map<std::vector<int>, u64 *> merge_masks;
+    const u64 *merge_mask(int dimension, int seg, int nl);
+    Ct base_similarity_chunk(const Ct &q, size_t t0, int C);  // EvalInnerProduct + Rescale on database ciphertexts t0 .. t0+C-1
+    void merge_single(Ct &c, int dimension);                   // mergeSingleCipher on every ciphertext of the batch
+    // mergeCiphers' placement: merged ciphertexts i0 .. i0+X-1 of a batch of n_cts into out (ceil(vpc n_cts / slots) outputs, allocated
+    // at the first call); the calls walk i upwards
+    void merge_place(const Ct &merged, size_t i0, int dimension, Ct &out, size_t n_out);
+    Ct merge_ciphers(const Ct &in, int dimension);
+    Ct base_similarity(const Ct &q);
+    Ct base_index_scenario(const Ct &q);
+    Ct base_membership_scenario(const Ct &q);
 
     // ---- HyDia sender (src/sender/sender_diag.cpp)
     Ct rotate_query(const Ct &q);                   // -> [dim][2][nQ][N]
@@ -409,6 +445,8 @@ void Context::par2(F0 &&here, F1 &&side) {
     HIP_CHECK(hipStreamWaitEvent(stream, par_ev[1], 0));
 }
 
+// inherent bytes of an evaluator operation into the byte ledger as "op:<name>" (evaluator.cpp)
+void op_bytes(const char *op, size_t N, double transforms, double other_bytes);
 // host residue of a real constant (value already multiplied by its scale)
 u64 double_to_mod(double v, u64 q);
 u64 powmod_u64(u64 a, u64 e, u64 q);

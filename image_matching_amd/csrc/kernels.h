@@ -313,6 +313,9 @@ void batch_sum(hipStream_t st, const ModC *mod, int N, const u64 *in, u64 *o, in
 // (a0 b0, a0 b1 + a1 b0, a1 b1) for X ciphertext pairs at nl limbs; o: [X][3][nl][N]
 void tensor(hipStream_t st, const ModC *mod, int N, const u64 *a, const u64 *b, u64 *o, int X, int nl, int a_ls, int b_ls,
             const u64 *c = nullptr, int c_ls = 0, const ScaleSel *kap = nullptr);
+// approach 1's query-broadcast product: ONE 2-component ciphertext q ([2][q_ls][N]) times X ciphertexts b ([X][2][b_ls][N], e.g. the
+// row-packed resident database read in place) -> o [X][3][nl][N]; the residues k_tensor gives for X copies of q
+void tensor_bcast(hipStream_t st, const ModC *mod, int N, const u64 *q, int q_ls, const u64 *b, int b_ls, u64 *o, int X, int nl);
 
 // ---- key switching
 // out[x][t][c] = sum_s y[x][s][c] * tab.f[s][t] mod q_{dsel.mod[t]} ; y coefficient form, residues < 2^60
@@ -365,7 +368,7 @@ bool ntt15_inverse_p1_narrow(hipStream_t st, const NttTables &T, u64 *dst, size_
 void moddown_combine(hipStream_t st, const ModC *mod, int logN, const u64 *acc, int acc_limbs, const u64 *conv,
                      const u64 *addend, size_t add_x_stride, size_t add_poly_stride, int add_polys, u64 *out, int X, int nl,
                      const ScaleSel &pinv, const unsigned *galois /* device [X] (or [1] with same_g) or null */,
-                     int same_g);
+                     int same_g, const u64 *self = nullptr, size_t self_x_stride = 0, size_t self_poly_stride = 0);
 // merged ModDown + Rescale (bit-identical to doing them in sequence), coefficient-domain part.
 // u  [xp][N]      : INTT of (acc_l P^{-1} + d_l)(x2), the dropped limb q_l of the would-be ModDown output
 // y  [xp][nP][N]  : INTT of acc's P limbs times (P/p_k)^{-1}

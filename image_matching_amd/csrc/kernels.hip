@@ -314,6 +314,36 @@ __global__ __launch_bounds__(256) void k_tensor(const ModC *__restrict__ mod, in
     *reinterpret_cast<ulonglong2 *>(o + po + ps) = d1;
     *reinterpret_cast<ulonglong2 *>(o + po + 2 * ps) = d2;
 }
+// Approach 1's product of ONE query ciphertext with X database ciphertexts (EvalInnerProduct's EvalMult, sender_base.cpp:93).
+// grid (N/512, nl, ceil(X / HY_BCAST_X)): a thread keeps its two coefficients of q0, q1 in registers and walks HY_BCAST_X database
+// ciphertexts, so the query is fetched once per HY_BCAST_X products from its single copy; b is read where it lies (the row-packed
+// resident database, [X][2][b_ls][N] plain residues), streamed once: non-temporal 16-byte loads.  Residues = k_tensor<false>'s.
+#define HY_BCAST_X 4
+__global__ __launch_bounds__(256) void k_tensor_bcast(const ModC *__restrict__ mod, int N, const u64 *__restrict__ qc, int q_ls,
+                                                      const u64 *__restrict__ b, int b_ls, u64 *__restrict__ o, int nl, int X) {
+    typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
+    const int j = blockIdx.y;
+    const ModC M = mod[j];
+    const size_t i = (size_t)j * N + (size_t)(blockIdx.x * 256 + threadIdx.x) * 2, ps = (size_t)nl * N;
+    const ulonglong2 a0 = *reinterpret_cast<const ulonglong2 *>(qc + i), a1 = *reinterpret_cast<const ulonglong2 *>(qc + (size_t)q_ls * N + i);
+    const int x0 = blockIdx.z * HY_BCAST_X, x1 = min(X, x0 + HY_BCAST_X);
+    for (int x = x0; x < x1; x++) {
+        const size_t pb = (size_t)x * 2 * b_ls * N + i;
+        const ull2 b0 = __builtin_nontemporal_load(reinterpret_cast<const ull2 *>(b + pb));
+        const ull2 b1 = __builtin_nontemporal_load(reinterpret_cast<const ull2 *>(b + pb + (size_t)b_ls * N));
+        ulonglong2 d0, d1, d2;
+        d0.x = mulmod(a0.x, b0.x, M);
+        d0.y = mulmod(a0.y, b0.y, M);
+        d1.x = reduce128k((u128)a0.x * b1.x + (u128)a1.x * b0.x, M);
+        d1.y = reduce128k((u128)a0.y * b1.y + (u128)a1.y * b0.y, M);
+        d2.x = mulmod(a1.x, b1.x, M);
+        d2.y = mulmod(a1.y, b1.y, M);
+        const size_t po = (size_t)x * 3 * ps + i;
+        *reinterpret_cast<ulonglong2 *>(o + po) = d0;
+        *reinterpret_cast<ulonglong2 *>(o + po + ps) = d1;
+        *reinterpret_cast<ulonglong2 *>(o + po + 2 * ps) = d2;
+    }
+}
 
 // ------------------------------------------------------------------------------------------------ key switching
 // grid (N/512, X): each thread reads its ns source residues ONCE (2 coefficients, 16 B loads) and produces all nt
@@ -460,7 +490,7 @@ __global__ __launch_bounds__(256) void k_moddown_combine(const ModC *__restrict_
                                                          const u64 *__restrict__ conv, const u64 *__restrict__ addend,
                                                          size_t axs, size_t aps, int add_polys, u64 *__restrict__ out, int nl,
                                                          ScaleSel pinv, const unsigned *__restrict__ galois,
-                                                         int same_g) {
+                                                         int same_g, const u64 *__restrict__ self, size_t sxs, size_t sps) {
     const int N = 1 << logN;
     const int j = blockIdx.y, xp = blockIdx.z, x = xp >> 1, p = xp & 1;
     const u64 q = mod[j].q;
@@ -476,6 +506,8 @@ __global__ __launch_bounds__(256) void k_moddown_combine(const ModC *__restrict_
     u64 v = submod(acc[((size_t)xp * acc_limbs + j) * N + c], conv[((size_t)xp * nl + j) * N + c], q);
     v = mulmod_shoup(v, pinv.s[j], pinv.s_sh[j], q);
     if (addend && p < add_polys) v = addmod(v, addend[(size_t)x * axs + (size_t)p * aps + (size_t)j * N + c], q);
+    // rotate-and-accumulate (approach 1's EvalSum and merge steps): self + Rot(t) leaves in this store, self read at the OUTPUT index
+    if (self) v = addmod(v, self[(size_t)x * sxs + (size_t)p * sps + (size_t)j * N + co], q);
     out[((size_t)xp * nl + j) * N + co] = v;
 }
 // grid (N/512, XP): see moddown_rescale_conv in kernels.h.  Two coefficients per thread.  (Sources are P-limb residues < 2^60:
@@ -1103,6 +1135,10 @@ static int small_launch_targets(int N, int X, int nt) {
     const int slices = std::min(nt, (512 + wgs - 1) / wgs);
     return (nt + slices - 1) / slices;
 }
+void tensor_bcast(hipStream_t st, const ModC *mod, int N, const u64 *q, int q_ls, const u64 *b, int b_ls, u64 *o, int X, int nl) {
+    ledger_add("k_tensor_bcast", (2.0 + 5.0 * X) * nl * LP_BYTES(N));  // q0 q1 once, b0 b1 in and d0 d1 d2 out per ciphertext
+    hipLaunchKernelGGL(k_tensor_bcast, dim3(N / 512, nl, (X + HY_BCAST_X - 1) / HY_BCAST_X), dim3(256), 0, st, mod, N, q, q_ls, b, b_ls, o, nl, X);
+}
 void base_convert(hipStream_t st, const ModC *mod, int N, const u64 *y, size_t yo, u64 *out, size_t oo, int X,
                   const ConvTab &tab, const LimbSel &dsel) {
     ledger_add("k_base_convert", (double)X * (tab.ns + tab.nt - (tab.skip_hi - tab.skip_lo)) * LP_BYTES(N));  // sources once, every target once
@@ -1143,10 +1179,10 @@ void key_pack(hipStream_t st, const ModC *mod, int N, int nQ, int nT, int nd, co
 }
 void moddown_combine(hipStream_t st, const ModC *mod, int logN, const u64 *acc, int acc_limbs, const u64 *conv,
                      const u64 *addend, size_t axs, size_t aps, int add_polys, u64 *out, int X, int nl,
-                     const ScaleSel &pinv, const unsigned *galois, int same_g) {
-    ledger_add("k_moddown_combine", (3.0 + (addend ? 0.5 * add_polys : 0.0)) * X * 2 * nl * LP_BYTES(1 << logN));
+                     const ScaleSel &pinv, const unsigned *galois, int same_g, const u64 *self, size_t sxs, size_t sps) {
+    ledger_add("k_moddown_combine", (3.0 + (addend ? 0.5 * add_polys : 0.0) + (self ? 1.0 : 0.0)) * X * 2 * nl * LP_BYTES(1 << logN));
     hipLaunchKernelGGL(k_moddown_combine, dim3((1 << logN) / 256, nl, X * 2), dim3(256), 0, st, mod, logN, acc, acc_limbs,
-                       conv, addend, axs, aps, add_polys, out, nl, pinv, galois, same_g);
+                       conv, addend, axs, aps, add_polys, out, nl, pinv, galois, same_g, self, sxs, sps);
 }
 void moddown_rescale_conv(hipStream_t st, const ModC *mod, int N, const u64 *y, size_t yo, const u64 *u, size_t uo, u64 *w, int XP, int l,
                           int nP, const ConvTab &tab) {

@@ -153,6 +153,13 @@ def load_library():
         "hydia_keygen_rotations": (i32, [vp, vp, vp, u32]),
         "hydia_eval_mult_plain": (i32, [vp, vp, vp, pp]),
         "hydia_binary_rotate": (i32, [vp, vp, i32, pp]),
+        "hydia_base_db_num_cts": (sz, [vp, sz]),
+        "hydia_base_db_enroll": (i32, [vp, vp, sz, vp]),
+        "hydia_base_compute_similarity": (i32, [vp, vp, pp]),
+        "hydia_base_index_scenario": (i32, [vp, vp, pp]),
+        "hydia_base_membership_scenario": (i32, [vp, vp, pp]),
+        "hydia_merge_ciphers": (i32, [vp, vp, sz, pp]),
+        "hydia_base_rotations": (i32, [u32, vp, sz, C.POINTER(sz)]),
         "hydia_kernel_time": (i32, [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(u64)]),
         "hydia_kernel_time_reset": (i32, [vp]),
         "hydia_byte_ledger": (i32, [i32, C.c_char_p, sz, C.POINTER(sz)]),
@@ -221,6 +228,16 @@ def params_for_approach(approach):
     p = _Params()
     _chk(load_library().hydia_params_for_approach(approach, C.byref(p)))
     return p
+
+
+def base_rotations(slots):
+    """Host-only: the rotation keys approach 1 needs on a ring of `slots` slots, {2^k} u {slots - 2^k} (hydia_base_rotations)."""
+    L = load_library()
+    n = C.c_size_t()
+    _chk(L.hydia_base_rotations(slots, None, 0, C.byref(n)))
+    out = np.zeros(n.value, dtype=np.int32)
+    _chk(L.hydia_base_rotations(slots, _p(out), n.value, C.byref(n)))
+    return [int(r) for r in out]
 
 
 def describe_params(params=None):
@@ -452,6 +469,17 @@ class Context:
         """OpenFHEWrapper::binaryRotate (src/openFHE_wrapper.cpp:103-128)."""
         return self._out(self.L.hydia_binary_rotate, ct.h, int(factor))
 
+    def merge_ciphers(self, ct, dimension):
+        """OpenFHEWrapper::mergeCiphers (src/openFHE_wrapper.cpp:191-218) on a batch: every dimension-th slot, packed in order."""
+        return self._out(self.L.hydia_merge_ciphers, ct.h, int(dimension))
+
+    def base_rotations(self):
+        """the key set of approach 1 for this context's slot count (pass it to keygen_rotations)"""
+        return base_rotations(self.slots)
+
+    def base_db_num_cts(self, n):
+        return int(self.L.hydia_base_db_num_cts(self.h, n))
+
     def chebyshev_compare(self, ct, delta=0.44, depth=10):
         """OpenFHEWrapper::chebyshevCompare (src/openFHE_wrapper.cpp:143-185)."""
         return self._out(self.L.hydia_chebyshev_compare, ct.h, delta, depth)
@@ -514,7 +542,7 @@ class Context:
         return {0: "auto", 1: "hoisted"}.get(m, m)
 
     def db_kind(self):
-        """0 none, 5 hoisted diagonals, 6 pre-rotated diagonals (baby-step / giant-step), 4 HERS columns"""
+        """0 none, 5 hoisted diagonals, 6 pre-rotated diagonals (baby-step / giant-step), 4 HERS columns, 1 rows (approach 1)"""
         return int(self.L.hydia_db_kind(self.h))
 
     def db_babies(self):
@@ -696,3 +724,37 @@ class HersSender:
 
     def indexScenario(self, query_cipher):
         return self.cc._out(self.cc.L.hydia_hers_index_scenario, query_cipher.h)
+
+
+# ---- the literature baseline, approach 1: include/enroller_base.h, include/receiver_base.h, include/sender_base.h
+class BaseEnroller:
+    def __init__(self, cc, num_vectors):
+        self.cc, self.numVectors = cc, num_vectors
+
+    def serializeDB(self, database, seed=None):
+        """BaseEnroller::serializeDB (src/enroller/enroller_base.cpp:13-56): slots / vector_dim vectors back to back per
+        ciphertext, normalises in place."""
+        assert database.dtype == np.float64 and database.flags.c_contiguous
+        assert database.shape == (self.numVectors, self.cc.dim)
+        _chk(self.cc.L.hydia_base_db_enroll(self.cc.h, _p(database), self.numVectors, _p(_seed(seed))))
+
+
+class BaseReceiver(HersReceiver):
+    """BaseReceiver::encryptQuery (src/receiver/receiver_base.cpp:13-26) is the tiled single ciphertext of approach 5; decrypt* are
+    HersReceiver's (include/receiver_base.h derives from it)."""
+
+    def encryptQuery(self, query, seed=None, nonce=1):
+        return DiagonalReceiver.encryptQuery(self, query, seed, nonce)
+
+
+class BaseSender(HersSender):
+    """include/sender_base.h (derives from HersSender) — computeSimilarity returns the merged score ciphertexts."""
+
+    def computeSimilarity(self, query_cipher):
+        return self.cc._out(self.cc.L.hydia_base_compute_similarity, query_cipher.h)
+
+    def membershipScenario(self, query_cipher):
+        return self.cc._out(self.cc.L.hydia_base_membership_scenario, query_cipher.h)
+
+    def indexScenario(self, query_cipher):
+        return self.cc._out(self.cc.L.hydia_base_index_scenario, query_cipher.h)

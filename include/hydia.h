@@ -172,7 +172,7 @@ int hydia_db_enroll_shard(hydia_ctx *ctx, double *db, size_t n, const uint8_t se
  * hydia_set_matvec mode: 0 auto (hydia_auto_babies: B grows with the blocks the enrolling context holds — at vector_dim 512: 64 up
  * to 3 blocks, 128 up to 12, 256 up to 40, hoisted above; measured, profiles/r04/matvec_sweep.txt), 1 hoisted, otherwise B itself; initial value from HYDIA_MATVEC=auto|hoisted|bsgs|<B>.
  * It takes effect at the NEXT enrolment; hydia_db_kind / hydia_db_babies tell what is resident (kind 0 none, 5 hoisted diagonals,
- * 6 pre-rotated diagonals, 4 HERS columns).  Ciphertexts imported one by one (hydia_db_alloc + hydia_db_import_ct: the reference
+ * 6 pre-rotated diagonals, 4 HERS columns, 1 the rows of approach 1 — hydia_base_db_enroll).  Ciphertexts imported one by one (hydia_db_alloc + hydia_db_import_ct: the reference
  * enroller's) are taken as hoisted unless hydia_db_set_babies says otherwise (a database of more than 8 blocks is then re-ordered in
  * HBM for the declared form, through a second buffer of its size — see hydia_db_group).  hydia_db_set_babies takes a DECLARED form:
  * vector_dim (hoisted) or a power of two >= 2 dividing it — 0, 1 and anything else are HYDIA_ERR_ARG; without a diagonal database
@@ -195,7 +195,10 @@ int hydia_db_export_ct(hydia_ctx *ctx, size_t t, uint64_t *data);
  * src/enroller/enroller_diag.cpp:158-166, and re-reads them every query; here the database stays in HBM and a file is only
  * what a server restart needs).  Own streaming format: a header (parameters, prime chain, packing) + the ciphertexts in order, each
  * as its packed residues (the ciphertext-major resident layout verbatim; a group-sequential database is converted on the way);
- * hydia_db_load refuses a file written for other parameters / primes / residue width. */
+ * hydia_db_load refuses a file written for other parameters / primes / residue width.
+ * A row-packed database (kind 1, approach 1) is NOT saved: the header's `packed` word states how the 45-bit limbs of EVERY ciphertext
+ * in the file are stored and is checked against the context's own packing on load, while kind 1 is resident as plain 8-byte residues
+ * whatever the context packs — hydia_db_save answers HYDIA_ERR_STATE for it, and no file carries kind 1. */
 int hydia_db_save(hydia_ctx *ctx, const char *path);
 int hydia_db_load(hydia_ctx *ctx, const char *path);
 /* benchmark filler: n_vectors worth of uniformly random residues (the kernels' cost is data independent) */
@@ -292,6 +295,37 @@ int hydia_hers_encrypt_query(hydia_ctx *ctx, const double *query, const uint8_t 
 int hydia_hers_compute_similarity(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out);
 int hydia_hers_index_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out);
 int hydia_hers_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out);
+
+/* ---- the literature baseline, approach 1 (BaseEnroller / BaseReceiver / BaseSender): row-packed database, one query ciphertext ----
+ * vpc = slots / vector_dim vectors per database ciphertext (64 at N = 2^16, dim 512).  The query is what hydia_encrypt_query returns
+ * (BaseReceiver::encryptQuery, src/receiver/receiver_base.cpp:13-26, is DiagonalReceiver's); results decrypt with
+ * hydia_decrypt_membership / hydia_decrypt_index.  Keys: hydia_keygen_rotations with the set of hydia_base_rotations.
+ * The database is walked in chunks of C ciphertexts (C from the free device memory; HYDIA_BASE_CHUNK=<C> overrides); every C gives
+ * the same bits.  A missing rotation or relinearisation key: HYDIA_ERR_STATE naming it, before any work is enqueued; another database
+ * kind resident: HYDIA_ERR_STATE; a query that is not one fresh 2-component ciphertext at full level: HYDIA_ERR_ARG. */
+/* ceil(n / vpc): database ciphertexts of n vectors (src/enroller/enroller_base.cpp:20-22) */
+size_t hydia_base_db_num_cts(const hydia_ctx *ctx, size_t n_vectors);
+/* BaseEnroller::serializeDB, src/enroller/enroller_base.cpp:13-56: normalises db IN PLACE, ciphertext i = vectors i vpc .. i vpc + vpc - 1
+ * back to back (zeros after a ragged end), encoded and encrypted on the GPU into database kind 1 (plain 8-byte residues
+ * [ct][2][n_q][N]; hydia_db_import_ct / hydia_db_export_ct then address these ciphertexts).  vector_dim must be a power of two
+ * <= slots (HYDIA_ERR_ARG). */
+int hydia_base_db_enroll(hydia_ctx *ctx, double *db /* n x vector_dim row-major */, size_t n, const uint8_t seed[32]);
+/* BaseSender::computeSimilarity, src/sender/sender_base.cpp:13-27 + :84-98: per database ciphertext EvalInnerProduct(query, db_i,
+ * vector_dim) (EvalMult with relinearisation, then c += Rot(c, 2^k), k = 0 .. log2(dim) - 1, at full level), one rescale, then
+ * OpenFHEWrapper::mergeCiphers.  out: ceil(vpc n_cts / slots) ciphertexts on n_q - 3 limbs, score of vector j in slot j mod slots of
+ * ciphertext j div slots */
+int hydia_base_compute_similarity(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out);
+/* BaseSender::indexScenario, src/sender/sender_base.cpp:69-81 */
+int hydia_base_index_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out);
+/* BaseSender::membershipScenario, src/sender/sender_base.cpp:50-66 */
+int hydia_base_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out);
+/* OpenFHEWrapper::mergeCiphers, src/openFHE_wrapper.cpp:191-218 (with mergeSingleCipher :223-249 and generateMergeMask :253-268) on a
+ * caller's batch: slot k dimension of ciphertext i -> slot (i slots / dimension + k) mod slots of output (i slots / dimension) div
+ * slots.  dimension: a power of two, 2 <= dimension <= slots; every ciphertext needs a limb per mask multiply. */
+int hydia_merge_ciphers(hydia_ctx *ctx, const hydia_ct *in, size_t dimension, hydia_ct **out);
+/* Host only: the rotation keys approach 1 needs on a ring of `slots` slots — {2^k} u {slots - 2^k}, 1 <= 2^k < slots, ascending —
+ * what src/main.cpp:195-206 generates for binaryRotate.  Writes at most cap entries; *n_out = the size of the set. */
+int hydia_base_rotations(uint32_t slots, int32_t *rots, size_t cap, size_t *n_out);
 
 /* ---- evaluator primitives (used by the parity tests and by adapters) ---- */
 int hydia_ntt(hydia_ctx *ctx, uint64_t *data /* host, [count][N] in place */, uint32_t count, uint32_t modulus_index,

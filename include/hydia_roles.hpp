@@ -1,4 +1,5 @@
-// include/hydia_roles.hpp — the reference's C++ role surface for approach 5 (HyDia) and approach 4 (HERS), over the C-ABI of hydia.h.
+// include/hydia_roles.hpp — the reference's C++ role surface for approach 5 (HyDia), approach 4 (HERS) and approach 1 (the literature
+// baseline: include/{enroller,receiver,sender}_base.h), over the C-ABI of hydia.h.
 //
 // Same class and method names as /root/reference/include/{sender,sender_diag,receiver,receiver_hers,receiver_diag,
 // enroller_diag,enroller_hers}.h and the same constructor arguments (include/sender.h:22 `(cc, pk, numVectors)`,
@@ -107,6 +108,23 @@ class CryptoContextImpl {
         if (!check(group ? hydia_group_keygen(group, seed) : hydia_keygen(h, seed), "key generation")) return KeyPair{};
         return KeyPair{PublicKey{this}, PrivateKey{this}};
     }
+    // approach 1's key set: secret, public, relinearisation and rotation keys {2^k} u {batch - 2^k} (hydia_base_rotations) — what
+    // src/main.cpp:195-206 generates for binaryRotate; hydia_keygen's set would not fit a 2^16 ring
+    KeyPair KeyGenBaseline(const uint8_t *seed32 = nullptr) {
+        uint8_t seed[32];
+        role_seed(seed, seed32);
+        if (group) {
+            last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: key generation: approach 1 does not run on a sharded context" << std::endl;
+            return KeyPair{};
+        }
+        size_t n = 0;
+        if (!check(hydia_base_rotations(info.slots, nullptr, 0, &n), "key generation")) return KeyPair{};
+        std::vector<int32_t> rots(n);
+        if (!check(hydia_base_rotations(info.slots, rots.data(), n, &n), "key generation")) return KeyPair{};
+        if (!check(hydia_keygen_rotations(h, seed, rots.data(), (uint32_t)n), "key generation")) return KeyPair{};
+        return KeyPair{PublicKey{this}, PrivateKey{this}};
+    }
     // src/main.cpp:187-206: the evaluation keys exist since KeyGen; these keep the reference's call sequence compiling
     void EvalMultKeyGen(const PrivateKey &) {}
     void EvalSumKeyGen(const PrivateKey &) {}
@@ -185,6 +203,22 @@ inline std::vector<double> decryptToVector(CryptoContext cc, Ciphertext ctxt) {
     cc->check(hydia_decrypt(cc->h, ctxt.batch->h, all.data()), "decrypt");
     return std::vector<double>(all.begin() + (size_t)ctxt.index * cc->info.slots,
                                all.begin() + (size_t)(ctxt.index + 1) * cc->info.slots);
+}
+// src/openFHE_wrapper.cpp:191-218: every dimension-th slot of every ciphertext, packed in order.  The ciphertexts must be the
+// elements 0 .. n-1 of ONE device batch, in order (what every role method here returns); otherwise an error and an empty result
+inline std::vector<Ciphertext> mergeCiphers(CryptoContext cc, std::vector<Ciphertext> &ctxts, size_t dimension) {
+    if (ctxts.empty() || !ctxts[0] || ctxts[0].batch->count() != ctxts.size()) {
+        std::cerr << "Error: mergeCiphers takes the whole of one ciphertext batch" << std::endl;
+        return {};
+    }
+    for (size_t i = 0; i < ctxts.size(); i++)
+        if (ctxts[i].batch != ctxts[0].batch || ctxts[i].index != i) {
+            std::cerr << "Error: mergeCiphers takes the whole of one ciphertext batch" << std::endl;
+            return {};
+        }
+    hydia_ct *out = nullptr;
+    if (!cc->check(hydia_merge_ciphers(cc->h, ctxts[0].batch->h, dimension, &out), "mergeCiphers")) return {};
+    return split_batch(cc, out);
 }
 }  // namespace OpenFHEWrapper
 
@@ -433,6 +467,59 @@ class HersEnroller : public EnrollerBase {  // include/enroller_hers.h:16-37
         if (!next_seed("serializeDB")) return;
         std::vector<double> flat = flatten(database);
         if (!cc->check(hydia_hers_db_enroll(cc->h, flat.data(), numVectors, seed), "serializeDB")) return;
+        write_back(flat, database);
+    }
+};
+
+// ---- the literature baseline, approach 1: include/sender_base.h (derives from HersSender), include/receiver_base.h (from
+// HersReceiver), include/enroller_base.h.  The query is ONE ciphertext; the database is row-packed (hydia_base_db_enroll).
+class BaseSender : public HersSender {
+  public:
+    BaseSender(CryptoContext ccParam, size_t vectorParam) : HersSender(std::move(ccParam), vectorParam) {}
+    BaseSender(CryptoContext ccParam, PublicKey pkParam, size_t vectorParam) : HersSender(std::move(ccParam), pkParam, vectorParam) {}  // sender_base.cpp:7-9
+    std::vector<Ciphertext> computeSimilarity(std::vector<Ciphertext> &queryCipher) override {  // sender_base.cpp:13-27
+        hydia_ct *out = run(queryCipher, hydia_base_compute_similarity, "computeSimilarity");
+        return out ? split_batch(cc, out) : std::vector<Ciphertext>{};
+    }
+    Ciphertext membershipScenario(std::vector<Ciphertext> &queryCipher) override {  // sender_base.cpp:50-66
+        hydia_ct *out = run(queryCipher, hydia_base_membership_scenario, "membershipScenario");
+        return out ? split_batch(cc, out)[0] : Ciphertext{};
+    }
+    std::vector<Ciphertext> indexScenario(std::vector<Ciphertext> &queryCipher) override {  // sender_base.cpp:69-81
+        hydia_ct *out = run(queryCipher, hydia_base_index_scenario, "indexScenario");
+        return out ? split_batch(cc, out) : std::vector<Ciphertext>{};
+    }
+
+  private:
+    hydia_ct *run(std::vector<Ciphertext> &q, int (*fn)(hydia_ctx *, const hydia_ct *, hydia_ct **), const char *what) {
+        hydia_ct *out = nullptr;
+        if (q.empty() || !q[0]) {
+            std::cerr << "Error: empty query ciphertext" << std::endl;
+            return nullptr;
+        }
+        return cc->check(fn(cc->h, q[0].batch->h, &out), what) ? out : nullptr;
+    }
+};
+class BaseReceiver : public HersReceiver {
+  public:
+    using HersReceiver::HersReceiver;
+    // src/receiver/receiver_base.cpp:13-26: normalise, tile to all slots, one ciphertext
+    std::vector<Ciphertext> encryptQuery(std::vector<double> query) override {
+        hydia_ct *out = nullptr;
+        if (query.size() < cc->info.vector_dim) query.resize(cc->info.vector_dim, 0.0);
+        if (!cc->check(hydia_encrypt_query(cc->h, query.data(), seed, ++nonce, &out), "encryptQuery")) return {};
+        return split_batch(cc, out);
+    }
+};
+class BaseEnroller : public EnrollerBase {  // include/enroller_base.h
+  public:
+    BaseEnroller(CryptoContext ccParam, size_t vectorParam, const uint8_t *seed32 = nullptr)
+        : EnrollerBase(std::move(ccParam), PublicKey{}, vectorParam, seed32) {}
+    BaseEnroller(CryptoContext ccParam, PublicKey pkParam, size_t vectorParam) : EnrollerBase(std::move(ccParam), pkParam, vectorParam, nullptr) {}
+    void serializeDB(std::vector<std::vector<double>> &database) {  // enroller_base.cpp:13-56
+        if (!next_seed("serializeDB")) return;
+        std::vector<double> flat = flatten(database);
+        if (!cc->check(hydia_base_db_enroll(cc->h, flat.data(), numVectors, seed), "serializeDB")) return;
         write_back(flat, database);
     }
 };
