@@ -6,6 +6,7 @@ raises if the HIP library is missing.
 """
 from .hydia import (Context, Ciphertext, DiagonalEnroller, DiagonalReceiver, DiagonalSender, HydiaError,  # noqa: F401
                     HersEnroller, HersReceiver, HersSender, BaseEnroller, BaseReceiver, BaseSender, base_rotations,
+                    GroteReceiver, GroteSender, grote_row_length,
                     byte_ledger, default_params, describe_params, compute_required_depth, lib_path, load_library,
                     params_for_approach)
 from .sharding import (ShardGroup, ShardedDiagonalEnroller, ShardedDiagonalSender, DistDiagonalEnroller,  # noqa: F401

@@ -20,29 +20,6 @@ static bool is_pow2(long v) { return v >= 1 && (v & (v - 1)) == 0; }
 
 #define HY_MERGE_MASKS 32
 
-// fn() between two events on the stream; the pair is stored only once both are recorded, so an exception inside fn leaves nothing behind
-template <class F>
-static void phase(Context &c, const char *name, F &&fn) {
-    if (!c.timing) {
-        fn();
-        return;
-    }
-    if (c.base_phase_pending.size() >= 2048) c.base_phase_collect();
-    struct Ev {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Ev() {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } e;
-    HIP_CHECK(hipEventCreate(&e.a));
-    HIP_CHECK(hipEventCreate(&e.b));
-    HIP_CHECK(hipEventRecord(e.a, c.stream));
-    fn();
-    HIP_CHECK(hipEventRecord(e.b, c.stream));
-    c.base_phase_pending.push_back({name, e.a, e.b});
-    e.a = e.b = nullptr;
-}
 void Context::base_phase_collect() {
     for (auto &e : base_phase_pending) {
         float ms = 0;
@@ -141,7 +118,7 @@ Ct Context::base_similarity_chunk(const Ct &qc, size_t t0, int C) {
 }
 
 // c += binaryRotate(c, factor) (openFHE_wrapper.cpp:241): all steps but the last are plain rotations, the last one accumulates
-static void add_binary_rotated(Context &cx, Ct &c, long factor) {
+void add_binary_rotated(Context &cx, Ct &c, long factor) {
     const std::vector<int> rots = cx.binary_rotations(factor);
     if (rots.empty()) {  // a multiple of the slot count: binaryRotate returns its input
         Ct t = cx.clone(c);

@@ -624,6 +624,38 @@ int hydia_base_rotations(uint32_t slots, int32_t *rots, size_t cap, size_t *n_ou
     *n_out = v.size();
     return HYDIA_OK;
 }
+// ------------------------------------------------------------------ approach 2 (GROTE group testing)
+uint32_t hydia_grote_row_length(uint32_t slots) {
+    if (slots < 2 || (slots & (slots - 1)) || slots > (1u << 30)) return 0;
+    return (uint32_t)Context::grote_row_length((long)slots);
+}
+/* receiver_grote.cpp:12-65 */
+int hydia_grote_decrypt_index(hydia_ctx *ctx, const hydia_ct *rows, const hydia_ct *cols, size_t n_vectors, size_t *out, size_t cap, size_t *n_out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && rows && cols && n_out, "null argument");
+    const size_t S = ctx->cx.slots, rl = (size_t)Context::grote_row_length((long)S), cl = S / rl;
+    const size_t mats = (n_vectors + S - 1) / S, num_row = (mats + rl - 1) / rl, num_col = (mats + cl - 1) / cl;  // :20-21
+    REQUIRE((size_t)rows->c.X == num_row && (size_t)cols->c.X == num_col, "incorrect parsing of index query results: the row / column ciphertext counts do not fit n_vectors");
+    std::vector<double> rv(num_row * S), cv(num_col * S);
+    client_decrypt(ctx->cx, rows->c, rv.data());
+    client_decrypt(ctx->cx, cols->c, cv.data());
+    std::vector<size_t> rm, cm;
+    for (size_t i = 0; i < rv.size(); i++)
+        if (rv[i] >= 1.0) rm.push_back(i);
+    for (size_t i = 0; i < cv.size(); i++)
+        if (cv[i] >= 1.0) cm.push_back(i);
+    size_t cnt = 0;
+    for (size_t r : rm)      // :51-62: rows outer, columns inner
+        for (size_t c : cm)
+            if (r / cl == c / rl) {
+                if (out && cnt < cap) out[cnt] = r * rl + c % rl;
+                cnt++;
+            }
+    *n_out = cnt;
+    return HYDIA_OK;
+    API_END
+}
 int hydia_db_save(hydia_ctx *ctx, const char *path) {
     API_BEGIN
     use_device(ctx);
@@ -758,6 +790,30 @@ int hydia_merge_ciphers(hydia_ctx *ctx, const hydia_ct *query, size_t dimension,
     SENDER_CALL(ctx->cx.merge_ciphers(query->c, (int)dimension))
 }
 
+int hydia_alpha_norm_rows(hydia_ctx *ctx, const hydia_ct *query, size_t alpha, size_t row_length, hydia_ct **out) {
+    if (alpha > 64 || row_length > (size_t)INT32_MAX) return fail(HYDIA_ERR_ARG, "hydia: row_length must be a power of two in 2 .. slots");
+    SENDER_CALL(ctx->cx.alpha_norm_rows(query->c, (int)alpha, (int)row_length))
+}
+int hydia_alpha_norm_columns(hydia_ctx *ctx, const hydia_ct *query, size_t alpha, size_t row_length, hydia_ct **out) {
+    if (alpha > 64 || row_length > (size_t)INT32_MAX) return fail(HYDIA_ERR_ARG, "hydia: row_length must be a power of two in 2 .. slots");
+    SENDER_CALL(ctx->cx.alpha_norm_columns(query->c, (int)alpha, (int)row_length))
+}
+int hydia_grote_index_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **rows, hydia_ct **cols) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && query && rows && cols, "null argument");
+    Ct r, c;
+    ctx->cx.grote_index_scenario(query->c, r, c);
+    *rows = wrap(ctx, std::move(r));
+    *cols = wrap(ctx, std::move(c));
+    return HYDIA_OK;
+    API_END
+}
+int hydia_grote_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.grote_membership_scenario(query->c)) }
+int hydia_eval_square_no_relin(hydia_ctx *ctx, const hydia_ct *query, uint32_t n_limbs, hydia_ct **out) {
+    if (query && n_limbs > (uint32_t)query->c.nl) return fail(HYDIA_ERR_ARG, "hydia: more limbs than the ciphertext has");
+    SENDER_CALL(ctx->cx.grote_square(query->c.alias(n_limbs ? (int)n_limbs : query->c.nl)))
+}
 // ------------------------------------------------------------------ primitives
 int hydia_ntt(hydia_ctx *ctx, uint64_t *data, uint32_t count, uint32_t m, int inverse) {
     API_BEGIN

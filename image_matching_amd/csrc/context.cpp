@@ -288,6 +288,7 @@ Context::Context(const Params &p, int dev) : HostParams(p), device(dev) {
     if (getenv("HYDIA_BASE_NO_ROTADD")) base_rotadd = false;
     if (getenv("HYDIA_BASE_NO_BCAST")) base_bcast = false;
     if (const char *e = getenv("HYDIA_BASE_CHUNK")) base_chunk_env = std::max(0, atoi(e));
+    if (getenv("HYDIA_GROTE_NO_SQ")) grote_sq = false;
     for (int k = 1; k < nlanes; k++) {
         hipStream_t st;
         HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));

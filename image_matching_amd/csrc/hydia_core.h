@@ -372,6 +372,23 @@ struct Context : HostParams {
     Ct base_index_scenario(const Ct &q);
     Ct base_membership_scenario(const Ct &q);
 
+    // ---- approach 2, GROTE group testing (src/sender/sender_grote.cpp, HersSender::alphaNormRows / alphaNormColumns,
+    // src/sender/sender_hers.cpp:118-178); grote.cpp.  Enrolment, query, keys and computeSimilarity are approach 1's
+    bool grote_sq = true;  // HYDIA_GROTE_NO_SQ: squares through mult_norelin(a, a) (k_tensor<false>) instead of k_tensor_sq; the same residues
+    static int grote_row_length(long slots);                     // 2^ceil(log2(slots) / 2)
+    int grote_masks(int row_length) const;                       // mask multiplies of mergeCiphers(., row_length)
+    Ct grote_square(const Ct &a);                                // the self product (3 components; the caller relinearises), no rescale
+    // the prefix rows and columns share: a = s^(2^alpha) (a square, a rescale, alpha times), then relin(a (x) s on a's limbs), NOT rescaled
+    Ct alpha_norm_product(const Ct &s, int alpha_depth);
+    Ct alpha_norm_rows_from(const Ct &p, int row_length);        // p as alpha_norm_product returns it
+    Ct alpha_norm_columns_from(const Ct &p, int row_length);
+    std::vector<int> grote_rotations(size_t n_cts, int row_length, bool rows, bool cols) const;
+    void grote_check(const Ct &in, int alpha_depth, int row_length, bool rows, bool cols) const;  // arguments, limb budget, keys: before any work
+    Ct alpha_norm_rows(const Ct &in, int alpha_depth, int row_length);
+    Ct alpha_norm_columns(const Ct &in, int alpha_depth, int row_length);
+    void grote_index_scenario(const Ct &q, Ct &rows, Ct &cols);
+    Ct grote_membership_scenario(const Ct &q);
+
     // ---- HyDia sender (src/sender/sender_diag.cpp)
     Ct rotate_query(const Ct &q);                   // -> [dim][2][nQ][N]
     // rotations first .. first+count-1 of the query (rotation 0 = the query itself) into out [count][2][nQ][N]: one rank's share of
@@ -444,6 +461,32 @@ void Context::par2(F0 &&here, F1 &&side) {
     here();
     HIP_CHECK(hipStreamWaitEvent(stream, par_ev[1], 0));
 }
+
+// fn() between two events on the stream; the pair is stored only once both are recorded, so an exception inside fn leaves nothing behind
+template <class F>
+void phase(Context &c, const char *name, F &&fn) {
+    if (!c.timing) {
+        fn();
+        return;
+    }
+    if (c.base_phase_pending.size() >= 2048) c.base_phase_collect();
+    struct Ev {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Ev() {
+            if (a) (void)hipEventDestroy(a);
+            if (b) (void)hipEventDestroy(b);
+        }
+    } e;
+    HIP_CHECK(hipEventCreate(&e.a));
+    HIP_CHECK(hipEventCreate(&e.b));
+    HIP_CHECK(hipEventRecord(e.a, c.stream));
+    fn();
+    HIP_CHECK(hipEventRecord(e.b, c.stream));
+    c.base_phase_pending.push_back({name, e.a, e.b});
+    e.a = e.b = nullptr;
+}
+// c += binaryRotate(c, factor) (openFHE_wrapper.cpp:241; base.cpp)
+void add_binary_rotated(Context &cx, Ct &c, long factor);
 
 // inherent bytes of an evaluator operation into the byte ledger as "op:<name>" (evaluator.cpp)
 void op_bytes(const char *op, size_t N, double transforms, double other_bytes);

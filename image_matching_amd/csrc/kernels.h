@@ -313,6 +313,9 @@ void batch_sum(hipStream_t st, const ModC *mod, int N, const u64 *in, u64 *o, in
 // (a0 b0, a0 b1 + a1 b0, a1 b1) for X ciphertext pairs at nl limbs; o: [X][3][nl][N]
 void tensor(hipStream_t st, const ModC *mod, int N, const u64 *a, const u64 *b, u64 *o, int X, int nl, int a_ls, int b_ls,
             const u64 *c = nullptr, int c_ls = 0, const ScaleSel *kap = nullptr);
+// EvalSquare (approach 2's alpha norm): (a0^2, 2 a0 a1, a1^2) for X ciphertexts at nl limbs, a a limb-strided view; o: [X][3][nl][N].
+// The residues tensor(a, a) gives, with half the loads
+void tensor_sq(hipStream_t st, const ModC *mod, int N, const u64 *a, u64 *o, int X, int nl, int a_ls);
 // approach 1's query-broadcast product: ONE 2-component ciphertext q ([2][q_ls][N]) times X ciphertexts b ([X][2][b_ls][N], e.g. the
 // row-packed resident database read in place) -> o [X][3][nl][N]; the residues k_tensor gives for X copies of q
 void tensor_bcast(hipStream_t st, const ModC *mod, int N, const u64 *q, int q_ls, const u64 *b, int b_ls, u64 *o, int X, int nl);

@@ -314,6 +314,30 @@ __global__ __launch_bounds__(256) void k_tensor(const ModC *__restrict__ mod, in
     *reinterpret_cast<ulonglong2 *>(o + po + ps) = d1;
     *reinterpret_cast<ulonglong2 *>(o + po + 2 * ps) = d2;
 }
+// EvalSquare on X ciphertexts (approach 2's alpha norm, sender_hers.cpp:124 / :153): d0 = c0^2, d1 = 2 c0 c1, d2 = c1^2.  Grid and limb
+// stride as k_tensor<false>; two 16-byte loads and three stores per coefficient pair where k_tensor on (a, a) loads four, three products
+// instead of four.  Canonical residues, so the bits are k_tensor<false>(a, a)'s.
+__global__ __launch_bounds__(256) void k_tensor_sq(const ModC *__restrict__ mod, int N, const u64 *__restrict__ a, u64 *__restrict__ o,
+                                                   int nl, int a_ls) {
+    const int j = blockIdx.y, x = blockIdx.z;
+    const ModC M = mod[j];
+    const size_t i = (size_t)j * N + (size_t)(blockIdx.x * 256 + threadIdx.x) * 2;
+    const size_t pa = (size_t)x * 2 * a_ls * N + i, ps = (size_t)nl * N;
+    const ulonglong2 a0 = *reinterpret_cast<const ulonglong2 *>(a + pa), a1 = *reinterpret_cast<const ulonglong2 *>(a + pa + (size_t)a_ls * N);
+    ulonglong2 d0, d1, d2;
+    d0.x = mulmod(a0.x, a0.x, M);
+    d0.y = mulmod(a0.y, a0.y, M);
+    d1.x = mulmod(a0.x, a1.x, M);
+    d1.y = mulmod(a0.y, a1.y, M);
+    d1.x = addmod(d1.x, d1.x, M.q);
+    d1.y = addmod(d1.y, d1.y, M.q);
+    d2.x = mulmod(a1.x, a1.x, M);
+    d2.y = mulmod(a1.y, a1.y, M);
+    const size_t po = (size_t)x * 3 * ps + i;
+    *reinterpret_cast<ulonglong2 *>(o + po) = d0;
+    *reinterpret_cast<ulonglong2 *>(o + po + ps) = d1;
+    *reinterpret_cast<ulonglong2 *>(o + po + 2 * ps) = d2;
+}
 // Approach 1's product of ONE query ciphertext with X database ciphertexts (EvalInnerProduct's EvalMult, sender_base.cpp:93).
 // grid (N/512, nl, ceil(X / HY_BCAST_X)): a thread keeps its two coefficients of q0, q1 in registers and walks HY_BCAST_X database
 // ciphertexts, so the query is fetched once per HY_BCAST_X products from its single copy; b is read where it lies (the row-packed
@@ -1134,6 +1158,10 @@ static int small_launch_targets(int N, int X, int nt) {
     if (nt <= 1 || wgs >= 512) return nt > 0 ? nt : 1;
     const int slices = std::min(nt, (512 + wgs - 1) / wgs);
     return (nt + slices - 1) / slices;
+}
+void tensor_sq(hipStream_t st, const ModC *mod, int N, const u64 *a, u64 *o, int X, int nl, int a_ls) {
+    ledger_add("k_tensor_sq", 5.0 * X * nl * LP_BYTES(N));  // a0 a1 in, d0 d1 d2 out
+    hipLaunchKernelGGL(k_tensor_sq, dim3(N / 512, nl, X), dim3(256), 0, st, mod, N, a, o, nl, a_ls);
 }
 void tensor_bcast(hipStream_t st, const ModC *mod, int N, const u64 *q, int q_ls, const u64 *b, int b_ls, u64 *o, int X, int nl) {
     ledger_add("k_tensor_bcast", (2.0 + 5.0 * X) * nl * LP_BYTES(N));  // q0 q1 once, b0 b1 in and d0 d1 d2 out per ciphertext

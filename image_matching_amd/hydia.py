@@ -160,6 +160,13 @@ def load_library():
         "hydia_base_membership_scenario": (i32, [vp, vp, pp]),
         "hydia_merge_ciphers": (i32, [vp, vp, sz, pp]),
         "hydia_base_rotations": (i32, [u32, vp, sz, C.POINTER(sz)]),
+        "hydia_grote_row_length": (u32, [u32]),
+        "hydia_alpha_norm_rows": (i32, [vp, vp, sz, sz, pp]),
+        "hydia_alpha_norm_columns": (i32, [vp, vp, sz, sz, pp]),
+        "hydia_grote_index_scenario": (i32, [vp, vp, pp, pp]),
+        "hydia_grote_membership_scenario": (i32, [vp, vp, pp]),
+        "hydia_grote_decrypt_index": (i32, [vp, vp, vp, sz, vp, sz, C.POINTER(sz)]),
+        "hydia_eval_square_no_relin": (i32, [vp, vp, u32, pp]),
         "hydia_kernel_time": (i32, [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(u64)]),
         "hydia_kernel_time_reset": (i32, [vp]),
         "hydia_byte_ledger": (i32, [i32, C.c_char_p, sz, C.POINTER(sz)]),
@@ -238,6 +245,14 @@ def base_rotations(slots):
     out = np.zeros(n.value, dtype=np.int32)
     _chk(L.hydia_base_rotations(slots, _p(out), n.value, C.byref(n)))
     return [int(r) for r in out]
+
+
+def grote_row_length(slots):
+    """Host-only: approach 2's row length 2^ceil(log2(slots) / 2) (hydia_grote_row_length)."""
+    r = int(load_library().hydia_grote_row_length(slots))
+    if r == 0:
+        raise HydiaError(-1, "hydia: slots must be a power of two >= 2")
+    return r
 
 
 def describe_params(params=None):
@@ -472,6 +487,22 @@ class Context:
     def merge_ciphers(self, ct, dimension):
         """OpenFHEWrapper::mergeCiphers (src/openFHE_wrapper.cpp:191-218) on a batch: every dimension-th slot, packed in order."""
         return self._out(self.L.hydia_merge_ciphers, ct.h, int(dimension))
+
+    def alpha_norm_rows(self, ct, alpha, row_length):
+        """HersSender::alphaNormRows (src/sender/sender_hers.cpp:118-132) on a batch."""
+        return self._out(self.L.hydia_alpha_norm_rows, ct.h, int(alpha), int(row_length))
+
+    def alpha_norm_columns(self, ct, alpha, row_length):
+        """HersSender::alphaNormColumns (src/sender/sender_hers.cpp:136-178) on a batch."""
+        return self._out(self.L.hydia_alpha_norm_columns, ct.h, int(alpha), int(row_length))
+
+    def grote_row_length(self):
+        """approach 2's row length for this context's slot count"""
+        return grote_row_length(self.slots)
+
+    def eval_square_no_relin(self, ct, n_limbs=0):
+        """(c0^2, 2 c0 c1, c1^2) on the first n_limbs limbs of ct read in place (0 = all)"""
+        return self._out(self.L.hydia_eval_square_no_relin, ct.h, int(n_limbs))
 
     def base_rotations(self):
         """the key set of approach 1 for this context's slot count (pass it to keygen_rotations)"""
@@ -758,3 +789,33 @@ class BaseSender(HersSender):
 
     def indexScenario(self, query_cipher):
         return self.cc._out(self.cc.L.hydia_base_index_scenario, query_cipher.h)
+
+
+# ---- GROTE group testing, approach 2: include/sender_grote.h (derives from BaseSender), include/receiver_grote.h (from BaseReceiver);
+# the enroller is BaseEnroller (src/main.cpp:236-238)
+class GroteSender(BaseSender):
+    """computeSimilarity is BaseSender's.  indexScenario returns the pair (rows, columns): the reference's single vector holds the row
+    ciphertexts followed by the column ciphertexts, which are two batches here (their limb counts differ by one)."""
+
+    def membershipScenario(self, query_cipher):
+        return self.cc._out(self.cc.L.hydia_grote_membership_scenario, query_cipher.h)
+
+    def indexScenario(self, query_cipher):
+        rows, cols = C.c_void_p(), C.c_void_p()
+        _chk(self.cc.L.hydia_grote_index_scenario(self.cc.h, query_cipher.h, C.byref(rows), C.byref(cols)))
+        return Ciphertext(self.cc, rows), Ciphertext(self.cc, cols)
+
+
+class GroteReceiver(BaseReceiver):
+    """GroteReceiver::decryptIndex (src/receiver/receiver_grote.cpp:12-65): rows x columns of one matrix -> indices."""
+
+    def decryptIndex(self, index_cipher):
+        rows, cols = index_cipher
+        cap = max(1, len(rows) * len(cols) * self.cc.slots)
+        while True:
+            out = np.zeros(cap, dtype=np.uint64)
+            n = C.c_size_t()
+            _chk(self.cc.L.hydia_grote_decrypt_index(self.cc.h, rows.h, cols.h, self.numVectors, _p(out), cap, C.byref(n)))
+            if n.value <= cap:
+                return [int(v) for v in out[:n.value]]
+            cap = n.value

@@ -327,7 +327,46 @@ int hydia_merge_ciphers(hydia_ctx *ctx, const hydia_ct *in, size_t dimension, hy
  * what src/main.cpp:195-206 generates for binaryRotate.  Writes at most cap entries; *n_out = the size of the set. */
 int hydia_base_rotations(uint32_t slots, int32_t *rots, size_t cap, size_t *n_out);
 
+/* ---- approach 2, GROTE group testing (GroteSender / GroteReceiver) ----
+ * Enrolment (hydia_base_db_enroll), the query (hydia_encrypt_query), the keys (hydia_base_rotations) and computeSimilarity
+ * (hydia_base_compute_similarity) are approach 1's, on the chain of hydia_params_for_approach(2): depth 18, 19 + 6 limbs, N = 2^16.
+ * The S merged score ciphertexts are read as matrices of colLength rows x rowLength columns, rowLength = hydia_grote_row_length(slots),
+ * colLength = slots / rowLength; the row sums and column sums of score^(2^alpha + 1) go through the comparator in place of the scores:
+ * ceil(S / rowLength) + ceil(S / colLength) ciphertexts instead of S.  Conventions derived from OpenFHE's behaviour under FIXEDMANUAL,
+ * unverified: EvalSquareInPlace / EvalMult(ct, ct) relinearise and do not rescale; a product of operands on
+ * different limb counts drops the surplus limbs of the longer one without rescaling; a short packed plaintext is zero-padded.
+ * Errors: a missing rotation or relinearisation key, too few limbs, another database kind resident: HYDIA_ERR_STATE, before any work is
+ * enqueued; a row_length that is not a power of two in 2 .. slots: HYDIA_ERR_ARG.  HYDIA_GROTE_NO_SQ=1 routes the squares through the
+ * general product kernel; the same bits. */
+/* pow(2, ceil(log2(slots) / 2)), src/sender/sender_grote.cpp:18 and :44, src/receiver/receiver_grote.cpp:16.  Host only; 0 unless slots
+ * is a power of two >= 2 */
+uint32_t hydia_grote_row_length(uint32_t slots);
+/* HersSender::alphaNormRows, src/sender/sender_hers.cpp:118-132, on a caller's batch of `count` 2-component ciphertexts: per ciphertext
+ * alpha x (square, relinearise, rescale), the product with the input on the remaining limbs, c += Rot(c, 2^k) for 2^k < row_length, one
+ * rescale, then OpenFHEWrapper::mergeCiphers(., row_length).  out: ceil(count (slots / row_length) / slots) ciphertexts */
+int hydia_alpha_norm_rows(hydia_ctx *ctx, const hydia_ct *in, size_t alpha, size_t row_length, hydia_ct **out);
+/* HersSender::alphaNormColumns, src/sender/sender_hers.cpp:136-178: the same power, a rescale, c += binaryRotate(c, -j) for j =
+ * row_length, 2 row_length, .. < slots, the mask ones[0, row_length) with its rescale, ciphertext i into output (i row_length) div slots
+ * at slot offset (i row_length) mod slots.  out: ceil(count row_length / slots) ciphertexts */
+int hydia_alpha_norm_columns(hydia_ctx *ctx, const hydia_ct *in, size_t alpha, size_t row_length, hydia_ct **out);
+/* GroteSender::indexScenario, src/sender/sender_grote.cpp:38-73: computeSimilarity, the rows and the columns (the shared power formed
+ * once), each through chebyshevCompare(., 0.44^(2^ALPHA_DEPTH), COMP_DEPTH).  The reference returns the rows followed by the columns
+ * in one vector; their limb counts differ by one, so they are two batches here */
+int hydia_grote_index_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **rows, hydia_ct **cols);
+/* GroteSender::membershipScenario, src/sender/sender_grote.cpp:13-36: its alphaNormColumns result is never read and is not computed
+ * here; the ciphertext is hydia_base_membership_scenario's on this chain */
+int hydia_grote_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out);
+/* GroteReceiver::decryptIndex, src/receiver/receiver_grote.cpp:12-65: matches are values >= 1.0; flat row R and flat column C pair when
+ * R div colLength == C div rowLength (the same matrix) and give index R rowLength + C mod rowLength, rows outer, columns inner.  Two
+ * matches of one matrix on different rows and columns decode to all four crossings (group testing).  rows / cols must hold
+ * ceil(ceil(n_vectors / slots) / rowLength) and ceil(ceil(n_vectors / slots) / colLength) ciphertexts (:20-24; the reference prints an
+ * error): otherwise HYDIA_ERR_ARG.  Writes at most cap entries; *n_out = the number of indices */
+int hydia_grote_decrypt_index(hydia_ctx *ctx, const hydia_ct *rows, const hydia_ct *cols, size_t n_vectors, size_t *out, size_t cap, size_t *n_out);
+
 /* ---- evaluator primitives (used by the parity tests and by adapters) ---- */
+/* EvalSquare without relinearisation on the first n_limbs limbs of ct, read in place (0 = all): (c0^2, 2 c0 c1, c1^2), 3 components at
+ * scale^2 — what hydia_eval_mult_no_relin(ct, ct) gives on those limbs (approach 2's squaring kernel; HYDIA_GROTE_NO_SQ) */
+int hydia_eval_square_no_relin(hydia_ctx *ctx, const hydia_ct *ct, uint32_t n_limbs, hydia_ct **out);
 int hydia_ntt(hydia_ctx *ctx, uint64_t *data /* host, [count][N] in place */, uint32_t count, uint32_t modulus_index,
               int inverse);
 int hydia_eval_rotate(hydia_ctx *ctx, const hydia_ct *in, int rot, hydia_ct **out);

@@ -1,5 +1,5 @@
-// include/hydia_roles.hpp — the reference's C++ role surface for approach 5 (HyDia), approach 4 (HERS) and approach 1 (the literature
-// baseline: include/{enroller,receiver,sender}_base.h), over the C-ABI of hydia.h.
+// include/hydia_roles.hpp — the reference's C++ role surface for approach 5 (HyDia), approach 4 (HERS), approach 1 (the literature
+// baseline: include/{enroller,receiver,sender}_base.h) and approach 2 (GROTE: include/{receiver,sender}_grote.h), over the C-ABI of hydia.h.
 //
 // Same class and method names as /root/reference/include/{sender,sender_diag,receiver,receiver_hers,receiver_diag,
 // enroller_diag,enroller_hers}.h and the same constructor arguments (include/sender.h:22 `(cc, pk, numVectors)`,
@@ -490,7 +490,7 @@ class BaseSender : public HersSender {
         return out ? split_batch(cc, out) : std::vector<Ciphertext>{};
     }
 
-  private:
+  protected:
     hydia_ct *run(std::vector<Ciphertext> &q, int (*fn)(hydia_ctx *, const hydia_ct *, hydia_ct **), const char *what) {
         hydia_ct *out = nullptr;
         if (q.empty() || !q[0]) {
@@ -521,6 +521,52 @@ class BaseEnroller : public EnrollerBase {  // include/enroller_base.h
         std::vector<double> flat = flatten(database);
         if (!cc->check(hydia_base_db_enroll(cc->h, flat.data(), numVectors, seed), "serializeDB")) return;
         write_back(flat, database);
+    }
+};
+
+// ---- GROTE group testing, approach 2: include/sender_grote.h (derives from BaseSender), include/receiver_grote.h (from BaseReceiver).
+// The enroller is BaseEnroller (src/main.cpp:236-238), the keys are KeyGenBaseline's, computeSimilarity is BaseSender's.
+class GroteSender : public BaseSender {
+  public:
+    GroteSender(CryptoContext ccParam, size_t vectorParam) : BaseSender(std::move(ccParam), vectorParam) {}
+    GroteSender(CryptoContext ccParam, PublicKey pkParam, size_t vectorParam) : BaseSender(std::move(ccParam), pkParam, vectorParam) {}  // sender_grote.cpp:7-9
+    // sender_grote.cpp:13-36: the reference's alphaNormColumns result is never read; BaseSender's ciphertext on this chain
+    Ciphertext membershipScenario(std::vector<Ciphertext> &queryCipher) override {
+        hydia_ct *out = run(queryCipher, hydia_grote_membership_scenario, "membershipScenario");
+        return out ? split_batch(cc, out)[0] : Ciphertext{};
+    }
+    // sender_grote.cpp:38-73: the row ciphertexts followed by the column ciphertexts (two device batches: their limb counts differ)
+    std::vector<Ciphertext> indexScenario(std::vector<Ciphertext> &queryCipher) override {
+        if (queryCipher.empty() || !queryCipher[0]) {
+            std::cerr << "Error: empty query ciphertext" << std::endl;
+            return {};
+        }
+        hydia_ct *rows = nullptr, *cols = nullptr;
+        if (!cc->check(hydia_grote_index_scenario(cc->h, queryCipher[0].batch->h, &rows, &cols), "indexScenario")) return {};
+        std::vector<Ciphertext> r = split_batch(cc, rows), c = split_batch(cc, cols);
+        r.insert(r.end(), c.begin(), c.end());
+        return r;
+    }
+};
+class GroteReceiver : public BaseReceiver {
+  public:
+    using BaseReceiver::BaseReceiver;
+    // receiver_grote.cpp:12-65: the vector is split by the reference's counts (:20-26); each part must be the whole of one batch
+    std::vector<size_t> decryptIndex(std::vector<Ciphertext> &indexCipher) override {
+        const size_t batchSize = cc->GetBatchSize(), rowLength = hydia_grote_row_length((uint32_t)batchSize), colLength = batchSize / rowLength;
+        const size_t mats = (numVectors + batchSize - 1) / batchSize;
+        const size_t numRowCiphers = (mats + rowLength - 1) / rowLength, numColCiphers = (mats + colLength - 1) / colLength;
+        if (numRowCiphers + numColCiphers != indexCipher.size() || !indexCipher[0] || !indexCipher[numRowCiphers] ||
+            indexCipher[0].batch->count() != numRowCiphers || indexCipher[numRowCiphers].batch->count() != numColCiphers) {
+            std::cerr << "Error: incorrect parsing of index query results" << std::endl;
+            return {};
+        }
+        const hydia_ct *rows = indexCipher[0].batch->h, *cols = indexCipher[numRowCiphers].batch->h;
+        size_t n = 0;
+        if (!cc->check(hydia_grote_decrypt_index(cc->h, rows, cols, numVectors, nullptr, 0, &n), "decryptIndex")) return {};
+        std::vector<size_t> out(n);
+        if (n && !cc->check(hydia_grote_decrypt_index(cc->h, rows, cols, numVectors, out.data(), n, &n), "decryptIndex")) return {};
+        return out;
     }
 };
 

@@ -4,7 +4,11 @@
 min, max, standard deviation over the timed steps), vectors/s, the split into similarity / merge / comparator by HIP events on the
 library's stream, and the byte ledger's inherent bytes (op:*) of one query.  The fused paths are switched by the environment
 (HYDIA_BASE_NO_ROTADD, HYDIA_BASE_NO_BCAST, HYDIA_BASE_CHUNK); the line records what was set.  Results are checked: the index is
-the planted matches."""
+the planted matches.
+
+--approach 2 runs GROTE group testing (GroteSender / GroteReceiver) on its own chain (hydia_params_for_approach(2): 19 + 6 limbs) over
+the same kind of database: the line then also splits the alpha norm (grote_alpha / grote_rows / grote_cols / grote_compare) and records
+HYDIA_GROTE_NO_SQ.  One match is planted there: group testing answers several matches of one matrix with all their crossings."""
 import argparse
 import json
 import os
@@ -16,18 +20,20 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import image_matching_amd as im  # noqa: E402
 
-PHASES = ("base_similarity", "base_merge", "base_compare")
+PHASES = {1: ("base_similarity", "base_merge", "base_compare"),
+          2: ("base_similarity", "base_merge", "grote_alpha", "grote_rows", "grote_cols", "grote_compare")}
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--approach", type=int, default=1, choices=(1, 2))
     ap.add_argument("--log2n", type=int, default=10)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--log-n", type=int, default=0, help="ring override for a quick look (0 = approach 1's own ring)")
+    ap.add_argument("--log-n", type=int, default=0, help="ring override for a quick look (0 = the approach's own ring)")
     ap.add_argument("--dim", type=int, default=512)
     args = ap.parse_args()
-    p = im.params_for_approach(1)
+    p = im.params_for_approach(args.approach)
     if args.log_n:
         p.log_n = args.log_n
     p.vector_dim = args.dim
@@ -36,7 +42,7 @@ def main():
     n = 1 << args.log2n
     rng = np.random.default_rng(args.log2n)
     db = rng.integers(-99, 100, size=(n, args.dim), dtype=np.int8).astype(np.float64)
-    planted = sorted(set([0, n // 2, n - 1]))
+    planted = sorted(set([0, n // 2, n - 1])) if args.approach == 1 else [n // 2 + 1]
     for i in planted:
         db[i] = rng.integers(1, 4, size=args.dim)
     query = np.ones(args.dim)
@@ -44,7 +50,7 @@ def main():
     im.BaseEnroller(cc, n).serializeDB(db, seed=3)
     cc.sync()
     enroll_s = time.time() - t0
-    receiver, sender = im.BaseReceiver(cc, n), im.BaseSender(cc, n)
+    receiver, sender = (im.BaseReceiver(cc, n), im.BaseSender(cc, n)) if args.approach == 1 else (im.GroteReceiver(cc, n), im.GroteSender(cc, n))
     q = receiver.encryptQuery(query, seed=5)
     for _ in range(args.warmup):
         idx = sender.indexScenario(q)
@@ -56,7 +62,7 @@ def main():
         idx = sender.indexScenario(q)
         cc.sync()
         ms.append((time.time() - t0) * 1e3)
-    split = {k: round(cc.kernel_time(k)[0] / args.steps, 3) for k in PHASES}
+    split = {k: round(cc.kernel_time(k)[0] / args.steps, 3) for k in PHASES[args.approach]}
     ok = receiver.decryptIndex(idx) == planted
     im.byte_ledger(1)
     idx = sender.indexScenario(q)
@@ -65,9 +71,9 @@ def main():
     ops = {k: b for k, (_, b) in led.items() if k.startswith("op:")}
     launches = sum(c for k, (c, _) in led.items() if not k.startswith("op:"))
     mean = float(np.mean(ms))
-    env = {k: os.environ[k] for k in ("HYDIA_BASE_NO_ROTADD", "HYDIA_BASE_NO_BCAST", "HYDIA_BASE_CHUNK") if k in os.environ}
+    env = {k: os.environ[k] for k in ("HYDIA_BASE_NO_ROTADD", "HYDIA_BASE_NO_BCAST", "HYDIA_BASE_CHUNK", "HYDIA_GROTE_NO_SQ") if k in os.environ}
     print(json.dumps({
-        "metric": "approach1_index_scenario", "log2n": args.log2n, "n": n, "ring_log_n": int(p.log_n), "vector_dim": args.dim,
+        "metric": "approach%d_index_scenario" % args.approach, "log2n": args.log2n, "n": n, "ring_log_n": int(p.log_n), "vector_dim": args.dim,
         "db_cts": cc.db_stats()[1], "db_bytes": cc.db_stats()[2], "env": env, "steps": args.steps, "warmup": args.warmup,
         "ms_per_query": round(mean, 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3), "ms_std": round(float(np.std(ms)), 3),
         "vectors_per_s": round(n / mean * 1e3, 1), "split_ms": split, "enroll_s": round(enroll_s, 2), "correct": bool(ok),
