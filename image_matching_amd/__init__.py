@@ -6,7 +6,7 @@ raises if the HIP library is missing.
 """
 from .hydia import (Context, Ciphertext, DiagonalEnroller, DiagonalReceiver, DiagonalSender, HydiaError,  # noqa: F401
                     HersEnroller, HersReceiver, HersSender, BaseEnroller, BaseReceiver, BaseSender, base_rotations,
-                    GroteReceiver, GroteSender, grote_row_length,
+                    GroteReceiver, GroteSender, grote_row_length, BlindEnroller, BlindReceiver, BlindSender, BLIND_CHUNK_LEN,
                     byte_ledger, default_params, describe_params, compute_required_depth, lib_path, load_library,
                     params_for_approach)
 from .sharding import (ShardGroup, ShardedDiagonalEnroller, ShardedDiagonalSender, DistDiagonalEnroller,  # noqa: F401
@@ -15,3 +15,4 @@ from .sharding import (ShardGroup, ShardedDiagonalEnroller, ShardedDiagonalSende
 MATCH_THRESHOLD = 0.44  # include/config.h:9
 COMP_DEPTH = 10         # include/config.h:14
 VECTOR_DIM = 512        # include/config.h:30
+CHUNK_LEN = BLIND_CHUNK_LEN  # include/config.h:34

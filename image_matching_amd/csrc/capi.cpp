@@ -310,6 +310,7 @@ int hydia_ct_export(hydia_ctx *ctx, const hydia_ct *ct, uint64_t *data) {
     API_BEGIN
     use_device(ctx);
     REQUIRE(ctx && ct && data, "null argument");
+    REQUIRE(ct->c.compact(), "a limb-prefix view is not exported: copy it with hydia_level_reduce first");
     ctx->cx.sync();
     HIP_CHECK(hipMemcpy(data, ct->c.d, ct->c.bytes(), hipMemcpyDeviceToHost));
     return HYDIA_OK;
@@ -333,6 +334,7 @@ int hydia_ct_copy_to_device(hydia_ctx *ctx, const hydia_ct *ct, void *dev_dst) {
     API_BEGIN
     use_device(ctx);
     REQUIRE(ctx && ct && dev_dst, "null argument");
+    REQUIRE(ct->c.compact(), "a limb-prefix view is not copied out: copy it with hydia_level_reduce first");
     HIP_CHECK(hipMemcpyAsync(dev_dst, ct->c.d, ct->c.bytes(), hipMemcpyDeviceToDevice, ctx->cx.stream));
     ctx->cx.sync();
     return HYDIA_OK;
@@ -366,6 +368,20 @@ int hydia_ct_view_device(hydia_ctx *ctx, void *dev_ptr, uint32_t count, uint32_t
     h->c.nl = h->c.lstride = (int)n_limbs;
     h->c.scale = scale;
     h->c.view = true;
+    h->owner = ctx;
+    ctx->refs.fetch_add(1);
+    *out = h;
+    return HYDIA_OK;
+    API_END
+}
+// a handle over the first n_limbs limbs of ct, read where they lie (no copy; the limb stride stays ct's): what a level drop without
+// rescaling leaves, and how the tests hand limb-strided operands to kernels that take a stride.  ct must outlive the handle
+int hydia_ct_limb_prefix(hydia_ctx *ctx, const hydia_ct *ct, uint32_t n_limbs, hydia_ct **out) {
+    API_BEGIN
+    REQUIRE(ctx && ct && out, "null argument");
+    REQUIRE(n_limbs >= 1 && (int)n_limbs <= ct->c.nl, "limb count outside 1 .. the ciphertext's");
+    hydia_ct *h = new hydia_ct;
+    h->c = ct->c.alias((int)n_limbs);
     h->owner = ctx;
     ctx->refs.fetch_add(1);
     *out = h;
@@ -656,6 +672,64 @@ int hydia_grote_decrypt_index(hydia_ctx *ctx, const hydia_ct *rows, const hydia_
     return HYDIA_OK;
     API_END
 }
+// ------------------------------------------------------------------ approach 3 (the Blind-Match method)
+size_t hydia_blind_db_num_cts(const hydia_ctx *ctx, size_t n, size_t chunk_len) {
+    if (!ctx || chunk_len > (size_t)INT32_MAX) return 0;
+    try {
+        (void)ctx->cx.blind_chunks((int)chunk_len);
+    } catch (...) {
+        return 0;
+    }
+    return ctx->cx.blind_db_cts(n, (int)chunk_len);
+}
+int hydia_blind_db_enroll(hydia_ctx *ctx, double *db, size_t n, size_t chunk_len, const uint8_t seed[32]) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && db && seed && n >= 1, "bad argument");
+    REQUIRE(chunk_len <= (size_t)INT32_MAX, "chunk_len must be a power of two in 2 .. slots that divides vector_dim");
+    Context &cx = ctx->cx;
+    (void)cx.blind_chunks((int)chunk_len);  // validates before the resident database is touched
+    cx.db_kind = 0;
+    cx.db_resize_rows(n, cx.blind_db_cts(n, (int)chunk_len));
+    client_blind_enroll(cx, db, n, (int)chunk_len, seed);
+    cx.db_kind = 3;
+    cx.db_babies = 0;
+    cx.db_chunk_len = (int)chunk_len;
+    return HYDIA_OK;
+    API_END
+}
+int hydia_blind_encrypt_query(hydia_ctx *ctx, const double *query, size_t chunk_len, const uint8_t seed[32], uint64_t nonce0, hydia_ct **out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && query && seed && out, "null argument");
+    REQUIRE(chunk_len <= (size_t)INT32_MAX, "chunk_len must be a power of two in 2 .. slots that divides vector_dim");
+    const int K = ctx->cx.blind_chunks((int)chunk_len);
+    REQUIRE(nonce0 < HYDIA_NONCE_LIMIT && nonce0 + (uint64_t)K <= HYDIA_NONCE_LIMIT, "nonce must be below 2^40");
+    *out = wrap(ctx, client_blind_encrypt_query(ctx->cx, query, (int)chunk_len, seed, nonce0));
+    return HYDIA_OK;
+    API_END
+}
+/* receiver_blind.cpp:28-54 */
+int hydia_blind_decrypt_index(hydia_ctx *ctx, const hydia_ct *cts, size_t chunk_len, size_t *out, size_t cap, size_t *n_out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && cts && n_out, "null argument");
+    const size_t S = ctx->cx.slots;
+    REQUIRE(chunk_len >= 1 && chunk_len <= S && (chunk_len & (chunk_len - 1)) == 0, "chunk_len must be a power of two of at most `slots`");
+    const size_t spb = S / chunk_len;  // scoresPerBatch
+    std::vector<double> v((size_t)cts->c.X * S);
+    client_decrypt(ctx->cx, cts->c, v.data());
+    size_t cnt = 0;
+    for (size_t i = 0; i < (size_t)cts->c.X; i++)
+        for (size_t j = 0; j < S; j++)
+            if (v[i * S + j] >= 1.0) {  // indices of the padding past n_vectors are NOT filtered: the reference does not either
+                if (out && cnt < cap) out[cnt] = i * S + j / chunk_len + (j % chunk_len) * spb;
+                cnt++;
+            }
+    *n_out = cnt;
+    return HYDIA_OK;
+    API_END
+}
 int hydia_db_save(hydia_ctx *ctx, const char *path) {
     API_BEGIN
     use_device(ctx);
@@ -813,6 +887,17 @@ int hydia_grote_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia
 int hydia_eval_square_no_relin(hydia_ctx *ctx, const hydia_ct *query, uint32_t n_limbs, hydia_ct **out) {
     if (query && n_limbs > (uint32_t)query->c.nl) return fail(HYDIA_ERR_ARG, "hydia: more limbs than the ciphertext has");
     SENDER_CALL(ctx->cx.grote_square(query->c.alias(n_limbs ? (int)n_limbs : query->c.nl)))
+}
+int hydia_blind_compute_similarity(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.blind_similarity(query->c)) }
+int hydia_blind_index_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.blind_index_scenario(query->c)) }
+int hydia_blind_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.blind_membership_scenario(query->c)) }
+int hydia_compress_ciphers(hydia_ctx *ctx, const hydia_ct *query, size_t dimension, hydia_ct **out) {
+    if (dimension > (size_t)INT32_MAX) return fail(HYDIA_ERR_ARG, "hydia: the compression dimension must be a power of two in 2 .. slots");
+    SENDER_CALL(ctx->cx.compress_ciphers(query->c, (int)dimension))
+}
+int hydia_eval_dot_no_relin(hydia_ctx *ctx, const hydia_ct *query, const hydia_ct *b, hydia_ct **out) {
+    if (!b) return fail(HYDIA_ERR_ARG, "null argument");
+    SENDER_CALL(ctx->cx.eval_dot_no_relin(query->c, b->c))
 }
 // ------------------------------------------------------------------ primitives
 int hydia_ntt(hydia_ctx *ctx, uint64_t *data, uint32_t count, uint32_t m, int inverse) {

@@ -8,8 +8,9 @@
 //
 //   HYDIA_DEVICES=0,1,2,3   shard the encrypted database over these GPUs (an index may repeat: several shards on one GPU)
 //   HYDIA_SEED=<integer>    reproducible key / encryption randomness (default: operating-system entropy)
-// Approaches 5 (HyDia), 4 (HERS) and 1 (the literature baseline, on the N = 2^16 ring of hydia_params_for_approach) exist on this
-// stack; 2 and 3 are refused.
+// Approaches 5 (HyDia), 4 (HERS) and 1 (the literature baseline, on the N = 2^16 ring of hydia_params_for_approach) have an entry
+// here; 2 (GROTE) and 3 (Blind-Match) run through their role classes (include/hydia_roles.hpp) and are refused here: the suite pins
+// that answer.
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -124,7 +125,8 @@ int main(int argc, char *argv[]) {
     for (const Approach &a : APPROACHES)
         if (a.id == wanted) approach = &a;
     if (!approach)
-        return usage_error("only approach 5 (novel diagonal transform, HyDia), approach 4 (HERS) and approach 1 (literature baseline) are built in hydia-mi355x");
+        return usage_error("only approach 5 (novel diagonal transform, HyDia), approach 4 (HERS) and approach 1 (literature baseline) have a command-line entry in hydia-mi355x; "
+                           "approach 2 (GROTE) and approach 3 (Blind-Match) run through the role classes of include/hydia_roles.hpp");
     std::ofstream csv("latency.csv" /* EXP_FILEPATH, include/config.h:36 */, std::ios::app);
     if (!csv.is_open()) return usage_error("experiment file not found");
 

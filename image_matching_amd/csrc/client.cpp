@@ -322,6 +322,48 @@ void client_base_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32
     cx.pool.put((u64 *)d_slots);
     cx.pool.put((u64 *)d_rows);
 }
+#define HY_BLIND_NONCE_BASE (1ull << 38)
+// BlindEnroller::serializeDB (/root/reference/src/enroller/enroller_blind.cpp:13-90): normalise in place, then per matrix m of
+// slots / chunk_len vectors the K = dim / chunk_len slot images of k_chunk_pack, encrypted with nonces HY_BLIND_NONCE_BASE + m K + c
+// straight into the resident kind-3 layout (ciphertext t = m K + c)
+void client_blind_enroll(Context &cx, double *db, size_t n, int chunk_len, const uint8_t seed[32]) {
+    const int dim = cx.prm.dim, Nh = cx.slots, K = dim / chunk_len;
+    for (size_t v = 0; v < n; v++) normalize(db + v * dim, dim);
+    const ChaChaKey key = make_key(seed);
+    const size_t cts = cx.db_cts, ct_elems = (size_t)2 * cx.nQ * cx.N, spb = (size_t)(Nh / chunk_len), M = cts / (size_t)K;
+    if (cts > HY_NONCE_LIMIT - HY_BLIND_NONCE_BASE) throw std::runtime_error("hydia: the database exceeds the 2^40 nonce space of the encryption sampler");
+    double *d_rows = (double *)cx.pool.get(sizeof(double) * spb * dim);
+    double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)K * Nh);
+    u64 *d_cts = cx.pool.get(sizeof(u64) * (size_t)K * ct_elems);
+    for (size_t m = 0; m < M; m++) {
+        const size_t first = m * spb, rows = n > first ? std::min(spb, n - first) : 0;
+        if (rows) HIP_CHECK(hipMemcpyAsync(d_rows, db + first * dim, sizeof(double) * rows * dim, hipMemcpyHostToDevice, cx.stream));
+        hc::chunk_pack(cx.stream, d_rows, (long long)rows, dim, chunk_len, Nh, d_slots);
+        encrypt_device(cx, d_slots, K, key, HY_BLIND_NONCE_BASE + m * (size_t)K, d_cts);
+        cx.db_store(m * (size_t)K, d_cts, K);
+    }
+    cx.sync();
+    cx.pool.put(d_cts);
+    cx.pool.put((u64 *)d_slots);
+    cx.pool.put((u64 *)d_rows);
+}
+// BlindReceiver::encryptQuery (/root/reference/src/receiver/receiver_blind.cpp:13-26, :58-71): normalise, then K = dim / chunk_len
+// ciphertexts, ciphertext c = chunk c tiled over all slots, nonce nonce0 + c
+Ct client_blind_encrypt_query(Context &cx, const double *query, int chunk_len, const uint8_t seed[32], uint64_t nonce0) {
+    const int dim = cx.prm.dim, Nh = cx.slots, K = dim / chunk_len;
+    std::vector<double> qn(query, query + dim);
+    normalize(qn.data(), dim);
+    double *d_q = (double *)cx.pool.get(sizeof(double) * (size_t)dim);
+    double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)K * Nh);
+    HIP_CHECK(hipMemcpyAsync(d_q, qn.data(), sizeof(double) * dim, hipMemcpyHostToDevice, cx.stream));
+    hc::chunk_tile(cx.stream, d_q, dim, chunk_len, Nh, d_slots);
+    Ct out(&cx, K, 2, cx.nQ, cx.delta);
+    encrypt_device(cx, d_slots, K, make_key(seed), nonce0, out.d);
+    cx.sync();  // qn is a stack-owned buffer
+    cx.pool.put((u64 *)d_slots);
+    cx.pool.put((u64 *)d_q);
+    return out;
+}
 // HersReceiver::encryptQuery (/root/reference/src/receiver/receiver_hers.cpp:13-24): vector_dim ciphertexts
 Ct client_hers_encrypt_query(Context &cx, const double *query, const uint8_t seed[32], uint64_t nonce0) {
     const int dim = cx.prm.dim, Nh = cx.slots;

@@ -24,4 +24,8 @@ void client_hers_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32
 Ct client_hers_encrypt_query(Context &cx, const double *query, const uint8_t seed[32], uint64_t nonce0);
 // BaseEnroller (approach 1, the literature baseline): row-packed enrolment into database kind 1; ciphertext t takes nonce base + t
 void client_base_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32]);
+// BlindEnroller / BlindReceiver (approach 3, Blind-Match): chunk-packed enrolment into database kind 3 (ciphertext m K + c = chunk c of
+// matrix m, nonce base + m K + c, K = vector_dim / chunk_len) and the K tiled query ciphertexts (nonces nonce0 + c)
+void client_blind_enroll(Context &cx, double *db, size_t n, int chunk_len, const uint8_t seed[32]);
+Ct client_blind_encrypt_query(Context &cx, const double *query, int chunk_len, const uint8_t seed[32], uint64_t nonce0);
 }  // namespace hydia

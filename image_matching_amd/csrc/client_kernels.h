@@ -40,5 +40,8 @@ void diag_pack(hipStream_t st, const double *dbg, long long rows_left, int dim, 
 void hers_pack(hipStream_t st, const double *dbg, long long rows_left, int dim, int Nh, double *slots);
 // BaseEnroller (approach 1): slot vector x = rows x vpc .. x vpc + vpc - 1 back to back (vpc = Nh / dim), zeros past the last row
 void row_pack(hipStream_t st, const double *dbg, long long elems_left, int Nh, double *slots, int X);
+// approach 3: the dim / chunk slot images of one matrix of Nh / chunk vectors, and the dim / chunk tiled images of a query
+void chunk_pack(hipStream_t st, const double *rows, long long rows_left, int dim, int chunk, int Nh, double *slots);
+void chunk_tile(hipStream_t st, const double *q, int dim, int chunk, int Nh, double *slots);
 void broadcast_rows(hipStream_t st, const double *vals, int dim, int Nh, double *slots);
 }  // namespace hc

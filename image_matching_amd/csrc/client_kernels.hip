@@ -281,6 +281,21 @@ __global__ __launch_bounds__(256) void k_row_pack(const double *__restrict__ dbg
     const long long e = (long long)blockIdx.y * Nh + s;
     slots[e] = e < elems_left ? dbg[e] : 0.0;
 }
+// BlindEnroller::serializeDBThread's packing (/root/reference/src/enroller/enroller_blind.cpp:66-80) for ONE matrix: slot image c holds
+// coordinates [c chunk, (c + 1) chunk) of vector v at slots [v chunk, (v + 1) chunk), zeros past the last row.  rows points at the
+// matrix's first vector (row-major, dim values each).  grid (Nh/256, dim / chunk)
+__global__ __launch_bounds__(256) void k_chunk_pack(const double *__restrict__ rows, long long rows_left, int dim, int chunk, int Nh,
+                                                    double *__restrict__ slots) {
+    const int s = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
+    const long long v = s / chunk;
+    slots[(size_t)c * Nh + s] = v < rows_left ? rows[(size_t)v * dim + (size_t)c * chunk + s % chunk] : 0.0;
+}
+// BlindReceiver::encryptQueryThread (/root/reference/src/receiver/receiver_blind.cpp:58-67): slot image c = chunk c of the query tiled
+// over all slots.  grid (Nh/256, dim / chunk)
+__global__ __launch_bounds__(256) void k_chunk_tile(const double *__restrict__ q, int chunk, int Nh, double *__restrict__ slots) {
+    const int s = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
+    slots[(size_t)c * Nh + s] = q[(size_t)c * chunk + s % chunk];
+}
 // HersReceiver::encryptQueryThread (/root/reference/src/receiver/receiver_hers.cpp:58-63): every slot = coordinate i
 __global__ __launch_bounds__(256) void k_broadcast_rows(const double *__restrict__ vals, int Nh, double *__restrict__ slots) {
     slots[(size_t)blockIdx.y * Nh + blockIdx.x * 256 + threadIdx.x] = vals[blockIdx.y];
@@ -349,6 +364,12 @@ void decode(hipStream_t st, const ModC *mod, const u64 *t, int nu, int N, int X,
 }
 void hers_pack(hipStream_t st, const double *dbg, long long rows_left, int dim, int Nh, double *slots) {
     hipLaunchKernelGGL(k_hers_pack, dim3(Nh / 256, dim), dim3(256), 0, st, dbg, rows_left, dim, Nh, slots);
+}
+void chunk_pack(hipStream_t st, const double *rows, long long rows_left, int dim, int chunk, int Nh, double *slots) {
+    hipLaunchKernelGGL(k_chunk_pack, dim3(Nh / 256, dim / chunk), dim3(256), 0, st, rows, rows_left, dim, chunk, Nh, slots);
+}
+void chunk_tile(hipStream_t st, const double *q, int dim, int chunk, int Nh, double *slots) {
+    hipLaunchKernelGGL(k_chunk_tile, dim3(Nh / 256, dim / chunk), dim3(256), 0, st, q, chunk, Nh, slots);
 }
 void row_pack(hipStream_t st, const double *dbg, long long elems_left, int Nh, double *slots, int X) {
     hipLaunchKernelGGL(k_row_pack, dim3(Nh / 256, X), dim3(256), 0, st, dbg, elems_left, Nh, slots);

@@ -289,6 +289,8 @@ Context::Context(const Params &p, int dev) : HostParams(p), device(dev) {
     if (getenv("HYDIA_BASE_NO_BCAST")) base_bcast = false;
     if (const char *e = getenv("HYDIA_BASE_CHUNK")) base_chunk_env = std::max(0, atoi(e));
     if (getenv("HYDIA_GROTE_NO_SQ")) grote_sq = false;
+    if (getenv("HYDIA_BLIND_NO_DOT")) blind_fused = false;
+    if (const char *e = getenv("HYDIA_BLIND_PASS")) blind_pass_env = std::max(0, atoi(e));
     for (int k = 1; k < nlanes; k++) {
         hipStream_t st;
         HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -578,8 +580,8 @@ void Context::db_resize(size_t n_vectors, size_t cts, int form) {
     // database, whose blocks are the (database block, giant step) pairs)
     db_lay = want;
 }
-// kind 1 (approach 1's rows): plain 8-byte residues, ciphertext-major, whatever the context packs — the query-broadcast product
-// reads the ciphertexts where they lie
+// kind 1 (approach 1's rows) and kind 3 (approach 3's chunks): plain 8-byte residues, ciphertext-major, whatever the context packs —
+// the query-broadcast product and the fused sum of products read the ciphertexts where they lie
 void Context::db_resize_rows(size_t n_vectors, size_t cts) {
     const bool keep = db_packed;
     db_packed = false;
@@ -672,6 +674,7 @@ struct DbConv {
 void Context::db_save(const char *path) {
     if (!d_db || db_cts == 0) throw StateError("hydia: no database resident");
     if (db_kind == 1) throw StateError("hydia: a row-packed database (approach 1) is not saved: the file format describes the context's packing, not kind 1's plain residues");
+    if (db_kind == 3) throw StateError("hydia: a chunk-packed database (approach 3) is not saved: the file format describes the context's packing, not kind 3's plain residues");
     sync_all();
     FileCloser fc{fopen(path, "wb")};
     if (!fc.f) throw std::runtime_error(std::string("hydia: cannot open ") + path + " for writing");

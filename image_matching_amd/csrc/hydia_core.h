@@ -160,7 +160,7 @@ struct Context : HostParams {
     // 48-bit residues when every scaling prime is below 2^48; HYDIA_DB_UNPACKED keeps plain [2][nQ][N] u64)
     unsigned char *d_db = nullptr;
     size_t db_vectors = 0, db_cts = 0;
-    int db_kind = 0;   // 0 none, 1 row packing (approach 1, the literature baseline: plain 8-byte residues, ciphertext-major), 5 diagonal packing (HyDia, approach 5), 6 the same with pre-rotated diagonals (BSGS mat-vec), 4 column packing (HERS)
+    int db_kind = 0;   // 0 none, 1 row packing (approach 1, the literature baseline: plain 8-byte residues, ciphertext-major), 3 chunk packing (approach 3, Blind-Match: the same storage, db_chunk_len), 5 diagonal packing (HyDia, approach 5), 6 the same with pre-rotated diagonals (BSGS mat-vec), 4 column packing (HERS)
     int db_babies = 0; // kind 5 / 6: hoisted (baby) rotations the resident database was enrolled for; == vector_dim for kind 5
     // Which form of the diagonal mat-vec a database enrolled on this context gets (HYDIA_MATVEC=auto|hoisted|bsgs|<B>, hydia_set_matvec).
     // With i = b + B g: B - 1 hoisted rotations of the query per QUERY, dim / B relinearisations + dim / B - 1 giant rotations per BLOCK.
@@ -350,7 +350,7 @@ struct Context : HostParams {
     void base_check_query(const Ct &q) const;
     void base_check_keys(const std::vector<int> &rots) const;  // StateError naming the first missing rotation (or the relinearisation key)
     std::vector<int> merge_rotations(size_t n_cts, int dimension) const;  // every key-switch rotation of mergeCiphers on n_cts ciphertexts
-    // HIP-event time of a query's phases ("base_similarity", "base_merge", "base_compare"), kept apart from `timers` because a phase
+    // HIP-event time of a query's phases ("base_similarity", "base_merge", "base_compare"; "blind_*" for approach 3), kept apart from `timers` because a phase
     // encloses timed launches: only completed pairs are ever stored; base_phase_collect adds them to timers[name] (hydia_kernel_time)
     struct PhaseEv {
         const char *name;
@@ -388,6 +388,30 @@ struct Context : HostParams {
     Ct alpha_norm_columns(const Ct &in, int alpha_depth, int row_length);
     void grote_index_scenario(const Ct &q, Ct &rows, Ct &cols);
     Ct grote_membership_scenario(const Ct &q);
+
+    // ---- approach 3, the Blind-Match method (src/sender/sender_blind.cpp, OpenFHEWrapper::compressCiphers); blind.cpp.  Database kind 3:
+    // matrix m = slots / chunk_len vectors as K = vector_dim / chunk_len ciphertexts m K + c, plain 8-byte residues like kind 1
+#define HY_BLIND_MAX_CHUNKS 32  // K: 2 K products below 2^120 fit k_tensor_dot's 128-bit lazy sums
+    int db_chunk_len = 0;       // kind 3: the chunk length the resident database was enrolled with
+    bool blind_fused = true;    // HYDIA_BLIND_NO_DOT: the sum of products through k_tensor<false> and additions instead of k_tensor_dot; the same residues
+    int blind_pass_env = 0;     // HYDIA_BLIND_PASS: matrices per pass (0 = from free memory)
+    int blind_chunks(int chunk_len) const;  // K; runtime_error unless chunk_len is a power of two dividing vector_dim with K <= 32
+    size_t blind_db_cts(size_t n_vectors, int chunk_len) const {
+        const size_t spb = (size_t)(slots / chunk_len);
+        return (n_vectors + spb - 1) / spb * (size_t)(prm.dim / chunk_len);
+    }
+    int blind_pass(size_t matrices);
+    Ct blind_dot(const u64 *q, int q_ls, const u64 *b, int b_ls, int C, int K, int nl, double scale);  // sum_c q[c] (x) b[x][c], 3 components
+    Ct eval_dot_no_relin(const Ct &q, const Ct &b);               // the same on caller's batches (q: K, b: M K ciphertexts)
+    Ct blind_similarity_chunk(const Ct &q, size_t m0, int C);     // computeSimilarityMatrix on matrices m0 .. m0+C-1
+    std::vector<int> compress_rotations(size_t n_cts, int dimension) const;  // every key-switch rotation of compressCiphers on n_cts ciphertexts
+    // compressCiphers' placement: masked ciphertexts i0 .. i0+X-1 into out (n_out outputs, allocated at the first call); the calls walk i upwards
+    void compress_place(const Ct &masked, size_t i0, int dimension, Ct &out, size_t n_out);
+    Ct compress_ciphers(const Ct &in, int dimension);
+    void blind_check_query(const Ct &q) const;  // StateError: no kind-3 database, chain too short; runtime_error: not K fresh ciphertexts
+    Ct blind_similarity(const Ct &q);
+    Ct blind_index_scenario(const Ct &q);
+    Ct blind_membership_scenario(const Ct &q);
 
     // ---- HyDia sender (src/sender/sender_diag.cpp)
     Ct rotate_query(const Ct &q);                   // -> [dim][2][nQ][N]

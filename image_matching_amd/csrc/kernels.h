@@ -319,6 +319,10 @@ void tensor_sq(hipStream_t st, const ModC *mod, int N, const u64 *a, u64 *o, int
 // approach 1's query-broadcast product: ONE 2-component ciphertext q ([2][q_ls][N]) times X ciphertexts b ([X][2][b_ls][N], e.g. the
 // row-packed resident database read in place) -> o [X][3][nl][N]; the residues k_tensor gives for X copies of q
 void tensor_bcast(hipStream_t st, const ModC *mod, int N, const u64 *q, int q_ls, const u64 *b, int b_ls, u64 *o, int X, int nl);
+// approach 3's fused sum of products: K query ciphertexts q ([K][2][q_ls][N]) times the K chunk ciphertexts of each of X matrices b
+// ([X][K][2][b_ls][N], e.g. the chunk-packed resident database read in place) -> o [X][3][nl][N], o[x] = sum_c q[c] (x) b[x][c]; the
+// residues K tensor products summed with add give.  K <= 32 (the 128-bit lazy sums hold 64 products on the 60-bit limb)
+void tensor_dot(hipStream_t st, const ModC *mod, int N, const u64 *q, int q_ls, const u64 *b, int b_ls, u64 *o, int X, int K, int nl);
 
 // ---- key switching
 // out[x][t][c] = sum_s y[x][s][c] * tab.f[s][t] mod q_{dsel.mod[t]} ; y coefficient form, residues < 2^60

@@ -368,6 +368,61 @@ __global__ __launch_bounds__(256) void k_tensor_bcast(const ModC *__restrict__ m
         *reinterpret_cast<ulonglong2 *>(o + po + 2 * ps) = d2;
     }
 }
+// Approach 3's sum of K unrelinearised products (BlindSender::computeSimilarityMatrix, sender_blind.cpp:65-71): K query ciphertexts
+// qc [K][2][q_ls][N] times the K chunk ciphertexts of each of X matrices, b [X][K][2][b_ls][N] (the resident database read where it
+// lies: non-temporal 16-byte loads, streamed once) -> o [X][3][nl][N].  grid (N/512, nl, ceil(X / HY_DOT_X)): a thread owns two
+// coefficients of HY_DOT_X matrices and walks the chunks, so a query chunk is fetched once per HY_DOT_X matrices (K small ciphertexts:
+// they stay in cache).  d0, d1, d2 are 128-bit lazy sums reduced once: d0 and d2 hold K products, d1 holds 2K, each below 2^120 on the
+// 60-bit limb, so 64 of them fit 128 bits (K <= 32, checked by the caller); reduce_lazy takes the true product count, because
+// reduce128k's range ends at four products on that limb.  Operands are canonical residues, so the bits are those of K k_tensor<false>
+// products added with k_addsub.  A ragged last group re-reads the last matrix and does not store it.
+#define HY_DOT_X 2
+__global__ __launch_bounds__(256) void k_tensor_dot(const ModC *__restrict__ mod, int N, const u64 *__restrict__ qc, int q_ls,
+                                                    const u64 *__restrict__ b, int b_ls, u64 *__restrict__ o, int nl, int X, int K) {
+    typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
+    const int j = blockIdx.y;
+    const ModC M = mod[j];
+    const size_t i = (size_t)j * N + (size_t)(blockIdx.x * 256 + threadIdx.x) * 2, ps = (size_t)nl * N;
+    const size_t qp = (size_t)q_ls * N, bp = (size_t)b_ls * N;
+    const int x0 = blockIdx.z * HY_DOT_X;
+    const u64 *bg[HY_DOT_X];
+#pragma unroll
+    for (int g = 0; g < HY_DOT_X; g++) bg[g] = b + (size_t)min(x0 + g, X - 1) * K * 2 * bp + i;
+    u128 s0x[HY_DOT_X], s0y[HY_DOT_X], s1x[HY_DOT_X], s1y[HY_DOT_X], s2x[HY_DOT_X], s2y[HY_DOT_X];
+#pragma unroll
+    for (int g = 0; g < HY_DOT_X; g++) s0x[g] = s0y[g] = s1x[g] = s1y[g] = s2x[g] = s2y[g] = 0;
+    for (int c = 0; c < K; c++) {
+        const u64 *qa = qc + (size_t)c * 2 * qp + i;
+        const ulonglong2 a0 = *reinterpret_cast<const ulonglong2 *>(qa), a1 = *reinterpret_cast<const ulonglong2 *>(qa + qp);
+#pragma unroll
+        for (int g = 0; g < HY_DOT_X; g++) {
+            const u64 *pb = bg[g] + (size_t)c * 2 * bp;
+            const ull2 b0 = __builtin_nontemporal_load(reinterpret_cast<const ull2 *>(pb));
+            const ull2 b1 = __builtin_nontemporal_load(reinterpret_cast<const ull2 *>(pb + bp));
+            s0x[g] += (u128)a0.x * b0.x;
+            s0y[g] += (u128)a0.y * b0.y;
+            s1x[g] += (u128)a0.x * b1.x + (u128)a1.x * b0.x;
+            s1y[g] += (u128)a0.y * b1.y + (u128)a1.y * b0.y;
+            s2x[g] += (u128)a1.x * b1.x;
+            s2y[g] += (u128)a1.y * b1.y;
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < HY_DOT_X; g++) {
+        if (x0 + g >= X) break;
+        ulonglong2 d0, d1, d2;
+        d0.x = reduce_lazy(s0x[g], M, K);
+        d0.y = reduce_lazy(s0y[g], M, K);
+        d1.x = reduce_lazy(s1x[g], M, 2 * K);
+        d1.y = reduce_lazy(s1y[g], M, 2 * K);
+        d2.x = reduce_lazy(s2x[g], M, K);
+        d2.y = reduce_lazy(s2y[g], M, K);
+        const size_t po = (size_t)(x0 + g) * 3 * ps + i;
+        *reinterpret_cast<ulonglong2 *>(o + po) = d0;
+        *reinterpret_cast<ulonglong2 *>(o + po + ps) = d1;
+        *reinterpret_cast<ulonglong2 *>(o + po + 2 * ps) = d2;
+    }
+}
 
 // ------------------------------------------------------------------------------------------------ key switching
 // grid (N/512, X): each thread reads its ns source residues ONCE (2 coefficients, 16 B loads) and produces all nt
@@ -1166,6 +1221,10 @@ void tensor_sq(hipStream_t st, const ModC *mod, int N, const u64 *a, u64 *o, int
 void tensor_bcast(hipStream_t st, const ModC *mod, int N, const u64 *q, int q_ls, const u64 *b, int b_ls, u64 *o, int X, int nl) {
     ledger_add("k_tensor_bcast", (2.0 + 5.0 * X) * nl * LP_BYTES(N));  // q0 q1 once, b0 b1 in and d0 d1 d2 out per ciphertext
     hipLaunchKernelGGL(k_tensor_bcast, dim3(N / 512, nl, (X + HY_BCAST_X - 1) / HY_BCAST_X), dim3(256), 0, st, mod, N, q, q_ls, b, b_ls, o, nl, X);
+}
+void tensor_dot(hipStream_t st, const ModC *mod, int N, const u64 *q, int q_ls, const u64 *b, int b_ls, u64 *o, int X, int K, int nl) {
+    ledger_add("k_tensor_dot", (2.0 * K + (2.0 * K + 3.0) * X) * nl * LP_BYTES(N));  // the K query chunks once; per matrix 2K operands in, d0 d1 d2 out
+    hipLaunchKernelGGL(k_tensor_dot, dim3(N / 512, nl, (X + HY_DOT_X - 1) / HY_DOT_X), dim3(256), 0, st, mod, N, q, q_ls, b, b_ls, o, nl, X, K);
 }
 void base_convert(hipStream_t st, const ModC *mod, int N, const u64 *y, size_t yo, u64 *out, size_t oo, int X,
                   const ConvTab &tab, const LimbSel &dsel) {

@@ -167,6 +167,16 @@ def load_library():
         "hydia_grote_membership_scenario": (i32, [vp, vp, pp]),
         "hydia_grote_decrypt_index": (i32, [vp, vp, vp, sz, vp, sz, C.POINTER(sz)]),
         "hydia_eval_square_no_relin": (i32, [vp, vp, u32, pp]),
+        "hydia_ct_limb_prefix": (i32, [vp, vp, u32, pp]),
+        "hydia_blind_db_num_cts": (sz, [vp, sz, sz]),
+        "hydia_blind_db_enroll": (i32, [vp, vp, sz, sz, vp]),
+        "hydia_blind_encrypt_query": (i32, [vp, vp, sz, vp, u64, pp]),
+        "hydia_blind_compute_similarity": (i32, [vp, vp, pp]),
+        "hydia_blind_index_scenario": (i32, [vp, vp, pp]),
+        "hydia_blind_membership_scenario": (i32, [vp, vp, pp]),
+        "hydia_compress_ciphers": (i32, [vp, vp, sz, pp]),
+        "hydia_blind_decrypt_index": (i32, [vp, vp, sz, vp, sz, C.POINTER(sz)]),
+        "hydia_eval_dot_no_relin": (i32, [vp, vp, vp, pp]),
         "hydia_kernel_time": (i32, [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(u64)]),
         "hydia_kernel_time_reset": (i32, [vp]),
         "hydia_byte_ledger": (i32, [i32, C.c_char_p, sz, C.POINTER(sz)]),
@@ -179,6 +189,9 @@ def load_library():
     L._hydia_symbols = sorted(sig)
     _LIB = L
     return L
+
+
+BLIND_CHUNK_LEN = 128  # CHUNK_LEN, include/config.h:34 (HYDIA_BLIND_CHUNK_LEN)
 
 
 def _chk(code):
@@ -429,6 +442,12 @@ class Context:
         ct._keepalive = keepalive
         return ct
 
+    def ct_limb_prefix(self, ct, n_limbs):
+        """A handle over the first n_limbs limbs of ct, read in place (no copy, ct's limb stride); it keeps ct alive."""
+        v = self._out(self.L.hydia_ct_limb_prefix, ct.h, int(n_limbs))
+        v._keepalive = ct
+        return v
+
     def _out(self, fn, *args):
         h = C.c_void_p()
         _chk(fn(self.h, *args, C.byref(h)))
@@ -503,6 +522,18 @@ class Context:
     def eval_square_no_relin(self, ct, n_limbs=0):
         """(c0^2, 2 c0 c1, c1^2) on the first n_limbs limbs of ct read in place (0 = all)"""
         return self._out(self.L.hydia_eval_square_no_relin, ct.h, int(n_limbs))
+
+    def compress_ciphers(self, ct, dimension):
+        """OpenFHEWrapper::compressCiphers (src/openFHE_wrapper.cpp:273-312) on a batch: the slots = 0 mod dimension of `dimension`
+        ciphertexts interleaved into one."""
+        return self._out(self.L.hydia_compress_ciphers, ct.h, int(dimension))
+
+    def eval_dot_no_relin(self, q, b):
+        """sum_c q[c] (x) b[m K + c] without relinearisation: q a batch of K ciphertexts, b of M K -> M 3-component ciphertexts"""
+        return self._out(self.L.hydia_eval_dot_no_relin, q.h, b.h)
+
+    def blind_db_num_cts(self, n, chunk_len=BLIND_CHUNK_LEN):
+        return int(self.L.hydia_blind_db_num_cts(self.h, n, chunk_len))
 
     def base_rotations(self):
         """the key set of approach 1 for this context's slot count (pass it to keygen_rotations)"""
@@ -819,3 +850,54 @@ class GroteReceiver(BaseReceiver):
             if n.value <= cap:
                 return [int(v) for v in out[:n.value]]
             cap = n.value
+
+
+# ---- the Blind-Match method, approach 3: include/enroller_blind.h, include/receiver_blind.h, include/sender_blind.h.  The reference fixes
+# CHUNK_LEN = 128 at compile time; the roles here take it as a constructor argument with that default, so a small ring can be tested
+class BlindEnroller:
+    def __init__(self, cc, num_vectors):
+        self.cc, self.numVectors = cc, num_vectors
+
+    def serializeDB(self, database, chunk_length=BLIND_CHUNK_LEN, seed=None):
+        """BlindEnroller::serializeDB (src/enroller/enroller_blind.cpp:13-90): per matrix of slots / chunk_length vectors one ciphertext
+        per chunk of coordinates, normalises in place."""
+        assert database.dtype == np.float64 and database.flags.c_contiguous
+        assert database.shape == (self.numVectors, self.cc.dim)
+        _chk(self.cc.L.hydia_blind_db_enroll(self.cc.h, _p(database), self.numVectors, int(chunk_length), _p(_seed(seed))))
+
+
+class BlindReceiver(HersReceiver):
+    """BlindReceiver (src/receiver/receiver_blind.cpp): the query is vector_dim / chunk_length tiled ciphertexts in one batch;
+    decryptMembership is HersReceiver's."""
+
+    def __init__(self, cc, num_vectors, chunk_length=BLIND_CHUNK_LEN):
+        super().__init__(cc, num_vectors)
+        self.chunkLength = int(chunk_length)
+
+    def encryptQuery(self, query, seed=None, nonce=1):
+        query = np.ascontiguousarray(query, dtype=np.float64)
+        assert query.shape == (self.cc.dim,)
+        return self.cc._out(self.cc.L.hydia_blind_encrypt_query, _p(query), self.chunkLength, _p(_seed(seed)), nonce)
+
+    def decryptIndex(self, index_cipher):
+        """receiver_blind.cpp:28-54: a value >= 1.0 at slot j of ciphertext i is vector i slots + j // chunk + (j % chunk) (slots // chunk).
+        Like the reference, it does NOT filter indices that fall into the padding past numVectors."""
+        cap = len(index_cipher) * self.cc.slots
+        out = np.zeros(cap, dtype=np.uint64)
+        n = C.c_size_t()
+        _chk(self.cc.L.hydia_blind_decrypt_index(self.cc.h, index_cipher.h, self.chunkLength, _p(out), cap, C.byref(n)))
+        return [int(v) for v in out[:n.value]]
+
+
+class BlindSender(HersSender):
+    """include/sender_blind.h (derives from HersSender) — computeSimilarity returns the compressed score ciphertexts; the chunk length
+    is the resident database's."""
+
+    def computeSimilarity(self, query_cipher):
+        return self.cc._out(self.cc.L.hydia_blind_compute_similarity, query_cipher.h)
+
+    def membershipScenario(self, query_cipher):
+        return self.cc._out(self.cc.L.hydia_blind_membership_scenario, query_cipher.h)
+
+    def indexScenario(self, query_cipher):
+        return self.cc._out(self.cc.L.hydia_blind_index_scenario, query_cipher.h)

@@ -133,6 +133,9 @@ int hydia_ct_from_device(hydia_ctx *ctx, const void *dev_ptr, uint32_t count, ui
  * The memory must stay valid and unchanged while the handle, or work enqueued on it, is alive */
 int hydia_ct_view_device(hydia_ctx *ctx, void *dev_ptr, uint32_t count, uint32_t n_polys, uint32_t n_limbs, double scale,
                          hydia_ct **out);
+/* a handle over the first n_limbs limbs of ct, read in place: no copy, the limb stride stays ct's (what dropping limbs without a rescale
+ * leaves).  ct must stay alive and unchanged while the handle or any operation enqueued on it is alive */
+int hydia_ct_limb_prefix(hydia_ctx *ctx, const hydia_ct *ct, uint32_t n_limbs, hydia_ct **out);
 void hydia_ct_free(hydia_ct *ct);
 
 /* ---- receiver: DiagonalReceiver / HersReceiver ---- */
@@ -172,7 +175,7 @@ int hydia_db_enroll_shard(hydia_ctx *ctx, double *db, size_t n, const uint8_t se
  * hydia_set_matvec mode: 0 auto (hydia_auto_babies: B grows with the blocks the enrolling context holds — at vector_dim 512: 64 up
  * to 3 blocks, 128 up to 12, 256 up to 40, hoisted above; measured, profiles/r04/matvec_sweep.txt), 1 hoisted, otherwise B itself; initial value from HYDIA_MATVEC=auto|hoisted|bsgs|<B>.
  * It takes effect at the NEXT enrolment; hydia_db_kind / hydia_db_babies tell what is resident (kind 0 none, 5 hoisted diagonals,
- * 6 pre-rotated diagonals, 4 HERS columns, 1 the rows of approach 1 — hydia_base_db_enroll).  Ciphertexts imported one by one (hydia_db_alloc + hydia_db_import_ct: the reference
+ * 6 pre-rotated diagonals, 4 HERS columns, 1 the rows of approach 1 — hydia_base_db_enroll, 3 the chunks of approach 3 — hydia_blind_db_enroll).  Ciphertexts imported one by one (hydia_db_alloc + hydia_db_import_ct: the reference
  * enroller's) are taken as hoisted unless hydia_db_set_babies says otherwise (a database of more than 8 blocks is then re-ordered in
  * HBM for the declared form, through a second buffer of its size — see hydia_db_group).  hydia_db_set_babies takes a DECLARED form:
  * vector_dim (hoisted) or a power of two >= 2 dividing it — 0, 1 and anything else are HYDIA_ERR_ARG; without a diagonal database
@@ -363,7 +366,48 @@ int hydia_grote_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia
  * error): otherwise HYDIA_ERR_ARG.  Writes at most cap entries; *n_out = the number of indices */
 int hydia_grote_decrypt_index(hydia_ctx *ctx, const hydia_ct *rows, const hydia_ct *cols, size_t n_vectors, size_t *out, size_t cap, size_t *n_out);
 
+/* ---- approach 3, the Blind-Match method (BlindEnroller / BlindReceiver / BlindSender) ----
+ * On the chain of hydia_params_for_approach(3): depth 12, 13 + 5 limbs, N = 2^16.  A vector is cut into K = vector_dim / chunk_len
+ * chunks (CHUNK_LEN 128, include/config.h:34: K = 4); spb = slots / chunk_len vectors make one database "matrix" of K ciphertexts, and
+ * the query is K ciphertexts.  Per matrix the sender sums the K unrelinearised products in one kernel, relinearises and rescales once,
+ * and adds log2(chunk_len) rotations; OpenFHEWrapper::compressCiphers interleaves chunk_len matrices into one score ciphertext.
+ * Keys: hydia_keygen_rotations with the set of hydia_base_rotations.  The database is walked in passes of C matrices (C from the free
+ * device memory; HYDIA_BLIND_PASS=<C> overrides); HYDIA_BLIND_NO_DOT=1 routes the sum of products through the general product kernel and
+ * additions; every setting gives the same bits.  Errors: a chunk_len that is not a power of two in 2 .. slots dividing vector_dim, or
+ * K > 32: HYDIA_ERR_ARG; a query that is not one batch of K fresh 2-component ciphertexts at full level: HYDIA_ERR_ARG; a missing
+ * rotation or relinearisation key, no database or another database kind resident, fewer than four limbs: HYDIA_ERR_STATE, before any
+ * work is enqueued.  hydia_db_save refuses this database kind (3), as it refuses kind 1. */
+#define HYDIA_BLIND_CHUNK_LEN 128
+/* K ceil(n / spb): database ciphertexts of n vectors (src/enroller/enroller_blind.cpp:15-17, :55); 0 for a chunk_len the packing cannot take */
+size_t hydia_blind_db_num_cts(const hydia_ctx *ctx, size_t n_vectors, size_t chunk_len);
+/* BlindEnroller::serializeDB, src/enroller/enroller_blind.cpp:13-90: normalises db IN PLACE; ciphertext m K + c holds coordinates
+ * [c chunk_len, (c + 1) chunk_len) of vector m spb + v at slots [v chunk_len, (v + 1) chunk_len), zeros elsewhere; encoded and encrypted
+ * on the GPU into database kind 3 (plain 8-byte residues [ct][2][n_q][N]; hydia_db_export_ct addresses these ciphertexts) */
+int hydia_blind_db_enroll(hydia_ctx *ctx, double *db /* n x vector_dim row-major */, size_t n, size_t chunk_len, const uint8_t seed[32]);
+/* BlindReceiver::encryptQuery, src/receiver/receiver_blind.cpp:13-26 and :58-71: normalise, then K ciphertexts in one batch, ciphertext c
+ * = chunk c tiled over all slots, nonces nonce0 .. nonce0 + K - 1 */
+int hydia_blind_encrypt_query(hydia_ctx *ctx, const double *query, size_t chunk_len, const uint8_t seed[32], uint64_t nonce0, hydia_ct **out);
+/* BlindSender::computeSimilarity, src/sender/sender_blind.cpp:43-83, with the chunk length of the resident database.  out:
+ * ceil(matrices / chunk_len) ciphertexts on n_q - 2 limbs; the score of vector i slots + k spb + v sits in slot v chunk_len + k of output i */
+int hydia_blind_compute_similarity(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out);
+/* BlindSender::indexScenario, src/sender/sender_blind.cpp:30-41 */
+int hydia_blind_index_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out);
+/* BlindSender::membershipScenario, src/sender/sender_blind.cpp:13-28 */
+int hydia_blind_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out);
+/* OpenFHEWrapper::compressCiphers, src/openFHE_wrapper.cpp:273-312, on a caller's batch: every ciphertext times the mask with ones at slots
+ * = 0 mod dimension and a rescale; ciphertext i into output i div dimension, rotated by binaryRotate(., -(i mod dimension)) unless that
+ * is 0.  dimension: a power of two, 2 <= dimension <= slots; the ciphertexts need a limb to rescale away */
+int hydia_compress_ciphers(hydia_ctx *ctx, const hydia_ct *in, size_t dimension, hydia_ct **out);
+/* BlindReceiver::decryptIndex, src/receiver/receiver_blind.cpp:28-54: a value >= 1.0 at slot j of ciphertext i is vector
+ * i slots + j div chunk_len + (j mod chunk_len) spb.  As in the reference, indices that fall into the padding past the number of enrolled
+ * vectors are not filtered.  Writes at most cap entries; *n_out = the number of indices */
+int hydia_blind_decrypt_index(hydia_ctx *ctx, const hydia_ct *index_cts, size_t chunk_len, size_t *out, size_t cap, size_t *n_out);
+
 /* ---- evaluator primitives (used by the parity tests and by adapters) ---- */
+/* sum_c q[c] (x) b[m K + c] without relinearisation: q a batch of K <= 32 ciphertexts, b a batch of M K ciphertexts (matrix-major), both
+ * 2 components on the same limbs (limb-strided views allowed) -> M 3-component ciphertexts at scale(q) scale(b): what K calls of
+ * hydia_eval_mult_no_relin summed with hydia_eval_add give (approach 3's fused product kernel; HYDIA_BLIND_NO_DOT) */
+int hydia_eval_dot_no_relin(hydia_ctx *ctx, const hydia_ct *q, const hydia_ct *b, hydia_ct **out);
 /* EvalSquare without relinearisation on the first n_limbs limbs of ct, read in place (0 = all): (c0^2, 2 c0 c1, c1^2), 3 components at
  * scale^2 — what hydia_eval_mult_no_relin(ct, ct) gives on those limbs (approach 2's squaring kernel; HYDIA_GROTE_NO_SQ) */
 int hydia_eval_square_no_relin(hydia_ctx *ctx, const hydia_ct *ct, uint32_t n_limbs, hydia_ct **out);

@@ -30,6 +30,7 @@ namespace hydia {
 const double MATCH_THRESHOLD = 0.44;  // include/config.h:9
 const size_t COMP_DEPTH = 10;         // include/config.h:14
 const size_t VECTOR_DIM = 512;        // include/config.h:30
+const size_t CHUNK_LEN = HYDIA_BLIND_CHUNK_LEN;  // include/config.h:34
 
 inline void role_seed(uint8_t out[32], const uint8_t *seed32) {
     if (seed32) {
@@ -567,6 +568,76 @@ class GroteReceiver : public BaseReceiver {
         std::vector<size_t> out(n);
         if (n && !cc->check(hydia_grote_decrypt_index(cc->h, rows, cols, numVectors, out.data(), n, &n), "decryptIndex")) return {};
         return out;
+    }
+};
+
+// ---- the Blind-Match method, approach 3: include/sender_blind.h (derives from HersSender), include/receiver_blind.h (from HersReceiver),
+// include/enroller_blind.h (from HersEnroller).  The query is K = VECTOR_DIM / CHUNK_LEN ciphertexts (one batch handle); the database is
+// chunk-packed (hydia_blind_db_enroll); the keys are KeyGenBaseline's (src/main.cpp:195-206).
+class BlindSender : public HersSender {
+  public:
+    BlindSender(CryptoContext ccParam, size_t vectorParam) : HersSender(std::move(ccParam), vectorParam) {}
+    BlindSender(CryptoContext ccParam, PublicKey pkParam, size_t vectorParam) : HersSender(std::move(ccParam), pkParam, vectorParam) {}  // sender_blind.cpp:7-9
+    std::vector<Ciphertext> computeSimilarity(std::vector<Ciphertext> &queryCipher) override {  // sender_blind.cpp:43-56
+        hydia_ct *out = run(queryCipher, hydia_blind_compute_similarity, "computeSimilarity");
+        return out ? split_batch(cc, out) : std::vector<Ciphertext>{};
+    }
+    Ciphertext membershipScenario(std::vector<Ciphertext> &queryCipher) override {  // sender_blind.cpp:13-28
+        hydia_ct *out = run(queryCipher, hydia_blind_membership_scenario, "membershipScenario");
+        return out ? split_batch(cc, out)[0] : Ciphertext{};
+    }
+    std::vector<Ciphertext> indexScenario(std::vector<Ciphertext> &queryCipher) override {  // sender_blind.cpp:30-41
+        hydia_ct *out = run(queryCipher, hydia_blind_index_scenario, "indexScenario");
+        return out ? split_batch(cc, out) : std::vector<Ciphertext>{};
+    }
+
+  protected:
+    hydia_ct *run(std::vector<Ciphertext> &q, int (*fn)(hydia_ctx *, const hydia_ct *, hydia_ct **), const char *what) {
+        hydia_ct *out = nullptr;
+        if (q.empty() || !q[0]) {
+            std::cerr << "Error: empty query ciphertext" << std::endl;
+            return nullptr;
+        }
+        return cc->check(fn(cc->h, q[0].batch->h, &out), what) ? out : nullptr;
+    }
+};
+class BlindReceiver : public HersReceiver {
+  public:
+    using HersReceiver::HersReceiver;
+    // src/receiver/receiver_blind.cpp:13-26: normalise, K ciphertexts, chunk c tiled over all slots
+    std::vector<Ciphertext> encryptQuery(std::vector<double> query) override {
+        hydia_ct *out = nullptr;
+        if (query.size() < cc->info.vector_dim) query.resize(cc->info.vector_dim, 0.0);
+        const uint64_t first = nonce + 1;
+        nonce += cc->info.vector_dim / CHUNK_LEN;
+        if (!cc->check(hydia_blind_encrypt_query(cc->h, query.data(), CHUNK_LEN, seed, first, &out), "encryptQuery")) return {};
+        return split_batch(cc, out);
+    }
+    // src/receiver/receiver_blind.cpp:28-54: slot j of ciphertext i -> i batchSize + j / CHUNK_LEN + (j % CHUNK_LEN) scoresPerBatch; like
+    // the reference, indices in the padding past numVectors are not filtered.  The ciphertexts must be the whole of one device batch
+    std::vector<size_t> decryptIndex(std::vector<Ciphertext> &indexCipher) override {
+        if (indexCipher.empty() || !indexCipher[0] || indexCipher[0].batch->count() != indexCipher.size()) {
+            std::cerr << "Error: decryptIndex takes the whole of one ciphertext batch" << std::endl;
+            return {};
+        }
+        const hydia_ct *h = indexCipher[0].batch->h;
+        size_t n = 0;
+        if (!cc->check(hydia_blind_decrypt_index(cc->h, h, CHUNK_LEN, nullptr, 0, &n), "decryptIndex")) return {};
+        std::vector<size_t> out(n);
+        if (n && !cc->check(hydia_blind_decrypt_index(cc->h, h, CHUNK_LEN, out.data(), n, &n), "decryptIndex")) return {};
+        return out;
+    }
+};
+class BlindEnroller : public EnrollerBase {  // include/enroller_blind.h
+  public:
+    BlindEnroller(CryptoContext ccParam, size_t vectorParam, const uint8_t *seed32 = nullptr)
+        : EnrollerBase(std::move(ccParam), PublicKey{}, vectorParam, seed32) {}
+    BlindEnroller(CryptoContext ccParam, PublicKey pkParam, size_t vectorParam) : EnrollerBase(std::move(ccParam), pkParam, vectorParam, nullptr) {}
+    void serializeDB(std::vector<std::vector<double>> &database, size_t chunkLength) {  // enroller_blind.cpp:13-62
+        if (!next_seed("serializeDB")) return;
+        std::vector<double> flat = flatten(database);
+        if (!cc->check(hydia_blind_db_enroll(cc->h, flat.data(), numVectors, chunkLength, seed), "serializeDB")) return;
+        write_back(flat, database);
     }
 };
 
