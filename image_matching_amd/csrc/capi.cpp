@@ -833,12 +833,15 @@ int hydia_ct_add_raw(hydia_ctx *ctx, hydia_ct *acc, const void *dev_src, int src
     use_device(ctx);
     REQUIRE(ctx && acc && dev_src, "null argument");
     Context &cx = ctx->cx;
-    u64 *tmp = cx.pool.get(acc->c.bytes());
+    // the source is compact: its size follows the accumulator's limb COUNT (bytes() follows the limb stride, which a limb-prefix view
+    // keeps from its parent and which would read past the end of the source)
+    const size_t bytes = (size_t)acc->c.X * acc->c.npoly * acc->c.nl * cx.N * sizeof(u64);
+    u64 *tmp = cx.pool.get(bytes);
     // on the context's own stream: a plain device-to-device hipMemcpy would run on the null stream, unordered with it
     if (src_device < 0 || src_device == cx.device)
-        HIP_CHECK(hipMemcpyAsync(tmp, dev_src, acc->c.bytes(), hipMemcpyDeviceToDevice, cx.stream));
+        HIP_CHECK(hipMemcpyAsync(tmp, dev_src, bytes, hipMemcpyDeviceToDevice, cx.stream));
     else
-        HIP_CHECK(hipMemcpyPeerAsync(tmp, cx.device, dev_src, src_device, acc->c.bytes(), cx.stream));
+        HIP_CHECK(hipMemcpyPeerAsync(tmp, cx.device, dev_src, src_device, bytes, cx.stream));
     cx.add_raw_inplace(acc->c, tmp);
     cx.sync();
     cx.pool.put(tmp);
