@@ -921,6 +921,11 @@ int hydia_ntt(hydia_ctx *ctx, uint64_t *data, uint32_t count, uint32_t m, int in
     return HYDIA_OK;
     API_END
 }
+int hydia_ntt_engine(const hydia_ctx *ctx) {
+    if (!ctx || ctx->cx.tabs.generic) return 0;
+    const int logN = ctx->cx.prm.logN;  // what hk::ntt_forward / ntt_inverse dispatch to
+    return logN == 15 ? 15 : (logN == 16 && ctx->cx.tabs.ntt16) ? 16 : 0;
+}
 int hydia_eval_rotate(hydia_ctx *ctx, const hydia_ct *query, int rot, hydia_ct **out) { SENDER_CALL(ctx->cx.rotate(query->c, rot)) }
 int hydia_eval_mult(hydia_ctx *ctx, const hydia_ct *query, const hydia_ct *b, hydia_ct **out) {
     if (!b) return fail(HYDIA_ERR_ARG, "null argument");

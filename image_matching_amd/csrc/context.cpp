@@ -372,6 +372,8 @@ Context::Context(const Params &p, int dev) : HostParams(p), device(dev) {
         const char *g = getenv("HYDIA_IP_GROUP");
         tabs.ip_group = g && atoi(g) > 0 ? atoi(g) : 8;
         tabs.generic = getenv("HYDIA_NTT_GENERIC") ? 1 : 0;
+        const char *n16 = getenv("HYDIA_NTT16");  // opt-in: the 2^16 two-pass transforms (not the default until they are measured)
+        tabs.ntt16 = n16 && atoi(n16) != 0 ? 1 : 0;
         tabs.cf_wide = getenv("HYDIA_COLFUSE_WIDE") ? 1 : 0;
         tabs.p2_wg_sync = getenv("HYDIA_P2_WG_SYNC") ? 1 : 0;
         tabs.no_tw_lds = getenv("HYDIA_NO_TW_LDS") ? 1 : 0;

@@ -32,7 +32,8 @@ struct NttTables {
     int no_tw_lds;                 // HYDIA_NO_TW_LDS: pass 2's phase A / B twiddles of the FP64 limbs as per-lane vector loads (round 4's form) instead of a wave-local LDS table
     int p2_wg_sync;                // HYDIA_P2_WG_SYNC: the plain N = 2^15 transforms through round 4's workgroup-synchronous pass 2 (parity variant)
     int cf_wide;                   // HYDIA_COLFUSE_WIDE: round 4's column-fused kernel (32-column tiles, 16 rows per lane, two workgroups per CU)
-    int generic;                   // HYDIA_NTT_GENERIC: the ring-size-generic transform kernels also at N = 2^15 (parity variant)
+    int generic;                   // HYDIA_NTT_GENERIC: the ring-size-generic transform kernels also at N = 2^15 and 2^16 (parity variant)
+    int ntt16;                     // HYDIA_NTT16=1: the plain transforms at N = 2^16 through k_ntt16_p1 / p2 (ntt16.hip) — opt-in until measured
 };
 
 // base conversion table: out[t] = sum_s y[s] * f[s][t] mod q_{dst t}
@@ -275,6 +276,11 @@ void ntt_forward(hipStream_t st, const NttTables &T, int logN, const u64 *src, u
 void ntt_inverse(hipStream_t st, const NttTables &T, int logN, const u64 *src, u64 *dst, size_t src_outer,
                  size_t dst_outer, int X, const LimbSel &sel, const ScaleSel &scale);
 
+// N = 2^16 register-radix plain transforms (ntt16.hip); ntt_forward / ntt_inverse dispatch to them when logN == 16 and NttTables::ntt16 is set
+void ntt16_forward(hipStream_t st, const NttTables &T, const u64 *src, u64 *dst, size_t src_outer, size_t dst_outer, int X,
+                   const LimbSel &sel);
+void ntt16_inverse(hipStream_t st, const NttTables &T, const u64 *src, u64 *dst, size_t src_outer, size_t dst_outer, int X,
+                   const LimbSel &sel, const ScaleSel &scale);
 // N = 2^15 register-radix fast path (ntt15.hip); ntt_forward / ntt_inverse dispatch to it when logN == 15
 void ntt15_forward(hipStream_t st, const NttTables &T, const u64 *src, u64 *dst, size_t src_outer, size_t dst_outer, int X,
                    const LimbSel &sel);

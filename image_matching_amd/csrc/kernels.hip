@@ -1138,6 +1138,7 @@ size_t ledger_dump(char *out, size_t cap) {
 void ntt_forward(hipStream_t st, const NttTables &T, int logN, const u64 *src, u64 *dst, size_t so, size_t dso, int X,
                  const LimbSel &sel) {
     if (logN == 15 && !T.generic) return ntt15_forward(st, T, src, dst, so, dso, X, sel);
+    if (logN == 16 && T.ntt16 && !T.generic) return ntt16_forward(st, T, src, dst, so, dso, X, sel);
     const int N = 1 << logN, R = N >> 8;
     ScaleSel dummy = {};
     hipLaunchKernelGGL(k_ntt_strided<false>, dim3(8, X * sel.n), dim3(256), (size_t)R * 32 * 8, st, T, logN, src, dst, so,
@@ -1147,6 +1148,7 @@ void ntt_forward(hipStream_t st, const NttTables &T, int logN, const u64 *src, u
 void ntt_inverse(hipStream_t st, const NttTables &T, int logN, const u64 *src, u64 *dst, size_t so, size_t dso, int X,
                  const LimbSel &sel, const ScaleSel &scale) {
     if (logN == 15 && !T.generic) return ntt15_inverse(st, T, src, dst, so, dso, X, sel, scale);
+    if (logN == 16 && T.ntt16 && !T.generic) return ntt16_inverse(st, T, src, dst, so, dso, X, sel, scale);
     const int N = 1 << logN, R = N >> 8;
     hipLaunchKernelGGL(k_ntt_contig<true>, dim3(N / 2048, X * sel.n), dim3(256), 0, st, T, logN, src, dst, so, dso, sel);
     hipLaunchKernelGGL(k_ntt_strided<true>, dim3(8, X * sel.n), dim3(256), (size_t)R * 32 * 8, st, T, logN, dst, dst, dso,

@@ -142,6 +142,7 @@ def load_library():
         "hydia_hers_index_scenario": (i32, [vp, vp, pp]),
         "hydia_hers_membership_scenario": (i32, [vp, vp, pp]),
         "hydia_ntt": (i32, [vp, vp, u32, u32, i32]),
+        "hydia_ntt_engine": (i32, [vp]),
         "hydia_eval_rotate": (i32, [vp, vp, i32, pp]),
         "hydia_eval_mult": (i32, [vp, vp, vp, pp]),
         "hydia_eval_mult_no_relin": (i32, [vp, vp, vp, pp]),
@@ -471,6 +472,12 @@ class Context:
         a2 = a.reshape(-1, self.N)
         _chk(self.L.hydia_ntt(self.h, _p(a2), a2.shape[0], modulus_index, int(inverse)))
         return a
+
+    @property
+    def ntt_engine(self):
+        """15 or 16: the ring whose specialised two-pass transform the plain transforms run on; 0: the ring-size-generic kernels
+        (another ring, HYDIA_NTT_GENERIC=1, or N = 2^16 without HYDIA_NTT16=1 when the context was created)."""
+        return int(self.L.hydia_ntt_engine(self.h))
 
     def eval_rotate(self, ct, rot):
         return self._out(self.L.hydia_eval_rotate, ct.h, rot)

@@ -413,6 +413,10 @@ int hydia_eval_dot_no_relin(hydia_ctx *ctx, const hydia_ct *q, const hydia_ct *b
 int hydia_eval_square_no_relin(hydia_ctx *ctx, const hydia_ct *ct, uint32_t n_limbs, hydia_ct **out);
 int hydia_ntt(hydia_ctx *ctx, uint64_t *data /* host, [count][N] in place */, uint32_t count, uint32_t modulus_index,
               int inverse);
+/* The ring size (15 or 16) whose specialised two-pass register-radix transform this context's plain transforms run on; 0 when they run
+ * on the ring-size-generic kernels: any other ring, a context created under HYDIA_NTT_GENERIC=1 (the bit-identical parity switch), and
+ * N = 2^16 unless the context was created under HYDIA_NTT16=1 — the 2^16 transforms are opt-in until they are measured */
+int hydia_ntt_engine(const hydia_ctx *ctx);
 int hydia_eval_rotate(hydia_ctx *ctx, const hydia_ct *in, int rot, hydia_ct **out);
 int hydia_eval_mult(hydia_ctx *ctx, const hydia_ct *a, const hydia_ct *b, hydia_ct **out); /* mult+relin+rescale */
 int hydia_eval_mult_no_relin(hydia_ctx *ctx, const hydia_ct *a, const hydia_ct *b, hydia_ct **out);
