@@ -552,6 +552,25 @@ int hydia_db_enroll(hydia_ctx *ctx, double *db, size_t n, const uint8_t seed[32]
 int hydia_db_enroll_shard(hydia_ctx *ctx, double *db, size_t n, const uint8_t seed[32], size_t first_block) {
     return hydia_db_enroll_shard_ex(ctx, db, n, seed, first_block, 0);
 }
+int hydia_db_update_shard(hydia_ctx *ctx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32], size_t first_block) {
+    API_BEGIN
+    REQUIRE(ctx, "null argument");
+    use_device(ctx);
+    Context &cx = ctx->cx;
+    if (!cx.d_db || cx.db_cts == 0 || (cx.db_kind != 5 && cx.db_kind != 6))
+        return fail(HYDIA_ERR_STATE, "hydia: no diagonal database resident (an update needs kind 5 or 6: hydia_db_enroll, hydia_db_load or an import)");
+    REQUIRE(seed, "null argument");
+    REQUIRE(first_vector <= cx.db_vectors, "first_vector lies past the end of the database (an update leaves no holes)");
+    REQUIRE(n <= SIZE_MAX / sizeof(double) / (size_t)cx.prm.dim && first_vector + n >= first_vector, "row count out of range");
+    if (n == 0) return HYDIA_OK;
+    REQUIRE(rows, "null rows");
+    client_db_update(cx, first_vector, rows, n, normalise, seed, first_block);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_db_update(hydia_ctx *ctx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32]) {
+    return hydia_db_update_shard(ctx, first_vector, rows, n, normalise, seed, 0);
+}
 int hydia_set_matvec(hydia_ctx *ctx, int mode) {
     API_BEGIN
     REQUIRE(ctx && mode >= 0, "mat-vec mode is 0 (auto), 1 (hoisted) or a baby count");

@@ -271,6 +271,40 @@ void client_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32], si
     cx.pool.put((u64 *)d_rows);
 }
 
+// In-place update of a resident diagonal database (kind 5 / 6): a FRESH encryption of the sparse diagonal image of `rows` at vectors
+// first_vector .. first_vector + n - 1 is added to the blocks they touch (append: first_vector = the vector count — the padding slots
+// hold encryptions of zero; remove: the negated template; replace: new - old, normalise = 0).  Per touched block: diag_pack with the
+// rows' first slot, encrypt_device with the enrolment's nonces, then db_accumulate for a block that existed or db_store for a new
+// one — a new block is bit-identical to that block of client_enroll on the same rows with the same seed.  Form and kind stay.
+void client_db_update(Context &cx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32], size_t first_block) {
+    if (n == 0) return;
+    const int dim = cx.prm.dim, Nh = cx.slots, babies = cx.db_babies;
+    if (normalise)
+        for (size_t v = 0; v < n; v++) normalize(rows + v * dim, dim);
+    const ChaChaKey key = make_key(seed);
+    const size_t G_old = cx.db_cts / dim, ct_elems = (size_t)2 * cx.nQ * cx.N;
+    const size_t n_new = std::max(cx.db_vectors, first_vector + n), G_new = (n_new + (size_t)Nh - 1) / (size_t)Nh;
+    if (first_block > (HY_NONCE_LIMIT - HY_DB_NONCE_BASE) / (size_t)dim || G_new > (HY_NONCE_LIMIT - HY_DB_NONCE_BASE) / (size_t)dim - first_block)
+        throw std::runtime_error("hydia: first_block + number of blocks exceeds the 2^40 nonce space of the encryption sampler");
+    cx.db_grow(n_new, G_new * (size_t)dim);  // (throws before anything is touched when a larger database does not fit)
+    double *d_rows = (double *)cx.pool.get(sizeof(double) * (size_t)Nh * dim);
+    double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)dim * Nh);
+    u64 *d_cts = cx.pool.get(sizeof(u64) * (size_t)dim * ct_elems);
+    const size_t end = first_vector + n;
+    for (size_t g = first_vector / (size_t)Nh; g * (size_t)Nh < end; g++) {
+        const size_t lo = std::max(first_vector, g * (size_t)Nh), hi = std::min(end, (g + 1) * (size_t)Nh);
+        HIP_CHECK(hipMemcpyAsync(d_rows, rows + (lo - first_vector) * dim, sizeof(double) * (hi - lo) * dim, hipMemcpyHostToDevice, cx.stream));
+        hc::diag_pack(cx.stream, d_rows, (long long)(hi - lo), dim, Nh, d_slots, (babies > 0 && babies < dim) ? babies : 0, (int)(lo - g * (size_t)Nh));
+        encrypt_device(cx, d_slots, dim, key, HY_DB_NONCE_BASE + (first_block + g) * dim, d_cts);
+        if (g < G_old) cx.db_accumulate(g * dim, d_cts, dim);
+        else cx.db_store(g * dim, d_cts, dim);
+    }
+    cx.sync();
+    cx.pool.put(d_cts);
+    cx.pool.put((u64 *)d_slots);
+    cx.pool.put((u64 *)d_rows);
+}
+
 #define HY_HERS_NONCE_BASE (1ull << 37)
 // HersEnroller::serializeDB (/root/reference/src/enroller/enroller_hers.cpp:40-93): normalise in place, then per matrix of
 // `slots` vectors one ciphertext per dimension holding that coordinate of every vector

@@ -19,6 +19,8 @@ void client_decrypt(Context &cx, const Ct &ct, double *out);
 // babies < vector_dim: diagonals pre-rotated for the baby-step / giant-step mat-vec with that many hoisted rotations
 // (Context::similarity_bsgs_sum); same ciphertext order and nonces.  0 or vector_dim: the reference's layout
 void client_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32], size_t first_block = 0, int babies = 0);
+// resident kind 5 / 6 database += a fresh encryption of the sparse diagonal image of rows[n][dim] at vectors first_vector ..
+void client_db_update(Context &cx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32], size_t first_block = 0);
 // HERS (approach 4): column-packed enrolment and the vector_dim broadcast query ciphertexts
 void client_hers_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32]);
 Ct client_hers_encrypt_query(Context &cx, const double *query, const uint8_t seed[32], uint64_t nonce0);

@@ -257,13 +257,15 @@ __global__ __launch_bounds__(256) void k_complex_real(const double2 *__restrict_
 // grid (slots/256, dim)
 // babies > 0 (baby-step / giant-step form of the mat-vec): diagonal i is rotated by -babies * (i / babies) slots in the clear, i.e. output
 // slot s takes what the plain layout has in slot s - babies * (i / babies) (mod Nh)
+// row0 > 0 (an in-place update: the sparse image of a block whose only non-zero rows are the given ones): dbg's rows go to slots
+// [row0, row0 + rows_left) of the plain layout and zeros go everywhere else, in both forms
 __global__ __launch_bounds__(256) void k_diag_pack(const double *__restrict__ dbg, long long rows_left, int dim, int Nh,
-                                                   double *__restrict__ slots, int babies) {
+                                                   double *__restrict__ slots, int babies, int row0) {
     const int so = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
     const int s = babies > 0 ? (so + Nh - (babies * (i / babies)) % Nh) % Nh : so;
     const int r = s % dim;
-    const long long v = s;  // row inside this group = j*dim + r = s
-    slots[(size_t)i * Nh + so] = v < rows_left ? dbg[(size_t)v * dim + (r + i) % dim] : 0.0;
+    const long long v = (long long)s - row0;  // row inside this group = j*dim + r = s; row of dbg = s - row0
+    slots[(size_t)i * Nh + so] = (v >= 0 && v < rows_left) ? dbg[(size_t)v * dim + (r + i) % dim] : 0.0;
 }
 
 // HersEnroller::serializeDBThread (/root/reference/src/enroller/enroller_hers.cpp:108-113): slots[j][k] = db[m*S + k][j].
@@ -377,8 +379,8 @@ void row_pack(hipStream_t st, const double *dbg, long long elems_left, int Nh, d
 void broadcast_rows(hipStream_t st, const double *vals, int dim, int Nh, double *slots) {
     hipLaunchKernelGGL(k_broadcast_rows, dim3(Nh / 256, dim), dim3(256), 0, st, vals, Nh, slots);
 }
-void diag_pack(hipStream_t st, const double *dbg, long long rows_left, int dim, int Nh, double *slots, int babies) {
-    hipLaunchKernelGGL(k_diag_pack, dim3(Nh / 256, dim), dim3(256), 0, st, dbg, rows_left, dim, Nh, slots, babies);
+void diag_pack(hipStream_t st, const double *dbg, long long rows_left, int dim, int Nh, double *slots, int babies, int row0) {
+    hipLaunchKernelGGL(k_diag_pack, dim3(Nh / 256, dim), dim3(256), 0, st, dbg, rows_left, dim, Nh, slots, babies, row0);
 }
 
 }  // namespace hc

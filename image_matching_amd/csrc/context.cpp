@@ -637,6 +637,61 @@ void Context::db_relayout(int form) {
     db_alloc_bytes = bytes;
     db_lay = want;
 }
+// An in-place update that appends past the last block (client_db_update): room for `cts` ciphertexts holding n_vectors, same kind and
+// same form.  The database lies afterwards where db_layout_for(cts, form) puts it — growing from 8 to 9 or more hoisted blocks moves
+// it from ciphertext-major 48-bit to group-sequential 46-bit, and a grown group-sequential database may get another group size — so
+// the old ciphertexts move into a second buffer (as db_relayout's do; a plain device copy where both layouts are ciphertext-major)
+// and the buffers are swapped.  The new blocks' bytes are the caller's to write (db_store).  When the second buffer does not fit the
+// call fails with a DeviceError BEFORE anything is touched.
+void Context::db_grow(size_t n_vectors, size_t cts) {
+    if (!d_db || db_cts == 0) throw StateError("hydia: no database resident");
+    if (cts <= db_cts) {
+        db_vectors = n_vectors;
+        return;
+    }
+    const DbLayout want = db_layout_for(cts, db_babies);
+    sync_all();
+    struct Scratch {
+        Context *c;
+        unsigned char *fresh = nullptr;
+        u64 *plain = nullptr;
+        ~Scratch() {
+            if (plain) c->pool.put(plain);
+            if (fresh) (void)hipFree(fresh);
+        }
+    } s{this};
+    const size_t bytes = db_alloc_size(want, cts);
+    hipError_t e = hipMalloc((void **)&s.fresh, bytes);
+    if (e != hipSuccess) {
+        pool.trim();
+        (void)hipGetLastError();
+        e = hipMalloc((void **)&s.fresh, bytes);
+    }
+    if (e != hipSuccess) {
+        s.fresh = nullptr;
+        (void)hipGetLastError();
+        throw DeviceError("hydia: growing the resident database needs a second buffer of " + std::to_string(bytes >> 20) +
+                          " MiB, which does not fit in device memory (" + hipGetErrorString(e) +
+                          "); the database is unchanged — enrol it as a whole, or shard it over more GPUs");
+    }
+    if (!want.seq && !db_lay.seq && want.ct_bytes == db_lay.ct_bytes) {
+        HIP_CHECK(hipMemcpyAsync(s.fresh, d_db, db_cts * db_lay.ct_bytes, hipMemcpyDeviceToDevice, stream));
+    } else {
+        const size_t chunk = 16;
+        s.plain = pool.get(chunk * 2 * nQ * N * sizeof(u64));
+        for (size_t t0 = 0; t0 < db_cts; t0 += chunk) {
+            const int cnt = (int)std::min(chunk, db_cts - t0);
+            hk::db_unpack(stream, N, nQ, s.plain, d_db, t0, cnt, db_lay);
+            hk::db_pack(stream, N, nQ, s.plain, s.fresh, t0, cnt, want);
+        }
+    }
+    sync_all();
+    std::swap(d_db, s.fresh);  // the old buffer leaves with the scratch object
+    db_alloc_bytes = bytes;
+    db_lay = want;
+    db_cts = cts;
+    db_vectors = n_vectors;
+}
 namespace {
 struct DbFileHeader {
     char magic[8];  // "HYDIADB1"
@@ -774,6 +829,11 @@ void Context::db_load(const char *path) {
     db_babies = h.kind == 4 ? 0 : (h.babies ? (int)h.babies : prm.dim);
 }
 void Context::db_store(size_t t0, const u64 *d_plain, int X) { hk::db_pack(stream, N, nQ, d_plain, d_db, t0, X, db_lay); }
+void Context::db_accumulate(size_t t0, const u64 *d_plain, int X) {
+    timer_begin("db_accumulate");
+    hk::db_accumulate(stream, d_mod, N, nQ, d_plain, d_db, t0, X, db_lay);
+    timer_end("db_accumulate");
+}
 void Context::db_fetch(size_t t0, u64 *d_plain, int X) { hk::db_unpack(stream, N, nQ, d_plain, d_db, t0, X, db_lay); }
 
 // ------------------------------------------------------------------ kernel timers

@@ -209,11 +209,13 @@ struct Context : HostParams {
     void db_resize(size_t n_vectors, size_t cts, int form);
     void db_resize_rows(size_t n_vectors, size_t cts);  // kind 1: `cts` ciphertexts as plain [ct][2][nQ][N] residues
     void db_relayout(int form);  // the same ciphertexts laid out for another form (a second buffer for the duration)
+    void db_grow(size_t n_vectors, size_t cts);  // kind 5 / 6: room for more blocks, old ciphertexts kept (a second buffer for the duration)
     // persistence of the resident database (own streaming format: header + the ciphertext-major layout verbatim, so a restart does
     // not re-enrol from plaintext; the reference keeps serial/db_diagonal/index<t>.bin, enroller_diag.cpp:158-166)
     void db_save(const char *path);
     void db_load(const char *path);
     void db_store(size_t t0, const u64 *d_plain, int X);  // [X][2][nQ][N] device residues -> ciphertexts t0..t0+X-1
+    void db_accumulate(size_t t0, const u64 *d_plain, int X);  // ciphertexts t0..t0+X-1 += [X][2][nQ][N] device residues, in place
     void db_fetch(size_t t0, u64 *d_plain, int X);
 
     std::map<std::string, KernelTimer> timers;

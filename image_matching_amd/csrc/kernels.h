@@ -267,6 +267,8 @@ DbLayout db_layout_seq(int N, int nQ, int packed, int bd, int blocks, int bpp, i
 // ciphertexts t0 .. t0+X-1 of the database at `db` <-> plain [X][2][nQ][N] residues
 void db_pack(hipStream_t st, int N, int nQ, const u64 *plain, void *db, size_t t0, int X, const DbLayout &L);
 void db_unpack(hipStream_t st, int N, int nQ, u64 *plain, const void *db, size_t t0, int X, const DbLayout &L);
+// ciphertexts t0 .. t0+X-1 of the database += plain [X][2][nQ][N] residues mod q_j, in place (db_accum.h; mod = the context's table)
+void db_accumulate(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *plain, void *db, size_t t0, int X, const DbLayout &L);
 // blocks per wave / waves per workgroup loop B uses for G blocks (bpp, nw = the context's caps)
 void tensor_split(int G, int bpp, int nw, int *B, int *W);
 

@@ -15,6 +15,7 @@
 #include <stdexcept>
 
 #include "kernels.h"
+#include "db_accum.h"  // the per-granule arithmetic of k_db_accumulate / k_db_accumulate46 (host-checkable)
 #include "ntt_arith.h"  // FpA: exact FP64 products for the limbs below 2^47
 
 #include <algorithm>
@@ -1083,6 +1084,35 @@ __global__ __launch_bounds__(256) void k_db_repack46(int N, int nQ, u64 *__restr
     }
 }
 
+// In-place update of the resident database: ciphertexts t0 .. t0+X-1 += fresh [X][2][nQ][N] residues, mod q_j.  Fused
+// read-add-reduce-write on k_db_repack's thread-to-bytes map (a residue pair per thread): every resident byte is read and written
+// once by the one thread that owns it, so no atomics and no unpacked copy of the block in HBM.  grid (N/512, nQ or 1, X*2)
+__global__ __launch_bounds__(256) void k_db_accumulate(const ModC *__restrict__ mod, int N, int nQ, const u64 *__restrict__ plain,
+                                                       unsigned char *__restrict__ db, DbLayout L, size_t t0) {
+    const int j = blockIdx.y, xp = blockIdx.z, x = xp >> 1, p = xp & 1;
+    const size_t c = (size_t)(blockIdx.x * 256 + threadIdx.x) * 2;
+    const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(plain + ((size_t)xp * nQ + j) * N + c);
+    db_accumulate_pair(db + db_offset(L, N, t0 + x, p, j, c), L.packed && j > 0, a.x, a.y, mod[j].q);
+}
+// ... the 46-bit limbs of a bits46 layout on k_db_repack46's map: a thread owns SIXTEEN residues = 23 whole dwords.  The sums are
+// reduced before they are packed (two residues below a prime above 2^45 can add up to more than 2^46).
+// grid (N/4096, nQ - 1, X*2): limb j = blockIdx.y + 1
+__global__ __launch_bounds__(256) void k_db_accumulate46(const ModC *__restrict__ mod, int N, int nQ, const u64 *__restrict__ plain,
+                                                         unsigned char *__restrict__ db, DbLayout L, size_t t0) {
+    const int j = blockIdx.y + 1, xp = blockIdx.z, x = xp >> 1, p = xp & 1;
+    const size_t c = (size_t)(blockIdx.x * 256 + threadIdx.x) * 16;
+    if (c >= (size_t)N) return;
+    const u64 *pl = plain + ((size_t)xp * nQ + j) * N + c;
+    u64 a[16];
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+        const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(pl + r);
+        a[r] = v.x;
+        a[r + 1] = v.y;
+    }
+    db_accumulate_granule46(reinterpret_cast<unsigned *>(db + db_offset(L, N, t0 + x, p, j, c)), a, mod[j].q);
+}
+
 __global__ __launch_bounds__(256) void k_fill_uniform_hash(const ModC *__restrict__ mod, int N, u64 *__restrict__ dst,
                                                            int nl, u64 seed) {
     const size_t lp = blockIdx.y + (size_t)blockIdx.z * gridDim.y;
@@ -1433,6 +1463,14 @@ void db_unpack(hipStream_t st, int N, int nQ, u64 *plain, const void *db, size_t
     const bool b46 = L.bits46 && L.seq && L.packed && nQ > 1;
     hipLaunchKernelGGL(k_db_repack<false>, dim3(N / 512, b46 ? 1 : nQ, X * 2), dim3(256), 0, st, N, nQ, plain, (unsigned char *)db, L, t0);
     if (b46) hipLaunchKernelGGL(k_db_repack46<false>, dim3((N / 16 + 255) / 256, nQ - 1, X * 2), dim3(256), 0, st, N, nQ, plain, (unsigned char *)db, L, t0);
+}
+// ciphertexts t0 .. t0+X-1 of the database at `db` += plain [X][2][nQ][N] residues (mod q_j): the launch shapes of db_pack
+void db_accumulate(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *plain, void *db, size_t t0, int X, const DbLayout &L) {
+    const bool b46 = L.bits46 && L.seq && L.packed && nQ > 1;
+    ledger_add("k_db_accumulate", (double)X * (2.0 * L.ct_bytes + 2.0 * nQ * N * 8));  // resident bytes read and written + the fresh ones read
+    hipLaunchKernelGGL(k_db_accumulate, dim3(N / 512, b46 ? 1 : nQ, X * 2), dim3(256), 0, st, mod, N, nQ, plain, (unsigned char *)db, L, t0);
+    if (b46)
+        hipLaunchKernelGGL(k_db_accumulate46, dim3((N / 16 + 255) / 256, nQ - 1, X * 2), dim3(256), 0, st, mod, N, nQ, plain, (unsigned char *)db, L, t0);
 }
 // grid (N/512, nl, XP): two coefficients per thread, the plaintext's residues and Shoup companions read beside the operand's
 __global__ __launch_bounds__(256) void k_mul_plain(const ModC *__restrict__ mod, int N, const u64 *__restrict__ a, int a_ls,

@@ -116,6 +116,8 @@ def load_library():
         "hydia_ct_add_raw": (i32, [vp, vp, vp, i32]),
         "hydia_ct_mod_reduce": (i32, [vp, vp]),
         "hydia_db_enroll_shard": (i32, [vp, vp, sz, vp, sz]),
+        "hydia_db_update": (i32, [vp, sz, vp, sz, i32, vp]),
+        "hydia_db_update_shard": (i32, [vp, sz, vp, sz, i32, vp, sz]),
         "hydia_db_enroll_shard_ex": (i32, [vp, vp, sz, vp, sz, i32]),
         "hydia_set_matvec": (i32, [vp, i32]),
         "hydia_get_matvec": (i32, [vp]),
@@ -587,6 +589,14 @@ class Context:
         _chk(self.L.hydia_db_export_ct(self.h, t, _p(out)))
         return out
 
+    def db_update(self, first_vector, rows, normalise=True, seed=None, first_block=0):
+        """hydia_db_update[_shard]: add a FRESH encryption of `rows` (k x vector_dim float64, normalised IN PLACE when `normalise`),
+        placed at vectors first_vector .., to the resident kind-5 / kind-6 database.  Append: first_vector = db_stats()[0]; remove:
+        the negated template; replace: new_normalised - old_normalised with normalise=False.  seed=None draws a fresh key from the OS
+        — a seed must NEVER be used twice on one database (include/hydia.h)."""
+        assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.ndim == 2 and rows.shape[1] == self.dim
+        _chk(self.L.hydia_db_update_shard(self.h, first_vector, _p(rows), rows.shape[0], 1 if normalise else 0, _p(_seed(seed)), first_block))
+
     def db_fill_random(self, n, seed=1):
         _chk(self.L.hydia_db_fill_random(self.h, n, seed))
 
@@ -679,6 +689,16 @@ class DiagonalEnroller:
         assert database.shape == (self.numVectors, self.cc.dim)
         mv = 0 if matvec is None else self.cc._matvec_code(matvec)
         _chk(self.cc.L.hydia_db_enroll_shard_ex(self.cc.h, _p(database), self.numVectors, _p(_seed(seed)), first_block, mv))
+
+    def updateRows(self, first_vector, rows, normalise=True, seed=None):
+        """In-place update (Context.db_update): a fresh encryption of `rows` at vectors first_vector .. is added to the blocks they
+        touch.  numVectors follows the database; a DiagonalSender / DiagonalReceiver built for the old count is rebuilt by the caller."""
+        self.cc.db_update(first_vector, rows, normalise, seed)
+        self.numVectors = max(self.numVectors, first_vector + rows.shape[0])
+
+    def appendDB(self, rows, seed=None):
+        """append `rows` (normalised in place) after the last enrolled vector"""
+        self.updateRows(self.numVectors, rows, True, seed)
 
 
 class DiagonalReceiver:

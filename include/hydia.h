@@ -164,6 +164,33 @@ int hydia_db_enroll(hydia_ctx *ctx, double *db /* n x vector_dim row-major */, s
  * this shard's rows and first_block is the index of its first block in the whole database, so the shard encrypts with exactly
  * the nonces the unsharded enrolment uses for those blocks (bit-identical ciphertexts). */
 int hydia_db_enroll_shard(hydia_ctx *ctx, double *db, size_t n, const uint8_t seed[32], size_t first_block);
+/* ---- in-place update of a resident diagonal database (kind 5 or 6): append, remove, replace rows.
+ * ONE primitive: a FRESH encryption of the sparse diagonal image of rows[n][vector_dim], placed at vectors first_vector ..
+ * first_vector + n - 1, is added to the resident ciphertexts of the blocks those vectors touch (residue by residue, mod q_j); every
+ * other block is not read, not written and not re-encrypted.  With slots = N / 2 and n_old = the resident vector count:
+ *   normalise != 0  every row is normalised IN PLACE like hydia_db_enroll's (a zero row passes through); 0 takes the rows as given
+ *   first_vector <= n_old (no holes); afterwards the database holds max(n_old, first_vector + n) vectors
+ *   a block that existed: ciphertext g vector_dim + i becomes old + E; a block the update creates: it becomes E — bit-identical to
+ *     that block of hydia_db_enroll_shard on the same rows with the same seed.  E = the encryption of the block's sparse image (in the
+ *     resident form: pre-rotated when hydia_db_babies < vector_dim) under `seed` with the ENROLMENT's nonce of that ciphertext.
+ *   append   first_vector = n_old, normalise = 1 (the padding slots of a ragged last block hold encryptions of zero: adding is appending)
+ *   remove   the NEGATED template at its index, normalise = 1 (a negated unit vector normalises to itself); the slot then holds 0 up to noise
+ *   replace  new_normalised - old_normalised at the index, normalise = 0
+ * The kind and the form (hydia_db_babies) stay what they are — hydia_set_matvec's auto policy is NOT re-run for the new block count —
+ * and the database lies afterwards where an enrolment of the new size in that form would put it: growing past 8 blocks moves a hoisted
+ * database from the ciphertext-major 48-bit layout to the group-sequential 46-bit one (hydia_db_group, hydia_db_residue_bits).  An
+ * update that adds blocks needs a second buffer of the NEW size for its duration; when that does not fit: HYDIA_ERR_DEVICE and the
+ * database is untouched.  A sender or receiver object built for the old vector count is rebuilt by the caller for the new one.
+ * NOISE: every update adds one fresh encryption's noise (about 2^-30 of the scale) to the blocks it touches; after k updates of one
+ * block its noise is that of a sum of k + 1 fresh ciphertexts — re-enrol a block that has seen many thousands.
+ * SEED: the seed of an update MUST NEVER HAVE BEEN USED ON THIS DATABASE BEFORE — not by its enrolment, not by an earlier update.  The
+ * nonces are the enrolment's, so a reused seed encrypts a changed plaintext under the same randomness and the difference of the two
+ * ciphertexts reveals the difference of the plaintexts.  Take every update's seed from hydia_random_seed.
+ * Errors: no database, or kind 1 / 3 / 4: HYDIA_ERR_STATE; first_vector > n_old, null seed, or null rows with n > 0: HYDIA_ERR_ARG;
+ * n == 0: HYDIA_OK and nothing changes.  hydia_db_update_shard: this context holds the blocks first_block .. of a larger database
+ * (first_vector counts within the shard); it is what a multi-GPU wrapper would call on the rank that owns the rows. */
+int hydia_db_update(hydia_ctx *ctx, size_t first_vector, double *rows /* n x vector_dim row-major */, size_t n, int normalise, const uint8_t seed[32]);
+int hydia_db_update_shard(hydia_ctx *ctx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32], size_t first_block);
 /* ---- the split of the diagonalised mat-vec.  With rotation i = b + B g: B - 1 hoisted ("baby") rotations of the
  * query per QUERY, vector_dim / B relinearised partial sums per BLOCK of which all but the first are rotated by B g ("giant" steps,
  * ordinary key switches with the rotation keys B, 2B, .. that src/main.cpp:195-206 already generates).  The enroller rotates

@@ -428,6 +428,32 @@ class DiagonalEnroller : public EnrollerBase {
             return;
         write_back(flat, database);
     }
+    // In-place update of the enrolled database (hydia_db_update; no counterpart in the reference, which re-enrols): a fresh
+    // encryption of `rows` placed at vectors first_vector .. is ADDED to the resident blocks they touch.  append: appendDB; remove:
+    // the negated template with normalise = true; replace: new_normalised - old_normalised with normalise = false.  Normalised rows are
+    // written back like serializeDB's.  seed32 == nullptr (the default) draws a fresh sampler key from the OS for this call; a
+    // supplied seed must NEVER have been used on this database before (not by serializeDB, not by an earlier update).  numVectors
+    // follows the database; senders and receivers constructed for the old count are rebuilt by the caller.
+    bool updateRows(size_t first_vector, std::vector<std::vector<double>> &rows, bool normalise = true, const uint8_t *seed32 = nullptr) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: updateRows: a sharded database is updated shard by shard (hydia_db_update_shard)" << std::endl;
+            return false;
+        }
+        const size_t dim = cc->info.vector_dim;
+        std::vector<double> flat(rows.size() * dim, 0.0);
+        for (size_t i = 0; i < rows.size(); i++)
+            for (size_t j = 0; j < dim && j < rows[i].size(); j++) flat[i * dim + j] = rows[i][j];
+        uint8_t s[32];
+        role_seed(s, seed32);
+        if (!cc->check(hydia_db_update(cc->h, first_vector, flat.data(), rows.size(), normalise ? 1 : 0, s), "updateRows")) return false;
+        for (size_t i = 0; i < rows.size(); i++)
+            for (size_t j = 0; j < dim && j < rows[i].size(); j++) rows[i][j] = flat[i * dim + j];
+        if (first_vector + rows.size() > numVectors) numVectors = first_vector + rows.size();
+        return true;
+    }
+    bool appendDB(std::vector<std::vector<double>> &rows, const uint8_t *seed32 = nullptr) { return updateRows(numVectors, rows, true, seed32); }
+    size_t size() const { return numVectors; }
 };
 
 // ---- HERS, approach 4: include/sender_hers.h:9-44, include/receiver_hers.h:9-28, include/enroller_hers.h:16-37.
