@@ -676,7 +676,7 @@ __global__ __launch_bounds__(256) void k_rescale_combine(const ModC *__restrict_
 // ------------------------------------------------------------------------------------------------ loop B
 // acc[g][{d0,d1,d2}][j][c] = sum_{i<dim} rot[i] (x) db[g][i] with 128-bit lazy accumulation: one double-word
 // Barrett per output instead of 4*dim reductions.  45/46-bit limbs never overflow (dim * 2^93 < 2^128); the 60-bit
-// limb folds its accumulators every 64 diagonals.  16 B per lane per operand (1 KiB per wave instruction).
+// limb folds its accumulators every 32 diagonals (Sums128::chunk).  16 B per lane per operand (1 KiB per wave instruction).
 //
 // Work split (HBM must see the 3 GiB of rotated queries ONCE, not once per block): a workgroup owns one 128-coefficient
 // tile of one limb and NW*BPP database blocks — each of its NW waves serves BPP blocks with one register copy of the
@@ -713,8 +713,11 @@ DEV DbWalk db_walk(const DbLayout &L, int N, int dim, int j, int tile, int lane,
 // Three products per coefficient instead of four — loop B is co-bound by the integer multiplier, not only by HBM.
 //
 // Two arithmetics (policies of k_hydia_tensor), same sums, one reduction per output:
-// - Sums128: 64x64->128 products in 128-bit lazy sums (gfx950 builds one from four v_mad_u64_u32).  45/46-bit limbs never
-//   overflow (dim * 2^93 < 2^128); the 60-bit limb folds its sums every 64 diagonals.
+// - Sums128: 64x64->128 products in 128-bit lazy sums (gfx950 builds one from four v_mad_u64_u32).  A Karatsuba product of a k-bit
+//   limb is budgeted at 2^(2k+2) and a sum folded every chunk = 2^(125 - 2k) diagonals, q + chunk 2^(2k+2) < 2^128: every 32 on a
+//   60-bit limb, 128 on a 59-bit one, never from 47 bits down (chunk = dim) nor, in effect, at 48 (2^29).  The budget is one bit
+//   above what residues below q reach — 64 (2q - 2)^2 + q < 256 q^2 < 2^128, so 64 would hold too; 65 would not
+//   (tests/test_loop_b_model_cpu.py; the kernels on saturated residues: tests/test_gpu_loop_b_edges.py).
 // - Halves24, on the packed limbs of a group-sequential database (residues and rotated-query residues below 2^48).  There HBM
 //   delivers 7 TB/s and the 128-bit multiply-accumulates (94 % of the vector issue slots at 6 TB/s) would be the limit, so the
 //   products are taken on 24-bit halves, a = ah 2^24 + al, b = bh 2^24 + bl: the partial sums  ll = sum al bl,
