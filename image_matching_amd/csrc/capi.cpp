@@ -478,6 +478,7 @@ int hydia_db_import_ct(hydia_ctx *ctx, size_t t, const uint64_t *data) {
     REQUIRE(ctx && data, "null argument");
     Context &cx = ctx->cx;
     if (!cx.d_db) return fail(HYDIA_ERR_STATE, "hydia: no database resident (call hydia_db_alloc)");
+    if (cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: it holds plaintexts (hydia_plain_db_import_pt), not ciphertexts");
     REQUIRE(t < cx.db_cts, "ciphertext index out of range");
     const size_t e = (size_t)2 * cx.nQ * cx.N;
     u64 *tmp = cx.pool.get(e * sizeof(u64));
@@ -499,6 +500,7 @@ int hydia_db_export_ct(hydia_ctx *ctx, size_t t, uint64_t *data) {
     REQUIRE(ctx && data, "null argument");
     Context &cx = ctx->cx;
     if (!cx.d_db) return fail(HYDIA_ERR_STATE, "hydia: no database resident");
+    if (cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: it holds plaintexts (hydia_plain_db_export_pt), not ciphertexts");
     REQUIRE(t < cx.db_cts, "ciphertext index out of range");
     const size_t e = (size_t)2 * cx.nQ * cx.N;
     u64 *tmp = cx.pool.get(e * sizeof(u64));
@@ -557,6 +559,7 @@ int hydia_db_update_shard(hydia_ctx *ctx, size_t first_vector, double *rows, siz
     REQUIRE(ctx, "null argument");
     use_device(ctx);
     Context &cx = ctx->cx;
+    if (cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: it is not updated in place yet (enrol it again)");
     if (!cx.d_db || cx.db_cts == 0 || (cx.db_kind != 5 && cx.db_kind != 6))
         return fail(HYDIA_ERR_STATE, "hydia: no diagonal database resident (an update needs kind 5 or 6: hydia_db_enroll, hydia_db_load or an import)");
     REQUIRE(seed, "null argument");
@@ -585,6 +588,7 @@ int hydia_db_set_babies(hydia_ctx *ctx, int babies) {
     API_BEGIN
     REQUIRE(ctx, "null argument");
     Context &cx = ctx->cx;
+    if (cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: its form is declared at allocation (hydia_plain_db_alloc)");
     if (!cx.d_db || cx.db_cts == 0 || (cx.db_kind != 5 && cx.db_kind != 6)) return fail(HYDIA_ERR_STATE, "hydia: no diagonal database resident");
     // a DECLARED form: vector_dim (hoisted) or a power of two >= 2 dividing it — never 0 / 1, which mean "auto" / "hoisted" only in
     // hydia_set_matvec's policy and would silently mark an imported hoisted database as pre-rotated
@@ -601,8 +605,82 @@ int hydia_db_set_babies(hydia_ctx *ctx, int babies) {
 }
 int hydia_get_matvec(const hydia_ctx *ctx) { return ctx ? ctx->cx.matvec_mode : -1; }
 int hydia_db_kind(const hydia_ctx *ctx) { return ctx ? ctx->cx.db_kind : 0; }
-int hydia_db_babies(const hydia_ctx *ctx) { return ctx && (ctx->cx.db_kind == 5 || ctx->cx.db_kind == 6) ? ctx->cx.db_babies : 0; }
+int hydia_db_babies(const hydia_ctx *ctx) { return ctx && ctx->cx.db_kind >= 5 && ctx->cx.db_kind <= 8 ? ctx->cx.db_babies : 0; }
 int hydia_auto_babies(const hydia_ctx *ctx, size_t blocks) { return ctx ? ctx->cx.babies_for(blocks) : 0; }
+// ------------------------------------------------------------------ plain gallery (database kinds 7 / 8)
+// the sender owns the templates: plaintext t is the slot image of hydia_db_enroll's ciphertext t, encoded at scale 2^scale_bits on all
+// n_q limbs, evaluation form, ONE polynomial — no seed, no nonce, no public key
+int hydia_plain_db_enroll(hydia_ctx *ctx, double *db, size_t n) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && db && n >= 1, "bad argument");
+    if (ctx->in_group) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is not enrolled on a shard of a group: the sharded senders do not serve it yet");
+    Context &cx = ctx->cx;
+    const size_t G = (n + (size_t)cx.slots - 1) / (size_t)cx.slots;
+    const int B = cx.babies_for(G, 0);
+    cx.db_kind = 0;
+    cx.db_resize(n, hydia_db_num_cts(ctx, n), B, true);
+    client_plain_enroll(cx, db, n, B);
+    cx.db_kind = B < cx.prm.dim ? 8 : 7;
+    cx.db_babies = B;
+    return HYDIA_OK;
+    API_END
+}
+int hydia_plain_db_alloc(hydia_ctx *ctx, size_t n_vectors, int babies) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && n_vectors >= 1, "bad argument");
+    if (ctx->in_group) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is not enrolled on a shard of a group: the sharded senders do not serve it yet");
+    Context &cx = ctx->cx;
+    const int dim = cx.prm.dim;
+    REQUIRE(babies == dim || (babies >= 2 && babies < dim && (babies & (babies - 1)) == 0 && dim % babies == 0),
+            "the declared baby count must be vector_dim or a power of two >= 2 dividing it");
+    cx.db_kind = 0;
+    cx.db_resize(n_vectors, hydia_db_num_cts(ctx, n_vectors), babies, true);
+    HIP_CHECK(hipMemsetAsync(cx.d_db, 0, cx.db_alloc_bytes, cx.stream));  // plaintexts never imported are zero polynomials
+    cx.sync();
+    cx.db_kind = babies < dim ? 8 : 7;
+    cx.db_babies = babies;
+    return HYDIA_OK;
+    API_END
+}
+int hydia_plain_db_import_pt(hydia_ctx *ctx, size_t t, const uint64_t *data) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && data, "null argument");
+    Context &cx = ctx->cx;
+    if (!cx.d_db || !cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: no plain gallery resident (call hydia_plain_db_alloc)");
+    REQUIRE(t < cx.db_cts, "plaintext index out of range");
+    // the packed layouts keep 46 / 48 bits of a residue and loop B's bounds assume canonical ones: checked before anything is written
+    for (int j = 0; j < cx.nQ; j++)
+        for (int c = 0; c < cx.N; c++)
+            REQUIRE(data[(size_t)j * cx.N + c] < cx.q[j], "plaintext residue at or above its modulus");
+    const size_t e = (size_t)cx.nQ * cx.N;
+    u64 *tmp = cx.pool.get(e * sizeof(u64));
+    cx.sync();
+    HIP_CHECK(hipMemcpy(tmp, data, e * sizeof(u64), hipMemcpyHostToDevice));
+    cx.db_store(t, tmp, 1);
+    cx.sync();
+    cx.pool.put(tmp);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_plain_db_export_pt(hydia_ctx *ctx, size_t t, uint64_t *data) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && data, "null argument");
+    Context &cx = ctx->cx;
+    if (!cx.d_db || !cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: no plain gallery resident");
+    REQUIRE(t < cx.db_cts, "plaintext index out of range");
+    const size_t e = (size_t)cx.nQ * cx.N;
+    u64 *tmp = cx.pool.get(e * sizeof(u64));
+    cx.db_fetch(t, tmp, 1);
+    cx.sync();
+    HIP_CHECK(hipMemcpy(data, tmp, e * sizeof(u64), hipMemcpyDeviceToHost));
+    cx.pool.put(tmp);
+    return HYDIA_OK;
+    API_END
+}
 int hydia_hers_db_enroll(hydia_ctx *ctx, double *db, size_t n, const uint8_t seed[32]) {
     API_BEGIN
     use_device(ctx);
@@ -793,6 +871,7 @@ int hydia_rotate_query_range_into(hydia_ctx *ctx, const hydia_ct *query, uint32_
     API_BEGIN
     use_device(ctx);
     REQUIRE(ctx && query && dev_dst, "null argument");
+    if (ctx->cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: split rotations are not served on it yet");
     REQUIRE(first <= (uint32_t)ctx->cx.prm.dim && count <= (uint32_t)ctx->cx.prm.dim - first, "rotation range outside 0 .. vector_dim");
     ctx->cx.rotate_query_range(query->c, (int)first, (int)count, static_cast<u64 *>(dev_dst));
     return HYDIA_OK;
@@ -802,6 +881,7 @@ int hydia_rotate_query_range(hydia_ctx *ctx, const hydia_ct *query, uint32_t fir
     API_BEGIN
     use_device(ctx);
     REQUIRE(ctx && query && out && count >= 1, "bad argument");
+    if (ctx->cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: split rotations are not served on it yet");
     // validated on the unsigned values BEFORE anything is allocated (first + count must not wrap)
     REQUIRE(first <= (uint32_t)ctx->cx.prm.dim && count <= (uint32_t)ctx->cx.prm.dim - first, "rotation range outside 0 .. vector_dim");
     Ct r(&ctx->cx, (int)count, 2, query->c.nl, query->c.scale);

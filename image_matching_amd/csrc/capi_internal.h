@@ -19,6 +19,7 @@ struct hydia_ctx {
     // (Pool::mu_), and hipSetDevice only sets the calling thread's current device.  Everything else on a context (queries, key
     // loading, the database) stays single-threaded: thread-compatible, not thread-safe, like the reference's classes.
     std::atomic<long> refs{1};
+    bool in_group = false;  // a shard of a hydia_group (group.cpp): its database is the group's to enrol
     hydia_ctx(const hydia::Params &p, int dev) : cx(p, dev) {}
 };
 struct hydia_ct {

@@ -241,6 +241,47 @@ void client_decrypt(Context &cx, const Ct &ct, double *out) {
     cx.pool.put(t);
 }
 
+// encode X slot vectors that already sit in HBM as plaintexts: the front half of encrypt_device (the encoder at scale 2^scale_bits,
+// the coefficients onto all n_q limbs with no error term, the forward transform); writes [X][nQ][N] canonical residues at dst.
+// Needs no key and no sampler
+static void encode_device(Context &cx, const double *d_slots, int X, u64 *dst) {
+    ensure_embedding_tables(cx);
+    const int N = cx.N, nQ = cx.nQ, Nh = cx.slots;
+    const LimbSel qsel = cx.sel_q(nQ);
+    double2 *work = (double2 *)cx.pool.get(sizeof(double2) * (size_t)X * Nh);
+    long long *coeffs = (long long *)cx.pool.get(sizeof(long long) * (size_t)X * N);
+    hc::encode(cx.stream, d_slots, work, coeffs, N, X, cx.delta, cx.d_rot_group, (const double2 *)cx.d_ksi);
+    const size_t pe = (size_t)nQ * N;
+    hc::small_to_limbs(cx.stream, cx.d_mod, N, nullptr, coeffs, dst, pe, X, qsel);
+    cx.ntt_fwd(dst, pe, X, qsel);
+    cx.pool.put((u64 *)coeffs);
+    cx.pool.put((u64 *)work);
+}
+// PlainEnroller::serializeDB — a gallery the sender may see (database kinds 7 / 8): normalise IN PLACE and pack the generalised
+// diagonals exactly as client_enroll does, then ENCODE the vector_dim slot vectors of each block (one polynomial each) into the resident
+// layout.  Plaintext t is the slot image of client_enroll's ciphertext t.
+void client_plain_enroll(Context &cx, double *db, size_t n, int babies) {
+    const int dim = cx.prm.dim, Nh = cx.slots;
+    for (size_t v = 0; v < n; v++) normalize(db + v * dim, dim);
+    const size_t G = cx.db_cts / dim, pt_elems = (size_t)cx.nQ * cx.N;
+    double *d_rows = (double *)cx.pool.get(sizeof(double) * (size_t)Nh * dim);
+    double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)dim * Nh);
+    u64 *d_pts = cx.pool.get(sizeof(u64) * (size_t)dim * pt_elems);
+    for (size_t g = 0; g < G; g++) {
+        const size_t first = g * (size_t)Nh;
+        const size_t rows = n > first ? std::min((size_t)Nh, n - first) : 0;
+        if (rows)
+            HIP_CHECK(hipMemcpyAsync(d_rows, db + first * dim, sizeof(double) * rows * dim, hipMemcpyHostToDevice, cx.stream));
+        hc::diag_pack(cx.stream, d_rows, (long long)rows, dim, Nh, d_slots, (babies > 0 && babies < dim) ? babies : 0);
+        encode_device(cx, d_slots, dim, d_pts);
+        cx.db_store(g * dim, d_pts, dim);
+    }
+    cx.sync();
+    cx.pool.put(d_pts);
+    cx.pool.put((u64 *)d_slots);
+    cx.pool.put((u64 *)d_rows);
+}
+
 #define HY_DB_NONCE_BASE (1ull << 36)
 #define HY_NONCE_LIMIT (1ull << 40)
 // DiagonalEnroller::serializeDB: normalise IN PLACE (enroller_diag.cpp:32-35), then per group of `slots` rows: pack the

@@ -556,16 +556,17 @@ void Context::load_eval_key(int rot, const u64 *host) {
 // ------------------------------------------------------------------ resident database
 // the layout loop B wants for `cts` ciphertexts in blocks of `form`: group-sequential for more than 8 blocks, and then with 46-bit
 // residues when every packed limb's modulus is below 2^46 (HYDIA_DB_48BIT keeps 6-byte residues)
-DbLayout Context::db_layout_for(size_t cts, int form) const {
-    const DbLayout ctm = hk::db_layout(N, nQ, db_packed ? 1 : 0);
+DbLayout Context::db_layout_for(size_t cts, int form, bool plain) const {
+    const DbLayout ctm = hk::db_layout(N, nQ, db_packed ? 1 : 0, plain);
     if (!(db_seq_ok && db_packed && form >= 2 && cts % (size_t)form == 0)) return ctm;
     bool b46 = db_bits46_ok;
     for (int j = 1; j < nQ; j++)
         if (q[j] >> 46) b46 = false;
-    return hk::db_layout_seq(N, nQ, 1, form, (int)(cts / (size_t)form), tensor_bpp, tensor_nw, b46);
+    // (a plain gallery: canonical residues of a plaintext are below q_j, so the same rule holds; its loop B has its own cap of blocks per wave)
+    return hk::db_layout_seq(N, nQ, 1, form, (int)(cts / (size_t)form), plain ? hk::PLAIN_BPP : tensor_bpp, tensor_nw, b46, plain);
 }
-void Context::db_resize(size_t n_vectors, size_t cts, int form) {
-    const DbLayout want = db_layout_for(cts, form);
+void Context::db_resize(size_t n_vectors, size_t cts, int form, bool plain) {
+    const DbLayout want = db_layout_for(cts, form, plain);
     const size_t bytes = db_alloc_size(want, cts);  // (+ the tail a lane's last 16-byte load may touch: db_layout.h)
     if (d_db) sync_all();  // the layout may change under a still asynchronous query
     if (d_db && db_alloc_bytes != bytes) {
@@ -599,6 +600,7 @@ void Context::db_resize_rows(size_t n_vectors, size_t cts) {
 // the resident database, its layout and its declared form stay what they were.
 void Context::db_relayout(int form) {
     if (!d_db || db_cts == 0) return;
+    if (db_plain()) throw StateError("hydia: a plain gallery (kind 7 / 8) declares its form at allocation");
     const DbLayout want = db_layout_for(db_cts, form);
     if (want.seq == db_lay.seq && want.bd == db_lay.bd && want.seq_bpp == db_lay.seq_bpp && want.bits46 == db_lay.bits46) return;
     sync_all();
@@ -645,6 +647,7 @@ void Context::db_relayout(int form) {
 // call fails with a DeviceError BEFORE anything is touched.
 void Context::db_grow(size_t n_vectors, size_t cts) {
     if (!d_db || db_cts == 0) throw StateError("hydia: no database resident");
+    if (db_plain()) throw StateError("hydia: a plain gallery (kind 7 / 8) is not updated in place");
     if (cts <= db_cts) {
         db_vectors = n_vectors;
         return;
@@ -730,6 +733,7 @@ struct DbConv {
 }  // namespace
 void Context::db_save(const char *path) {
     if (!d_db || db_cts == 0) throw StateError("hydia: no database resident");
+    if (db_plain()) throw StateError("hydia: a plain gallery (kind 7 / 8) is not saved: the file format holds ciphertexts");
     if (db_kind == 1) throw StateError("hydia: a row-packed database (approach 1) is not saved: the file format describes the context's packing, not kind 1's plain residues");
     if (db_kind == 3) throw StateError("hydia: a chunk-packed database (approach 3) is not saved: the file format describes the context's packing, not kind 3's plain residues");
     sync_all();

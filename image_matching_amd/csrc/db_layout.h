@@ -16,13 +16,19 @@
 //     at bit 92 l of the unit and fetches them with one 16-byte load from dword (92 l) >> 5 (measured: the stream takes 5.5 % less
 //     time, stream_rate.hip).  Sixteen residues = 92 bytes = 23 dwords is the granule everything else (enrolment, export, files) uses.
 // Both hold ct_bytes per ciphertext; a ciphertext's address is db_offset() in either.
+// A PLAIN gallery (database kinds 7 / 8: unencrypted templates, one encoded polynomial per diagonal) lies in the same two layouts with
+// ONE polynomial per entry instead of two: `plain` != 0, db_polys() = 1, ct_bytes = poly_bytes.  The zero value means two polynomials,
+// so a DbLayout{} filled in by hand describes a ciphertext database as before.
 struct DbLayout {
     unsigned long long ct_bytes, poly_bytes;
     int packed;
     int seq, seq_bpp;  // group size gs (0 = ciphertext-major) and the blocks per wave it was chosen with (waves = gs / seq_bpp)
     int bd, blocks;    // seq: ciphertexts per block (the diagonal count), blocks resident
     int bits46;        // seq && packed: 46-bit residues in 736-byte units (else 48-bit in 768)
+    int plain;         // != 0: one polynomial per entry (a plain gallery); 0: the two of a ciphertext
 };
+// polynomials per database entry
+HD size_t db_polys(const DbLayout &L) { return L.plain ? 1 : 2; }
 
 // bytes of 128 consecutive residues of limb j
 HD size_t db_unit_bytes(const DbLayout &L, int j) { return (L.packed && j > 0) ? (L.bits46 ? 736 : 768) : 1024; }
@@ -38,9 +44,9 @@ HD size_t db_offset(const DbLayout &L, int N, size_t t, int p, int j, size_t c) 
     const size_t es = (L.packed && j > 0) ? 6 : 8;
     if (!L.seq) return t * L.ct_bytes + (size_t)p * L.poly_bytes + db_limb_offset(L, N, j) + c * es;
     const size_t g = t / L.bd, i = t % L.bd, grp = g / L.seq, u = g % L.seq, tile = c >> 7, cc = c & 127, groups = L.blocks / L.seq;
-    const size_t unit = ((((tile * groups + grp) * L.bd + i) * L.seq + u) * 2 + p) * db_unit_bytes(L, j);
+    const size_t unit = ((((tile * groups + grp) * L.bd + i) * L.seq + u) * db_polys(L) + p) * db_unit_bytes(L, j);
     const size_t in_unit = (L.bits46 && L.packed && j > 0) ? (cc >> 4) * 92 : cc * es;
-    return (size_t)L.blocks * L.bd * 2 * db_limb_offset(L, N, j) + unit + in_unit;
+    return (size_t)L.blocks * L.bd * db_polys(L) * db_limb_offset(L, N, j) + unit + in_unit;
 }
 
 // first byte of the 16-byte load lane `lane` of a loop-B wave issues inside a 46-bit unit (its two residues start at bit 92 lane)

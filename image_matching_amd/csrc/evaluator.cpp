@@ -1045,7 +1045,12 @@ void Context::rotate_query_range(const Ct &qc, int first, int count, u64 *out) {
 }
 // computeSimilarity (sender_diag.cpp:12-33): all G blocks of the resident DB in one tensor-accumulate launch
 Ct Context::similarity(const Ct &qc) {
-    if (db_kind == 6) {
+    if (db_kind == 7) {  // plain gallery: loop A, the two-component loop B, rescale — no relinearisation
+        Ct acc = similarity_accumulate(qc);
+        rescale(acc);
+        return acc;
+    }
+    if (db_kind == 6 || db_kind == 8) {
         Ct sum = similarity_bsgs_sum(qc);
         rescale(sum);
         return sum;
@@ -1106,7 +1111,7 @@ void Context::build_giants(int G) {
     giants_G = G;
 }
 Ct Context::similarity_bsgs_sum(const Ct &qc) {
-    if (!d_db || db_cts == 0 || db_kind != 6) throw StateError("hydia: no database resident (pre-rotated diagonal packing)");
+    if (!d_db || db_cts == 0 || (db_kind != 6 && db_kind != 8)) throw StateError("hydia: no database resident (pre-rotated diagonal packing)");
     if (qc.nl != nQ) throw StateError("hydia: query must be a fresh (level 0) ciphertext");
     const int dim = prm.dim, B = db_babies, NG = (dim + B - 1) / B;
     if (B < 1 || dim % B) throw StateError("hydia: the resident database carries no valid baby count");
@@ -1115,6 +1120,10 @@ Ct Context::similarity_bsgs_sum(const Ct &qc) {
     // babies: rotations 0 .. B-1 of the query (loop A on B - 1 keys)
     Ct rot(this, B, 2, nl, qc.scale);
     rotate_query_range(qc, 0, B, rot.d);
+    if (db_kind == 8) {  // plain gallery: two-component inner sums, so the giant steps start at their key switch
+        Ct acc = plain_accumulate(rot, B, NG);
+        return giant_step_sum(acc, NG);
+    }
     // inner sums: ciphertext t = (block*NG + g)*B + b is "diagonal b of block block*NG + g"; the accumulators come out giant-major
     // (slot g*G + block), so every later step is ONE batch over all database blocks
     Ct acc(this, G * NG, 3, nl, qc.scale * delta);
@@ -1124,7 +1133,20 @@ Ct Context::similarity_bsgs_sum(const Ct &qc) {
     timer_end("hydia_tensor");
     return giant_step_sum(acc, NG);
 }
-// the giant steps of the BSGS mat-vec on giant-major degree-2 accumulators [NG X0] (slot g X0 + x): relinearise, the partial sums
+// Loop B over a plain gallery: rot = the R rotations of the query loop A made, blocks of R plaintexts (kind 7: R = dim, NG = 1;
+// kind 8: R = the babies, NG giants per database block, accumulators giant-major).  Scale and level are kind 5's partial sums'.
+Ct Context::plain_accumulate(const Ct &rot, int R, int NG) {
+    if (!d_db || db_cts == 0 || !db_plain() || !db_lay.plain) throw StateError("hydia: no plain gallery resident");
+    const int G = (int)(db_cts / prm.dim), nl = nQ;
+    Ct acc(this, G * NG, 2, nl, rot.scale * delta);
+    op_bytes("op:loop_b_plain", N, 0, (double)db_cts * (double)db_lay.ct_bytes + ((double)R * 2 + (double)G * NG * 2) * nl * N * 8);
+    timer_begin("hydia_plain");
+    hk::hydia_plain_accumulate(stream, d_mod, N, rot.d, d_db, acc.d, G * NG, R, nl, db_lay, db_kind == 8 ? NG : 0, hk::PLAIN_BPP, tensor_nw);
+    timer_end("hydia_plain");
+    return acc;
+}
+// the giant steps of the BSGS mat-vec on giant-major degree-2 accumulators [NG X0] (slot g X0 + x): relinearise (a plain gallery's
+// two-component sums need none: relinearize returns them as they are), the partial sums
 // g >= 1 of ALL X0 through one batched key switch, rotation key B g for slot (g, x) (the automorphism rides in the ModDown
 // epilogue); then out[x] = sum over g of slot (g, x)
 Ct Context::giant_step_sum(Ct &acc, int NG) {
@@ -1483,12 +1505,14 @@ Ct Context::relin_compare_lanes(Ct &acc, double dlt, int sign_depth) {
 }
 // the degree-2 accumulators of loop B for all resident blocks (computeSimilarity without its relinearise / rescale tail)
 Ct Context::similarity_accumulate(const Ct &qc) {
-    if (!d_db || db_cts == 0 || db_kind != 5) throw StateError("hydia: no database resident (diagonal packing)");
+    if (!d_db || db_cts == 0 || (db_kind != 5 && db_kind != 7)) throw StateError("hydia: no database resident (diagonal packing)");
     if (qc.nl != nQ) throw StateError("hydia: query must be a fresh (level 0) ciphertext");
     Ct rot = rotate_query(qc);
+    if (db_kind == 7) return plain_accumulate(rot, prm.dim, 1);  // 2 components
     return similarity_accumulate_rot(rot);
 }
 Ct Context::similarity_accumulate_rot(const Ct &rot) {
+    if (db_plain()) throw StateError("hydia: a plain gallery (kind 7 / 8) is resident: caller-supplied rotations are not served on it yet");
     if (!d_db || db_cts == 0 || db_kind != 5) throw StateError("hydia: no database resident (diagonal packing)");
     const int dim = prm.dim;
     if (rot.X != dim || rot.npoly != 2 || rot.nl != nQ || !rot.compact())
@@ -1512,7 +1536,7 @@ Ct Context::index_scenario_rot(const Ct &rot) {
 }
 // indexScenario (sender_diag.cpp:52-63): loop A, loop B, then the per-block tails on the comparator lanes
 Ct Context::index_scenario(const Ct &qc) {
-    Ct acc = db_kind == 6 ? similarity_bsgs_sum(qc) : similarity_accumulate(qc);  // 2 components (relinearised) : 3
+    Ct acc = db_kind == 6 || db_kind == 8 ? similarity_bsgs_sum(qc) : similarity_accumulate(qc);  // 2 components (relinearised, or a plain gallery's) : 3
     return relin_compare_lanes(acc, 0.44 /* MATCH_THRESHOLD, include/config.h:9 */, 10 /* COMP_DEPTH, :14 */);
 }
 // membershipScenario (sender_diag.cpp:35-50): EvalAddManyInPlace over blocks, then EvalSum over all slots
@@ -1569,6 +1593,7 @@ void Context::check_multi(const std::vector<const Ct *> &qs) const {
     for (const Ct *q : qs)
         if (!q || q->X != 1 || q->npoly != 2 || q->nl != nQ || !q->compact() || q->scale != qs[0]->scale)
             throw std::runtime_error("hydia: every query of a batch must be one fresh 2-component ciphertext at full level");
+    if (db_plain()) throw StateError("hydia: a plain gallery (kind 7 / 8) is resident: batches of queries are not served on it yet");
     if (!d_db || db_cts == 0 || (db_kind != 5 && db_kind != 6)) throw StateError("hydia: no database resident (diagonal packing)");
 }
 // queries one batch takes: what free HBM (plus the pool's cache) holds of a query's rotation set, accumulators and comparator

@@ -209,7 +209,10 @@ int hydia_group_create(const hydia_params *p, const int *devices, uint32_t n_sha
                                                      std::to_string(ndev) + " HIP device(s) visible"));
         }
         g = new hydia_group;
-        for (uint32_t r = 0; r < n_shards; r++) g->shard.push_back(new hydia_ctx(hydia_to_params(p), devices[r]));
+        for (uint32_t r = 0; r < n_shards; r++) {
+            g->shard.push_back(new hydia_ctx(hydia_to_params(p), devices[r]));
+            g->shard.back()->in_group = true;
+        }
         g->blk_lo.assign(n_shards, 0);
         g->blk_hi.assign(n_shards, 0);
         // shards on different GPUs exchange the query and the results by peer copies

@@ -160,8 +160,9 @@ struct Context : HostParams {
     // 48-bit residues when every scaling prime is below 2^48; HYDIA_DB_UNPACKED keeps plain [2][nQ][N] u64)
     unsigned char *d_db = nullptr;
     size_t db_vectors = 0, db_cts = 0;
-    int db_kind = 0;   // 0 none, 1 row packing (approach 1, the literature baseline: plain 8-byte residues, ciphertext-major), 3 chunk packing (approach 3, Blind-Match: the same storage, db_chunk_len), 5 diagonal packing (HyDia, approach 5), 6 the same with pre-rotated diagonals (BSGS mat-vec), 4 column packing (HERS)
-    int db_babies = 0; // kind 5 / 6: hoisted (baby) rotations the resident database was enrolled for; == vector_dim for kind 5
+    int db_kind = 0;   // 0 none, 1 row packing (approach 1, the literature baseline: plain 8-byte residues, ciphertext-major), 3 chunk packing (approach 3, Blind-Match: the same storage, db_chunk_len), 5 diagonal packing (HyDia, approach 5), 6 the same with pre-rotated diagonals (BSGS mat-vec), 4 column packing (HERS), 7 / 8 a PLAIN gallery (unencrypted templates, one encoded polynomial per diagonal) in the form of 5 / 6
+    bool db_plain() const { return db_kind == 7 || db_kind == 8; }
+    int db_babies = 0; // kind 5 / 6 / 7 / 8: hoisted (baby) rotations the resident database was enrolled for; == vector_dim for kind 5
     // Which form of the diagonal mat-vec a database enrolled on this context gets (HYDIA_MATVEC=auto|hoisted|bsgs|<B>, hydia_set_matvec).
     // With i = b + B g: B - 1 hoisted rotations of the query per QUERY, dim / B relinearisations + dim / B - 1 giant rotations per BLOCK.
     //   hoisted  B = dim: the reference's own form (dim - 1 hoisted rotations, one relinearisation per block, no giant step)
@@ -200,13 +201,14 @@ struct Context : HostParams {
     bool db_seq_ok = true;  // many-block hoisted databases take the group-sequential layout (HYDIA_DB_CT_MAJOR turns it off)
     bool db_bits46_ok = true;  // ... with 46-bit residues for the packed limbs (HYDIA_DB_48BIT turns that off)
     size_t db_alloc_bytes = 0;
-    DbLayout db_layout_for(size_t cts, int form) const;
+    DbLayout db_layout_for(size_t cts, int form, bool plain = false) const;
     DbLayout db_lay{};      // layout of the resident database (set by db_resize)
     DbLayout db_layout() const { return d_db ? db_lay : hk::db_layout(N, nQ, db_packed ? 1 : 0); }
     // (re)allocates the resident database for `cts` ciphertexts.  form = the hoisted-rotation count its diagonals will be laid out
     // for (vector_dim = the reference's form, or the baby count): loop B walks blocks of `form` ciphertexts, and more than 8 of them
     // take the group-sequential layout; -1 (HERS' column packing) stays ciphertext-major
-    void db_resize(size_t n_vectors, size_t cts, int form);
+    // plain: a plain gallery, one polynomial per entry (kinds 7 / 8)
+    void db_resize(size_t n_vectors, size_t cts, int form, bool plain = false);
     void db_resize_rows(size_t n_vectors, size_t cts);  // kind 1: `cts` ciphertexts as plain [ct][2][nQ][N] residues
     void db_relayout(int form);  // the same ciphertexts laid out for another form (a second buffer for the duration)
     void db_grow(size_t n_vectors, size_t cts);  // kind 5 / 6: room for more blocks, old ciphertexts kept (a second buffer for the duration)
@@ -214,7 +216,7 @@ struct Context : HostParams {
     // not re-enrol from plaintext; the reference keeps serial/db_diagonal/index<t>.bin, enroller_diag.cpp:158-166)
     void db_save(const char *path);
     void db_load(const char *path);
-    void db_store(size_t t0, const u64 *d_plain, int X);  // [X][2][nQ][N] device residues -> ciphertexts t0..t0+X-1
+    void db_store(size_t t0, const u64 *d_plain, int X);  // [X][2][nQ][N] device residues -> ciphertexts t0..t0+X-1 ([X][nQ][N] -> plaintexts of a plain gallery)
     void db_accumulate(size_t t0, const u64 *d_plain, int X);  // ciphertexts t0..t0+X-1 += [X][2][nQ][N] device residues, in place
     void db_fetch(size_t t0, u64 *d_plain, int X);
 
@@ -423,6 +425,8 @@ struct Context : HostParams {
     Ct similarity(const Ct &q);                     // -> [G][2][nQ-1][N]
     // the same scenarios on rotations supplied by the caller ([dim][2][nQ][N], as rotate_query returns them)
     Ct similarity_bsgs_sum(const Ct &q);            // BSGS mat-vec up to (not including) the rescale: [G][2][nQ][N]
+    // loop B over a plain gallery (kind 7: R = dim, NG = 1; kind 8: the babies, giant-major): [G NG][2][nQ][N], nothing to relinearise
+    Ct plain_accumulate(const Ct &rot, int R, int NG);
     Ct similarity_accumulate_rot(const Ct &rot);
     Ct similarity_rot(const Ct &rot);
     Ct index_scenario_rot(const Ct &rot);
@@ -442,7 +446,7 @@ struct Context : HostParams {
     void check_multi(const std::vector<const Ct *> &qs) const;  // runtime_error: a query is not fresh; StateError: no diagonal database
     int multi_batch(int Q);
     Ct loop_b_multi(const std::vector<const Ct *> &qs, int q0, int Qb);
-    Ct giant_step_sum(Ct &acc, int NG);  // BSGS giant steps on [NG X0] giant-major accumulators -> [X0][2][nQ][N] (relinearises acc)
+    Ct giant_step_sum(Ct &acc, int NG);  // BSGS giant steps on [NG X0] giant-major accumulators -> [X0][2][nQ][N] (relinearises a 3-component acc)
     Ct batch_slice(const Ct &b, int q, int per);
     // ---- HERS sender (approach 4, src/sender/sender_hers.cpp): q = dim query ciphertexts
     Ct hers_similarity(const Ct &q);

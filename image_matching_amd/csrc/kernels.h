@@ -262,9 +262,10 @@ void ledger_enable(bool on);
 void ledger_add(const char *kernel, double bytes);
 size_t ledger_dump(char *out, size_t cap);  // "kernel\tlaunches\tbytes\n" per line; returns the size needed
 
-DbLayout db_layout(int N, int nQ, int packed);                                                     // ciphertext-major
-DbLayout db_layout_seq(int N, int nQ, int packed, int bd, int blocks, int bpp, int nw, bool bits46 = false);          // group-sequential when it applies
-// ciphertexts t0 .. t0+X-1 of the database at `db` <-> plain [X][2][nQ][N] residues
+// plain: a plain gallery, one polynomial per entry (DbLayout::plain)
+DbLayout db_layout(int N, int nQ, int packed, bool plain = false);                                 // ciphertext-major
+DbLayout db_layout_seq(int N, int nQ, int packed, int bd, int blocks, int bpp, int nw, bool bits46 = false, bool plain = false);  // group-sequential when it applies
+// ciphertexts t0 .. t0+X-1 of the database at `db` <-> plain [X][np][nQ][N] residues, np = db_polys(L)
 void db_pack(hipStream_t st, int N, int nQ, const u64 *plain, void *db, size_t t0, int X, const DbLayout &L);
 void db_unpack(hipStream_t st, int N, int nQ, u64 *plain, const void *db, size_t t0, int X, const DbLayout &L);
 // ciphertexts t0 .. t0+X-1 of the database += plain [X][2][nQ][N] residues mod q_j, in place (db_accum.h; mod = the context's table)
@@ -409,6 +410,11 @@ constexpr int TENSOR_BATCH = 0;
 void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G,
                              int dim, int nl, const DbLayout &L, int ng, int bpp, int nw);
 int hydia_tensor_mq_width(const DbLayout &L);  // queries one pass over the database serves
+// Loop B over a plain gallery (database kinds 7 / 8, L.plain): acc [G][2][nl][N] (slot map as above with a batch of one),
+// acc[slot][p] = sum_i rot[i].c_p * m[g][i] mod q_j — no third component, nothing to relinearise.  bpp, nw: split caps (tensor_split)
+void hydia_plain_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, const void *db, u64 *acc, int G, int dim, int nl,
+                            const DbLayout &L, int ng, int bpp, int nw);
+constexpr int PLAIN_BPP = 2;  // blocks per wave of a plain gallery's loop B (resources of every instantiation)
 
 // EvalMult(ct, plaintext) residue-wise (approach 1's merge masks): o[xp][j] = a[xp][j] * m[j] mod q_j with the Shoup companions ms;
 // XP polynomials of nl limbs (a at limb stride a_ls, o compact), m / ms [nl][N]

@@ -7,6 +7,7 @@
 //   k_inner_product       <digits, evk> of EvalFastRotation (sender_diag.cpp:25) and RelinearizeInPlace (:79)
 //   k_moddown_combine     ModDown's (acc - conv) / P, + c0, + the evaluation-form automorphism of EvalFastRotation
 //   k_hydia_tensor        512 x EvalMultNoRelin + 511 x EvalAddInPlace per block (sender_diag.cpp:70-77, :93)
+//   k_hydia_plain         the same sums against a PLAIN gallery (one encoded polynomial per diagonal; no counterpart in the reference)
 //   k_rescale_*           RescaleInPlace (sender_diag.cpp:80)
 //   k_tensor, k_lincomb*  ct x ct products and Chebyshev/f4 leaves of chebyshevCompare (src/openFHE_wrapper.cpp:143-185)
 //   k_batch_sum           HERS: sum of the per-dimension products (src/sender/sender_hers.cpp:60-87)
@@ -699,12 +700,12 @@ DEV DbWalk db_walk(const DbLayout &L, int N, int dim, int j, int tile, int lane,
         w.si = L.ct_bytes;
         w.sp = L.poly_bytes;
     } else {
-        const size_t groups = L.blocks / L.seq, ub = db_unit_bytes(L, j);
+        const size_t groups = L.blocks / L.seq, ub = db_unit_bytes(L, j), np = db_polys(L);
         // (bits46: the lane's two residues start at bit 92 lane of the unit; it loads 16 bytes from the dword that holds that bit)
         const size_t in_unit = (L.bits46 && j > 0) ? db_lane_load46(lane) : (size_t)lane * 2 * es;
-        w.base = (size_t)L.blocks * L.bd * 2 * db_limb_offset(L, N, j) + ((((size_t)tile * groups + grp) * L.bd) * L.seq + u0) * 2 * ub + in_unit;
-        w.su = 2 * ub;
-        w.si = (size_t)L.seq * 2 * ub;
+        w.base = (size_t)L.blocks * L.bd * np * db_limb_offset(L, N, j) + ((((size_t)tile * groups + grp) * L.bd) * L.seq + u0) * np * ub + in_unit;
+        w.su = np * ub;
+        w.si = (size_t)L.seq * np * ub;
         w.sp = ub;
     }
     return w;
@@ -1024,11 +1025,171 @@ __global__ __launch_bounds__(64 * KS) void k_hydia_tensor_sk(const ModC *__restr
     }
 }
 
-// unpacked [X][2][nQ][N] u64  <->  database layout.  grid (N/512, nQ, X*2)
+// ------------------------------------------------------------------------------------------------ loop B for a plain gallery
+// Database kinds 7 / 8: the templates are NOT encrypted, entry t is ONE encoded polynomial m (DbLayout::plain).  Per coefficient
+//   acc[slot][p][j][c] = sum_{i<dim} rot[i].c_p[j][c] * m[g][i][j][c] mod q_j,  p = 0, 1
+// — two sums instead of Karatsuba's three, one database operand per diagonal instead of two, a 2-component accumulator that needs no
+// relinearisation.  Work split, XCD tile map, non-temporal database loads, prefetch depth, one barrier per diagonal and the slot map are
+// k_hydia_tensor's; the arithmetic policies are used as they are.  Bounds (tests/test_plain_gallery_model_cpu.py):
+// - Halves24: no operand sums, so every half is below 2^24 and every product below 2^48; ll and hh take one product per diagonal, mid
+//   two: 4096 diagonals (the launcher's limit) x 2 x 2^48 = 2^61 < 2^63.
+// - Sums128: the fold chunk of the encrypted kernel is kept.  It budgets a product at 2^(2k+2) (Karatsuba's operand sums); a plain
+//   product of residues below q < 2^k is below 2^(2k), so the chunk is conservative by two bits: q + chunk 2^(2k) < 2^126.  The fold
+//   path stays exercised on 59/60-bit limbs (every 128 / 32 diagonals).
+template <class A, int BPP, int NW>
+__global__ __launch_bounds__(64 * NW, 2) void k_hydia_plain(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot,
+                                                            const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                            int Gq, int xcd_map, DbLayout L, int j0, int G, int ng, int nblk) {
+    typedef typename A::T T;
+    const int j = blockIdx.y + j0;
+    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
+    const int gq = xcd_map ? k % Gq : blockIdx.x % Gq;
+    const int tile = xcd_map ? xcd + 8 * (k / Gq) : blockIdx.x / Gq;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const ModC M = mod[j];
+    const size_t c = (size_t)tile * 128 + lane * 2;
+    const size_t ps = (size_t)nl * N, cs = 2 * ps;  // rot / acc poly stride, ciphertext stride (elements)
+    const int g0 = (gq * NW + wv) * BPP;
+    const u64 *ra = rot + (size_t)j * N + c;
+    const DbWalk dw = db_walk(L, N, dim, j, tile, lane, g0, gq, wv * BPP);
+    const unsigned char *da = db + dw.base;
+    const A ar(M, dim, lane);
+    typename A::Sum s[BPP][2][2];  // [block][component][coefficient of the lane's pair]
+#pragma unroll
+    for (int u = 0; u < BPP; u++)
+#pragma unroll
+        for (int p = 0; p < 2; p++) s[u][p][0] = s[u][p][1] = typename A::Sum{};
+    struct Operands {
+        ulonglong2 a0, a1;
+        typename A::Raw b[BPP];
+    };
+    auto fetch = [&](Operands &o, int i) {
+        o.a0 = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * cs);
+        o.a1 = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * cs + ps);
+#pragma unroll
+        for (int u = 0; u < BPP; u++) o.b[u].template load<true>(da + u * dw.su + (size_t)i * dw.si);
+    };
+    auto accumulate = [&](const Operands &o) {
+        const T a[2][2] = {{A::rot(o.a0.x), A::rot(o.a0.y)}, {A::rot(o.a1.x), A::rot(o.a1.y)}};
+#pragma unroll
+        for (int u = 0; u < BPP; u++) {
+            T b[2];
+            ar.cut(o.b[u], b);
+#pragma unroll
+            for (int p = 0; p < 2; p++)
+#pragma unroll
+                for (int e = 0; e < 2; e++) A::mac(s[u][p][e], a[p][e], b[e]);
+        }
+    };
+    if constexpr (A::depth == 3) {
+        Operands S0, S1, S2;
+        fetch(S0, 0);
+        fetch(S1, 1);
+        int i = 0;
+        for (; i + 2 < dim; i += 3) {  // branch-free inside: clamped re-fetches of the last diagonal are never accumulated
+            fetch(S2, i + 2);
+            accumulate(S0);
+            if (NW > 1) __builtin_amdgcn_s_barrier();  // keep the waves on the same diagonal (no memory wait implied)
+            fetch(S0, i + 3 < dim ? i + 3 : dim - 1);
+            accumulate(S1);
+            if (NW > 1) __builtin_amdgcn_s_barrier();
+            fetch(S1, i + 4 < dim ? i + 4 : dim - 1);
+            accumulate(S2);
+            if (NW > 1) __builtin_amdgcn_s_barrier();
+        }
+        if (i < dim) accumulate(S0);
+        if (i + 1 < dim) accumulate(S1);
+    } else {
+        Operands cur, nxt;
+        fetch(cur, 0);
+        for (int i0 = 0; i0 < dim; i0 += ar.chunk) {
+            const int i1 = i0 + ar.chunk < dim ? i0 + ar.chunk : dim;
+            for (int i = i0; i < i1; i += 2) {  // dim and every chunk are even (k_hydia_tensor)
+                fetch(nxt, i + 1);
+                accumulate(cur);
+                if (NW > 1) __builtin_amdgcn_s_barrier();
+                fetch(cur, i + 2 < dim ? i + 2 : i + 1);
+                accumulate(nxt);
+                if (NW > 1) __builtin_amdgcn_s_barrier();
+            }
+            if (i1 < dim) {
+#pragma unroll
+                for (int u = 0; u < BPP; u++)
+#pragma unroll
+                    for (int p = 0; p < 2; p++) {
+                        A::fold(s[u][p][0], M);
+                        A::fold(s[u][p][1], M);
+                    }
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < BPP; u++) {
+        u64 *o = acc + (mq_slot(0, g0 + u, G, ng, nblk, 1) * 2 * nl + j) * N + c;
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+            *reinterpret_cast<ulonglong2 *>(o + p * ps) = make_ulonglong2(A::reduce(s[u][p][0], M), A::reduce(s[u][p][1], M));
+    }
+}
+// Limb 0 of a SMALL ciphertext-major plain gallery (at most 8 blocks): k_hydia_tensor_sk's split of the diagonals over KS waves with
+// four sums per lane instead of six (the streaming kernel's 256 x G one-wave workgroups are as latency-bound here as there).
+// grid (N/128 * G, 1)
+template <int KS>
+__global__ __launch_bounds__(64 * KS) void k_hydia_plain_sk(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot,
+                                                            const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                            DbLayout L, int G, int ng, int nblk) {
+    typedef Sums128<false> A;
+    __shared__ u64 part[KS][4][64];
+    const int tiles = N / 128;
+    const int tile = blockIdx.x % tiles, g = blockIdx.x / tiles;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const ModC M = mod[0];
+    const size_t c = (size_t)tile * 128 + lane * 2;
+    const size_t ps = (size_t)nl * N, cs = 2 * ps;
+    const u64 *ra = rot + c;
+    const unsigned char *da = db + (size_t)g * dim * L.ct_bytes + c * 8;
+    const A ar(M, dim, lane);
+    u128 s[2][2] = {};
+    int since = 0;
+    for (int i = wv; i < dim; i += KS) {
+        A::Raw r;
+        r.load<true>(da + (size_t)i * L.ct_bytes);
+        u64 b[2];
+        ar.cut(r, b);
+        const ulonglong2 a0 = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * cs);
+        const ulonglong2 a1 = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * cs + ps);
+        A::mac(s[0][0], a0.x, b[0]);
+        A::mac(s[0][1], a0.y, b[1]);
+        A::mac(s[1][0], a1.x, b[0]);
+        A::mac(s[1][1], a1.y, b[1]);
+        if (++since == ar.chunk) {
+            since = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) A::fold(s[k / 2][k % 2], M);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) part[wv][k][lane] = A::reduce(s[k / 2][k % 2], M);
+    __syncthreads();
+    if (wv == 0) {
+        u64 r[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            u64 t = part[0][k][lane];
+            for (int w = 1; w < KS; w++) t = addmod(t, part[w][k][lane], M.q);
+            r[k] = t;
+        }
+        u64 *o = acc + mq_slot(0, g, G, ng, nblk, 1) * 2 * nl * N + c;
+        *reinterpret_cast<ulonglong2 *>(o) = make_ulonglong2(r[0], r[1]);
+        *reinterpret_cast<ulonglong2 *>(o + ps) = make_ulonglong2(r[2], r[3]);
+    }
+}
+
+// unpacked [X][np][nQ][N] u64  <->  database layout (np = db_polys(L): 2, or 1 for a plain gallery).  grid (N/512, nQ, X*np)
 template <bool PACK>
 __global__ __launch_bounds__(256) void k_db_repack(int N, int nQ, u64 *__restrict__ plain, unsigned char *__restrict__ db,
                                                    DbLayout L, size_t t0) {
-    const int j = blockIdx.y, xp = blockIdx.z, x = xp >> 1, p = xp & 1;
+    const int j = blockIdx.y, xp = blockIdx.z, x = L.plain ? xp : xp >> 1, p = L.plain ? 0 : xp & 1;
     const size_t c = (size_t)(blockIdx.x * 256 + threadIdx.x) * 2;
     u64 *pl = plain + ((size_t)xp * nQ + j) * N + c;
     const bool pk = L.packed && j > 0;
@@ -1051,10 +1212,10 @@ __global__ __launch_bounds__(256) void k_db_repack(int N, int nQ, u64 *__restric
 }
 
 // the 46-bit limbs of a bits46 layout: a thread moves SIXTEEN residues = 23 dwords (the granule that starts on a dword).
-// grid (N/4096, nQ - 1, X*2): limb j = blockIdx.y + 1
+// grid (N/4096, nQ - 1, X*np): limb j = blockIdx.y + 1
 template <bool PACK>
 __global__ __launch_bounds__(256) void k_db_repack46(int N, int nQ, u64 *__restrict__ plain, unsigned char *__restrict__ db, DbLayout L, size_t t0) {
-    const int j = blockIdx.y + 1, xp = blockIdx.z, x = xp >> 1, p = xp & 1;
+    const int j = blockIdx.y + 1, xp = blockIdx.z, x = L.plain ? xp : xp >> 1, p = L.plain ? 0 : xp & 1;
     const size_t c = (size_t)(blockIdx.x * 256 + threadIdx.x) * 16;
     if (c >= (size_t)N) return;
     u64 *pl = plain + ((size_t)xp * nQ + j) * N + c;
@@ -1430,17 +1591,80 @@ void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *
         else stream((Sums128<true> *)nullptr, 1, nl - 1);
     }
 }
-DbLayout db_layout(int N, int nQ, int packed) {
+// ---- loop B for a plain gallery.  The split is tensor_split's with the gallery's own cap of blocks per wave (PLAIN_BPP = 2): at two
+// blocks per wave the 46-bit kernel takes 125 VGPRs (four waves per SIMD, the encrypted one two); four blocks per wave compiled to 231
+// (two waves per SIMD: the same blocks in flight per SIMD, half the waves to hide latency with) and is not instantiated
+template <class A, int BPP, class... Args>
+static void launch_plain(hipStream_t st, int nw, dim3 grid, Args... args) {
+    switch (nw) {
+    case 1: hipLaunchKernelGGL((k_hydia_plain<A, BPP, 1>), grid, dim3(64), 0, st, args...); return;
+    case 2: hipLaunchKernelGGL((k_hydia_plain<A, BPP, 2>), grid, dim3(128), 0, st, args...); return;
+    case 4: hipLaunchKernelGGL((k_hydia_plain<A, BPP, 4>), grid, dim3(256), 0, st, args...); return;
+    }
+    throw std::logic_error("hydia: no plain loop B kernel for this split");
+}
+void hydia_plain_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, const void *db, u64 *acc, int G, int dim, int nl,
+                            const DbLayout &L, int ng, int bpp, int nw) {
+    if (!L.plain) throw std::logic_error("hydia: plain loop B launched against a ciphertext database");
+    if (G < 1 || dim < 2 || (ng > 0 && G % ng)) throw std::logic_error("hydia: loop B with a bad shape");
+    if (L.bits46 && !(L.packed && L.seq && dim <= 4096)) throw std::logic_error("hydia: 46-bit database outside the 24-bit-halves loop B");
+    if (L.seq && (G != L.blocks || dim != L.bd || G % L.seq || G <= 8 || L.seq % L.seq_bpp || (L.seq & (L.seq - 1)) || L.seq > 8))
+        throw std::logic_error("hydia: loop B launched against a group-sequential database with another shape");
+    int B, W;
+    if (L.seq) {
+        B = L.seq_bpp;
+        W = L.seq / L.seq_bpp;
+    } else {
+        tensor_split(G, bpp, nw, &B, &W);
+    }
+    const int Gq = G / (B * W), nblk = ng > 0 ? G / ng : 0;
+    const int xm = (N / 128) % 8 == 0 ? 1 : 0;
+    const unsigned char *dbb = (const unsigned char *)db;
+    // ledger bytes: the resident plaintexts (one polynomial each) + the rotation set once + G two-component accumulators
+    const double per_lp8 = LP_BYTES(N), per_lp6 = (double)N * (L.bits46 ? 5.75 : 6.0);
+    const double rot_acc = (double)dim * 2 * per_lp8 + (double)G * 2 * per_lp8;
+    auto bytes = [&](int limbs, double per_lp) { return limbs * ((double)G * dim * per_lp + rot_acc); };
+    auto stream = [&](auto *policy, int j0, int limbs) {
+        typedef typename std::remove_pointer<decltype(policy)>::type A;
+        const dim3 grid((N / 128) * Gq, limbs);
+        char n[96];
+        snprintf(n, sizeof n, "k_hydia_plain<%s, %d, %d>", A::name, B, W);
+        ledger_add(n, bytes(limbs, j0 ? per_lp6 : per_lp8));
+        if (B == 2) launch_plain<A, 2>(st, W, grid, mod, N, rot, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk);
+        else launch_plain<A, 1>(st, W, grid, mod, N, rot, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk);
+    };
+    if (!L.packed) {
+        stream((Sums128<false> *)nullptr, 0, nl);
+        return;
+    }
+    if (!L.seq && G <= 8) {
+        const int ks = G <= 2 ? 8 : 4;
+        char n[96];
+        snprintf(n, sizeof n, "k_hydia_plain_sk<%d>", ks);
+        ledger_add(n, bytes(1, per_lp8));
+        const dim3 grid((N / 128) * G, 1);
+        if (ks == 8) hipLaunchKernelGGL((k_hydia_plain_sk<8>), grid, dim3(512), 0, st, mod, N, rot, dbb, acc, dim, nl, L, G, ng, nblk);
+        else hipLaunchKernelGGL((k_hydia_plain_sk<4>), grid, dim3(256), 0, st, mod, N, rot, dbb, acc, dim, nl, L, G, ng, nblk);
+    } else {
+        stream((Sums128<false> *)nullptr, 0, 1);
+    }
+    if (nl == 1) return;
+    if (L.bits46) stream((Halves24<true> *)nullptr, 1, nl - 1);
+    else if (L.seq && dim <= 4096) stream((Halves24<false> *)nullptr, 1, nl - 1);
+    else stream((Sums128<true> *)nullptr, 1, nl - 1);
+}
+DbLayout db_layout(int N, int nQ, int packed, bool plain) {
     DbLayout L{};
     L.packed = packed;
+    L.plain = plain ? 1 : 0;
     L.poly_bytes = packed ? (unsigned long long)N * 8 + (unsigned long long)(nQ - 1) * N * 6 : (unsigned long long)nQ * N * 8;
-    L.ct_bytes = 2 * L.poly_bytes;
+    L.ct_bytes = db_polys(L) * L.poly_bytes;
     return L;
 }
 // group-sequential for `blocks` blocks of bd ciphertexts: only where loop B is a stream worth shaping (more than 8 blocks, whole
 // 128-residue tiles) — otherwise the ciphertext-major layout comes back
-DbLayout db_layout_seq(int N, int nQ, int packed, int bd, int blocks, int bpp, int nw, bool bits46) {
-    DbLayout L = db_layout(N, nQ, packed);
+DbLayout db_layout_seq(int N, int nQ, int packed, int bd, int blocks, int bpp, int nw, bool bits46, bool plain) {
+    DbLayout L = db_layout(N, nQ, packed, plain);
     if (blocks <= 8 || N % 128) return L;
     int B, W;
     tensor_split(blocks, bpp, nw, &B, &W);
@@ -1451,21 +1675,23 @@ DbLayout db_layout_seq(int N, int nQ, int packed, int bd, int blocks, int bpp, i
     if (bits46 && packed && bd <= 4096) {  // 46-bit residues for the packed limbs (the caller vouches for the moduli)
         L.bits46 = 1;
         L.poly_bytes = (unsigned long long)N * 8 + (unsigned long long)(nQ - 1) * (N / 128) * 736;
-        L.ct_bytes = 2 * L.poly_bytes;
+        L.ct_bytes = db_polys(L) * L.poly_bytes;
     }
     return L;
 }
 void db_pack(hipStream_t st, int N, int nQ, const u64 *plain, void *db, size_t t0, int X, const DbLayout &L) {
+    const int np = (int)db_polys(L);
     const bool b46 = L.bits46 && L.seq && L.packed && nQ > 1;  // limb 0 through the pair kernel, the 46-bit limbs through the granule kernel
-    hipLaunchKernelGGL(k_db_repack<true>, dim3(N / 512, b46 ? 1 : nQ, X * 2), dim3(256), 0, st, N, nQ, const_cast<u64 *>(plain),
+    hipLaunchKernelGGL(k_db_repack<true>, dim3(N / 512, b46 ? 1 : nQ, X * np), dim3(256), 0, st, N, nQ, const_cast<u64 *>(plain),
                        (unsigned char *)db, L, t0);
     if (b46)
-        hipLaunchKernelGGL(k_db_repack46<true>, dim3((N / 16 + 255) / 256, nQ - 1, X * 2), dim3(256), 0, st, N, nQ, const_cast<u64 *>(plain), (unsigned char *)db, L, t0);
+        hipLaunchKernelGGL(k_db_repack46<true>, dim3((N / 16 + 255) / 256, nQ - 1, X * np), dim3(256), 0, st, N, nQ, const_cast<u64 *>(plain), (unsigned char *)db, L, t0);
 }
 void db_unpack(hipStream_t st, int N, int nQ, u64 *plain, const void *db, size_t t0, int X, const DbLayout &L) {
+    const int np = (int)db_polys(L);
     const bool b46 = L.bits46 && L.seq && L.packed && nQ > 1;
-    hipLaunchKernelGGL(k_db_repack<false>, dim3(N / 512, b46 ? 1 : nQ, X * 2), dim3(256), 0, st, N, nQ, plain, (unsigned char *)db, L, t0);
-    if (b46) hipLaunchKernelGGL(k_db_repack46<false>, dim3((N / 16 + 255) / 256, nQ - 1, X * 2), dim3(256), 0, st, N, nQ, plain, (unsigned char *)db, L, t0);
+    hipLaunchKernelGGL(k_db_repack<false>, dim3(N / 512, b46 ? 1 : nQ, X * np), dim3(256), 0, st, N, nQ, plain, (unsigned char *)db, L, t0);
+    if (b46) hipLaunchKernelGGL(k_db_repack46<false>, dim3((N / 16 + 255) / 256, nQ - 1, X * np), dim3(256), 0, st, N, nQ, plain, (unsigned char *)db, L, t0);
 }
 // ciphertexts t0 .. t0+X-1 of the database at `db` += plain [X][2][nQ][N] residues (mod q_j): the launch shapes of db_pack
 void db_accumulate(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *plain, void *db, size_t t0, int X, const DbLayout &L) {

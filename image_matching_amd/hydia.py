@@ -96,6 +96,10 @@ def load_library():
         "hydia_db_num_cts": (sz, [vp, sz]),
         "hydia_db_enroll": (i32, [vp, vp, sz, vp]),
         "hydia_db_alloc": (i32, [vp, sz]),
+        "hydia_plain_db_enroll": (i32, [vp, vp, sz]),
+        "hydia_plain_db_alloc": (i32, [vp, sz, i32]),
+        "hydia_plain_db_import_pt": (i32, [vp, sz, vp]),
+        "hydia_plain_db_export_pt": (i32, [vp, sz, vp]),
         "hydia_db_import_ct": (i32, [vp, sz, vp]),
         "hydia_db_export_ct": (i32, [vp, sz, vp]),
         "hydia_db_fill_random": (i32, [vp, sz, u64]),
@@ -589,6 +593,21 @@ class Context:
         _chk(self.L.hydia_db_export_ct(self.h, t, _p(out)))
         return out
 
+    # ---- plain gallery (kinds 7 / 8, include/hydia.h): unencrypted templates, one encoded polynomial [n_q][N] per diagonal
+    def plain_db_alloc(self, n, babies=None):
+        """room for n vectors in a declared form: babies = vector_dim (hoisted, the default) or a power of two >= 2 dividing it"""
+        _chk(self.L.hydia_plain_db_alloc(self.h, n, self.dim if babies is None else int(babies)))
+
+    def plain_db_import_pt(self, t, data):
+        data = np.ascontiguousarray(data, dtype=np.uint64)
+        assert data.size == self.nQ * self.N
+        _chk(self.L.hydia_plain_db_import_pt(self.h, t, _p(data)))
+
+    def plain_db_export_pt(self, t):
+        out = np.zeros((self.nQ, self.N), dtype=np.uint64)
+        _chk(self.L.hydia_plain_db_export_pt(self.h, t, _p(out)))
+        return out
+
     def db_update(self, first_vector, rows, normalise=True, seed=None, first_block=0):
         """hydia_db_update[_shard]: add a FRESH encryption of `rows` (k x vector_dim float64, normalised IN PLACE when `normalise`),
         placed at vectors first_vector .., to the resident kind-5 / kind-6 database.  Append: first_vector = db_stats()[0]; remove:
@@ -621,7 +640,8 @@ class Context:
         return {0: "auto", 1: "hoisted"}.get(m, m)
 
     def db_kind(self):
-        """0 none, 5 hoisted diagonals, 6 pre-rotated diagonals (baby-step / giant-step), 4 HERS columns, 1 rows (approach 1)"""
+        """0 none, 5 hoisted diagonals, 6 pre-rotated diagonals (baby-step / giant-step), 4 HERS columns, 1 rows (approach 1),
+        7 / 8 a plain gallery in the form of 5 / 6"""
         return int(self.L.hydia_db_kind(self.h))
 
     def db_babies(self):
@@ -699,6 +719,23 @@ class DiagonalEnroller:
     def appendDB(self, rows, seed=None):
         """append `rows` (normalised in place) after the last enrolled vector"""
         self.updateRows(self.numVectors, rows, True, seed)
+
+
+class PlainEnroller:
+    """A gallery the sender may see (database kinds 7 / 8; no counterpart in the reference): DiagonalEnroller's constructor shape,
+    serializeDB without a seed — the diagonals are encoded, not encrypted.  DiagonalSender and DiagonalReceiver are used unchanged.
+    Trust model (include/hydia.h): the sender sees the gallery; the query and the result stay encrypted under the receiver's key."""
+
+    def __init__(self, cc, num_vectors):
+        if not isinstance(cc, Context):  # a ShardGroup: the sharded senders do not serve a plain gallery (its shard contexts refuse too)
+            raise HydiaError(-2, "hydia: a plain gallery (kind 7 / 8) is not enrolled on a sharded context")
+        self.cc, self.numVectors = cc, num_vectors
+
+    def serializeDB(self, database):
+        """normalises `database` IN PLACE like DiagonalEnroller.serializeDB; the form follows Context.set_matvec"""
+        assert database.dtype == np.float64 and database.flags.c_contiguous
+        assert database.shape == (self.numVectors, self.cc.dim)
+        _chk(self.cc.L.hydia_plain_db_enroll(self.cc.h, _p(database), self.numVectors))
 
 
 class DiagonalReceiver:

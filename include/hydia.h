@@ -202,7 +202,8 @@ int hydia_db_update_shard(hydia_ctx *ctx, size_t first_vector, double *rows, siz
  * hydia_set_matvec mode: 0 auto (hydia_auto_babies: B grows with the blocks the enrolling context holds — at vector_dim 512: 64 up
  * to 3 blocks, 128 up to 12, 256 up to 40, hoisted above; measured, profiles/r04/matvec_sweep.txt), 1 hoisted, otherwise B itself; initial value from HYDIA_MATVEC=auto|hoisted|bsgs|<B>.
  * It takes effect at the NEXT enrolment; hydia_db_kind / hydia_db_babies tell what is resident (kind 0 none, 5 hoisted diagonals,
- * 6 pre-rotated diagonals, 4 HERS columns, 1 the rows of approach 1 — hydia_base_db_enroll, 3 the chunks of approach 3 — hydia_blind_db_enroll).  Ciphertexts imported one by one (hydia_db_alloc + hydia_db_import_ct: the reference
+ * 6 pre-rotated diagonals, 4 HERS columns, 1 the rows of approach 1 — hydia_base_db_enroll, 3 the chunks of approach 3 — hydia_blind_db_enroll,
+ * 7 a plain gallery's hoisted diagonals and 8 its pre-rotated ones — hydia_plain_db_enroll; hydia_db_babies answers for kinds 5 to 8).  Ciphertexts imported one by one (hydia_db_alloc + hydia_db_import_ct: the reference
  * enroller's) are taken as hoisted unless hydia_db_set_babies says otherwise (a database of more than 8 blocks is then re-ordered in
  * HBM for the declared form, through a second buffer of its size — see hydia_db_group).  hydia_db_set_babies takes a DECLARED form:
  * vector_dim (hoisted) or a power of two >= 2 dividing it — 0, 1 and anything else are HYDIA_ERR_ARG; without a diagonal database
@@ -221,6 +222,36 @@ int hydia_db_enroll_shard_ex(hydia_ctx *ctx, double *db, size_t n, const uint8_t
 int hydia_db_alloc(hydia_ctx *ctx, size_t n_vectors);
 int hydia_db_import_ct(hydia_ctx *ctx, size_t t, const uint64_t *data /* [2][n_q][N] */);
 int hydia_db_export_ct(hydia_ctx *ctx, size_t t, uint64_t *data);
+/* ---- plain gallery (database kinds 7 / 8): an encrypted query against UNENCRYPTED templates.  An extension with no counterpart in
+ * the reference, for the deployment where the operator of the sender owns the gallery (a watchlist, an access list) and only the
+ * probe is private.  TRUST MODEL:
+ *   - the sender SEES the gallery: the templates lie in its memory as encoded plaintexts;
+ *   - the query and every result stay encrypted under the receiver's key — the receiver, the query, the keys and the decrypt rules
+ *     are exactly those of an encrypted database;
+ *   - no circuit privacy is claimed, as before: a result ciphertext may reveal more about the gallery than the scores it decrypts to.
+ * Plaintext t = block * vector_dim + diagonal is the slot image hydia_db_enroll makes for ciphertext t (pre-rotated when
+ * hydia_db_babies < vector_dim), encoded at scale 2^scale_bits on all n_q limbs, in evaluation form, as ONE polynomial [n_q][N] of
+ * canonical residues — no seed, no nonce, no public key.  The gallery lies where a ciphertext database of the same block count and
+ * form lies (hydia_db_group, hydia_db_residue_bits) with one polynomial per entry: hydia_db_stats reports the count of plaintexts
+ * and half the bytes.  Loop B forms the two components c_p * m directly (no third component), so hydia_compute_similarity on a plain
+ * gallery needs NO relinearisation key; the comparator of the scenarios still does.
+ *   hydia_plain_db_enroll     normalises db IN PLACE like hydia_db_enroll, follows hydia_set_matvec exactly as an encrypted
+ *                             enrolment does (hydia_auto_babies' thresholds were measured on encrypted databases and are
+ *                             unmeasured for this kind), replaces the resident database
+ *   hydia_plain_db_alloc      room for n_vectors in a DECLARED form: babies = vector_dim, or a power of two >= 2 dividing it (else
+ *                             HYDIA_ERR_ARG); every plaintext starts as the zero polynomial
+ *   hydia_plain_db_import_pt  a residue at or above its q_j: HYDIA_ERR_ARG, nothing written; without a plain gallery HYDIA_ERR_STATE
+ * Served on a plain gallery, by dispatch on the resident kind: hydia_compute_similarity, hydia_index_scenario,
+ * hydia_membership_scenario, hydia_rotate_query, hydia_db_kind / _babies / _stats / _group / _residue_bits.
+ * NOT served yet — each answers HYDIA_ERR_STATE with a message naming the plain gallery, before any work is enqueued and with the
+ * gallery untouched: hydia_*_multi, hydia_*_rotated, hydia_rotate_query_range*, hydia_db_update*, hydia_db_save, hydia_db_import_ct,
+ * hydia_db_export_ct, hydia_db_set_babies; there is no hydia_group_* enrolment of a plain gallery, and hydia_plain_db_enroll /
+ * hydia_plain_db_alloc on a context that is a shard of a group (hydia_group_ctx) answer HYDIA_ERR_STATE the same way.  hydia_db_load of a ciphertext
+ * file, like any enrolment, replaces the gallery. */
+int hydia_plain_db_enroll(hydia_ctx *ctx, double *db /* n x vector_dim row-major */, size_t n);
+int hydia_plain_db_alloc(hydia_ctx *ctx, size_t n_vectors, int babies);
+int hydia_plain_db_import_pt(hydia_ctx *ctx, size_t t, const uint64_t *data /* [n_q][N] */);
+int hydia_plain_db_export_pt(hydia_ctx *ctx, size_t t, uint64_t *data);
 /* Persistence of the enrolled database (the reference keeps one serial/db_diagonal/index<t>.bin per ciphertext,
  * src/enroller/enroller_diag.cpp:158-166, and re-reads them every query; here the database stays in HBM and a file is only
  * what a server restart needs).  Own streaming format: a header (parameters, prime chain, packing) + the ciphertexts in order, each

@@ -456,6 +456,36 @@ class DiagonalEnroller : public EnrollerBase {
     size_t size() const { return numVectors; }
 };
 
+// ---- a plain gallery (database kinds 7 / 8; an extension with no counterpart in the reference): the operator of the sender owns the
+// templates, so they are ENCODED, not encrypted — DiagonalEnroller's constructor shape, serializeDB with no seed (nothing is sampled).
+// DiagonalSender and DiagonalReceiver are used unchanged.  Trust model (include/hydia.h): the sender sees the gallery; the query
+// and the result stay encrypted under the receiver's key; no circuit privacy is claimed.  A sharded context is refused.
+class PlainEnroller {
+  public:
+    PlainEnroller(CryptoContext ccParam, size_t vectorParam) : cc(std::move(ccParam)), numVectors(vectorParam) {}
+    PlainEnroller(CryptoContext ccParam, PublicKey, size_t vectorParam) : cc(std::move(ccParam)), numVectors(vectorParam) {}
+    // normalises `database` in place like DiagonalEnroller::serializeDB; the form follows hydia_set_matvec
+    void serializeDB(std::vector<std::vector<double>> &database) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: serializeDB: a plain gallery (kind 7 / 8) is not enrolled on a sharded context" << std::endl;
+            return;
+        }
+        const size_t dim = cc->info.vector_dim;
+        std::vector<double> flat(numVectors * dim, 0.0);
+        for (size_t i = 0; i < numVectors && i < database.size(); i++)
+            for (size_t j = 0; j < dim && j < database[i].size(); j++) flat[i * dim + j] = database[i][j];
+        if (!cc->check(hydia_plain_db_enroll(cc->h, flat.data(), numVectors), "serializeDB")) return;
+        for (size_t i = 0; i < numVectors && i < database.size(); i++)
+            for (size_t j = 0; j < dim && j < database[i].size(); j++) database[i][j] = flat[i * dim + j];
+    }
+    size_t size() const { return numVectors; }
+
+  private:
+    CryptoContext cc;
+    size_t numVectors;
+};
+
 // ---- HERS, approach 4: include/sender_hers.h:9-44, include/receiver_hers.h:9-28, include/enroller_hers.h:16-37.
 // The query is vector_dim ciphertexts (one batch handle, split per element like the reference's vector).
 class HersSender : public Sender {
