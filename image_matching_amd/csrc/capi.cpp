@@ -895,6 +895,58 @@ int hydia_index_scenario_rotated(hydia_ctx *ctx, const hydia_ct *query, hydia_ct
 int hydia_index_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.index_scenario(query->c)) }
 int hydia_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.membership_scenario(query->c)) }
 // a batch of queries in one pass over the database: out[q] = the single-query result for queries[q]; on any error every out[q] is NULL
+// ------------------------------------------------------------------ plain query (the sender knows the probe; kinds 5 / 6 only)
+static hydia_pt *wrap_pt(hydia_ctx *owner, Ct &&c) {
+    hydia_pt *h = new hydia_pt;
+    h->c = std::move(c);
+    h->owner = owner;
+    owner->refs.fetch_add(1);
+    return h;
+}
+int hydia_encode_query(hydia_ctx *ctx, const double *query, hydia_pt **out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && query && out, "null argument");
+    *out = wrap_pt(ctx, client_encode_query(ctx->cx, query));
+    return HYDIA_OK;
+    API_END
+}
+int hydia_pt_import(hydia_ctx *ctx, const uint64_t *data, double scale, hydia_pt **out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && data && out, "null argument");
+    Context &cx = ctx->cx;
+    // loop B's bounds and the packed halves assume canonical residues: checked before anything is created
+    for (int j = 0; j < cx.nQ; j++)
+        for (int c = 0; c < cx.N; c++)
+            REQUIRE(data[(size_t)j * cx.N + c] < cx.q[j], "plaintext residue at or above its modulus");
+    Ct c(&cx, 1, 1, cx.nQ, scale);
+    cx.sync();
+    HIP_CHECK(hipMemcpy(c.d, data, c.bytes(), hipMemcpyHostToDevice));
+    *out = wrap_pt(ctx, std::move(c));
+    return HYDIA_OK;
+    API_END
+}
+int hydia_pt_export(hydia_ctx *ctx, const hydia_pt *pt, uint64_t *data) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && pt && data, "null argument");
+    ctx->cx.sync();
+    HIP_CHECK(hipMemcpy(data, pt->c.d, pt->c.bytes(), hipMemcpyDeviceToHost));
+    return HYDIA_OK;
+    API_END
+}
+void hydia_pt_free(hydia_pt *pt) {
+    if (!pt) return;
+    hydia_ctx *owner = pt->owner;
+    use_device(owner);
+    delete pt;
+    if (owner && owner->refs.fetch_sub(1) == 1) delete owner;
+}
+int hydia_compute_similarity_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out) { SENDER_CALL(ctx->cx.similarity_pq(query->c)) }
+int hydia_index_scenario_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out) { SENDER_CALL(ctx->cx.index_scenario_pq(query->c)) }
+int hydia_membership_scenario_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out) { SENDER_CALL(ctx->cx.membership_scenario_pq(query->c)) }
+
 static int scenario_multi_call(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out, int what) {
     if (out)
         for (uint32_t q = 0; q < n_queries; q++) out[q] = nullptr;

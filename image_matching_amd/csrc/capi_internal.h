@@ -27,6 +27,13 @@ struct hydia_ct {
     hydia_ctx *owner = nullptr;
 };
 
+// a plain query: ONE encoded polynomial [1][1][n_q][N]; a type of its own, so no ciphertext entry point can be handed one.  It pins
+// its context exactly as a hydia_ct does
+struct hydia_pt {
+    hydia::Ct c;
+    hydia_ctx *owner = nullptr;
+};
+
 int hydia_fail(int code, const std::string &msg);  // records the calling thread's last error and returns `code`
 
 #define API_BEGIN try {

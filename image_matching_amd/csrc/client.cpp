@@ -257,6 +257,22 @@ static void encode_device(Context &cx, const double *d_slots, int X, u64 *dst) {
     cx.pool.put((u64 *)coeffs);
     cx.pool.put((u64 *)work);
 }
+// DiagonalSender::encodeQuery — a probe the sender knows: exactly the plaintext client_encrypt_query encrypts (normalised, tiled to all
+// slots, encoded at 2^scale_bits on all n_q limbs), as ONE polynomial [1][1][nQ][N].  No seed, no nonce, no public key
+Ct client_encode_query(Context &cx, const double *query) {
+    const int dim = cx.prm.dim;
+    std::vector<double> qn(query, query + dim), batch(cx.slots);
+    normalize(qn.data(), dim);
+    for (int i = 0; i < cx.slots; i += dim) std::memcpy(&batch[i], qn.data(), sizeof(double) * dim);
+    const size_t bytes = sizeof(double) * (size_t)cx.slots;
+    double *d_slots = (double *)cx.pool.get(bytes);
+    HIP_CHECK(hipMemcpyAsync(d_slots, batch.data(), bytes, hipMemcpyHostToDevice, cx.stream));
+    Ct out(&cx, 1, 1, cx.nQ, cx.delta);
+    encode_device(cx, d_slots, 1, out.d);
+    cx.pool.put((u64 *)d_slots);
+    cx.sync();  // `batch` is host memory of this call
+    return out;
+}
 // PlainEnroller::serializeDB — a gallery the sender may see (database kinds 7 / 8): normalise IN PLACE and pack the generalised
 // diagonals exactly as client_enroll does, then ENCODE the vector_dim slot vectors of each block (one polynomial each) into the resident
 // layout.  Plaintext t is the slot image of client_enroll's ciphertext t.

@@ -22,6 +22,8 @@ void client_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32], si
 // resident kind 5 / 6 database += a fresh encryption of the sparse diagonal image of rows[n][dim] at vectors first_vector ..
 // a plain gallery (kinds 7 / 8): the same slot images, encoded and not encrypted, into the resident one-polynomial layout
 void client_plain_enroll(Context &cx, double *db, size_t n, int babies);
+// a plain query: the plaintext client_encrypt_query encrypts, encoded and not encrypted ([1][1][nQ][N])
+Ct client_encode_query(Context &cx, const double *query);
 void client_db_update(Context &cx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32], size_t first_block = 0);
 // HERS (approach 4): column-packed enrolment and the vector_dim broadcast query ciphertexts
 void client_hers_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32]);

@@ -427,6 +427,8 @@ Context::~Context() {
         if (kv.second.dev) (void)hipFree(kv.second.dev);
     for (auto &kv : merge_masks)
         if (kv.second) (void)hipFree(kv.second);
+    for (auto &kv : pq_galois)
+        if (kv.second) (void)hipFree(kv.second);
     for (auto &e : base_phase_pending) {
         (void)hipEventDestroy(e.a);
         (void)hipEventDestroy(e.b);

@@ -1584,6 +1584,73 @@ Ct Context::sum_and_evalsum(const Ct &s) {
     eval_sum_inplace(m);
     return m;
 }
+// ------------------------------------------------------------------ a plain query against the encrypted database (an extension: the
+// reference's sender only ever sees an encrypted probe).  The oracle's sender path on the trivial ciphertext (m, 0), bit for bit:
+// Rot_i(m, 0) = (sigma_i(m), 0) — the key switch of the zero polynomial is zero — so loop A is ONE batched permutation with no key,
+// and (sigma_i(m), 0) x (c0, c1) = (sigma_i(m) c0, sigma_i(m) c1, 0): loop B writes two components and the relinearisation of a
+// zero third component changes nothing.  From there on the tails are the plain gallery's (2-component accumulators).
+void Context::pq_check(const Ct &pt, int what) {
+    if (pt.X != 1 || pt.npoly != 1 || pt.nl != nQ || !pt.compact()) throw std::runtime_error("hydia: a plain query must be one encoded polynomial at full level");
+    if (db_plain())
+        throw StateError("hydia: a plain gallery (kind 7 / 8) is resident: a plain query against it would keep nothing private (encrypt the query, or enrol the gallery encrypted)");
+    if (!d_db || db_cts == 0 || (db_kind != 5 && db_kind != 6)) throw StateError("hydia: no database resident (a plain query needs diagonal packing, kind 5 or 6)");
+    const int dim = prm.dim, B = db_babies;
+    if (db_kind == 6 && (B < 1 || dim % B)) throw StateError("hydia: the resident database carries no valid baby count");
+    if (what >= 1 && !relin_key.d) throw StateError("hydia: relinearisation key not loaded");
+    if (db_kind == 6)
+        for (int g = 1; g < dim / B; g++)
+            if (!rot_keys.count(g * B)) throw StateError("hydia: rotation key " + std::to_string(g * B) + " not loaded");
+    if (what == 2)
+        for (int r = 1; r < slots; r <<= 1)
+            if (!rot_keys.count(r)) throw StateError("hydia: rotation key " + std::to_string(r) + " not loaded");
+}
+const unsigned *Context::pq_galois_table(int R) {
+    auto it = pq_galois.find(R);
+    if (it != pq_galois.end()) return it->second;
+    std::vector<unsigned> gal(R);
+    for (int i = 0; i < R; i++) gal[i] = (unsigned)galois_elt(i);
+    unsigned *d = nullptr;
+    HIP_CHECK(hipMalloc((void **)&d, sizeof(unsigned) * (size_t)R));
+    HIP_CHECK(hipMemcpy(d, gal.data(), sizeof(unsigned) * (size_t)R, hipMemcpyHostToDevice));
+    pq_galois[R] = d;
+    return d;
+}
+Ct Context::pq_rotations(const Ct &pt, int R) {
+    const unsigned *gal = pq_galois_table(R);
+    Ct rot(this, R, 1, pt.nl, pt.scale);
+    hk::automorph_batch(stream, prm.logN, pt.d, rot.d, pt.nl, R, gal);
+    return rot;
+}
+Ct Context::pq_accumulate(const Ct &pt) {
+    const int dim = prm.dim, nl = nQ, G = (int)(db_cts / dim);
+    const int R = db_kind == 6 ? db_babies : dim, NG = dim / R;
+    if (db_kind == 6) build_giants(G);
+    Ct rot = pq_rotations(pt, R);
+    Ct acc(this, G * NG, 2, nl, pt.scale * delta);
+    op_bytes("op:loop_b_pq", N, 0, (double)db_cts * (double)db_lay.ct_bytes + ((double)R + (double)G * NG * 2) * nl * N * 8);
+    timer_begin("hydia_pq");
+    hk::hydia_pq_accumulate(stream, d_mod, N, rot.d, d_db, acc.d, G * NG, R, nl, db_lay, db_kind == 6 ? NG : 0, tensor_bpp, tensor_nw);
+    timer_end("hydia_pq");
+    if (db_kind == 6) return giant_step_sum(acc, NG);
+    return acc;
+}
+Ct Context::similarity_pq(const Ct &pt) {
+    pq_check(pt, 0);
+    Ct acc = pq_accumulate(pt);
+    rescale(acc);
+    return acc;
+}
+Ct Context::index_scenario_pq(const Ct &pt) {
+    pq_check(pt, 1);
+    Ct acc = pq_accumulate(pt);
+    return relin_compare_lanes(acc, 0.44, 10);
+}
+Ct Context::membership_scenario_pq(const Ct &pt) {
+    pq_check(pt, 2);
+    Ct acc = pq_accumulate(pt);
+    Ct s = relin_compare_lanes(acc, 0.44, 10);
+    return sum_and_evalsum(s);
+}
 // ------------------------------------------------------------------ a batch of queries in one pass over the database (an extension:
 // the reference serves one query per call).  Loop A runs per query into one [Q][R][2][nQ][N] rotation buffer; loop B is ONE multi-query
 // launch set (ceil(Q / QW) passes over the database); the per-block tails run once on the [Q G] batch.  Every ciphertext is what the

@@ -446,6 +446,18 @@ struct Context : HostParams {
     void check_multi(const std::vector<const Ct *> &qs) const;  // runtime_error: a query is not fresh; StateError: no diagonal database
     int multi_batch(int Q);
     Ct loop_b_multi(const std::vector<const Ct *> &qs, int q0, int Qb);
+    // ---- a PLAIN QUERY (an extension; evaluator.cpp): the sender knows the probe, the database (kinds 5 / 6) stays encrypted.  pt is
+    // ONE encoded polynomial [1][1][nQ][N] (canonical residues, evaluation form).  Bit for bit the encrypted-query path on the trivial
+    // ciphertext (pt, 0): rotating a plaintext is a permutation, pt x ct has two components — no rotation key 1 .. R-1 is looked at
+    // (build_rotptrs is not on this path), nothing is relinearised per block.  what: 0 similarity, 1 index, 2 membership
+    void pq_check(const Ct &pt, int what);          // StateError naming the kind or the missing key, BEFORE any work is enqueued
+    const unsigned *pq_galois_table(int R);         // device [R]: Galois elements of rotations 0 .. R-1, uploaded once per R
+    std::map<int, unsigned *> pq_galois;
+    Ct pq_rotations(const Ct &pt, int R);           // -> [R][1][nQ][N], one launch
+    Ct pq_accumulate(const Ct &pt);                 // rotations + loop B (+ the giant steps of kind 6): [G][2][nQ][N] at scale(pt) * delta
+    Ct similarity_pq(const Ct &pt);
+    Ct index_scenario_pq(const Ct &pt);
+    Ct membership_scenario_pq(const Ct &pt);
     Ct giant_step_sum(Ct &acc, int NG);  // BSGS giant steps on [NG X0] giant-major accumulators -> [X0][2][nQ][N] (relinearises a 3-component acc)
     Ct batch_slice(const Ct &b, int q, int per);
     // ---- HERS sender (approach 4, src/sender/sender_hers.cpp): q = dim query ciphertexts

@@ -415,6 +415,13 @@ int hydia_tensor_mq_width(const DbLayout &L);  // queries one pass over the data
 void hydia_plain_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, const void *db, u64 *acc, int G, int dim, int nl,
                             const DbLayout &L, int ng, int bpp, int nw);
 constexpr int PLAIN_BPP = 2;  // blocks per wave of a plain gallery's loop B (resources of every instantiation)
+// Loop B for a PLAIN QUERY against an encrypted database (kinds 5 / 6; L.plain is refused): rot [dim][nl][N] = the rotations of the
+// known probe's plaintext, ONE polynomial each (automorph_batch); acc [G][2][nl][N] (slot map as above with a batch of one),
+// acc[slot][p] = sum_i rot[i] * db[g][i].c_p mod q_j — no third component, nothing to relinearise.  bpp, nw: split caps (tensor_split)
+void hydia_pq_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, const void *db, u64 *acc, int G, int dim, int nl,
+                         const DbLayout &L, int ng, int bpp, int nw);
+// out[i][j][c] = m[j][perm_{galois[i]}(c)], i < R, in one launch (m [nl][N], out [R][nl][N]; galois: device [R], 1 = identity)
+void automorph_batch(hipStream_t st, int logN, const u64 *m, u64 *out, int nl, int R, const unsigned *galois);
 
 // EvalMult(ct, plaintext) residue-wise (approach 1's merge masks): o[xp][j] = a[xp][j] * m[j] mod q_j with the Shoup companions ms;
 // XP polynomials of nl limbs (a at limb stride a_ls, o compact), m / ms [nl][N]

@@ -1185,6 +1185,185 @@ __global__ __launch_bounds__(64 * KS) void k_hydia_plain_sk(const ModC *__restri
     }
 }
 
+// ------------------------------------------------------------------------------------------------ loop B for a plain query
+// The mirror image of the plain gallery: the QUERY is a known plaintext m and the database (kinds 5 / 6) stays encrypted.  rot holds the
+// R evaluation-form rotations sigma_i(m) as [R][nl][N] (k_automorph_batch), ONE polynomial each.  Per coefficient
+//   acc[slot][p][j][c] = sum_{i<R} rot[i][j][c] * db[g][i].c_p[j][c] mod q_j,  p = 0, 1
+// — one query operand and two database operands per diagonal and block: four multiply-accumulates per lane pair and block against
+// Karatsuba's six with operand sums, and a 2-component accumulator that needs no relinearisation.  Work split, XCD tile map, db_walk,
+// non-temporal database loads, prefetch depth, one barrier per diagonal and the slot map are k_hydia_tensor's; the arithmetic policies
+// are used as they are.  Bounds: the plain gallery's (tests/test_plain_gallery_model_cpu.py), since every product is again one
+// canonical residue times one canonical residue with no operand sums:
+// - Halves24: every half is below 2^24 and every product below 2^48; ll and hh take one product per diagonal, mid two: 4096 diagonals
+//   (the launcher's limit) x 2 x 2^48 = 2^61 < 2^63.
+// - Sums128: the fold chunk of the encrypted kernel is kept.  It budgets a product at 2^(2k+2) (Karatsuba's operand sums); a product
+//   of residues below q < 2^k is below 2^(2k), so the chunk is conservative by two bits: q + chunk 2^(2k) < 2^126.
+template <class A, int BPP, int NW>
+__global__ __launch_bounds__(64 * NW, 2) void k_hydia_pq(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot,
+                                                         const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                         int Gq, int xcd_map, DbLayout L, int j0, int G, int ng, int nblk) {
+    typedef typename A::T T;
+    const int j = blockIdx.y + j0;
+    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
+    const int gq = xcd_map ? k % Gq : blockIdx.x % Gq;
+    const int tile = xcd_map ? xcd + 8 * (k / Gq) : blockIdx.x / Gq;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const ModC M = mod[j];
+    const size_t c = (size_t)tile * 128 + lane * 2;
+    const size_t ps = (size_t)nl * N;  // rot stride per rotation = acc poly stride (elements)
+    const int g0 = (gq * NW + wv) * BPP;
+    const u64 *ra = rot + (size_t)j * N + c;
+    const DbWalk dw = db_walk(L, N, dim, j, tile, lane, g0, gq, wv * BPP);
+    const unsigned char *da = db + dw.base;
+    const A ar(M, dim, lane);
+    typename A::Sum s[BPP][2][2];  // [block][component][coefficient of the lane's pair]
+#pragma unroll
+    for (int u = 0; u < BPP; u++)
+#pragma unroll
+        for (int p = 0; p < 2; p++) s[u][p][0] = s[u][p][1] = typename A::Sum{};
+    struct Operands {
+        ulonglong2 a;
+        typename A::Raw b0[BPP], b1[BPP];
+    };
+    auto fetch = [&](Operands &o, int i) {
+        o.a = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * ps);
+#pragma unroll
+        for (int u = 0; u < BPP; u++) {
+            o.b0[u].template load<true>(da + u * dw.su + (size_t)i * dw.si);
+            o.b1[u].template load<true>(da + u * dw.su + (size_t)i * dw.si + dw.sp);
+        }
+    };
+    auto accumulate = [&](const Operands &o) {
+        const T a[2] = {A::rot(o.a.x), A::rot(o.a.y)};
+#pragma unroll
+        for (int u = 0; u < BPP; u++) {
+            T b[2][2];
+            ar.cut(o.b0[u], b[0]);
+            ar.cut(o.b1[u], b[1]);
+#pragma unroll
+            for (int p = 0; p < 2; p++)
+#pragma unroll
+                for (int e = 0; e < 2; e++) A::mac(s[u][p][e], a[e], b[p][e]);
+        }
+    };
+    if constexpr (A::depth == 3) {
+        Operands S0, S1, S2;
+        fetch(S0, 0);
+        fetch(S1, 1);
+        int i = 0;
+        for (; i + 2 < dim; i += 3) {  // branch-free inside: clamped re-fetches of the last diagonal are never accumulated
+            fetch(S2, i + 2);
+            accumulate(S0);
+            if (NW > 1) __builtin_amdgcn_s_barrier();  // keep the waves on the same diagonal (no memory wait implied)
+            fetch(S0, i + 3 < dim ? i + 3 : dim - 1);
+            accumulate(S1);
+            if (NW > 1) __builtin_amdgcn_s_barrier();
+            fetch(S1, i + 4 < dim ? i + 4 : dim - 1);
+            accumulate(S2);
+            if (NW > 1) __builtin_amdgcn_s_barrier();
+        }
+        if (i < dim) accumulate(S0);
+        if (i + 1 < dim) accumulate(S1);
+    } else {
+        Operands cur, nxt;
+        fetch(cur, 0);
+        for (int i0 = 0; i0 < dim; i0 += ar.chunk) {
+            const int i1 = i0 + ar.chunk < dim ? i0 + ar.chunk : dim;
+            for (int i = i0; i < i1; i += 2) {  // dim and every chunk are even (k_hydia_tensor)
+                fetch(nxt, i + 1);
+                accumulate(cur);
+                if (NW > 1) __builtin_amdgcn_s_barrier();
+                fetch(cur, i + 2 < dim ? i + 2 : i + 1);
+                accumulate(nxt);
+                if (NW > 1) __builtin_amdgcn_s_barrier();
+            }
+            if (i1 < dim) {
+#pragma unroll
+                for (int u = 0; u < BPP; u++)
+#pragma unroll
+                    for (int p = 0; p < 2; p++) {
+                        A::fold(s[u][p][0], M);
+                        A::fold(s[u][p][1], M);
+                    }
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < BPP; u++) {
+        u64 *o = acc + (mq_slot(0, g0 + u, G, ng, nblk, 1) * 2 * nl + j) * N + c;
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+            *reinterpret_cast<ulonglong2 *>(o + p * ps) = make_ulonglong2(A::reduce(s[u][p][0], M), A::reduce(s[u][p][1], M));
+    }
+}
+// Limb 0 of a SMALL ciphertext-major database (at most 8 blocks) under a plain query: k_hydia_tensor_sk's split of the diagonals over
+// KS waves, combined through LDS, with four sums per lane instead of six.  grid (N/128 * G, 1)
+template <int KS>
+__global__ __launch_bounds__(64 * KS) void k_hydia_pq_sk(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot,
+                                                         const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                         DbLayout L, int G, int ng, int nblk) {
+    typedef Sums128<false> A;
+    __shared__ u64 part[KS][4][64];
+    const int tiles = N / 128;
+    const int tile = blockIdx.x % tiles, g = blockIdx.x / tiles;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const ModC M = mod[0];
+    const size_t c = (size_t)tile * 128 + lane * 2;
+    const size_t ps = (size_t)nl * N;
+    const u64 *ra = rot + c;
+    const unsigned char *da = db + (size_t)g * dim * L.ct_bytes + c * 8;
+    const A ar(M, dim, lane);
+    u128 s[2][2] = {};
+    int since = 0;
+    for (int i = wv; i < dim; i += KS) {
+        A::Raw r0, r1;
+        r0.load<true>(da + (size_t)i * L.ct_bytes);
+        r1.load<true>(da + (size_t)i * L.ct_bytes + L.poly_bytes);
+        u64 b[2][2];
+        ar.cut(r0, b[0]);
+        ar.cut(r1, b[1]);
+        const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * ps);
+        A::mac(s[0][0], a.x, b[0][0]);
+        A::mac(s[0][1], a.y, b[0][1]);
+        A::mac(s[1][0], a.x, b[1][0]);
+        A::mac(s[1][1], a.y, b[1][1]);
+        if (++since == ar.chunk) {
+            since = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) A::fold(s[k / 2][k % 2], M);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) part[wv][k][lane] = A::reduce(s[k / 2][k % 2], M);
+    __syncthreads();
+    if (wv == 0) {
+        u64 r[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            u64 t = part[0][k][lane];
+            for (int w = 1; w < KS; w++) t = addmod(t, part[w][k][lane], M.q);
+            r[k] = t;
+        }
+        u64 *o = acc + mq_slot(0, g, G, ng, nblk, 1) * 2 * nl * N + c;
+        *reinterpret_cast<ulonglong2 *>(o) = make_ulonglong2(r[0], r[1]);
+        *reinterpret_cast<ulonglong2 *>(o + ps) = make_ulonglong2(r[2], r[3]);
+    }
+}
+// The R rotations of a plaintext in ONE launch: out[i][j][co] = m[j][perm_{g_i}(co)] (the gather form of the evaluation-form
+// automorphism, k_moddown_combine's index map), galois[i] = 5^i mod 2N, identity for g = 1 (rotation 0).  grid (N/256, nl, R)
+__global__ __launch_bounds__(256) void k_automorph_batch(int logN, const u64 *__restrict__ m, u64 *__restrict__ out, int nl,
+                                                         const unsigned *__restrict__ galois) {
+    const unsigned N = 1u << logN;
+    const int j = blockIdx.y, i = blockIdx.z;
+    const unsigned co = blockIdx.x * 256 + threadIdx.x, g = galois[i];
+    unsigned c = co;
+    if (g != 1u) {
+        const unsigned e = ((2u * brev_n(co, logN) + 1u) * g) & (2u * N - 1u);
+        c = brev_n((e - 1u) >> 1, logN);
+    }
+    out[((size_t)i * nl + j) * N + co] = m[(size_t)j * N + c];
+}
+
 // unpacked [X][np][nQ][N] u64  <->  database layout (np = db_polys(L): 2, or 1 for a plain gallery).  grid (N/512, nQ, X*np)
 template <bool PACK>
 __global__ __launch_bounds__(256) void k_db_repack(int N, int nQ, u64 *__restrict__ plain, unsigned char *__restrict__ db,
@@ -1652,6 +1831,72 @@ void hydia_plain_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *r
     if (L.bits46) stream((Halves24<true> *)nullptr, 1, nl - 1);
     else if (L.seq && dim <= 4096) stream((Halves24<false> *)nullptr, 1, nl - 1);
     else stream((Sums128<true> *)nullptr, 1, nl - 1);
+}
+// ---- loop B for a plain query against an ENCRYPTED database (kinds 5 / 6).  The split is the encrypted loop B's (tensor_split with the
+// context's caps; a group-sequential layout fixes it), so every layout an encrypted query reads is read here unchanged.  Resources of
+// every instantiation: DESIGN.md §4
+template <class A, int BPP, class... Args>
+static void launch_pq(hipStream_t st, int nw, dim3 grid, Args... args) {
+    switch (nw) {
+    case 1: hipLaunchKernelGGL((k_hydia_pq<A, BPP, 1>), grid, dim3(64), 0, st, args...); return;
+    case 2: hipLaunchKernelGGL((k_hydia_pq<A, BPP, 2>), grid, dim3(128), 0, st, args...); return;
+    case 4: hipLaunchKernelGGL((k_hydia_pq<A, BPP, 4>), grid, dim3(256), 0, st, args...); return;
+    }
+    throw std::logic_error("hydia: no plain-query loop B kernel for this split");
+}
+void hydia_pq_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, const void *db, u64 *acc, int G, int dim, int nl,
+                         const DbLayout &L, int ng, int bpp, int nw) {
+    if (L.plain) throw std::logic_error("hydia: plain-query loop B launched against a plain gallery");
+    if (G < 1 || dim < 2 || (ng > 0 && G % ng)) throw std::logic_error("hydia: loop B with a bad shape");
+    if (L.bits46 && !(L.packed && L.seq && dim <= 4096)) throw std::logic_error("hydia: 46-bit database outside the 24-bit-halves loop B");
+    if (L.seq && (G != L.blocks || dim != L.bd || G % L.seq || G <= 8 || L.seq % L.seq_bpp || (L.seq & (L.seq - 1)) || L.seq > 8))
+        throw std::logic_error("hydia: loop B launched against a group-sequential database with another shape");
+    int B, W;
+    if (L.seq) {
+        B = L.seq_bpp;
+        W = L.seq / L.seq_bpp;
+    } else {
+        tensor_split(G, bpp, nw, &B, &W);
+    }
+    const int Gq = G / (B * W), nblk = ng > 0 ? G / ng : 0;
+    const int xm = (N / 128) % 8 == 0 ? 1 : 0;
+    const unsigned char *dbb = (const unsigned char *)db;
+    // ledger bytes: the resident ciphertexts (two polynomials each) + the rotated plaintexts once + G two-component accumulators
+    const double per_lp8 = LP_BYTES(N), per_lp6 = (double)N * (L.bits46 ? 5.75 : 6.0);
+    const double rot_acc = (double)dim * per_lp8 + (double)G * 2 * per_lp8;
+    auto bytes = [&](int limbs, double per_lp) { return limbs * ((double)G * dim * 2 * per_lp + rot_acc); };
+    auto stream = [&](auto *policy, int j0, int limbs) {
+        typedef typename std::remove_pointer<decltype(policy)>::type A;
+        const dim3 grid((N / 128) * Gq, limbs);
+        char n[96];
+        snprintf(n, sizeof n, "k_hydia_pq<%s, %d, %d>", A::name, B, W);
+        ledger_add(n, bytes(limbs, j0 ? per_lp6 : per_lp8));
+        if (B == 2) launch_pq<A, 2>(st, W, grid, mod, N, rot, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk);
+        else launch_pq<A, 1>(st, W, grid, mod, N, rot, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk);
+    };
+    if (!L.packed) {
+        stream((Sums128<false> *)nullptr, 0, nl);
+        return;
+    }
+    if (!L.seq && G <= 8) {
+        const int ks = G <= 2 ? 8 : 4;
+        char n[96];
+        snprintf(n, sizeof n, "k_hydia_pq_sk<%d>", ks);
+        ledger_add(n, bytes(1, per_lp8));
+        const dim3 grid((N / 128) * G, 1);
+        if (ks == 8) hipLaunchKernelGGL((k_hydia_pq_sk<8>), grid, dim3(512), 0, st, mod, N, rot, dbb, acc, dim, nl, L, G, ng, nblk);
+        else hipLaunchKernelGGL((k_hydia_pq_sk<4>), grid, dim3(256), 0, st, mod, N, rot, dbb, acc, dim, nl, L, G, ng, nblk);
+    } else {
+        stream((Sums128<false> *)nullptr, 0, 1);
+    }
+    if (nl == 1) return;
+    if (L.bits46) stream((Halves24<true> *)nullptr, 1, nl - 1);
+    else if (L.seq && dim <= 4096) stream((Halves24<false> *)nullptr, 1, nl - 1);
+    else stream((Sums128<true> *)nullptr, 1, nl - 1);
+}
+void automorph_batch(hipStream_t st, int logN, const u64 *m, u64 *out, int nl, int R, const unsigned *galois) {
+    ledger_add("k_automorph_batch", (1.0 + R) * nl * LP_BYTES(1 << logN));
+    hipLaunchKernelGGL(k_automorph_batch, dim3((1u << logN) / 256, nl, R), dim3(256), 0, st, logN, m, out, nl, galois);
 }
 DbLayout db_layout(int N, int nQ, int packed, bool plain) {
     DbLayout L{};

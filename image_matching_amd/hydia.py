@@ -100,6 +100,13 @@ def load_library():
         "hydia_plain_db_alloc": (i32, [vp, sz, i32]),
         "hydia_plain_db_import_pt": (i32, [vp, sz, vp]),
         "hydia_plain_db_export_pt": (i32, [vp, sz, vp]),
+        "hydia_encode_query": (i32, [vp, vp, pp]),
+        "hydia_pt_import": (i32, [vp, vp, dbl, pp]),
+        "hydia_pt_export": (i32, [vp, vp, vp]),
+        "hydia_pt_free": (None, [vp]),
+        "hydia_compute_similarity_pq": (i32, [vp, vp, pp]),
+        "hydia_index_scenario_pq": (i32, [vp, vp, pp]),
+        "hydia_membership_scenario_pq": (i32, [vp, vp, pp]),
         "hydia_db_import_ct": (i32, [vp, sz, vp]),
         "hydia_db_export_ct": (i32, [vp, sz, vp]),
         "hydia_db_fill_random": (i32, [vp, sz, u64]),
@@ -326,6 +333,24 @@ class Ciphertext:
         return ptr.value, n.value
 
 
+class Plaintext:
+    """Handle of a plain query (include/hydia.h, hydia_pt): ONE encoded polynomial [n_q][N] resident in HBM — a probe the sender
+    knows.  A type of its own: the ciphertext methods do not take it."""
+
+    def __init__(self, cc, h):
+        self.cc, self.h = cc, h
+
+    def __del__(self):
+        if getattr(self, "h", None):  # pins its context inside the library like a Ciphertext
+            self.cc.L.hydia_pt_free(self.h)
+            self.h = None
+
+    def export(self):
+        out = np.zeros((self.cc.nQ, self.cc.N), dtype=np.uint64)
+        _chk(self.cc.L.hydia_pt_export(self.cc.h, self.h, _p(out)))
+        return out
+
+
 class Context:
     """CKKS context + keys + resident database on one GPU (replaces CryptoContext<DCRTPoly>, src/main.cpp:169-206)."""
 
@@ -459,6 +484,14 @@ class Context:
         h = C.c_void_p()
         _chk(fn(self.h, *args, C.byref(h)))
         return Ciphertext(self, h)
+
+    def pt_import(self, data, scale=None):
+        """a plain query from its residues [n_q][N] (canonical, evaluation form); scale defaults to 2^scale_bits"""
+        data = np.ascontiguousarray(data, dtype=np.uint64)
+        assert data.size == self.nQ * self.N
+        h = C.c_void_p()
+        _chk(self.L.hydia_pt_import(self.h, _p(data), float(self.delta if scale is None else scale), C.byref(h)))
+        return Plaintext(self, h)
 
     def encrypt(self, slots, seed=None, nonce0=0):
         slots = np.ascontiguousarray(slots, dtype=np.float64)
@@ -768,22 +801,47 @@ class DiagonalSender:
     def __init__(self, cc, num_vectors):
         self.cc, self.numVectors = cc, num_vectors
 
+    # ---- plain query (include/hydia.h: the sender knows the probe, the database stays encrypted; kinds 5 / 6 only)
+    def encodeQuery(self, query):
+        """exactly the plaintext DiagonalReceiver.encryptQuery encrypts, encoded and not encrypted: no seed, no nonce, no public key"""
+        if not isinstance(self.cc, Context):
+            raise HydiaError(-2, "hydia: a plain query is not served on a sharded context")
+        query = np.ascontiguousarray(query, dtype=np.float64)
+        assert query.shape == (self.cc.dim,)
+        h = C.c_void_p()
+        _chk(self.cc.L.hydia_encode_query(self.cc.h, _p(query), C.byref(h)))
+        return Plaintext(self.cc, h)
+
+    @staticmethod
+    def _no_plain(what, *queries):
+        if any(isinstance(q, Plaintext) for q in queries):
+            raise HydiaError(-1, "hydia: %s does not take a plain query (batches and caller-supplied rotations are not served for it)" % what)
+
     def rotateQuery(self, query_cipher):
+        self._no_plain("rotateQuery", query_cipher)
         return self.cc._out(self.cc.L.hydia_rotate_query, query_cipher.h)
 
     def computeSimilarity(self, query_cipher):
+        if isinstance(query_cipher, Plaintext):
+            return self.cc._out(self.cc.L.hydia_compute_similarity_pq, query_cipher.h)
         return self.cc._out(self.cc.L.hydia_compute_similarity, query_cipher.h)
 
     def membershipScenario(self, query_cipher):
+        if isinstance(query_cipher, Plaintext):
+            return self.cc._out(self.cc.L.hydia_membership_scenario_pq, query_cipher.h)
         return self.cc._out(self.cc.L.hydia_membership_scenario, query_cipher.h)
 
     def indexScenario(self, query_cipher):
+        if isinstance(query_cipher, Plaintext):
+            return self.cc._out(self.cc.L.hydia_index_scenario_pq, query_cipher.h)
         return self.cc._out(self.cc.L.hydia_index_scenario, query_cipher.h)
 
     # ---- several queries in one pass over the database (an extension: the reference serves one query per call).  A list of query
     # ciphertexts in, a list out: per query exactly what the single-query method returns
     def _multi(self, fn, query_ciphers):
         qs = list(query_ciphers)
+        self._no_plain("a *Multi method", *qs)
+        fn = getattr(self.cc.L, fn)
         n = len(qs)
         hs = (C.c_void_p * max(n, 1))(*[q.h for q in qs])
         out = (C.c_void_p * max(n, 1))()
@@ -791,27 +849,31 @@ class DiagonalSender:
         return [Ciphertext(self.cc, C.c_void_p(out[i])) for i in range(n)]
 
     def computeSimilarityMulti(self, query_ciphers):
-        return self._multi(self.cc.L.hydia_compute_similarity_multi, query_ciphers)
+        return self._multi("hydia_compute_similarity_multi", query_ciphers)
 
     def indexScenarioMulti(self, query_ciphers):
-        return self._multi(self.cc.L.hydia_index_scenario_multi, query_ciphers)
+        return self._multi("hydia_index_scenario_multi", query_ciphers)
 
     def membershipScenarioMulti(self, query_ciphers):
-        return self._multi(self.cc.L.hydia_membership_scenario_multi, query_ciphers)
+        return self._multi("hydia_membership_scenario_multi", query_ciphers)
 
     # ---- loop A split over the GPUs of a node (sender_diag.cpp:23-26 cut into ranges; image_matching_amd.sharding)
     def rotateQueryRange(self, query_cipher, first, count):
         """rotations first .. first+count-1 of the query (0 = the query itself) as a batch of `count` ciphertexts"""
+        self._no_plain("rotateQueryRange", query_cipher)
         return self.cc._out(self.cc.L.hydia_rotate_query_range, query_cipher.h, first, count)
 
     def rotateQueryRangeInto(self, query_cipher, first, count, dev_ptr):
         """rotations first .. first+count-1 of the query (0 = the query itself) into device memory [count][2][nQ][N]"""
+        self._no_plain("rotateQueryRangeInto", query_cipher)
         _chk(self.cc.L.hydia_rotate_query_range_into(self.cc.h, query_cipher.h, first, count, C.c_void_p(dev_ptr)))
 
     def computeSimilarityRotated(self, rotations):
+        self._no_plain("computeSimilarityRotated", rotations)
         return self.cc._out(self.cc.L.hydia_compute_similarity_rotated, rotations.h)
 
     def indexScenarioRotated(self, rotations):
+        self._no_plain("indexScenarioRotated", rotations)
         return self.cc._out(self.cc.L.hydia_index_scenario_rotated, rotations.h)
 
 

@@ -299,6 +299,34 @@ int hydia_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **
 int hydia_compute_similarity_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out);
 int hydia_index_scenario_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out);
 int hydia_membership_scenario_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out);
+/* ---- plain query: a KNOWN probe against the ENCRYPTED database (kinds 5 / 6).  An extension with no counterpart in the reference,
+ * for the deployment where the operator of the sender produces the probe itself (it runs the cameras or the door) and the gallery
+ * belongs to someone else (an agency's watchlist, another company's staff list).  TRUST MODEL:
+ *   - the sender SEES the probe: it lies in its memory as an encoded plaintext;
+ *   - the gallery and every result stay encrypted under the receiver's key — enrolment, the database layouts, the receiver and the
+ *     decrypt rules are exactly those of an encrypted query;
+ *   - no circuit privacy is claimed, as before: a result ciphertext may reveal more about the probe than the scores it decrypts to.
+ * A hydia_pt is ONE encoded polynomial [n_q][N], evaluation form, canonical residues, resident in HBM; a type of its own, so no
+ * ciphertext entry point can be handed one.  A context stays alive until its last hydia_pt is freed, as for hydia_ct.
+ *   hydia_encode_query   exactly the plaintext hydia_encrypt_query encrypts: normalise, tile to all slots, encode at 2^scale_bits on
+ *                        all n_q limbs — no seed, no nonce, no public key
+ *   hydia_pt_import      for adapters and tests; a residue at or above its q_j: HYDIA_ERR_ARG, nothing is created
+ * The *_pq entries return what the encrypted-query entries return (the same count, limbs, scale and block order): bit for bit the
+ * sender's path on the trivial ciphertext (m, 0).  Rotating a plaintext is a permutation and plaintext x ciphertext has two
+ * components, so rotation keys 1 .. vector_dim-1 are never looked at and nothing is relinearised per block: hydia_compute_similarity_pq
+ * on a hoisted database needs NO evaluation key at all.  A key that IS needed and missing answers HYDIA_ERR_STATE naming it, before
+ * any work is enqueued: the relinearisation key (the comparator of the scenarios), a giant-step key B g (kind 6), a power-of-two key
+ * (the EvalSum of membership).
+ * Served on kinds 5 and 6 only.  A plain gallery (kind 7 / 8) answers HYDIA_ERR_STATE: with both sides in the clear nothing would be
+ * private.  No database, or kinds 1 / 3 / 4: HYDIA_ERR_STATE.  NOT served: batches, caller-supplied rotations, hydia_group_*. */
+typedef struct hydia_pt hydia_pt;
+int hydia_encode_query(hydia_ctx *ctx, const double *query /* vector_dim */, hydia_pt **out);
+int hydia_pt_import(hydia_ctx *ctx, const uint64_t *data /* [n_q][N] */, double scale, hydia_pt **out);
+int hydia_pt_export(hydia_ctx *ctx, const hydia_pt *pt, uint64_t *data);
+void hydia_pt_free(hydia_pt *pt);
+int hydia_compute_similarity_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out);
+int hydia_index_scenario_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out);
+int hydia_membership_scenario_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out);
 /* OpenFHEWrapper::chebyshevCompare (src/openFHE_wrapper.cpp:143-185) on every ciphertext of the batch */
 int hydia_chebyshev_compare(hydia_ctx *ctx, const hydia_ct *in, double delta, size_t sign_depth, hydia_ct **out);
 /* multi-GPU membership tail: sum the batch into one ciphertext, then EvalSum over all slots (:46-47) */

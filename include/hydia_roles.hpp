@@ -174,6 +174,20 @@ struct Ciphertext {
     uint32_t index = 0;
     explicit operator bool() const { return batch && batch->h; }
 };
+// a plain query (hydia.h, "plain query"): a probe the sender knows, ONE encoded polynomial in HBM.  A type of its own — the methods
+// that take ciphertexts do not take it
+struct PtHandle {
+    CryptoContext cc;
+    hydia_pt *h = nullptr;
+    PtHandle(CryptoContext c, hydia_pt *p) : cc(std::move(c)), h(p) {}
+    PtHandle(const PtHandle &) = delete;
+    PtHandle &operator=(const PtHandle &) = delete;
+    ~PtHandle() { hydia_pt_free(h); }
+};
+struct Plaintext {
+    std::shared_ptr<PtHandle> pt;
+    explicit operator bool() const { return pt && pt->h; }
+};
 inline std::vector<Ciphertext> split_batch(const CryptoContext &cc, hydia_ct *h) {
     std::vector<Ciphertext> v;
     if (!h) return v;
@@ -274,8 +288,42 @@ class DiagonalSender : public Sender {
         for (hydia_ct *h : run_multi(queryCiphers, hydia_index_scenario_multi, "indexScenarioMulti")) r.push_back(split_batch(cc, h));
         return r;
     }
+    // A plain query (an extension; hydia.h): the sender knows the probe, the database (kinds 5 / 6) stays encrypted and so does every
+    // result.  encodeQuery makes exactly the plaintext DiagonalReceiver::encryptQuery encrypts — no seed, no key; the overloads return
+    // what the ciphertext methods return.  No rotation key 1 .. vector_dim-1 is needed.  Not on a sharded context: an error, empty.
+    Plaintext encodeQuery(std::vector<double> query) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: encodeQuery: a plain query is not served on a sharded context" << std::endl;
+            return {};
+        }
+        query.resize(cc->info.vector_dim, 0.0);
+        hydia_pt *h = nullptr;
+        if (!cc->check(hydia_encode_query(cc->h, query.data(), &h), "encodeQuery")) return {};
+        return Plaintext{std::make_shared<PtHandle>(cc, h)};
+    }
+    std::vector<Ciphertext> computeSimilarity(const Plaintext &query) {
+        hydia_ct *out = run_pq(query, hydia_compute_similarity_pq, "computeSimilarity");
+        return out ? split_batch(cc, out) : std::vector<Ciphertext>{};
+    }
+    Ciphertext membershipScenario(const Plaintext &query) {
+        hydia_ct *out = run_pq(query, hydia_membership_scenario_pq, "membershipScenario");
+        return out ? split_batch(cc, out)[0] : Ciphertext{};
+    }
+    std::vector<Ciphertext> indexScenario(const Plaintext &query) {
+        hydia_ct *out = run_pq(query, hydia_index_scenario_pq, "indexScenario");
+        return out ? split_batch(cc, out) : std::vector<Ciphertext>{};
+    }
 
   private:
+    hydia_ct *run_pq(const Plaintext &q, int (*one)(hydia_ctx *, const hydia_pt *, hydia_ct **), const char *what) {
+        if (!q || cc->group) {
+            std::cerr << "Error: " << what << ": " << (q ? "a plain query is not served on a sharded context" : "empty plain query") << std::endl;
+            return nullptr;
+        }
+        hydia_ct *out = nullptr;
+        return cc->check(one(cc->h, q.pt->h, &out), what) ? out : nullptr;
+    }
     std::vector<hydia_ct *> run_multi(std::vector<std::vector<Ciphertext>> &qs,
                                       int (*multi)(hydia_ctx *, const hydia_ct *const *, uint32_t, hydia_ct **), const char *what) {
         if (cc->group) {
