@@ -400,6 +400,10 @@ void rescale_spread(hipStream_t st, const ModC *mod, int N, const u64 *t, u64 *t
 void rescale_combine(hipStream_t st, const ModC *mod, int N, const u64 *in, const u64 *tmp, u64 *out, int X, int l,
                      const ScaleSel &qlinv, int in_ls);
 
+// The three hydia_*_accumulate functions are one routine over the product form (kernels.hip: FormCtCt, FormCtPlain, FormPlainCt): the
+// shape checks, the block / wave split, the limb schedule, the choice of arithmetic and the ledger bytes are shared, so every layout
+// one of them reads the others read the same way.
+//
 // ---- loop B of the HyDia sender: acc[q][g][3][nl][N] = sum_i rot[q][i] (x) db[g][i], fully reduced, for Q queries whose rotation sets
 // lie rqs elements apart.  bpp, nw: a single query's launch (Q = 1) with the context's split caps (tensor_split); bpp = TENSOR_BATCH:
 // a batch, ceil(Q / QW) passes over the database (QW = hydia_tensor_mq_width), one block per wave.  Every accumulator equals the

@@ -8,6 +8,8 @@
 //   k_moddown_combine     ModDown's (acc - conv) / P, + c0, + the evaluation-form automorphism of EvalFastRotation
 //   k_hydia_tensor        512 x EvalMultNoRelin + 511 x EvalAddInPlace per block (sender_diag.cpp:70-77, :93)
 //   k_hydia_plain         the same sums against a PLAIN gallery (one encoded polynomial per diagonal; no counterpart in the reference)
+//   k_hydia_pq            the same sums for a PLAIN query against the encrypted database (one encoded polynomial per rotation; no
+//                         counterpart in the reference), k_automorph_batch: the rotations of that plaintext
 //   k_rescale_*           RescaleInPlace (sender_diag.cpp:80)
 //   k_tensor, k_lincomb*  ct x ct products and Chebyshev/f4 leaves of chebyshevCompare (src/openFHE_wrapper.cpp:143-185)
 //   k_batch_sum           HERS: sum of the per-dimension products (src/sender/sender_hers.cpp:60-87)
@@ -834,6 +836,80 @@ DEV void store_karatsuba(u64 *o, size_t ps, ulonglong2 r0, ulonglong2 rk, ulongl
     *reinterpret_cast<ulonglong2 *>(o + ps) = make_ulonglong2(submod(submod(rk.x, r0.x, q), r2.x, q), submod(submod(rk.y, r0.y, q), r2.y, q));
     *reinterpret_cast<ulonglong2 *>(o + 2 * ps) = r2;
 }
+// ------------------------------------------------------------------------------------------------ loop B: the three products
+// The product-form policy beside the arithmetic policy.  A form F states what one diagonal multiplies:
+//   qp     polynomials per rotated-query entry (so one rotation is qp limb-polynomial sets: the rot stride per rotation)
+//   dp     polynomials per database entry
+//   sums   lazy sums per block, query and coefficient;  comps  components stored per accumulator slot
+//   mac    feeds the sums of a lane's coefficient pair from the prepared operands a[polynomial][coefficient], b[polynomial][coefficient]
+//   store  writes the reduced sums r[sum] (one coefficient pair each) as the slot's components, ps elements apart
+//   name   of the kernel family (k_hydia_<name>, k_hydia_<name>_sk);  batch: the launcher serves batches of queries with it (QW = 2
+//          passes, NW = 8 workgroups), and its instantiation names carry QW
+// The split-diagonal body and the launcher are written over F.  The three streaming kernels spell the same products out (below).
+// Ciphertext x ciphertext (database kinds 5 / 6): acc[slot][{d0,d1,d2}][j][c] = sum_{i<dim} rot[q][i] (x) db[g][i], Karatsuba
+struct FormCtCt {
+    static constexpr int qp = 2, dp = 2, sums = 3, comps = 3;  // sums: d0, d2, dk
+    static constexpr const char *name = "tensor";
+    static constexpr bool batch = true;
+    template <class A>
+    DEV static void mac(typename A::Sum (&s)[3][2], const typename A::T (&a)[2][2], const typename A::T (&b)[2][2]) {
+        kara_mac<A>(s, a, b);
+    }
+    DEV static void store(u64 *o, size_t ps, const ulonglong2 (&r)[3], u64 q) { store_karatsuba(o, ps, r[0], r[2], r[1], q); }
+};
+// The two plain forms: one side is NOT encrypted and has ONE encoded polynomial m per entry, so there are two sums instead of
+// Karatsuba's three, four multiply-accumulates per lane pair against six with operand sums, and a 2-component accumulator that needs no
+// relinearisation.  Bounds (tests/test_plain_gallery_model_cpu.py): every product is one canonical residue times one canonical
+// residue, with no operand sums.
+// - Halves24: every half is below 2^24 and every product below 2^48; ll and hh take one product per diagonal, mid two: 4096 diagonals
+//   (the launcher's limit) x 2 x 2^48 = 2^61 < 2^63.
+// - Sums128: the fold chunk of the encrypted form is kept.  It budgets a product at 2^(2k+2) (Karatsuba's operand sums); a plain
+//   product of residues below q < 2^k is below 2^(2k), so the chunk is conservative by two bits: q + chunk 2^(2k) < 2^126.  The fold
+//   path stays exercised on 59/60-bit limbs (every 128 / 32 diagonals).
+struct FormPlain {
+    static constexpr int sums = 2, comps = 2;
+    static constexpr bool batch = false;
+    DEV static void store(u64 *o, size_t ps, const ulonglong2 (&r)[2], u64) {
+        *reinterpret_cast<ulonglong2 *>(o) = r[0];
+        *reinterpret_cast<ulonglong2 *>(o + ps) = r[1];
+    }
+};
+// Ciphertext query x plain gallery (database kinds 7 / 8, DbLayout::plain; no counterpart in the reference):
+//   acc[slot][p][j][c] = sum_{i<dim} rot[i].c_p[j][c] * m[g][i][j][c] mod q_j,  p = 0, 1
+struct FormCtPlain : FormPlain {
+    static constexpr int qp = 2, dp = 1;
+    static constexpr const char *name = "plain";
+    template <class A>
+    DEV static void mac(typename A::Sum (&s)[2][2], const typename A::T (&a)[2][2], const typename A::T (&b)[1][2]) {
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+#pragma unroll
+            for (int e = 0; e < 2; e++) A::mac(s[p][e], a[p][e], b[0][e]);
+    }
+};
+// Plain query x ciphertext database (kinds 5 / 6), the mirror image: rot holds the R evaluation-form rotations sigma_i(m) of the known
+// probe as [R][nl][N] (k_automorph_batch), ONE polynomial each:
+//   acc[slot][p][j][c] = sum_{i<R} rot[i][j][c] * db[g][i].c_p[j][c] mod q_j,  p = 0, 1
+struct FormPlainCt : FormPlain {
+    static constexpr int qp = 1, dp = 2;
+    static constexpr const char *name = "pq";
+    template <class A>
+    DEV static void mac(typename A::Sum (&s)[2][2], const typename A::T (&a)[1][2], const typename A::T (&b)[2][2]) {
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+#pragma unroll
+            for (int e = 0; e < 2; e++) A::mac(s[p][e], a[0][e], b[p][e]);
+    }
+};
+
+// The streaming kernels.  k_hydia_tensor, k_hydia_plain and k_hydia_pq hold the SAME pipeline (tile map, db_walk, rotating operand
+// sets with the clamped re-fetch, one s_barrier per diagonal, fold, reduction, mq_slot store): a change to it is made in all three.
+// It is written out in each entry point on purpose.  Called as one device function the pipeline is optimised twice, alone and again
+// after inlining, and the second pass orders the multiply-accumulates differently: k_hydia_tensor<Halves24<true>, 1, 2, *> took 186 /
+// 188 VGPRs instead of 164 (2 waves per SIMD instead of 3), k_hydia_pq<Halves24<true>, 2, *> 151 instead of 120 (3 instead of 4),
+// k_hydia_plain / k_hydia_pq<Sums128<false>, 1, *> 77 / 78 instead of 70 / 72 (6 instead of 7) — profiles/loop_b_forms/README.md.
+// Moving k_hydia_tensor's body into a function unchanged does the same to it.
+//
 // acc[slot][{d0,d1,d2}][j][c] = sum_{i<dim} rot[q][i] (x) db[g][i] for BPP database blocks x QW queries per wave (rot: the queries'
 // rotation sets, rqs elements apart, from query q0 on).  One pass reads a database operand ONCE per diagonal for its QW queries.
 //
@@ -962,80 +1038,101 @@ __global__ __launch_bounds__(64 * NW, 2) void k_hydia_tensor(const ModC *__restr
         }
 }
 
-// Limb 0 of SMALL ciphertext-major databases (at most 8 blocks on this GPU): k_hydia_tensor's limb-0 launch has only 256 x G waves, each
-// walking all `dim` diagonals — latency-bound (0.6 ms at G = 1 for 0.5 GB).  Here KS waves of a workgroup share one (block, tile)
-// and take every KS-th diagonal for QW queries; the partial sums are reduced modulo q_0 through LDS, one query at a time.  Same
-// residues as the one-wave kernel (a sum modulo q does not depend on how it is split).  grid (N/128 * G, 1)
-template <int KS, int QW>
-__global__ __launch_bounds__(64 * KS) void k_hydia_tensor_sk(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs,
-                                                             const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
-                                                             DbLayout L, int G, int ng, int nblk, int q0, int Qt) {
+// The split-diagonal body of every form, for limb 0 of SMALL ciphertext-major databases (at most 8 blocks on this GPU): the streaming
+// kernel's limb-0 launch has only 256 x G waves, each walking all `dim` diagonals — latency-bound (0.6 ms at G = 1 for 0.5 GB).  Here
+// KS waves of a workgroup share one (block, tile) and take every KS-th diagonal for QW queries; the partial sums are reduced modulo
+// q_0 through LDS, one query at a time.  Same residues as the one-wave kernel (a sum modulo q does not depend on how it is split).
+// grid (N/128 * G, 1)
+template <class F, int KS, int QW>
+DEV void loop_b_split(const ModC *mod, int N, const u64 *rot, size_t rqs, const unsigned char *db,
+                      u64 *acc, int dim, int nl, const DbLayout &L, int G, int ng, int nblk, int q0, int Qt) {
     typedef Sums128<false> A;
-    __shared__ u64 part[KS][6][64];
+    constexpr int NS = 2 * F::sums;  // sums of a lane: [sum of the form][coefficient of its pair]
+    __shared__ u64 part[KS][NS][64];
+    static_assert(sizeof(part) == (F::sums == 3 ? 3072 : 2048) * KS, "24 / 12 KiB of LDS for the encrypted form, 16 / 8 KiB for the plain ones");
     const int tiles = N / 128;
     const int tile = blockIdx.x % tiles, g = blockIdx.x / tiles;
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const ModC M = mod[0];
     const size_t c = (size_t)tile * 128 + lane * 2;
-    const size_t ps = (size_t)nl * N, cs = 2 * ps;
+    const size_t ps = (size_t)nl * N, cs = F::qp * ps;
     const u64 *ra = rot + (size_t)q0 * rqs + c;
     const unsigned char *da = db + (size_t)g * dim * L.ct_bytes + c * 8;
     const A ar(M, dim, lane);
-    u128 s[QW][3][2] = {};
+    u128 s[QW][F::sums][2] = {};
     int since = 0;
     for (int i = wv; i < dim; i += KS) {
-        A::Raw r0, r1;
-        r0.load<true>(da + (size_t)i * L.ct_bytes);
-        r1.load<true>(da + (size_t)i * L.ct_bytes + L.poly_bytes);
-        u64 b[2][2];
-        ar.cut(r0, b[0]);
-        ar.cut(r1, b[1]);
+        A::Raw r[F::dp];
+#pragma unroll
+        for (int p = 0; p < F::dp; p++) r[p].template load<true>(da + (size_t)i * L.ct_bytes + p * L.poly_bytes);
+        u64 b[F::dp][2];
+#pragma unroll
+        for (int p = 0; p < F::dp; p++) ar.cut(r[p], b[p]);
 #pragma unroll
         for (int q = 0; q < QW; q++) {
-            const ulonglong2 a0 = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs);
-            const ulonglong2 a1 = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs + ps);
-            const u64 a[2][2] = {{a0.x, a0.y}, {a1.x, a1.y}};
-            kara_mac<A>(s[q], a, b);
+            u64 a[F::qp][2];
+#pragma unroll
+            for (int p = 0; p < F::qp; p++) {
+                const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs + p * ps);
+                a[p][0] = v.x;
+                a[p][1] = v.y;
+            }
+            F::template mac<A>(s[q], a, b);
         }
-        if (++since == ar.chunk) {
+        if (++since == ar.chunk) {  // the fold interval counts this wave's diagonals
             since = 0;
 #pragma unroll
             for (int q = 0; q < QW; q++)
 #pragma unroll
-                for (int k = 0; k < 6; k++) A::fold(s[q][k / 2][k % 2], M);
+                for (int k = 0; k < NS; k++) A::fold(s[q][k / 2][k % 2], M);
         }
     }
 #pragma unroll
     for (int q = 0; q < QW; q++) {
 #pragma unroll
-        for (int k = 0; k < 6; k++) part[wv][k][lane] = A::reduce(s[q][k / 2][k % 2], M);
+        for (int k = 0; k < NS; k++) part[wv][k][lane] = A::reduce(s[q][k / 2][k % 2], M);
         __syncthreads();
         if (wv == 0) {
-            u64 r[6];
+            ulonglong2 r[F::sums];
 #pragma unroll
-            for (int k = 0; k < 6; k++) {
-                u64 t = part[0][k][lane];
-                for (int w = 1; w < KS; w++) t = addmod(t, part[w][k][lane], M.q);
-                r[k] = t;
+            for (int k = 0; k < F::sums; k++) {
+                u64 t0 = part[0][2 * k][lane], t1 = part[0][2 * k + 1][lane];
+                for (int w = 1; w < KS; w++) {
+                    t0 = addmod(t0, part[w][2 * k][lane], M.q);
+                    t1 = addmod(t1, part[w][2 * k + 1][lane], M.q);
+                }
+                r[k] = make_ulonglong2(t0, t1);
             }
-            store_karatsuba(acc + mq_slot(q0 + q, g, G, ng, nblk, Qt) * 3 * nl * N + c, ps, make_ulonglong2(r[0], r[1]),
-                            make_ulonglong2(r[4], r[5]), make_ulonglong2(r[2], r[3]), M.q);
+            F::store(acc + mq_slot(q0 + q, g, G, ng, nblk, Qt) * F::comps * nl * N + c, ps, r, M.q);
         }
-        __syncthreads();
+        if (q + 1 < QW) __syncthreads();  // the next query reuses part
     }
 }
 
+
+// The three split-diagonal entry points: the names rocprofv3 prints and the byte ledger records
+template <int KS, int QW>
+__global__ __launch_bounds__(64 * KS) void k_hydia_tensor_sk(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs,
+                                                             const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                             DbLayout L, int G, int ng, int nblk, int q0, int Qt) {
+    loop_b_split<FormCtCt, KS, QW>(mod, N, rot, rqs, db, acc, dim, nl, L, G, ng, nblk, q0, Qt);
+}
+template <int KS>
+__global__ __launch_bounds__(64 * KS) void k_hydia_plain_sk(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot,
+                                                            const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                            DbLayout L, int G, int ng, int nblk) {
+    loop_b_split<FormCtPlain, KS, 1>(mod, N, rot, 0, db, acc, dim, nl, L, G, ng, nblk, 0, 1);
+}
+template <int KS>
+__global__ __launch_bounds__(64 * KS) void k_hydia_pq_sk(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot,
+                                                         const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                         DbLayout L, int G, int ng, int nblk) {
+    loop_b_split<FormPlainCt, KS, 1>(mod, N, rot, 0, db, acc, dim, nl, L, G, ng, nblk, 0, 1);
+}
+
 // ------------------------------------------------------------------------------------------------ loop B for a plain gallery
-// Database kinds 7 / 8: the templates are NOT encrypted, entry t is ONE encoded polynomial m (DbLayout::plain).  Per coefficient
-//   acc[slot][p][j][c] = sum_{i<dim} rot[i].c_p[j][c] * m[g][i][j][c] mod q_j,  p = 0, 1
-// — two sums instead of Karatsuba's three, one database operand per diagonal instead of two, a 2-component accumulator that needs no
-// relinearisation.  Work split, XCD tile map, non-temporal database loads, prefetch depth, one barrier per diagonal and the slot map are
-// k_hydia_tensor's; the arithmetic policies are used as they are.  Bounds (tests/test_plain_gallery_model_cpu.py):
-// - Halves24: no operand sums, so every half is below 2^24 and every product below 2^48; ll and hh take one product per diagonal, mid
-//   two: 4096 diagonals (the launcher's limit) x 2 x 2^48 = 2^61 < 2^63.
-// - Sums128: the fold chunk of the encrypted kernel is kept.  It budgets a product at 2^(2k+2) (Karatsuba's operand sums); a plain
-//   product of residues below q < 2^k is below 2^(2k), so the chunk is conservative by two bits: q + chunk 2^(2k) < 2^126.  The fold
-//   path stays exercised on 59/60-bit limbs (every 128 / 32 diagonals).
+// FormCtPlain as a streaming kernel: k_hydia_tensor's pipeline with one database operand per diagonal, two sums and a 2-component
+// accumulator; the arithmetic policies are used as they are (bounds: at the forms)
 template <class A, int BPP, int NW>
 __global__ __launch_bounds__(64 * NW, 2) void k_hydia_plain(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot,
                                                             const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
@@ -1131,73 +1228,9 @@ __global__ __launch_bounds__(64 * NW, 2) void k_hydia_plain(const ModC *__restri
             *reinterpret_cast<ulonglong2 *>(o + p * ps) = make_ulonglong2(A::reduce(s[u][p][0], M), A::reduce(s[u][p][1], M));
     }
 }
-// Limb 0 of a SMALL ciphertext-major plain gallery (at most 8 blocks): k_hydia_tensor_sk's split of the diagonals over KS waves with
-// four sums per lane instead of six (the streaming kernel's 256 x G one-wave workgroups are as latency-bound here as there).
-// grid (N/128 * G, 1)
-template <int KS>
-__global__ __launch_bounds__(64 * KS) void k_hydia_plain_sk(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot,
-                                                            const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
-                                                            DbLayout L, int G, int ng, int nblk) {
-    typedef Sums128<false> A;
-    __shared__ u64 part[KS][4][64];
-    const int tiles = N / 128;
-    const int tile = blockIdx.x % tiles, g = blockIdx.x / tiles;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const ModC M = mod[0];
-    const size_t c = (size_t)tile * 128 + lane * 2;
-    const size_t ps = (size_t)nl * N, cs = 2 * ps;
-    const u64 *ra = rot + c;
-    const unsigned char *da = db + (size_t)g * dim * L.ct_bytes + c * 8;
-    const A ar(M, dim, lane);
-    u128 s[2][2] = {};
-    int since = 0;
-    for (int i = wv; i < dim; i += KS) {
-        A::Raw r;
-        r.load<true>(da + (size_t)i * L.ct_bytes);
-        u64 b[2];
-        ar.cut(r, b);
-        const ulonglong2 a0 = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * cs);
-        const ulonglong2 a1 = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * cs + ps);
-        A::mac(s[0][0], a0.x, b[0]);
-        A::mac(s[0][1], a0.y, b[1]);
-        A::mac(s[1][0], a1.x, b[0]);
-        A::mac(s[1][1], a1.y, b[1]);
-        if (++since == ar.chunk) {
-            since = 0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) A::fold(s[k / 2][k % 2], M);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) part[wv][k][lane] = A::reduce(s[k / 2][k % 2], M);
-    __syncthreads();
-    if (wv == 0) {
-        u64 r[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            u64 t = part[0][k][lane];
-            for (int w = 1; w < KS; w++) t = addmod(t, part[w][k][lane], M.q);
-            r[k] = t;
-        }
-        u64 *o = acc + mq_slot(0, g, G, ng, nblk, 1) * 2 * nl * N + c;
-        *reinterpret_cast<ulonglong2 *>(o) = make_ulonglong2(r[0], r[1]);
-        *reinterpret_cast<ulonglong2 *>(o + ps) = make_ulonglong2(r[2], r[3]);
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ loop B for a plain query
-// The mirror image of the plain gallery: the QUERY is a known plaintext m and the database (kinds 5 / 6) stays encrypted.  rot holds the
-// R evaluation-form rotations sigma_i(m) as [R][nl][N] (k_automorph_batch), ONE polynomial each.  Per coefficient
-//   acc[slot][p][j][c] = sum_{i<R} rot[i][j][c] * db[g][i].c_p[j][c] mod q_j,  p = 0, 1
-// — one query operand and two database operands per diagonal and block: four multiply-accumulates per lane pair and block against
-// Karatsuba's six with operand sums, and a 2-component accumulator that needs no relinearisation.  Work split, XCD tile map, db_walk,
-// non-temporal database loads, prefetch depth, one barrier per diagonal and the slot map are k_hydia_tensor's; the arithmetic policies
-// are used as they are.  Bounds: the plain gallery's (tests/test_plain_gallery_model_cpu.py), since every product is again one
-// canonical residue times one canonical residue with no operand sums:
-// - Halves24: every half is below 2^24 and every product below 2^48; ll and hh take one product per diagonal, mid two: 4096 diagonals
-//   (the launcher's limit) x 2 x 2^48 = 2^61 < 2^63.
-// - Sums128: the fold chunk of the encrypted kernel is kept.  It budgets a product at 2^(2k+2) (Karatsuba's operand sums); a product
-//   of residues below q < 2^k is below 2^(2k), so the chunk is conservative by two bits: q + chunk 2^(2k) < 2^126.
+// FormPlainCt as a streaming kernel: k_hydia_tensor's pipeline with ONE query operand (rot is [R][nl][N]) and two database operands per
+// diagonal and block, two sums and a 2-component accumulator; the arithmetic policies are used as they are (bounds: at the forms)
 template <class A, int BPP, int NW>
 __global__ __launch_bounds__(64 * NW, 2) void k_hydia_pq(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot,
                                                          const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
@@ -1294,59 +1327,6 @@ __global__ __launch_bounds__(64 * NW, 2) void k_hydia_pq(const ModC *__restrict_
 #pragma unroll
         for (int p = 0; p < 2; p++)
             *reinterpret_cast<ulonglong2 *>(o + p * ps) = make_ulonglong2(A::reduce(s[u][p][0], M), A::reduce(s[u][p][1], M));
-    }
-}
-// Limb 0 of a SMALL ciphertext-major database (at most 8 blocks) under a plain query: k_hydia_tensor_sk's split of the diagonals over
-// KS waves, combined through LDS, with four sums per lane instead of six.  grid (N/128 * G, 1)
-template <int KS>
-__global__ __launch_bounds__(64 * KS) void k_hydia_pq_sk(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot,
-                                                         const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
-                                                         DbLayout L, int G, int ng, int nblk) {
-    typedef Sums128<false> A;
-    __shared__ u64 part[KS][4][64];
-    const int tiles = N / 128;
-    const int tile = blockIdx.x % tiles, g = blockIdx.x / tiles;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const ModC M = mod[0];
-    const size_t c = (size_t)tile * 128 + lane * 2;
-    const size_t ps = (size_t)nl * N;
-    const u64 *ra = rot + c;
-    const unsigned char *da = db + (size_t)g * dim * L.ct_bytes + c * 8;
-    const A ar(M, dim, lane);
-    u128 s[2][2] = {};
-    int since = 0;
-    for (int i = wv; i < dim; i += KS) {
-        A::Raw r0, r1;
-        r0.load<true>(da + (size_t)i * L.ct_bytes);
-        r1.load<true>(da + (size_t)i * L.ct_bytes + L.poly_bytes);
-        u64 b[2][2];
-        ar.cut(r0, b[0]);
-        ar.cut(r1, b[1]);
-        const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(ra + (size_t)i * ps);
-        A::mac(s[0][0], a.x, b[0][0]);
-        A::mac(s[0][1], a.y, b[0][1]);
-        A::mac(s[1][0], a.x, b[1][0]);
-        A::mac(s[1][1], a.y, b[1][1]);
-        if (++since == ar.chunk) {
-            since = 0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) A::fold(s[k / 2][k % 2], M);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) part[wv][k][lane] = A::reduce(s[k / 2][k % 2], M);
-    __syncthreads();
-    if (wv == 0) {
-        u64 r[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            u64 t = part[0][k][lane];
-            for (int w = 1; w < KS; w++) t = addmod(t, part[w][k][lane], M.q);
-            r[k] = t;
-        }
-        u64 *o = acc + mq_slot(0, g, G, ng, nblk, 1) * 2 * nl * N + c;
-        *reinterpret_cast<ulonglong2 *>(o) = make_ulonglong2(r[0], r[1]);
-        *reinterpret_cast<ulonglong2 *>(o + ps) = make_ulonglong2(r[2], r[3]);
     }
 }
 // The R rotations of a plaintext in ONE launch: out[i][j][co] = m[j][perm_{g_i}(co)] (the gather form of the evaluation-form
@@ -1687,38 +1667,93 @@ void tensor_split(int G, int bpp, int nw, int *Bo, int *Wo) {
 // QW = 2 the kernels keep what the single-query kernels at BPP = 2 take (three waves per SIMD)
 constexpr int MQ_QW = 2;
 int hydia_tensor_mq_width(const DbLayout &) { return MQ_QW; }
-// a loop-B launch's ledger entry, under the instantiation's name as rocprofv3 prints it (namespaces dropped); policy = nullptr: the
-// split-diagonal kernel <x = KS, qw>, else the streaming kernel <policy, x = BPP, qw, nw>
-static void ledger_tensor(double bytes, const char *policy, int x, int qw, int nw) {
-    char n[96];
-    if (policy) snprintf(n, sizeof n, "k_hydia_tensor<%s, %d, %d, %d>", policy, x, qw, nw);
-    else snprintf(n, sizeof n, "k_hydia_tensor_sk<%d, %d>", x, qw);
-    ledger_add(n, bytes);
+// what every loop-B entry point takes, in the launcher's words (a plain form ignores rqs, q0 and Qt)
+struct LoopB {
+    const ModC *mod;
+    int N;
+    const u64 *rot;
+    size_t rqs;
+    const unsigned char *db;
+    u64 *acc;
+    int dim, nl, Gq, xm;
+    DbLayout L;
+    int G, ng, nblk, q0, Qt;
+};
+// a form's two entry points with the argument lists they have: streaming <A, BPP, QW, NW> from limb j0 on, split-diagonal <KS, QW>
+template <class A, int BPP, int QW, int NW>
+static void launch_stream(FormCtCt, hipStream_t st, dim3 grid, const LoopB &p, int j0) {
+    hipLaunchKernelGGL((k_hydia_tensor<A, BPP, QW, NW>), grid, dim3(64 * NW), 0, st, p.mod, p.N, p.rot, p.rqs, p.db, p.acc, p.dim, p.nl, p.Gq,
+                       p.xm, p.L, j0, p.G, p.ng, p.nblk, p.q0, p.Qt);
 }
-template <class A, int BPP, int QW, class... Args>
-static void launch_stream(hipStream_t st, int nw, dim3 grid, Args... args) {
+template <class A, int BPP, int QW, int NW>
+static void launch_stream(FormCtPlain, hipStream_t st, dim3 grid, const LoopB &p, int j0) {
+    hipLaunchKernelGGL((k_hydia_plain<A, BPP, NW>), grid, dim3(64 * NW), 0, st, p.mod, p.N, p.rot, p.db, p.acc, p.dim, p.nl, p.Gq, p.xm, p.L, j0,
+                       p.G, p.ng, p.nblk);
+}
+template <class A, int BPP, int QW, int NW>
+static void launch_stream(FormPlainCt, hipStream_t st, dim3 grid, const LoopB &p, int j0) {
+    hipLaunchKernelGGL((k_hydia_pq<A, BPP, NW>), grid, dim3(64 * NW), 0, st, p.mod, p.N, p.rot, p.db, p.acc, p.dim, p.nl, p.Gq, p.xm, p.L, j0,
+                       p.G, p.ng, p.nblk);
+}
+template <int KS, int QW>
+static void launch_split(FormCtCt, hipStream_t st, dim3 grid, const LoopB &p) {
+    hipLaunchKernelGGL((k_hydia_tensor_sk<KS, QW>), grid, dim3(64 * KS), 0, st, p.mod, p.N, p.rot, p.rqs, p.db, p.acc, p.dim, p.nl, p.L, p.G,
+                       p.ng, p.nblk, p.q0, p.Qt);
+}
+template <int KS, int QW>
+static void launch_split(FormCtPlain, hipStream_t st, dim3 grid, const LoopB &p) {
+    hipLaunchKernelGGL((k_hydia_plain_sk<KS>), grid, dim3(64 * KS), 0, st, p.mod, p.N, p.rot, p.db, p.acc, p.dim, p.nl, p.L, p.G, p.ng, p.nblk);
+}
+template <int KS, int QW>
+static void launch_split(FormPlainCt, hipStream_t st, dim3 grid, const LoopB &p) {
+    hipLaunchKernelGGL((k_hydia_pq_sk<KS>), grid, dim3(64 * KS), 0, st, p.mod, p.N, p.rot, p.db, p.acc, p.dim, p.nl, p.L, p.G, p.ng, p.nblk);
+}
+// an instantiation's name as rocprofv3 prints it (namespaces dropped), which is what the byte ledger records; QW only where the form
+// has batches
+template <class F>
+static std::string stream_name(const char *policy, int bpp, int qw, int nw) {
+    char n[96];
+    if (F::batch) snprintf(n, sizeof n, "k_hydia_%s<%s, %d, %d, %d>", F::name, policy, bpp, qw, nw);
+    else snprintf(n, sizeof n, "k_hydia_%s<%s, %d, %d>", F::name, policy, bpp, nw);
+    return n;
+}
+template <class F>
+static std::string split_name(int ks, int qw) {
+    char n[96];
+    if (F::batch) snprintf(n, sizeof n, "k_hydia_%s_sk<%d, %d>", F::name, ks, qw);
+    else snprintf(n, sizeof n, "k_hydia_%s_sk<%d>", F::name, ks);
+    return n;
+}
+// the streaming kernel <A, BPP, QW, nw> of form F with its ledger entry.  NW = 8 is a batch over a group-sequential layout of
+// eight-block groups
+template <class F, class A, int BPP, int QW>
+static void stream_nw(hipStream_t st, int nw, dim3 grid, const LoopB &p, int j0, double bytes) {
+    ledger_add(stream_name<F>(A::name, BPP, QW, nw).c_str(), bytes);
     switch (nw) {
-    case 1: hipLaunchKernelGGL((k_hydia_tensor<A, BPP, QW, 1>), grid, dim3(64), 0, st, args...); return;
-    case 2: hipLaunchKernelGGL((k_hydia_tensor<A, BPP, QW, 2>), grid, dim3(128), 0, st, args...); return;
-    case 4: hipLaunchKernelGGL((k_hydia_tensor<A, BPP, QW, 4>), grid, dim3(256), 0, st, args...); return;
-    case 8:  // a batch over a group-sequential layout of eight-block groups
-        if constexpr (BPP == 1) {
-            hipLaunchKernelGGL((k_hydia_tensor<A, BPP, QW, 8>), grid, dim3(512), 0, st, args...);
+    case 1: launch_stream<A, BPP, QW, 1>(F{}, st, grid, p, j0); return;
+    case 2: launch_stream<A, BPP, QW, 2>(F{}, st, grid, p, j0); return;
+    case 4: launch_stream<A, BPP, QW, 4>(F{}, st, grid, p, j0); return;
+    case 8:
+        if constexpr (F::batch && BPP == 1) {
+            launch_stream<A, BPP, QW, 8>(F{}, st, grid, p, j0);
             return;
         }
     }
     throw std::logic_error("hydia: no loop B kernel for this split");
 }
-template <class... Args>
-static void launch_sk(hipStream_t st, int ks, int qw, dim3 grid, Args... args) {
-    if (ks == 8 && qw == 2) hipLaunchKernelGGL((k_hydia_tensor_sk<8, 2>), grid, dim3(512), 0, st, args...);
-    else if (ks == 8) hipLaunchKernelGGL((k_hydia_tensor_sk<8, 1>), grid, dim3(512), 0, st, args...);
-    else if (qw == 2) hipLaunchKernelGGL((k_hydia_tensor_sk<4, 2>), grid, dim3(256), 0, st, args...);
-    else hipLaunchKernelGGL((k_hydia_tensor_sk<4, 1>), grid, dim3(256), 0, st, args...);
+// the split-diagonal kernel <KS, qw> of form F with its ledger entry
+template <class F, int KS>
+static void split_qw(hipStream_t st, int qw, dim3 grid, const LoopB &p, double bytes) {
+    ledger_add(split_name<F>(KS, qw).c_str(), bytes);
+    if constexpr (F::batch)
+        if (qw == 2) return launch_split<KS, 2>(F{}, st, grid, p);
+    launch_split<KS, 1>(F{}, st, grid, p);
 }
-void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G,
-                             int dim, int nl, const DbLayout &L, int ng, int bpp, int nw) {
-    const bool batch = bpp == TENSOR_BATCH;
+// Loop B of every form: Q queries (one unless the form has batches and bpp = TENSOR_BATCH) against G blocks of dim diagonals
+template <class F>
+static void loop_b(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G, int dim,
+                   int nl, const DbLayout &L, int ng, int bpp, int nw) {
+    const bool batch = F::batch && bpp == TENSOR_BATCH;
     if (Q < 1 || (!batch && Q != 1) || G < 1 || dim < 2 || (ng > 0 && G % ng)) throw std::logic_error("hydia: loop B with a bad shape");
     if (L.bits46 && !(L.packed && L.seq && dim <= 4096)) throw std::logic_error("hydia: 46-bit database outside the 24-bit-halves loop B");
     if (L.seq && (G != L.blocks || dim != L.bd || G % L.seq || G <= 8 || L.seq % L.seq_bpp || (L.seq & (L.seq - 1)) || L.seq > 8))
@@ -1734,22 +1769,24 @@ void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *
     } else {
         tensor_split(G, bpp, nw, &B, &W);
     }
-    const int Gq = G / (B * W), nblk = ng > 0 ? G / ng : 0;
-    const int xm = (N / 128) % 8 == 0 ? 1 : 0;  // XCD-aware tile -> workgroup map
-    const unsigned char *dbb = (const unsigned char *)db;
-    // ledger bytes: resident database (6- or 8-byte residues, 5.75 for 46-bit) + the QW rotation sets once + QW x G accumulators
+    LoopB p{mod, N, rot, rqs, (const unsigned char *)db, acc, dim, nl, G / (B * W), (N / 128) % 8 == 0 ? 1 : 0 /* XCD-aware tile map */,
+            L, G, ng, ng > 0 ? G / ng : 0, 0, Q};
+    // ledger bytes per limb: the resident database (dp polynomials per entry; 6- or 8-byte residues, 5.75 for 46-bit) + the QW rotation
+    // sets (qp polynomials per rotation) once + QW x G accumulators of `comps` components
     const double per_lp8 = LP_BYTES(N), per_lp6 = (double)N * (L.bits46 ? 5.75 : 6.0);
-    for (int q0 = 0; q0 < Q; q0 += MQ_QW) {  // one pass over the database per QW queries (an odd last one alone)
-        const int QW = Q - q0 >= MQ_QW ? MQ_QW : 1;
-        const double rot_acc = QW * ((double)dim * 2 * per_lp8 + (double)G * 3 * per_lp8);
-        auto bytes = [&](int limbs, double per_lp) { return limbs * ((double)G * dim * 2 * per_lp + rot_acc); };
+    for (p.q0 = 0; p.q0 < Q; p.q0 += MQ_QW) {  // one pass over the database per QW queries (an odd last one alone)
+        const int QW = Q - p.q0 >= MQ_QW ? MQ_QW : 1;
+        auto bytes = [&](int limbs, double per_lp) {
+            return limbs * ((double)G * dim * F::dp * per_lp + QW * ((double)dim * F::qp + (double)G * F::comps) * per_lp8);
+        };
         auto stream = [&](auto *policy, int j0, int limbs) {  // policy: a null pointer of the arithmetic's type
             typedef typename std::remove_pointer<decltype(policy)>::type A;
-            const dim3 grid((N / 128) * Gq, limbs);
-            ledger_tensor(bytes(limbs, j0 ? per_lp6 : per_lp8), A::name, B, QW, W);
-            if (B == 2) launch_stream<A, 2, 1>(st, W, grid, mod, N, rot, rqs, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Q);
-            else if (QW == 2) launch_stream<A, 1, 2>(st, W, grid, mod, N, rot, rqs, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Q);
-            else launch_stream<A, 1, 1>(st, W, grid, mod, N, rot, rqs, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk, q0, Q);
+            const dim3 grid((N / 128) * p.Gq, limbs);
+            const double by = bytes(limbs, j0 ? per_lp6 : per_lp8);
+            if constexpr (F::batch)
+                if (QW == 2) return stream_nw<F, A, 1, 2>(st, W, grid, p, j0, by);  // (a batch has B = 1)
+            if (B == 2) stream_nw<F, A, 2, 1>(st, W, grid, p, j0, by);
+            else stream_nw<F, A, 1, 1>(st, W, grid, p, j0, by);
         };
         if (!L.packed) {  // 8-byte residues everywhere: one launch over all limbs
             stream((Sums128<false> *)nullptr, 0, nl);
@@ -1758,9 +1795,9 @@ void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *
         // limb 0 (8-byte residues) and limbs 1.. (6-byte or 46-bit residues) as two launches: no shared register budget
         if (!L.seq && G <= 8) {  // few blocks: 256 x G one-wave workgroups cannot hide the latency of dim dependent steps -> split the
             // diagonals (eight waves: sixteen hold a lane to 128 registers and the kernel spilled 69 of them — round 5)
-            const int ks = G <= 2 ? 8 : 4;
-            ledger_tensor(bytes(1, per_lp8), nullptr, ks, QW, 0);
-            launch_sk(st, ks, QW, dim3((N / 128) * G, 1), mod, N, rot, rqs, dbb, acc, dim, nl, L, G, ng, nblk, q0, Q);
+            const dim3 grid((N / 128) * G, 1);
+            if (G <= 2) split_qw<F, 8>(st, QW, grid, p, bytes(1, per_lp8));
+            else split_qw<F, 4>(st, QW, grid, p, bytes(1, per_lp8));
         } else {
             stream((Sums128<false> *)nullptr, 0, 1);
         }
@@ -1770,129 +1807,23 @@ void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *
         else stream((Sums128<true> *)nullptr, 1, nl - 1);
     }
 }
-// ---- loop B for a plain gallery.  The split is tensor_split's with the gallery's own cap of blocks per wave (PLAIN_BPP = 2): at two
-// blocks per wave the 46-bit kernel takes 125 VGPRs (four waves per SIMD, the encrypted one two); four blocks per wave compiled to 231
-// (two waves per SIMD: the same blocks in flight per SIMD, half the waves to hide latency with) and is not instantiated
-template <class A, int BPP, class... Args>
-static void launch_plain(hipStream_t st, int nw, dim3 grid, Args... args) {
-    switch (nw) {
-    case 1: hipLaunchKernelGGL((k_hydia_plain<A, BPP, 1>), grid, dim3(64), 0, st, args...); return;
-    case 2: hipLaunchKernelGGL((k_hydia_plain<A, BPP, 2>), grid, dim3(128), 0, st, args...); return;
-    case 4: hipLaunchKernelGGL((k_hydia_plain<A, BPP, 4>), grid, dim3(256), 0, st, args...); return;
-    }
-    throw std::logic_error("hydia: no plain loop B kernel for this split");
+void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G,
+                             int dim, int nl, const DbLayout &L, int ng, int bpp, int nw) {
+    loop_b<FormCtCt>(st, mod, N, rot, rqs, db, acc, Q, G, dim, nl, L, ng, bpp, nw);
 }
+// The split of a plain gallery is tensor_split's with the gallery's own cap of blocks per wave (PLAIN_BPP = 2): at two blocks per wave
+// the 46-bit kernel takes 125 VGPRs (four waves per SIMD, the encrypted one two); four blocks per wave compiled to 231 (two waves per
+// SIMD: the same blocks in flight per SIMD, half the waves to hide latency with) and is not instantiated
 void hydia_plain_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, const void *db, u64 *acc, int G, int dim, int nl,
                             const DbLayout &L, int ng, int bpp, int nw) {
     if (!L.plain) throw std::logic_error("hydia: plain loop B launched against a ciphertext database");
-    if (G < 1 || dim < 2 || (ng > 0 && G % ng)) throw std::logic_error("hydia: loop B with a bad shape");
-    if (L.bits46 && !(L.packed && L.seq && dim <= 4096)) throw std::logic_error("hydia: 46-bit database outside the 24-bit-halves loop B");
-    if (L.seq && (G != L.blocks || dim != L.bd || G % L.seq || G <= 8 || L.seq % L.seq_bpp || (L.seq & (L.seq - 1)) || L.seq > 8))
-        throw std::logic_error("hydia: loop B launched against a group-sequential database with another shape");
-    int B, W;
-    if (L.seq) {
-        B = L.seq_bpp;
-        W = L.seq / L.seq_bpp;
-    } else {
-        tensor_split(G, bpp, nw, &B, &W);
-    }
-    const int Gq = G / (B * W), nblk = ng > 0 ? G / ng : 0;
-    const int xm = (N / 128) % 8 == 0 ? 1 : 0;
-    const unsigned char *dbb = (const unsigned char *)db;
-    // ledger bytes: the resident plaintexts (one polynomial each) + the rotation set once + G two-component accumulators
-    const double per_lp8 = LP_BYTES(N), per_lp6 = (double)N * (L.bits46 ? 5.75 : 6.0);
-    const double rot_acc = (double)dim * 2 * per_lp8 + (double)G * 2 * per_lp8;
-    auto bytes = [&](int limbs, double per_lp) { return limbs * ((double)G * dim * per_lp + rot_acc); };
-    auto stream = [&](auto *policy, int j0, int limbs) {
-        typedef typename std::remove_pointer<decltype(policy)>::type A;
-        const dim3 grid((N / 128) * Gq, limbs);
-        char n[96];
-        snprintf(n, sizeof n, "k_hydia_plain<%s, %d, %d>", A::name, B, W);
-        ledger_add(n, bytes(limbs, j0 ? per_lp6 : per_lp8));
-        if (B == 2) launch_plain<A, 2>(st, W, grid, mod, N, rot, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk);
-        else launch_plain<A, 1>(st, W, grid, mod, N, rot, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk);
-    };
-    if (!L.packed) {
-        stream((Sums128<false> *)nullptr, 0, nl);
-        return;
-    }
-    if (!L.seq && G <= 8) {
-        const int ks = G <= 2 ? 8 : 4;
-        char n[96];
-        snprintf(n, sizeof n, "k_hydia_plain_sk<%d>", ks);
-        ledger_add(n, bytes(1, per_lp8));
-        const dim3 grid((N / 128) * G, 1);
-        if (ks == 8) hipLaunchKernelGGL((k_hydia_plain_sk<8>), grid, dim3(512), 0, st, mod, N, rot, dbb, acc, dim, nl, L, G, ng, nblk);
-        else hipLaunchKernelGGL((k_hydia_plain_sk<4>), grid, dim3(256), 0, st, mod, N, rot, dbb, acc, dim, nl, L, G, ng, nblk);
-    } else {
-        stream((Sums128<false> *)nullptr, 0, 1);
-    }
-    if (nl == 1) return;
-    if (L.bits46) stream((Halves24<true> *)nullptr, 1, nl - 1);
-    else if (L.seq && dim <= 4096) stream((Halves24<false> *)nullptr, 1, nl - 1);
-    else stream((Sums128<true> *)nullptr, 1, nl - 1);
+    loop_b<FormCtPlain>(st, mod, N, rot, 0, db, acc, 1, G, dim, nl, L, ng, bpp, nw);
 }
-// ---- loop B for a plain query against an ENCRYPTED database (kinds 5 / 6).  The split is the encrypted loop B's (tensor_split with the
-// context's caps; a group-sequential layout fixes it), so every layout an encrypted query reads is read here unchanged.  Resources of
-// every instantiation: DESIGN.md §4
-template <class A, int BPP, class... Args>
-static void launch_pq(hipStream_t st, int nw, dim3 grid, Args... args) {
-    switch (nw) {
-    case 1: hipLaunchKernelGGL((k_hydia_pq<A, BPP, 1>), grid, dim3(64), 0, st, args...); return;
-    case 2: hipLaunchKernelGGL((k_hydia_pq<A, BPP, 2>), grid, dim3(128), 0, st, args...); return;
-    case 4: hipLaunchKernelGGL((k_hydia_pq<A, BPP, 4>), grid, dim3(256), 0, st, args...); return;
-    }
-    throw std::logic_error("hydia: no plain-query loop B kernel for this split");
-}
+// A plain query reads every layout an encrypted query reads, unchanged, with the encrypted loop B's split
 void hydia_pq_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, const void *db, u64 *acc, int G, int dim, int nl,
                          const DbLayout &L, int ng, int bpp, int nw) {
     if (L.plain) throw std::logic_error("hydia: plain-query loop B launched against a plain gallery");
-    if (G < 1 || dim < 2 || (ng > 0 && G % ng)) throw std::logic_error("hydia: loop B with a bad shape");
-    if (L.bits46 && !(L.packed && L.seq && dim <= 4096)) throw std::logic_error("hydia: 46-bit database outside the 24-bit-halves loop B");
-    if (L.seq && (G != L.blocks || dim != L.bd || G % L.seq || G <= 8 || L.seq % L.seq_bpp || (L.seq & (L.seq - 1)) || L.seq > 8))
-        throw std::logic_error("hydia: loop B launched against a group-sequential database with another shape");
-    int B, W;
-    if (L.seq) {
-        B = L.seq_bpp;
-        W = L.seq / L.seq_bpp;
-    } else {
-        tensor_split(G, bpp, nw, &B, &W);
-    }
-    const int Gq = G / (B * W), nblk = ng > 0 ? G / ng : 0;
-    const int xm = (N / 128) % 8 == 0 ? 1 : 0;
-    const unsigned char *dbb = (const unsigned char *)db;
-    // ledger bytes: the resident ciphertexts (two polynomials each) + the rotated plaintexts once + G two-component accumulators
-    const double per_lp8 = LP_BYTES(N), per_lp6 = (double)N * (L.bits46 ? 5.75 : 6.0);
-    const double rot_acc = (double)dim * per_lp8 + (double)G * 2 * per_lp8;
-    auto bytes = [&](int limbs, double per_lp) { return limbs * ((double)G * dim * 2 * per_lp + rot_acc); };
-    auto stream = [&](auto *policy, int j0, int limbs) {
-        typedef typename std::remove_pointer<decltype(policy)>::type A;
-        const dim3 grid((N / 128) * Gq, limbs);
-        char n[96];
-        snprintf(n, sizeof n, "k_hydia_pq<%s, %d, %d>", A::name, B, W);
-        ledger_add(n, bytes(limbs, j0 ? per_lp6 : per_lp8));
-        if (B == 2) launch_pq<A, 2>(st, W, grid, mod, N, rot, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk);
-        else launch_pq<A, 1>(st, W, grid, mod, N, rot, dbb, acc, dim, nl, Gq, xm, L, j0, G, ng, nblk);
-    };
-    if (!L.packed) {
-        stream((Sums128<false> *)nullptr, 0, nl);
-        return;
-    }
-    if (!L.seq && G <= 8) {
-        const int ks = G <= 2 ? 8 : 4;
-        char n[96];
-        snprintf(n, sizeof n, "k_hydia_pq_sk<%d>", ks);
-        ledger_add(n, bytes(1, per_lp8));
-        const dim3 grid((N / 128) * G, 1);
-        if (ks == 8) hipLaunchKernelGGL((k_hydia_pq_sk<8>), grid, dim3(512), 0, st, mod, N, rot, dbb, acc, dim, nl, L, G, ng, nblk);
-        else hipLaunchKernelGGL((k_hydia_pq_sk<4>), grid, dim3(256), 0, st, mod, N, rot, dbb, acc, dim, nl, L, G, ng, nblk);
-    } else {
-        stream((Sums128<false> *)nullptr, 0, 1);
-    }
-    if (nl == 1) return;
-    if (L.bits46) stream((Halves24<true> *)nullptr, 1, nl - 1);
-    else if (L.seq && dim <= 4096) stream((Halves24<false> *)nullptr, 1, nl - 1);
-    else stream((Sums128<true> *)nullptr, 1, nl - 1);
+    loop_b<FormPlainCt>(st, mod, N, rot, 0, db, acc, 1, G, dim, nl, L, ng, bpp, nw);
 }
 void automorph_batch(hipStream_t st, int logN, const u64 *m, u64 *out, int nl, int R, const unsigned *galois) {
     ledger_add("k_automorph_batch", (1.0 + R) * nl * LP_BYTES(1 << logN));

@@ -22,11 +22,17 @@ with one residue in 16 replaced, so every operand position still decides the res
   g  batches of 2 and 3 queries on 2, 8 and 16 blocks (46- and 48-bit): sk<8, 2>, sk<4, 2>, <Halves24<true>, 1, 2, 8>,
      <Sums128<true>, 1, 2, 8>, and the QW = 1 pass an odd batch ends with
   h  16 blocks as (block, giant step) pairs with 2 and 4 giant steps, 1 and 3 queries: the giant-major slot map
+  i  the splits no other case takes, at dim 16 (the launcher picks (BPP, NW) from the block count alone): 9 blocks -> groups of one
+     block, one block per wave and one wave; 12 blocks -> two blocks per wave, two waves; both with 46- and 48-bit residues, and as
+     batches of 3 (one block per wave, NW = the group size 1 / 4); HYDIA_TENSOR_BPP=1 on 10 and 12 blocks of 48-bit residues ->
+     Halves24<false> at one block per wave and two / four waves.  With them every k_hydia_tensor / k_hydia_tensor_sk instantiation
+     the library ships is run by this file, except the five the launcher never selects: <Halves24<false>, 1, 2, *> and
+     <Halves24<false>, 1, 1, 8> (a batch keeps Sums128<true> on 48-bit group-sequential residues)
 
 No shape here is refused by the context or the launcher.  Not reached: Halves24 at its 4096-diagonal limit (tests/test_loop_b_model_cpu.py
 says why), xcd_map = 0 (a ring below 1024 coefficients), N = 2^15 with saturated operands (the same kernels; minutes of host work).
 
-Measured on one MI355X: the file's 24 cases take 31 s; the slowest are f-16-blocks 2.6 s, g-8-blocks-3q 2.5 s, d-48bit 2.5 s."""
+Measured on one MI355X: the 24 cases a - h take 31 s, the i cases under 4 s each; the slowest are f-16-blocks 2.6 s, g-8-blocks-3q 2.5 s, d-48bit 2.5 s."""
 import functools
 import os
 import re
@@ -73,7 +79,8 @@ def batch(names, queries):
     return out
 
 
-# id, blocks, dim, layout mode, chain, queries, giants, layout text, residue text, kernels (as single-query QW = 1 names, one block per wave for batches)
+# id, blocks, dim, layout mode, chain, queries, giants, layout text, residue text, kernels (as single-query QW = 1 names, one block per wave for
+# batches)[, environment of the checker]
 CASES = [
     ("a-1-blocks", 1, 512, 1, None, 1, 0, MAJOR, "48-bit packed", {split(8, 1), stream(S_PK, 1, 1, 1)}),
     ("a-2-blocks", 2, 512, 1, None, 1, 0, MAJOR, "48-bit packed", {split(8, 1), stream(S_PK, 2, 1, 1)}),
@@ -100,10 +107,21 @@ for NG in (2, 4):
         ("h-%d-giants-1q" % NG, 16, 64, 1, None, 1, NG, GROUP, "46-bit packed", {stream(S_8B, 2, 1, 4), stream(H46, 2, 1, 4)}),
         ("h-%d-giants-3q" % NG, 16, 64, 1, None, 3, NG, GROUP, "46-bit packed", batch({stream(S_8B, 1, 1, 8), stream(H46, 1, 1, 8)}, 3)),
     ]
+CASES += [
+    ("i-9-blocks", 9, 16, 1, None, 1, 0, GROUP, "46-bit packed", {stream(S_8B, 1, 1, 1), stream(H46, 1, 1, 1)}),
+    ("i-9-blocks-48bit", 9, 16, 2, None, 1, 0, GROUP, "48-bit packed", {stream(S_8B, 1, 1, 1), stream(H48, 1, 1, 1)}),
+    ("i-12-blocks", 12, 16, 1, None, 1, 0, GROUP, "46-bit packed", {stream(S_8B, 2, 1, 2), stream(H46, 2, 1, 2)}),
+    ("i-12-blocks-48bit", 12, 16, 2, None, 1, 0, GROUP, "48-bit packed", {stream(S_8B, 2, 1, 2), stream(H48, 2, 1, 2)}),
+    ("i-9-blocks-3q", 9, 16, 1, None, 3, 0, GROUP, "46-bit packed", batch({stream(S_8B, 1, 1, 1), stream(H46, 1, 1, 1)}, 3)),
+    ("i-12-blocks-3q", 12, 16, 1, None, 3, 0, GROUP, "46-bit packed", batch({stream(S_8B, 1, 1, 4), stream(H46, 1, 1, 4)}, 3)),
+    ("i-10-blocks-48bit-bpp1", 10, 16, 2, None, 1, 0, GROUP, "48-bit packed", {stream(S_8B, 1, 1, 2), stream(H48, 1, 1, 2)}, {"HYDIA_TENSOR_BPP": "1"}),
+    ("i-12-blocks-48bit-bpp1", 12, 16, 2, None, 1, 0, GROUP, "48-bit packed", {stream(S_8B, 1, 1, 4), stream(H48, 1, 1, 4)}, {"HYDIA_TENSOR_BPP": "1"}),
+]
 
 
-@pytest.mark.parametrize("blocks,dim,mode,chain_name,queries,giants,layout,residues,kernels", [c[1:] for c in CASES], ids=[c[0] for c in CASES])
-def test_loop_b_on_saturated_and_edge_residues(blocks, dim, mode, chain_name, queries, giants, layout, residues, kernels):
+@pytest.mark.parametrize("blocks,dim,mode,chain_name,queries,giants,layout,residues,kernels,env", [(c[1:] + ({},))[:10] for c in CASES],
+                         ids=[c[0] for c in CASES])
+def test_loop_b_on_saturated_and_edge_residues(blocks, dim, mode, chain_name, queries, giants, layout, residues, kernels, env):
     assert os.path.exists(EXE), "tests/csrc/loop_b_check is built by __graft_entry__.build()"
     cmd = [EXE, str(blocks), str(dim), str(LOG_N), str(mode), "--patterns", ",".join(PAIRS)]
     if chain_name:
@@ -113,7 +131,7 @@ def test_loop_b_on_saturated_and_edge_residues(blocks, dim, mode, chain_name, qu
     if giants:
         cmd += ["--giants", str(giants)]
     try:
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
     except subprocess.TimeoutExpired as ex:
         pytest.fail("loop_b_check ran into its time limit: " + str(ex.stdout)[-2000:])
     tail = r.stdout[-3000:] + r.stderr[-2000:]

@@ -235,6 +235,10 @@ def test_saturated_and_edge_residues(im, chain, blocks, dim, pair):
     through plain_db_alloc / plain_db_import_pt / import_ct, against Or.compute_similarity on the same trivial ciphertexts.  default
     chain: 48-bit ciphertext-major up to 8 blocks, 46-bit group-sequential at 16; evaluator chain: 48-bit residues; transform chain:
     unpacked, folding sums on the 59/60-bit limbs.  The byte ledger says which instantiations ran."""
+    check_edge_case(im, chain, blocks, dim, pair)
+
+
+def check_edge_case(im, chain, blocks, dim, pair):
     P, K, Or, cc = world(im, chain, dim)
     qname, mname = pair.split("/")
     n = blocks * P.slots
@@ -256,6 +260,20 @@ def test_saturated_and_edge_residues(im, chain, blocks, dim, pair):
     assert len(want) == blocks
     for g in range(blocks):
         assert np.array_equal(got[g], want[g].data()), g
+
+
+# the splits EDGE_SHAPES does not take (tensor_split picks blocks per wave and waves per workgroup from the block count alone), at dim 16:
+# 2 and 4 blocks (<., 2, 1> and <., 2, 2>, the latter also unpacked), 9 (groups of one block: <., 1, 1> on 46- and 48-bit halves), 10
+# (Halves24<false> at <., 2, 1>) and 12 (<., 2, 2> on both halves).  With them every k_hydia_plain / k_hydia_plain_sk instantiation the
+# library ships is run by this file, except <., 1, 2> and <., 1, 4>: a gallery's cap is two blocks per wave (hk::PLAIN_BPP), so one block
+# per wave means an odd block count, and that has no two waves
+OTHER_SPLITS = [("default", 2), ("default", 4), ("transform", 4), ("default", 9), ("evaluator", 9), ("evaluator", 10), ("default", 12),
+                ("evaluator", 12)]
+
+
+@pytest.mark.parametrize("chain,blocks", OTHER_SPLITS, ids=["%s-%d" % c for c in OTHER_SPLITS])
+def test_saturated_residues_on_the_other_splits(im, chain, blocks):
+    check_edge_case(im, chain, blocks, 16, "sat/sat")
 
 
 # ------------------------------------------------------------------ the full ring

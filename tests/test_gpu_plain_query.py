@@ -7,6 +7,7 @@ run.  The GPU contexts hold NO rotation key 1 .. vector_dim-1 beyond the powers 
 (the giant steps of B = 8): the oracle rotates the trivial ciphertext with its full key set and gets the same bits."""
 import ctypes
 import functools
+import os
 
 import numpy as np
 import pytest
@@ -54,16 +55,27 @@ def oracle_world(chain, dim, seed):
     return _ORACLE[key]
 
 
-def world(im, chain="default", dim=64, seed=7, giants=True):
-    """oracle with its full key set; GPU context with the power-of-two rotation keys and (giants, dim 64) the multiples of 8 only"""
-    key = (chain, dim, giants)
+def world(im, chain="default", dim=64, seed=7, giants=True, bpp=2):
+    """oracle with its full key set; GPU context with the power-of-two rotation keys and (giants, dim 64) the multiples of 8 only.
+    bpp = 1: the context is created under HYDIA_TENSOR_BPP=1 (it reads the cap once), one database block per wave"""
+    key = (chain, dim, giants) if bpp == 2 else (chain, dim, giants, bpp)
     P, K, Or = oracle_world(chain, dim, seed)
     if key not in _CTX:
         moduli = chain_moduli(chain)
-        if moduli is None:
-            cc = im.Context(im.default_params(log_n=11, vector_dim=dim), 0)
-        else:
-            cc = im.Context(im.default_params(log_n=11, vector_dim=dim), 0, moduli=moduli, roots=P.roots, n_p=4)
+        before = os.environ.get("HYDIA_TENSOR_BPP")
+        if bpp != 2:
+            os.environ["HYDIA_TENSOR_BPP"] = str(bpp)
+        try:
+            if moduli is None:
+                cc = im.Context(im.default_params(log_n=11, vector_dim=dim), 0)
+            else:
+                cc = im.Context(im.default_params(log_n=11, vector_dim=dim), 0, moduli=moduli, roots=P.roots, n_p=4)
+        finally:
+            if bpp != 2:
+                if before is None:
+                    del os.environ["HYDIA_TENSOR_BPP"]
+                else:
+                    os.environ["HYDIA_TENSOR_BPP"] = before
         rots = set(pow2_rotations(P.slots))
         if giants and dim == 64:
             rots |= set(range(8, dim, 8))
@@ -113,11 +125,11 @@ def take(dim, slots, blocks, ragged):
     return src[:blocks * slots - (3 if ragged else 0)].copy()
 
 
-def pq_kernels(chain, G):
+def pq_kernels(chain, G, bpp=2):
     """the loop-B launches of a plain query over G loop-B blocks (blocks, or (block, giant step) pairs), as the byte ledger names them:
     tensor_split's blocks per wave / waves per workgroup, the split-diagonal kernel on limb 0 of <= 8 ciphertext-major blocks, one
     8-byte launch over all limbs on the unpacked transform chain, the 24-bit halves on a group-sequential layout"""
-    B = 2 if G % 2 == 0 else 1
+    B = 2 if bpp >= 2 and G % 2 == 0 else 1
     W = 4 if (G // B) % 4 == 0 else 2 if (G // B) % 2 == 0 else 1
     stream = lambda policy: "k_hydia_pq<%s, %d, %d>" % (policy, B, W)  # noqa: E731
     if chain == "transform":
@@ -282,7 +294,11 @@ def test_saturated_and_edge_residues(im, chain, blocks, dim, pair):
     q - 1 patterns), through pt_import and db_alloc / db_import_ct, against Or.compute_similarity on the trivial ciphertext of the
     same plaintext.  default chain: 48-bit ciphertext-major up to 8 blocks, 46-bit group-sequential at 16; evaluator chain: 48-bit
     residues; transform chain: unpacked, folding sums on the 59/60-bit limbs.  The byte ledger says which instantiations ran."""
-    P, K, Or, cc = world(im, chain, dim, giants=False)
+    check_edge_case(im, chain, blocks, dim, pair)
+
+
+def check_edge_case(im, chain, blocks, dim, pair, bpp=2):
+    P, K, Or, cc = world(im, chain, dim, giants=False, bpp=bpp)
     qname, mname = pair.split("/")
     n = blocks * P.slots
     pc = pattern_ct(P, mname)
@@ -300,11 +316,26 @@ def test_saturated_and_edge_residues(im, chain, blocks, dim, pair):
     want = Or.compute_similarity(pattern_query(P, qname), pattern_db(P, mname, blocks * P.dim), n)
     sender = im.DiagonalSender(cc, n)
     sim, ran, _ = with_ledger(im, lambda: sender.computeSimilarity(pt))
-    assert ran == pq_kernels(chain, blocks), sorted(ran)
+    assert ran == pq_kernels(chain, blocks, bpp), sorted(ran)
     got = sim.export()
     assert len(want) == blocks
     for g in range(blocks):
         assert np.array_equal(got[g], want[g].data()), g
+
+
+# the splits EDGE_SHAPES does not take (tensor_split picks blocks per wave and waves per workgroup from the block count and the context's
+# cap alone), at dim 16.  Cap 2: 4 blocks (<., 2, 2>, also unpacked), 9 (groups of one block: <., 1, 1> on 46- and 48-bit halves), 10
+# (Halves24<false> at <., 2, 1>), 12 (<., 2, 2> on both halves).  Cap 1 (HYDIA_TENSOR_BPP=1): 2 / 4 / 10 / 12 blocks -> one block per
+# wave and two / four waves, for every arithmetic.  With them every k_hydia_pq / k_hydia_pq_sk instantiation the library ships is run
+# by this file
+OTHER_SPLITS = [("default", 4, 2), ("transform", 4, 2), ("default", 9, 2), ("evaluator", 9, 2), ("evaluator", 10, 2), ("default", 12, 2),
+                ("evaluator", 12, 2), ("default", 2, 1), ("default", 4, 1), ("transform", 2, 1), ("transform", 4, 1), ("default", 10, 1),
+                ("default", 12, 1), ("evaluator", 10, 1), ("evaluator", 12, 1)]
+
+
+@pytest.mark.parametrize("chain,blocks,bpp", OTHER_SPLITS, ids=["%s-%d-bpp%d" % c for c in OTHER_SPLITS])
+def test_saturated_residues_on_the_other_splits(im, chain, blocks, bpp):
+    check_edge_case(im, chain, blocks, 16, "sat/sat", bpp)
 
 
 # ------------------------------------------------------------------ 5. keys
