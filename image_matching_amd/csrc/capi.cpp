@@ -574,6 +574,24 @@ int hydia_db_update_shard(hydia_ctx *ctx, size_t first_vector, double *rows, siz
 int hydia_db_update(hydia_ctx *ctx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32]) {
     return hydia_db_update_shard(ctx, first_vector, rows, n, normalise, seed, 0);
 }
+size_t hydia_switch_key_words(const hydia_ctx *ctx) { return ctx ? (size_t)ctx->cx.prm.dnum * 2 * ctx->cx.nT * ctx->cx.N : 0; }
+int hydia_keygen_switch(hydia_ctx *ctx, const uint64_t *old_secret, const uint8_t seed[32], uint64_t *key_out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && old_secret && seed && key_out, "null argument");
+    client_keygen_switch(ctx->cx, reinterpret_cast<const u64 *>(old_secret), seed, reinterpret_cast<u64 *>(key_out));
+    return HYDIA_OK;
+    API_END
+}
+int hydia_db_rekey_chunked(hydia_ctx *ctx, const uint64_t *switch_key, int max_chunk) {
+    API_BEGIN
+    REQUIRE(ctx, "null argument");
+    use_device(ctx);
+    ctx->cx.db_rekey(reinterpret_cast<const u64 *>(switch_key), max_chunk);  // (every refusal — the resident kind, then a null key — before any work is enqueued)
+    return HYDIA_OK;
+    API_END
+}
+int hydia_db_rekey(hydia_ctx *ctx, const uint64_t *switch_key) { return hydia_db_rekey_chunked(ctx, switch_key, 0); }
 int hydia_set_matvec(hydia_ctx *ctx, int mode) {
     API_BEGIN
     REQUIRE(ctx && mode >= 0, "mat-vec mode is 0 (auto), 1 (hoisted) or a baby count");

@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "../../include/hydia.h"  // HY_EVK_ID_SWITCH
 #include "client_kernels.h"
 
 namespace hydia {
@@ -56,10 +57,10 @@ static u64 inv_mod_pow2(u64 g, u64 M) {
     return x & (M - 1);
 }
 
-// hybrid switching key from secret s_from (Q limbs) to secret s_enc (Q u P limbs)
-static void gen_evk(Context &cx, const ChaChaKey &key, int key_id, const u64 *s_enc, const u64 *s_from) {
+// hybrid switching key from secret s_from (Q limbs) to secret s_enc (Q u P limbs), written to evk [dnum][2][nT][N] (device memory);
+// key_id addresses the sampler streams
+static void gen_evk(Context &cx, const ChaChaKey &key, u64 key_id, const u64 *s_enc, const u64 *s_from, u64 *evk) {
     const int N = cx.N, nT = cx.nT, dnum = cx.prm.dnum;
-    u64 *evk = cx.eval_key_storage(key_id);
     const LimbSel all = cx.sel_range(0, nT);
     hc::sample_uniform(cx.stream, key, cx.d_mod, N, HY_STREAM(HY_DOM_EVK_A, key_id, 0, 0), 1ull, 1ull << 8,
                        evk + (size_t)nT * N, (size_t)N, (size_t)2 * nT * N, all, dnum);
@@ -123,17 +124,33 @@ static void keygen_impl(Context &cx, const uint8_t seed[32], const std::vector<i
     // relinearisation key: s^2 -> s
     u64 *tmp = cx.pool.get(sizeof(u64) * (size_t)nT * N);
     hc::mul(cx.stream, cx.d_mod, N, cx.d_sk, cx.d_sk, tmp, qsel);
-    gen_evk(cx, key, 0, cx.d_sk, tmp);
+    gen_evk(cx, key, 0, cx.d_sk, tmp, cx.eval_key_storage(0));
     // rotation keys: key r switches s -> sigma_g^{-1}(s), g = 5^r, so EvalFastRotation needs a single automorphism at the very end
     // (see evaluator.cpp, rotate_query); the sampler streams are addressed by r, whatever set r belongs to
     const u64 M = 2ull * N;
     for (int r : rots) {
         const u64 ginv = inv_mod_pow2(cx.galois_elt(r), M);
         hc::automorph(cx.stream, cx.prm.logN, cx.d_sk, tmp, (unsigned)ginv, nT);
-        gen_evk(cx, key, r, tmp, cx.d_sk);
+        gen_evk(cx, key, (u64)r, tmp, cx.d_sk, cx.eval_key_storage(r));
     }
     cx.pool.put(tmp);
     cx.sync();
+}
+
+// The switching key of a re-keyed database (Context::db_rekey): from the OLD receiver's secret (old_secret, host memory, [nT][N] in
+// evaluation form as hydia_export_secret_key gives it; its Q limbs are read) to THIS context's secret — gen_evk's key with the
+// reserved id HY_EVK_ID_SWITCH, into out (host memory, [dnum][2][nT][N]).  Nothing of the context changes
+void client_keygen_switch(Context &cx, const u64 *old_secret, const uint8_t seed[32], u64 *out) {
+    if (!cx.d_sk) throw StateError("hydia: secret key not loaded (a switching key is generated by the NEW receiver, which holds its secret)");
+    const size_t sk_elems = (size_t)cx.nT * cx.N, key_elems = (size_t)cx.prm.dnum * 2 * sk_elems;
+    u64 *d_old = cx.pool.get(sk_elems * sizeof(u64)), *d_key = cx.pool.get(key_elems * sizeof(u64));
+    cx.sync();
+    HIP_CHECK(hipMemcpy(d_old, old_secret, sk_elems * sizeof(u64), hipMemcpyHostToDevice));
+    gen_evk(cx, make_key(seed), HY_EVK_ID_SWITCH, cx.d_sk, d_old, d_key);
+    cx.sync();
+    HIP_CHECK(hipMemcpy(out, d_key, key_elems * sizeof(u64), hipMemcpyDeviceToHost));
+    cx.pool.put(d_key);
+    cx.pool.put(d_old);
 }
 
 // encode + encrypt X slot vectors that already sit in HBM; writes [X][2][nQ][N] at dst

@@ -8,6 +8,9 @@ void client_keygen(Context &cx, const uint8_t seed[32]);
 // sk, pk and relinearisation key exactly as client_keygen, rotation keys for exactly `rots` (each in [1, slots)); every other
 // rotation key is released.  A key that client_keygen also makes comes out bit-identical (same sampler streams).
 void client_keygen_rotations(Context &cx, const uint8_t seed[32], const std::vector<int> &rots);
+// the switching key of Context::db_rekey: old_secret (host, [nT][N], evaluation form) -> this context's secret, into out (host,
+// [dnum][2][nT][N]); sampler streams of key id HY_EVK_ID_SWITCH.  StateError without a secret; the context's own keys are untouched
+void client_keygen_switch(Context &cx, const u64 *old_secret, const uint8_t seed[32], u64 *out);
 // MakeCKKSPackedPlaintext(slots) at scale 2^scale_bits on limbs 0..nl-1 in evaluation form, with the Shoup companion of every
 // residue for hk::mul_plain: pt [2][nl][N] (row 0 residues, row 1 companions)
 void client_encode_plain(Context &cx, const double *slots, int nl, u64 *pt);

@@ -842,6 +842,81 @@ void Context::db_accumulate(size_t t0, const u64 *d_plain, int X) {
 }
 void Context::db_fetch(size_t t0, u64 *d_plain, int X) { hk::db_unpack(stream, N, nQ, d_plain, d_db, t0, X, db_lay); }
 
+// ciphertexts per pass of db_rekey: what the free device memory (and the pool's cache) holds of one ciphertext's gathered c1, key-switch
+// digits, accumulator, ModDown images and output; at most 256, at least 1
+int Context::rekey_chunk(size_t cts) {
+    const int nE = nQ + nP, nd = (nQ + alpha - 1) / alpha;
+    // c1 [nQ], ModUp's coefficient image [nQ], digits [nd][nE], accumulator [2][nE], [2][nP] + [2][nQ] ModDown images, output [2][nQ]
+    const double per_ct = (double)(nQ + nQ + nd * nE + 2 * nE + 2 * nP + 2 * nQ + 2 * nQ) * N * 8;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 1;
+    const double avail = 0.8 * ((double)free_b + (double)pool.bytes_cached);
+    return (int)std::max(1.0, std::min({(double)cts, 256.0, std::floor(avail / per_ct)}));
+}
+// Re-key the resident database in place: every ciphertext (c0, c1) := (c0 + ks0, ks1), (ks0, ks1) the hybrid key switch of c1 with the
+// caller's switching key (old secret -> this receiver's, client_keygen_switch) on all n_q limbs, no automorphism — Context::rotate
+// without its permutation, through the resident layouts.  The key lives in a temporary device buffer: the context's own evaluation
+// keys and rot_keys are neither read nor changed, so a context that borrows its keys (adopt_keys) or is a shard is served like any
+// other.  Every check precedes the first launch; a device error in mid-pass leaves some ciphertexts under the old key, some under the new.
+void Context::db_rekey(const u64 *host_key, int max_chunk) {
+    if (db_plain())
+        throw StateError("hydia: a plain gallery (kind " + std::to_string(db_kind) + ") is resident: nothing is encrypted, so there is nothing to re-key");
+    if (!d_db || db_cts == 0 || db_kind == 0) throw StateError("hydia: no database resident (kind 0): nothing to re-key");
+    if (db_kind != 4 && db_kind != 5 && db_kind != 6)
+        throw StateError("hydia: a database of kind " + std::to_string(db_kind) + " is resident: re-keying serves kinds 4, 5 and 6 (enrol kinds 1 and 3 again under the new key)");
+    if (!host_key) throw std::runtime_error("hydia: null switching key");
+    if (max_chunk < 0) throw std::runtime_error("hydia: the chunk is 0 (from free device memory) or a ciphertext count");
+    const int nl = nQ, nE = nl + nP, nd = (nl + alpha - 1) / alpha;
+    const size_t key_elems = (size_t)prm.dnum * 2 * nT * N;
+    sync_all();  // no query may read a half re-keyed database
+    struct Scratch {
+        u64 *key = nullptr;
+        const u64 **cell = nullptr;
+        ~Scratch() {
+            if (key) (void)hipFree(key);
+            if (cell) (void)hipFree((void *)cell);
+        }
+    } s;
+    HIP_CHECK(hipMalloc((void **)&s.key, key_elems * sizeof(u64)));
+    HIP_CHECK(hipMalloc((void **)&s.cell, sizeof(u64 *)));
+    HIP_CHECK(hipMemcpy(s.key, host_key, key_elems * sizeof(u64), hipMemcpyHostToDevice));
+    const u64 *self = s.key;
+    HIP_CHECK(hipMemcpy((void *)s.cell, &self, sizeof(u64 *), hipMemcpyHostToDevice));
+    int C = rekey_chunk(db_cts);
+    if (max_chunk > 0) C = std::min(C, max_chunk);
+    const size_t pe = (size_t)nl * N;
+    u64 *c1 = pool.get((size_t)C * pe * sizeof(u64)), *ks = pool.get((size_t)C * 2 * pe * sizeof(u64));
+    try {
+        for (size_t t0 = 0; t0 < db_cts; t0 += (size_t)C) {
+            const int X = (int)std::min((size_t)C, db_cts - t0);
+            timer_begin("db_rekey_gather");
+            hk::db_gather_poly(stream, N, nQ, c1, d_db, t0, X, db_lay);
+            timer_end("db_rekey_gather");
+            timer_begin("db_rekey_switch");
+            if (ks_fused_ok()) {
+                ks_fused(c1, pe, X, nl, s.key, s.cell, nullptr, nullptr, 0, 0, 0, nullptr, 0, false, ks);
+            } else {
+                u64 *dig = pool.get((size_t)X * nd * nE * N * sizeof(u64));
+                modup_digits(c1, pe, X, nl, dig);
+                ks_apply(dig, (size_t)nd * nE * N, X, nl, s.cell, 1, nullptr, 0, 0, 0, nullptr, nullptr, 0, false, ks);
+                pool.put(dig);
+            }
+            timer_end("db_rekey_switch");
+            timer_begin("db_rekey_store");
+            hk::db_rekey_store(stream, d_mod, N, nQ, ks, d_db, t0, X, db_lay);
+            timer_end("db_rekey_store");
+        }
+        sync_all();
+    } catch (...) {
+        (void)hipDeviceSynchronize();  // the temporary key must outlive whatever still reads it
+        pool.put(ks);
+        pool.put(c1);
+        throw;
+    }
+    pool.put(ks);
+    pool.put(c1);
+}
+
 // ------------------------------------------------------------------ kernel timers
 void Context::timer_begin(const char *name) {
     if (!timing) return;

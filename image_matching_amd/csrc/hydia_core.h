@@ -219,6 +219,12 @@ struct Context : HostParams {
     void db_store(size_t t0, const u64 *d_plain, int X);  // [X][2][nQ][N] device residues -> ciphertexts t0..t0+X-1 ([X][nQ][N] -> plaintexts of a plain gallery)
     void db_accumulate(size_t t0, const u64 *d_plain, int X);  // ciphertexts t0..t0+X-1 += [X][2][nQ][N] device residues, in place
     void db_fetch(size_t t0, u64 *d_plain, int X);
+    // kinds 4 / 5 / 6: every resident ciphertext key-switched in place with the caller's switching key (host memory, [dnum][2][nT][N]:
+    // client_keygen_switch) — (c0, c1) := (c0 + ks0, ks1); layout, form, kind, scale and order stay.  In chunks sized from free device
+    // memory (rekey_chunk, at most 256 ciphertexts; max_chunk > 0 caps it further — the tests' way to a ragged last chunk).  Timers
+    // "db_rekey_gather", "db_rekey_switch", "db_rekey_store"
+    void db_rekey(const u64 *host_key, int max_chunk = 0);
+    int rekey_chunk(size_t cts);
 
     std::map<std::string, KernelTimer> timers;
     bool timing = true;

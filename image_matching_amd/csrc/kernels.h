@@ -270,6 +270,10 @@ void db_pack(hipStream_t st, int N, int nQ, const u64 *plain, void *db, size_t t
 void db_unpack(hipStream_t st, int N, int nQ, u64 *plain, const void *db, size_t t0, int X, const DbLayout &L);
 // ciphertexts t0 .. t0+X-1 of the database += plain [X][2][nQ][N] residues mod q_j, in place (db_accum.h; mod = the context's table)
 void db_accumulate(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *plain, void *db, size_t t0, int X, const DbLayout &L);
+// re-keying (Context::db_rekey): polynomial 1 of ciphertexts t0 .. t0+X-1 -> out [X][nQ][N] residues (the key switch's operand), and the
+// key switch's output ks [X][2][nQ][N] back in place: (c0, c1) := (c0 + ks0 mod q_j, ks1)
+void db_gather_poly(hipStream_t st, int N, int nQ, u64 *out, const void *db, size_t t0, int X, const DbLayout &L);
+void db_rekey_store(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *ks, void *db, size_t t0, int X, const DbLayout &L);
 // blocks per wave / waves per workgroup loop B uses for G blocks (bpp, nw = the context's caps)
 void tensor_split(int G, int bpp, int nw, int *B, int *W);
 

@@ -1436,6 +1436,81 @@ __global__ __launch_bounds__(256) void k_db_accumulate46(const ModC *__restrict_
     db_accumulate_granule46(reinterpret_cast<unsigned *>(db + db_offset(L, N, t0 + x, p, j, c)), a, mod[j].q);
 }
 
+// Re-keying the resident database (Context::db_rekey): polynomial 1 ALONE of ciphertexts t0 .. t0+X-1 out of the resident layout into
+// out [X][nQ][N] u64 — the key switch's c1 operand — on k_db_repack<false>'s thread-to-bytes map; polynomial 0 is never unpacked (the
+// store below adds to it where it lies).  grid (N/512, nQ or 1, X)
+__global__ __launch_bounds__(256) void k_db_gather_poly(int N, int nQ, u64 *__restrict__ out, const unsigned char *__restrict__ db,
+                                                        DbLayout L, size_t t0) {
+    const int j = blockIdx.y, x = blockIdx.z;
+    const size_t c = (size_t)(blockIdx.x * 256 + threadIdx.x) * 2;
+    const unsigned char *d = db + db_offset(L, N, t0 + x, 1, j, c);
+    *reinterpret_cast<ulonglong2 *>(out + ((size_t)x * nQ + j) * N + c) = (L.packed && j > 0) ? db_load2<true, false>(d) : db_load2<false, false>(d);
+}
+// ... the 46-bit limbs of a bits46 layout on k_db_repack46<false>'s map (sixteen residues = 23 dwords per thread).
+// grid (N/4096, nQ - 1, X): limb j = blockIdx.y + 1
+__global__ __launch_bounds__(256) void k_db_gather_poly46(int N, int nQ, u64 *__restrict__ out, const unsigned char *__restrict__ db,
+                                                          DbLayout L, size_t t0) {
+    const int j = blockIdx.y + 1, x = blockIdx.z;
+    const size_t c = (size_t)(blockIdx.x * 256 + threadIdx.x) * 16;
+    if (c >= (size_t)N) return;
+    const unsigned *d = reinterpret_cast<const unsigned *>(db + db_offset(L, N, t0 + x, 1, j, c));
+    unsigned w[23];
+    u64 v[16];
+#pragma unroll
+    for (int k = 0; k < 23; k++) w[k] = d[k];
+    db_unpack_granule46(w, v);
+    u64 *o = out + ((size_t)x * nQ + j) * N + c;
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) *reinterpret_cast<ulonglong2 *>(o + r) = make_ulonglong2(v[r], v[r + 1]);
+}
+// The key switch's output ks [X][2][nQ][N] (canonical residues, no addend) back into ciphertexts t0 .. t0+X-1: (c0, c1) := (c0 + ks0, ks1).
+// Polynomial 0 is k_db_accumulate's fused read-add-reduce-write (the sum is reduced before it is packed), polynomial 1 an overwrite
+// on the same map: one thread owns every dword it touches, no atomics, no unpacked copy of c0 in HBM.  grid (N/512, nQ or 1, X*2)
+__global__ __launch_bounds__(256) void k_db_rekey_store(const ModC *__restrict__ mod, int N, int nQ, const u64 *__restrict__ ks,
+                                                        unsigned char *__restrict__ db, DbLayout L, size_t t0) {
+    const int j = blockIdx.y, xp = blockIdx.z, x = xp >> 1, p = xp & 1;
+    const size_t c = (size_t)(blockIdx.x * 256 + threadIdx.x) * 2;
+    const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(ks + ((size_t)xp * nQ + j) * N + c);
+    unsigned char *d = db + db_offset(L, N, t0 + x, p, j, c);
+    const bool pk = L.packed && j > 0;
+    if (p == 0) {
+        db_accumulate_pair(d, pk, a.x, a.y, mod[j].q);
+    } else if (pk) {
+        unsigned w[3];
+        db_pack_pair48(a.x, a.y, w);
+        unsigned *o = reinterpret_cast<unsigned *>(d);
+        o[0] = w[0];
+        o[1] = w[1];
+        o[2] = w[2];
+    } else {
+        *reinterpret_cast<ulonglong2 *>(d) = a;
+    }
+}
+// ... the 46-bit limbs of a bits46 layout on k_db_repack46's map.  grid (N/4096, nQ - 1, X*2): limb j = blockIdx.y + 1
+__global__ __launch_bounds__(256) void k_db_rekey_store46(const ModC *__restrict__ mod, int N, int nQ, const u64 *__restrict__ ks,
+                                                          unsigned char *__restrict__ db, DbLayout L, size_t t0) {
+    const int j = blockIdx.y + 1, xp = blockIdx.z, x = xp >> 1, p = xp & 1;
+    const size_t c = (size_t)(blockIdx.x * 256 + threadIdx.x) * 16;
+    if (c >= (size_t)N) return;
+    const u64 *pl = ks + ((size_t)xp * nQ + j) * N + c;
+    u64 a[16];
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+        const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(pl + r);
+        a[r] = v.x;
+        a[r + 1] = v.y;
+    }
+    unsigned *d = reinterpret_cast<unsigned *>(db + db_offset(L, N, t0 + x, p, j, c));
+    if (p == 0) {
+        db_accumulate_granule46(d, a, mod[j].q);
+    } else {
+        unsigned w[23];
+        db_pack_granule46(a, w);
+#pragma unroll
+        for (int k = 0; k < 23; k++) d[k] = w[k];
+    }
+}
+
 __global__ __launch_bounds__(256) void k_fill_uniform_hash(const ModC *__restrict__ mod, int N, u64 *__restrict__ dst,
                                                            int nl, u64 seed) {
     const size_t lp = blockIdx.y + (size_t)blockIdx.z * gridDim.y;
@@ -1876,6 +1951,22 @@ void db_accumulate(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *pl
     hipLaunchKernelGGL(k_db_accumulate, dim3(N / 512, b46 ? 1 : nQ, X * 2), dim3(256), 0, st, mod, N, nQ, plain, (unsigned char *)db, L, t0);
     if (b46)
         hipLaunchKernelGGL(k_db_accumulate46, dim3((N / 16 + 255) / 256, nQ - 1, X * 2), dim3(256), 0, st, mod, N, nQ, plain, (unsigned char *)db, L, t0);
+}
+// polynomial 1 of ciphertexts t0 .. t0+X-1 -> out [X][nQ][N] residues: the launch shapes of db_unpack, one polynomial per ciphertext
+void db_gather_poly(hipStream_t st, int N, int nQ, u64 *out, const void *db, size_t t0, int X, const DbLayout &L) {
+    const bool b46 = L.bits46 && L.seq && L.packed && nQ > 1;
+    ledger_add("k_db_gather_poly", (double)X * (1.0 * L.poly_bytes + 1.0 * nQ * N * 8));  // one resident polynomial read, its residues written
+    hipLaunchKernelGGL(k_db_gather_poly, dim3(N / 512, b46 ? 1 : nQ, X), dim3(256), 0, st, N, nQ, out, (const unsigned char *)db, L, t0);
+    if (b46)
+        hipLaunchKernelGGL(k_db_gather_poly46, dim3((N / 16 + 255) / 256, nQ - 1, X), dim3(256), 0, st, N, nQ, out, (const unsigned char *)db, L, t0);
+}
+// ciphertexts t0 .. t0+X-1 := (c0 + ks0, ks1), ks [X][2][nQ][N] residues (mod q_j): the launch shapes of db_accumulate
+void db_rekey_store(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *ks, void *db, size_t t0, int X, const DbLayout &L) {
+    const bool b46 = L.bits46 && L.seq && L.packed && nQ > 1;
+    ledger_add("k_db_rekey_store", (double)X * (1.5 * L.ct_bytes + 2.0 * nQ * N * 8));  // c0 read and written, c1 written + the key switch's output read
+    hipLaunchKernelGGL(k_db_rekey_store, dim3(N / 512, b46 ? 1 : nQ, X * 2), dim3(256), 0, st, mod, N, nQ, ks, (unsigned char *)db, L, t0);
+    if (b46)
+        hipLaunchKernelGGL(k_db_rekey_store46, dim3((N / 16 + 255) / 256, nQ - 1, X * 2), dim3(256), 0, st, mod, N, nQ, ks, (unsigned char *)db, L, t0);
 }
 // grid (N/512, nl, XP): two coefficients per thread, the plaintext's residues and Shoup companions read beside the operand's
 __global__ __launch_bounds__(256) void k_mul_plain(const ModC *__restrict__ mod, int N, const u64 *__restrict__ a, int a_ls,

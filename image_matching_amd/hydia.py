@@ -129,6 +129,10 @@ def load_library():
         "hydia_db_enroll_shard": (i32, [vp, vp, sz, vp, sz]),
         "hydia_db_update": (i32, [vp, sz, vp, sz, i32, vp]),
         "hydia_db_update_shard": (i32, [vp, sz, vp, sz, i32, vp, sz]),
+        "hydia_keygen_switch": (i32, [vp, vp, vp, vp]),
+        "hydia_db_rekey": (i32, [vp, vp]),
+        "hydia_db_rekey_chunked": (i32, [vp, vp, i32]),
+        "hydia_switch_key_words": (sz, [vp]),
         "hydia_db_enroll_shard_ex": (i32, [vp, vp, sz, vp, sz, i32]),
         "hydia_set_matvec": (i32, [vp, i32]),
         "hydia_get_matvec": (i32, [vp]),
@@ -443,6 +447,18 @@ class Context:
         _chk(self.L.hydia_export_secret_key(self.h, _p(out)))
         return out
 
+    def keygen_switch(self, old_secret, seed=None):
+        """hydia_keygen_switch, on the NEW receiver's context: the switching key [dnum][2][n_q+n_p][N] from `old_secret` (the old
+        receiver's export_secret_key()) to this context's secret — what Context.db_rekey on the sender takes.  Treat it like an
+        evaluation key; seed=None draws a fresh one from the OS (use a fresh seed per switching key: include/hydia.h)."""
+        if old_secret is not None:
+            old_secret = np.ascontiguousarray(old_secret, dtype=np.uint64)
+            assert old_secret.size == self.nT * self.N
+        out = np.zeros((self.dnum, 2, self.nT, self.N), dtype=np.uint64)
+        assert out.size == self.L.hydia_switch_key_words(self.h)
+        _chk(self.L.hydia_keygen_switch(self.h, None if old_secret is None else _p(old_secret), _p(_seed(seed)), _p(out)))
+        return out
+
     def fill_eval_keys_random(self, seed=1):
         _chk(self.L.hydia_fill_eval_keys_random(self.h, seed))
 
@@ -649,6 +665,15 @@ class Context:
         assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.ndim == 2 and rows.shape[1] == self.dim
         _chk(self.L.hydia_db_update_shard(self.h, first_vector, _p(rows), rows.shape[0], 1 if normalise else 0, _p(_seed(seed)), first_block))
 
+    def db_rekey(self, key, chunk=0):
+        """hydia_db_rekey: key-switch every ciphertext of the resident kind-4 / 5 / 6 database in place with `key` (keygen_switch of
+        the NEW receiver's context).  Layout, form, kind and order stay; afterwards import the new receiver's evaluation and public
+        keys, and encrypt later updates under the new public key.  chunk > 0 (tests only) caps the ciphertexts per pass."""
+        if key is not None:
+            key = np.ascontiguousarray(key, dtype=np.uint64)
+            assert key.size == self.dnum * 2 * self.nT * self.N
+        _chk(self.L.hydia_db_rekey_chunked(self.h, None if key is None else _p(key), int(chunk)))
+
     def db_fill_random(self, n, seed=1):
         _chk(self.L.hydia_db_fill_random(self.h, n, seed))
 
@@ -753,6 +778,13 @@ class DiagonalEnroller:
         """append `rows` (normalised in place) after the last enrolled vector"""
         self.updateRows(self.numVectors, rows, True, seed)
 
+    def rekeyDB(self, key):
+        """Re-key the enrolled database in place (Context.db_rekey) with the switching key DiagonalReceiver.genSwitchKey of the NEW
+        receiver made.  A sharded database is re-keyed shard by shard (db_rekey on every shard context, same key)."""
+        if not isinstance(self.cc, Context):
+            raise HydiaError(-2, "hydia: a sharded database is re-keyed shard by shard (Context.db_rekey on every shard context)")
+        self.cc.db_rekey(key)
+
 
 class PlainEnroller:
     """A gallery the sender may see (database kinds 7 / 8; no counterpart in the reference): DiagonalEnroller's constructor shape,
@@ -781,6 +813,11 @@ class DiagonalReceiver:
         query = np.ascontiguousarray(query, dtype=np.float64)
         assert query.shape == (self.cc.dim,)
         return self.cc._out(self.cc.L.hydia_encrypt_query, _p(query), _p(_seed(seed)), nonce)
+
+    def genSwitchKey(self, old_secret, seed=None):
+        """the switching key from the OLD receiver's secret (its Context.export_secret_key()) to this receiver's
+        (Context.keygen_switch): hand it to the enroller / sender for DiagonalEnroller.rekeyDB"""
+        return self.cc.keygen_switch(old_secret, seed)
 
     def decryptMembership(self, membership_cipher):
         r = C.c_int()

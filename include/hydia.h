@@ -191,6 +191,42 @@ int hydia_db_enroll_shard(hydia_ctx *ctx, double *db, size_t n, const uint8_t se
  * (first_vector counts within the shard); it is what a multi-GPU wrapper would call on the rank that owns the rows. */
 int hydia_db_update(hydia_ctx *ctx, size_t first_vector, double *rows /* n x vector_dim row-major */, size_t n, int normalise, const uint8_t seed[32]);
 int hydia_db_update_shard(hydia_ctx *ctx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32], size_t first_block);
+/* ---- re-keying a resident database in place under a NEW receiver key (kinds 4, 5 and 6; no counterpart in the reference, which
+ * re-enrols from the plaintext templates).  The receiver's key expires, is suspected lost or passes to another custodian: the NEW
+ * receiver makes one switching key from the old secret to its own, and the sender key-switches every resident ciphertext with it.
+ *   hydia_keygen_switch   on the NEW receiver's context (it needs that context's secret; without one: HYDIA_ERR_STATE).  old_secret is
+ *                         the OLD receiver's secret [n_q+n_p][N] in evaluation form, as hydia_export_secret_key gives it.  key_out
+ *                         [dnum][2][n_q+n_p][N] (hydia_switch_key_words() words), evaluation form, laid out as hydia_export_eval_key
+ *                         lays keys out: digit d holds (b_d, a_d) = (-a_d s_new + e_d + P [limb in digit d] s_old, a_d) — exactly the
+ *                         key of a rotation without its automorphism.  Its sampler streams are the evaluation keys' with the reserved
+ *                         key id HY_EVK_ID_SWITCH (rotation ids are below slots <= 2^15, relinearisation is 0, the field is 40 bits
+ *                         wide: nothing collides).  The context's own keys are not changed.
+ *   hydia_db_rekey        on the SENDER's context: every resident ciphertext (c0, c1), on all n_q limbs, becomes (c0 + ks0, ks1) with
+ *                         (ks0, ks1) the hybrid key switch of c1 under switch_key (ModUp per digit, inner product, ModDown; no
+ *                         automorphism).  Scale, limb count, ciphertext order, layout (hydia_db_group, hydia_db_residue_bits), kind
+ *                         and form (hydia_db_babies) all stay; the stored residues are canonical.  The key is uploaded to a
+ *                         temporary buffer and released at the end: the context's own evaluation keys are neither read nor changed,
+ *                         so a context that shares another's keys, or one shard of a group (hydia_group_ctx: call it on every
+ *                         shard with the same key), is served like any other.  The database is walked in chunks of at most 256
+ *                         ciphertexts, sized from free device memory.
+ * TRUST MODEL: the sender learns neither secret.  The switching key is a proxy re-encryption key from the old key to the new one:
+ * whoever holds it can turn ANY ciphertext under the old key into one under the new key, so treat it like an evaluation key (the new
+ * receiver makes it, the sender uses it and may discard it afterwards).  Making it needs BOTH secrets in one place for the duration of
+ * hydia_keygen_switch — the hand-over between custodians.  Use a FRESH seed (hydia_random_seed) for every switching key.
+ * NOISE: every re-key adds one key switch's noise (that of one rotation, far below the scale) to every ciphertext.
+ * AFTERWARDS the caller imports the NEW receiver's relinearisation / rotation keys (hydia_import_eval_key) and public key into the
+ * sender, queries are encrypted under the new public key, and every later hydia_db_update encrypts under the NEW public key — a
+ * re-keyed database no longer opens under the old secret.
+ * Errors, all BEFORE any work is enqueued and with the database untouched: no database, kinds 1 and 3, and a plain gallery (kinds 7 /
+ * 8: nothing is encrypted) answer HYDIA_ERR_STATE with a message naming the kind; a null key HYDIA_ERR_ARG.  A device error in
+ * mid-pass (HYDIA_ERR_DEVICE) leaves a MIXED database — the chunks already stored are under the new key, the rest under the old one;
+ * there is no way to tell them apart afterwards: enrol again, or restore a saved file (hydia_db_load) and re-key that. */
+#define HY_EVK_ID_SWITCH (1ull << 24)
+int hydia_keygen_switch(hydia_ctx *ctx, const uint64_t *old_secret /* [n_q+n_p][N] */, const uint8_t seed[32], uint64_t *key_out);
+int hydia_db_rekey(hydia_ctx *ctx, const uint64_t *switch_key /* [dnum][2][n_q+n_p][N] */);
+size_t hydia_switch_key_words(const hydia_ctx *ctx);
+/* hydia_db_rekey with the chunk capped at max_chunk ciphertexts (0 = no cap): for tests of the chunk boundaries; same result */
+int hydia_db_rekey_chunked(hydia_ctx *ctx, const uint64_t *switch_key, int max_chunk);
 /* ---- the split of the diagonalised mat-vec.  With rotation i = b + B g: B - 1 hoisted ("baby") rotations of the
  * query per QUERY, vector_dim / B relinearised partial sums per BLOCK of which all but the first are rotated by B g ("giant" steps,
  * ordinary key switches with the rotation keys B, 2B, .. that src/main.cpp:195-206 already generates).  The enroller rotates

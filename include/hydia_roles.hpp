@@ -418,6 +418,23 @@ class DiagonalReceiver : public HersReceiver {
         if (!cc->check(hydia_encrypt_query(cc->h, query.data(), seed, ++nonce, &out), "encryptQuery")) return {};
         return split_batch(cc, out);
     }
+    // The switching key of a re-keyed database (hydia_keygen_switch; no counterpart in the reference): from the OLD receiver's secret
+    // (oldSecret, [n_q+n_p][N] as hydia_export_secret_key gives it) to THIS receiver's, for DiagonalEnroller::rekeyDB.  Treat it like an
+    // evaluation key.  seed32 == nullptr draws a fresh sampler key from the OS (use a fresh one per switching key).  Empty on failure.
+    std::vector<uint64_t> genSwitchKey(const std::vector<uint64_t> &oldSecret, const uint8_t *seed32 = nullptr) {
+        const size_t sk_words = (size_t)(cc->info.n_q + cc->info.n_p) * cc->info.n;
+        if (cc->group || oldSecret.size() != sk_words) {
+            cc->last_status = cc->group ? HYDIA_ERR_STATE : HYDIA_ERR_ARG;
+            std::cerr << "Error: genSwitchKey: " << (cc->group ? "a switching key is generated on the receiver's own context" : "the old secret holds (n_q + n_p) N words")
+                      << std::endl;
+            return {};
+        }
+        uint8_t s[32];
+        role_seed(s, seed32);
+        std::vector<uint64_t> key(hydia_switch_key_words(cc->h));
+        if (!cc->check(hydia_keygen_switch(cc->h, oldSecret.data(), s, key.data()), "genSwitchKey")) return {};
+        return key;
+    }
 };
 
 // ---- enrollers.  Randomness: without a caller-supplied seed EVERY serializeDB call draws a fresh sampler key from the OS (the
@@ -501,6 +518,22 @@ class DiagonalEnroller : public EnrollerBase {
         return true;
     }
     bool appendDB(std::vector<std::vector<double>> &rows, const uint8_t *seed32 = nullptr) { return updateRows(numVectors, rows, true, seed32); }
+    // Re-key the enrolled database in place under a new receiver key (hydia_db_rekey; no counterpart in the reference, which re-enrols):
+    // every resident ciphertext is key-switched with `key`, the NEW receiver's DiagonalReceiver::genSwitchKey.  Afterwards the caller
+    // imports the new receiver's evaluation and public keys; later updateRows / appendDB calls encrypt under the new public key.
+    bool rekeyDB(const std::vector<uint64_t> &key) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: rekeyDB: a sharded database is re-keyed shard by shard (hydia_db_rekey on every hydia_group_ctx)" << std::endl;
+            return false;
+        }
+        if (key.size() != hydia_switch_key_words(cc->h)) {
+            cc->last_status = HYDIA_ERR_ARG;
+            std::cerr << "Error: rekeyDB: the switching key holds dnum * 2 * (n_q + n_p) * N words" << std::endl;
+            return false;
+        }
+        return cc->check(hydia_db_rekey(cc->h, key.data()), "rekeyDB");
+    }
     size_t size() const { return numVectors; }
 };
 
