@@ -991,6 +991,41 @@ int hydia_index_scenario_multi(hydia_ctx *ctx, const hydia_ct *const *queries, u
 int hydia_membership_scenario_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out) {
     return scenario_multi_call(ctx, queries, n_queries, out, 2);
 }
+// a batch of plain queries: the output convention of scenario_multi_call
+static int scenario_pq_multi_call(hydia_ctx *ctx, const hydia_pt *const *queries, uint32_t n_queries, hydia_ct **out, int what) {
+    if (out)
+        for (uint32_t q = 0; q < n_queries; q++) out[q] = nullptr;
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && queries && out, "null argument");
+    REQUIRE(n_queries >= 1, "a batch of plain queries needs at least one query");
+    std::vector<const Ct *> qs(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) {
+        REQUIRE(queries[q], "null query in the batch");
+        qs[q] = &queries[q]->c;
+    }
+    std::vector<Ct> r = ctx->cx.scenario_pq_multi(qs, what);
+    for (uint32_t q = 0; q < n_queries; q++) out[q] = wrap(ctx, std::move(r[q]));  // compact and owning: no copy, cannot fail
+    return HYDIA_OK;
+    API_END
+}
+int hydia_compute_similarity_pq_multi(hydia_ctx *ctx, const hydia_pt *const *queries, uint32_t n_queries, hydia_ct **out) {
+    return scenario_pq_multi_call(ctx, queries, n_queries, out, 0);
+}
+int hydia_index_scenario_pq_multi(hydia_ctx *ctx, const hydia_pt *const *queries, uint32_t n_queries, hydia_ct **out) {
+    return scenario_pq_multi_call(ctx, queries, n_queries, out, 1);
+}
+int hydia_membership_scenario_pq_multi(hydia_ctx *ctx, const hydia_pt *const *queries, uint32_t n_queries, hydia_ct **out) {
+    return scenario_pq_multi_call(ctx, queries, n_queries, out, 2);
+}
+int hydia_set_pq_batch_width(hydia_ctx *ctx, uint32_t width) {
+    API_BEGIN
+    REQUIRE(ctx, "null argument");
+    REQUIRE(width == 0 || width == 1 || width == 2 || width == 4, "a plain-query batch serves 1, 2 or 4 queries per pass (0 = the default)");
+    ctx->cx.pq_mq_width = (int)width;
+    return HYDIA_OK;
+    API_END
+}
 int hydia_chebyshev_compare(hydia_ctx *ctx, const hydia_ct *query, double delta, size_t sign_depth, hydia_ct **out) {
     SENDER_CALL(ctx->cx.chebyshev_compare(query->c, delta, (int)sign_depth))
 }

@@ -1667,10 +1667,11 @@ void Context::check_multi(const std::vector<const Ct *> &qs) const {
 // temporaries (48 full-level ciphertexts per block: at 2^20 vectors a batch of 8 with 24 per block ran out of HBM inside the comparator
 // and the allocator's trim-and-retry made it 7x slower than 8 single calls), never fewer than one — a batch of one needs what a
 // single-query call needs
-int Context::multi_batch(int Q) {
+int Context::multi_batch(int Q, bool plain_queries) {
     const int dim = prm.dim, R = db_kind == 6 ? db_babies : dim, NG = db_kind == 6 ? dim / db_babies : 1, G = (int)(db_cts / dim);
     const double lp = (double)nQ * N * 8;
-    const double per_query = (double)R * 2 * lp + (double)G * NG * 3 * lp + (double)G * 48 * 2 * lp;
+    // a plain query's rotations are one polynomial each and its accumulators have two components; the comparator's share is the same
+    const double per_query = (double)R * (plain_queries ? 1 : 2) * lp + (double)G * NG * (plain_queries ? 2 : 3) * lp + (double)G * 48 * 2 * lp;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 1;
     const double avail = 0.85 * ((double)free_b + (double)pool.bytes_cached);
@@ -1708,37 +1709,84 @@ Ct Context::batch_slice(const Ct &b, int q, int per) {
 // 0 similarity, 1 index scenario, 2 membership scenario
 std::vector<Ct> Context::scenario_multi(const std::vector<const Ct *> &qs, int what) {
     check_multi(qs);
-    const int Q = (int)qs.size(), G = (int)(db_cts / prm.dim);
+    const int Q = (int)qs.size();
     std::vector<Ct> res;
     res.reserve(Q);
     for (int q0 = 0; q0 < Q;) {
         const int Qb = multi_batch(Q - q0);
         Ct acc = loop_b_multi(qs, q0, Qb);  // [Qb G]: 3 components (hoisted) : 2 (BSGS, relinearised)
-        Ct r;
-        if (what == 0) {
-            if (acc.npoly == 3) relin_rescale(acc);
-            else rescale(acc);
-            r = std::move(acc);
-        } else {
-            r = relin_compare_lanes(acc, 0.44 /* MATCH_THRESHOLD */, 10 /* COMP_DEPTH */);
-            acc = Ct();
+        tails_multi(acc, Qb, what, res);
+        q0 += Qb;
+    }
+    return res;
+}
+// the tails of a batch's accumulators [Qb G] (query-major; 3 components, or 2: BSGS sums, a plain query's), run once on the whole batch;
+// the Qb results are appended to res
+void Context::tails_multi(Ct &acc, int Qb, int what, std::vector<Ct> &res) {
+    const int G = (int)(db_cts / prm.dim);
+    Ct r;
+    if (what == 0) {
+        if (acc.npoly == 3) relin_rescale(acc);
+        else rescale(acc);
+        r = std::move(acc);
+    } else {
+        r = relin_compare_lanes(acc, 0.44 /* MATCH_THRESHOLD */, 10 /* COMP_DEPTH */);
+        acc = Ct();
+    }
+    if (what == 2) {  // EvalAddMany per query (segmented over the batch), then ONE EvalSum over the Qb sums
+        Ct m;
+        for (int q = 0; q < Qb; q++) {
+            Ct v = r.alias(r.nl);
+            v.X = G;
+            v.d = r.d + (size_t)q * G * r.ct_elems();
+            Ct s = add_many(v);
+            if (q == 0) m = Ct(this, Qb, s.npoly, s.nl, s.scale);
+            hk::copy_limbs(stream, N, s.d, m.d + (size_t)q * m.ct_elems(), s.poly_elems(), m.poly_elems(), s.npoly, s.nl);
         }
-        if (what == 2) {  // EvalAddMany per query (segmented over the batch), then ONE EvalSum over the Qb sums
-            Ct m;
-            for (int q = 0; q < Qb; q++) {
-                Ct v = r.alias(r.nl);
-                v.X = G;
-                v.d = r.d + (size_t)q * G * r.ct_elems();
-                Ct s = add_many(v);
-                if (q == 0) m = Ct(this, Qb, s.npoly, s.nl, s.scale);
-                hk::copy_limbs(stream, N, s.d, m.d + (size_t)q * m.ct_elems(), s.poly_elems(), m.poly_elems(), s.npoly, s.nl);
+        r = Ct();
+        eval_sum_inplace(m);
+        for (int q = 0; q < Qb; q++) res.push_back(batch_slice(m, q, 1));
+    } else {
+        for (int q = 0; q < Qb; q++) res.push_back(batch_slice(r, q, G));
+    }
+}
+// ------------------------------------------------------------------ a batch of PLAIN queries in one pass over the database: per query
+// one k_automorph_batch launch into one [Qb][R][nQ][N] buffer, ONE batched loop B (ceil(Qb / width) passes), for kind 6 the giant steps
+// on the 2-component [NG][Qb G] accumulators, then the batch's tails.  Every refusal is the single call's, made for every query before
+// anything is enqueued
+std::vector<Ct> Context::scenario_pq_multi(const std::vector<const Ct *> &pts, int what) {
+    if (pts.empty()) throw std::runtime_error("hydia: a batch of plain queries needs at least one query");
+    for (const Ct *pt : pts) {
+        if (!pt) throw std::runtime_error("hydia: null query in the batch");
+        pq_check(*pt, what);
+        if (pt->scale != pts[0]->scale) throw std::runtime_error("hydia: every plain query of a batch must carry the same scale");
+    }
+    const int Q = (int)pts.size(), dim = prm.dim, nl = nQ, G = (int)(db_cts / dim);
+    const int R = db_kind == 6 ? db_babies : dim, NG = dim / R;
+    std::vector<Ct> res;
+    res.reserve(Q);
+    for (int q0 = 0; q0 < Q;) {
+        const int Qb = multi_batch(Q - q0, true);
+        if (db_kind == 6) build_giants(Qb * G);  // one table entry per (giant step, query, block)
+        Ct acc(this, Qb * G * NG, 2, nl, pts[q0]->scale * delta);
+        {
+            const unsigned *gal = pq_galois_table(R);
+            Ct rot(this, Qb * R, 1, nl, pts[q0]->scale);
+            const size_t rqs = (size_t)R * rot.ct_elems();
+            for (int q = 0; q < Qb; q++) hk::automorph_batch(stream, prm.logN, pts[q0 + q]->d, rot.d + (size_t)q * rqs, nl, R, gal);
+            const int w = pq_mq_width > 0 ? pq_mq_width : hk::hydia_pq_mq_width(db_lay);
+            int passes = 0;
+            for (int left = Qb, qw = w; left > 0; passes++) {  // the launcher's schedule: the widest width that still fits what is left
+                while (qw > left) qw >>= 1;
+                left -= qw;
             }
-            r = Ct();
-            eval_sum_inplace(m);
-            for (int q = 0; q < Qb; q++) res.push_back(batch_slice(m, q, 1));
-        } else {
-            for (int q = 0; q < Qb; q++) res.push_back(batch_slice(r, q, G));
+            op_bytes("op:loop_b_pq_multi", N, 0, (double)passes * db_cts * (double)db_lay.ct_bytes + ((double)Qb * R + (double)Qb * G * NG * 2) * nl * N * 8);
+            timer_begin("hydia_pq_multi");
+            hk::hydia_pq_accumulate_multi(stream, d_mod, N, rot.d, rqs, d_db, acc.d, Qb, G * NG, R, nl, db_lay, db_kind == 6 ? NG : 0, w);
+            timer_end("hydia_pq_multi");
         }
+        if (db_kind == 6) acc = giant_step_sum(acc, NG);  // slot (giant g, query q, block) = (g Qb + q) G + block
+        tails_multi(acc, Qb, what, res);
         q0 += Qb;
     }
     return res;

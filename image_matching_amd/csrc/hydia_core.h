@@ -450,7 +450,8 @@ struct Context : HostParams {
     // does not hold it (multi_batch); the split changes no result
     std::vector<Ct> scenario_multi(const std::vector<const Ct *> &qs, int what);
     void check_multi(const std::vector<const Ct *> &qs) const;  // runtime_error: a query is not fresh; StateError: no diagonal database
-    int multi_batch(int Q);
+    int multi_batch(int Q, bool plain_queries = false);  // queries one batch takes, from free HBM and the form's per-query bytes
+    void tails_multi(Ct &acc, int Qb, int what, std::vector<Ct> &res);  // the tails of [Qb G] accumulators, shared by both batch kinds
     Ct loop_b_multi(const std::vector<const Ct *> &qs, int q0, int Qb);
     // ---- a PLAIN QUERY (an extension; evaluator.cpp): the sender knows the probe, the database (kinds 5 / 6) stays encrypted.  pt is
     // ONE encoded polynomial [1][1][nQ][N] (canonical residues, evaluation form).  Bit for bit the encrypted-query path on the trivial
@@ -464,6 +465,10 @@ struct Context : HostParams {
     Ct similarity_pq(const Ct &pt);
     Ct index_scenario_pq(const Ct &pt);
     Ct membership_scenario_pq(const Ct &pt);
+    // a batch of plain queries in one pass over the database: one result per query, each exactly what the single call returns.  Every
+    // query passes pq_check and all carry one scale (runtime_error otherwise) before anything is enqueued
+    std::vector<Ct> scenario_pq_multi(const std::vector<const Ct *> &pts, int what);
+    int pq_mq_width = 0;  // queries per pass of a plain-query batch (1, 2, 4); 0 = hk::hydia_pq_mq_width, the measured choice
     Ct giant_step_sum(Ct &acc, int NG);  // BSGS giant steps on [NG X0] giant-major accumulators -> [X0][2][nQ][N] (relinearises a 3-component acc)
     Ct batch_slice(const Ct &b, int q, int per);
     // ---- HERS sender (approach 4, src/sender/sender_hers.cpp): q = dim query ciphertexts

@@ -428,6 +428,13 @@ constexpr int PLAIN_BPP = 2;  // blocks per wave of a plain gallery's loop B (DE
 // acc[slot][p] = sum_i rot[i] * db[g][i].c_p mod q_j — no third component, nothing to relinearise.  bpp, nw: split caps (tensor_split)
 void hydia_pq_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, const void *db, u64 *acc, int G, int dim, int nl,
                          const DbLayout &L, int ng, int bpp, int nw);
+// The same for a BATCH of Q plain queries whose rotation sets [dim][nl][N] lie rqs elements apart: ceil over hydia_pq_mq_width passes
+// over the database (what is left over takes the narrower widths, a last odd query one of its own), one block per wave; acc
+// [Q G][2][nl][N] with the batch slot map of hydia_tensor_accumulate.  Every accumulator equals hydia_pq_accumulate's for that query,
+// bit for bit.  width: queries per pass (1, 2 or 4); 0 = hydia_pq_mq_width(L), the measured choice
+void hydia_pq_accumulate_multi(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G,
+                               int dim, int nl, const DbLayout &L, int ng, int width = 0);
+int hydia_pq_mq_width(const DbLayout &L);  // queries one pass serves for this form
 // out[i][j][c] = m[j][perm_{galois[i]}(c)], i < R, in one launch (m [nl][N], out [R][nl][N]; galois: device [R], 1 = identity)
 void automorph_batch(hipStream_t st, int logN, const u64 *m, u64 *out, int nl, int R, const unsigned *galois);
 

@@ -10,6 +10,7 @@
 //   k_hydia_plain         the same sums against a PLAIN gallery (one encoded polynomial per diagonal; no counterpart in the reference)
 //   k_hydia_pq            the same sums for a PLAIN query against the encrypted database (one encoded polynomial per rotation; no
 //                         counterpart in the reference), k_automorph_batch: the rotations of that plaintext
+//   k_hydia_pq_mq         the same for a BATCH of plain queries: QW probes per pass over the database
 //   k_rescale_*           RescaleInPlace (sender_diag.cpp:80)
 //   k_tensor, k_lincomb*  ct x ct products and Chebyshev/f4 leaves of chebyshevCompare (src/openFHE_wrapper.cpp:143-185)
 //   k_batch_sum           HERS: sum of the per-dimension products (src/sender/sender_hers.cpp:60-87)
@@ -850,7 +851,8 @@ DEV void store_karatsuba(u64 *o, size_t ps, ulonglong2 r0, ulonglong2 rk, ulongl
 struct FormCtCt {
     static constexpr int qp = 2, dp = 2, sums = 3, comps = 3;  // sums: d0, d2, dk
     static constexpr const char *name = "tensor";
-    static constexpr bool batch = true;
+    static constexpr bool batch = true, bpp_arg = true;  // bpp_arg: the streaming kernel's template list names BPP
+    static constexpr int max_qw = 2;                     // widest QW instantiated
     template <class A>
     DEV static void mac(typename A::Sum (&s)[3][2], const typename A::T (&a)[2][2], const typename A::T (&b)[2][2]) {
         kara_mac<A>(s, a, b);
@@ -868,7 +870,8 @@ struct FormCtCt {
 //   path stays exercised on 59/60-bit limbs (every 128 / 32 diagonals).
 struct FormPlain {
     static constexpr int sums = 2, comps = 2;
-    static constexpr bool batch = false;
+    static constexpr bool batch = false, bpp_arg = true;
+    static constexpr int max_qw = 1;
     DEV static void store(u64 *o, size_t ps, const ulonglong2 (&r)[2], u64) {
         *reinterpret_cast<ulonglong2 *>(o) = r[0];
         *reinterpret_cast<ulonglong2 *>(o + ps) = r[1];
@@ -902,8 +905,19 @@ struct FormPlainCt : FormPlain {
     }
 };
 
-// The streaming kernels.  k_hydia_tensor, k_hydia_plain and k_hydia_pq hold the SAME pipeline (tile map, db_walk, rotating operand
-// sets with the clamped re-fetch, one s_barrier per diagonal, fold, reduction, mq_slot store): a change to it is made in all three.
+// A BATCH of plain queries (k_hydia_pq_mq, k_hydia_pq_mq_sk): the same products for QW probes per pass, every probe with its own rotation
+// set (rqs elements apart) and its OWN sums, so the bounds stated at FormPlain are unchanged — a sum still takes one product of two
+// canonical residues per diagonal, whatever the number of queries beside it.  The batch has a tag of its own so that FormPlainCt (batch =
+// false) and with it k_hydia_pq / k_hydia_pq_sk, their names and their code stay what they are; its streaming kernel serves one block
+// per wave and has no BPP in its template list (bpp_arg)
+struct FormPlainCtMq : FormPlainCt {
+    static constexpr const char *name = "pq_mq";
+    static constexpr bool batch = true, bpp_arg = false;
+    static constexpr int max_qw = 4;
+};
+
+// The streaming kernels.  k_hydia_tensor, k_hydia_plain, k_hydia_pq and k_hydia_pq_mq hold the SAME pipeline (tile map, db_walk, rotating operand
+// sets with the clamped re-fetch, one s_barrier per diagonal, fold, reduction, mq_slot store): a change to it is made in all four.
 // It is written out in each entry point on purpose.  Called as one device function the pipeline is optimised twice, alone and again
 // after inlining, and the second pass orders the multiply-accumulates differently: k_hydia_tensor<Halves24<true>, 1, 2, *> took 186 /
 // 188 VGPRs instead of 164 (2 waves per SIMD instead of 3), k_hydia_pq<Halves24<true>, 2, *> 151 instead of 120 (3 instead of 4),
@@ -1329,6 +1343,119 @@ __global__ __launch_bounds__(64 * NW, 2) void k_hydia_pq(const ModC *__restrict_
             *reinterpret_cast<ulonglong2 *>(o + p * ps) = make_ulonglong2(A::reduce(s[u][p][0], M), A::reduce(s[u][p][1], M));
     }
 }
+// ------------------------------------------------------------------------------------------------ loop B for a batch of plain queries
+// k_hydia_pq's pipeline with a query dimension added the way k_hydia_tensor has one, at ONE block per wave: rot holds the queries'
+// rotation sets [R][nl][N], rqs elements apart, from query q0 on.  A database operand is loaded and cut once per diagonal and shared by
+// the QW queries; each query's operand is loaded once.  Every query has its own two sums, so the bounds are FormPlain's, unchanged.
+// The store goes through mq_slot into [slot][2][nl][N] (Qt = queries of the whole batch).  QW = 4 on eight-wave workgroups asks for one
+// workgroup per CU: at two the 128 registers a lane may then hold do not take four queries' sums
+template <class A, int QW, int NW>
+__global__ __launch_bounds__(64 * NW, (QW >= 4 && NW >= 8) ? 1 : 2) void k_hydia_pq_mq(
+    const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs, const unsigned char *__restrict__ db, u64 *__restrict__ acc,
+    int dim, int nl, int Gq, int xcd_map, DbLayout L, int j0, int G, int ng, int nblk, int q0, int Qt) {
+    typedef typename A::T T;
+    const int j = blockIdx.y + j0;
+    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
+    const int gq = xcd_map ? k % Gq : blockIdx.x % Gq;
+    const int tile = xcd_map ? xcd + 8 * (k / Gq) : blockIdx.x / Gq;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const ModC M = mod[j];
+    const size_t c = (size_t)tile * 128 + lane * 2;
+    const size_t ps = (size_t)nl * N;  // rot stride per rotation = acc poly stride (elements)
+    const int g = gq * NW + wv;        // the wave's block
+    const u64 *ra = rot + (size_t)q0 * rqs + (size_t)j * N + c;
+    const DbWalk dw = db_walk(L, N, dim, j, tile, lane, g, gq, wv);
+    const unsigned char *da = db + dw.base;
+    const A ar(M, dim, lane);
+    typename A::Sum s[QW][2][2];  // [query][component][coefficient of the lane's pair]
+#pragma unroll
+    for (int q = 0; q < QW; q++)
+#pragma unroll
+        for (int p = 0; p < 2; p++) s[q][p][0] = s[q][p][1] = typename A::Sum{};
+    struct Operands {
+        ulonglong2 a[QW];
+        typename A::Raw b0, b1;
+    };
+    auto fetch = [&](Operands &o, int i) {
+#pragma unroll
+        for (int q = 0; q < QW; q++) o.a[q] = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * ps);
+        o.b0.template load<true>(da + (size_t)i * dw.si);
+        o.b1.template load<true>(da + (size_t)i * dw.si + dw.sp);
+    };
+    auto accumulate = [&](const Operands &o) {
+        T b[2][2];
+#pragma unroll
+        for (int q = 0; q < QW; q++) {
+            const T a[2] = {A::rot(o.a[q].x), A::rot(o.a[q].y)};
+            if (q == 0) {  // (k_hydia_tensor's nesting: the block's operands are cut with the first query)
+                ar.cut(o.b0, b[0]);
+                ar.cut(o.b1, b[1]);
+            }
+#pragma unroll
+            for (int p = 0; p < 2; p++)
+#pragma unroll
+                for (int e = 0; e < 2; e++) A::mac(s[q][p][e], a[e], b[p][e]);
+        }
+    };
+    if constexpr (A::depth == 3) {
+        Operands S0, S1, S2;
+        fetch(S0, 0);
+        fetch(S1, 1);
+        int i = 0;
+        for (; i + 2 < dim; i += 3) {  // branch-free inside: clamped re-fetches of the last diagonal are never accumulated
+            fetch(S2, i + 2);
+            accumulate(S0);
+            if (NW > 1) __builtin_amdgcn_s_barrier();  // keep the waves on the same diagonal (no memory wait implied)
+            fetch(S0, i + 3 < dim ? i + 3 : dim - 1);
+            accumulate(S1);
+            if (NW > 1) __builtin_amdgcn_s_barrier();
+            fetch(S1, i + 4 < dim ? i + 4 : dim - 1);
+            accumulate(S2);
+            if (NW > 1) __builtin_amdgcn_s_barrier();
+        }
+        if (i < dim) accumulate(S0);
+        if (i + 1 < dim) accumulate(S1);
+    } else {
+        Operands cur, nxt;
+        fetch(cur, 0);
+        for (int i0 = 0; i0 < dim; i0 += ar.chunk) {
+            const int i1 = i0 + ar.chunk < dim ? i0 + ar.chunk : dim;
+            for (int i = i0; i < i1; i += 2) {  // dim and every chunk are even (k_hydia_tensor)
+                fetch(nxt, i + 1);
+                accumulate(cur);
+                if (NW > 1) __builtin_amdgcn_s_barrier();
+                fetch(cur, i + 2 < dim ? i + 2 : i + 1);
+                accumulate(nxt);
+                if (NW > 1) __builtin_amdgcn_s_barrier();
+            }
+            if (i1 < dim) {
+#pragma unroll
+                for (int q = 0; q < QW; q++)
+#pragma unroll
+                    for (int p = 0; p < 2; p++) {
+                        A::fold(s[q][p][0], M);
+                        A::fold(s[q][p][1], M);
+                    }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < QW; q++) {
+        u64 *o = acc + (mq_slot(q0 + q, g, G, ng, nblk, Qt) * 2 * nl + j) * N + c;
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+            *reinterpret_cast<ulonglong2 *>(o + p * ps) = make_ulonglong2(A::reduce(s[q][p][0], M), A::reduce(s[q][p][1], M));
+    }
+}
+// its split-diagonal entry (limb 0 of small ciphertext-major databases).  The body is instantiated on the batch's own tag, which is
+// FormPlainCt in everything the body reads, so that loop_b_split<FormPlainCt, KS, 1> keeps k_hydia_pq_sk as its only caller and that
+// kernel's code stays what it is
+template <int KS, int QW>
+__global__ __launch_bounds__(64 * KS) void k_hydia_pq_mq_sk(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs,
+                                                            const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                            DbLayout L, int G, int ng, int nblk, int q0, int Qt) {
+    loop_b_split<FormPlainCtMq, KS, QW>(mod, N, rot, rqs, db, acc, dim, nl, L, G, ng, nblk, q0, Qt);
+}
 // The R rotations of a plaintext in ONE launch: out[i][j][co] = m[j][perm_{g_i}(co)] (the gather form of the evaluation-form
 // automorphism, k_moddown_combine's index map), galois[i] = 5^i mod 2N, identity for g = 1 (rotation 0).  grid (N/256, nl, R)
 __global__ __launch_bounds__(256) void k_automorph_batch(int logN, const u64 *__restrict__ m, u64 *__restrict__ out, int nl,
@@ -1742,6 +1869,11 @@ void tensor_split(int G, int bpp, int nw, int *Bo, int *Wo) {
 // QW = 2 the kernels keep what the single-query kernels at BPP = 2 take (three waves per SIMD)
 constexpr int MQ_QW = 2;
 int hydia_tensor_mq_width(const DbLayout &) { return MQ_QW; }
+// A batch of plain queries: two sums per query instead of three leave room for QW = 4 without scratch, and batches of
+// four or more take it — the measured choice (profiles/plain_query_batch/README.md).  Two or three queries take QW = 2 (and 1): the
+// launcher serves what is left with the narrower widths
+constexpr int PQ_MQ_QW = 4;
+int hydia_pq_mq_width(const DbLayout &) { return PQ_MQ_QW; }
 // what every loop-B entry point takes, in the launcher's words (a plain form ignores rqs, q0 and Qt)
 struct LoopB {
     const ModC *mod;
@@ -1783,12 +1915,26 @@ template <int KS, int QW>
 static void launch_split(FormPlainCt, hipStream_t st, dim3 grid, const LoopB &p) {
     hipLaunchKernelGGL((k_hydia_pq_sk<KS>), grid, dim3(64 * KS), 0, st, p.mod, p.N, p.rot, p.db, p.acc, p.dim, p.nl, p.L, p.G, p.ng, p.nblk);
 }
+template <class A, int BPP, int QW, int NW>
+static void launch_stream(FormPlainCtMq, hipStream_t st, dim3 grid, const LoopB &p, int j0) {
+    // (Halves24<false> is not instantiated for this family: a batch keeps the 128-bit sums where a single query takes it, see loop_b)
+    if constexpr (BPP == 1 && !std::is_same<A, Halves24<false>>::value)
+        hipLaunchKernelGGL((k_hydia_pq_mq<A, QW, NW>), grid, dim3(64 * NW), 0, st, p.mod, p.N, p.rot, p.rqs, p.db, p.acc, p.dim, p.nl, p.Gq,
+                           p.xm, p.L, j0, p.G, p.ng, p.nblk, p.q0, p.Qt);
+    else throw std::logic_error("hydia: no such kernel for a batch of plain queries (one block per wave; 128-bit sums or 46-bit halves)");
+}
+template <int KS, int QW>
+static void launch_split(FormPlainCtMq, hipStream_t st, dim3 grid, const LoopB &p) {
+    hipLaunchKernelGGL((k_hydia_pq_mq_sk<KS, QW>), grid, dim3(64 * KS), 0, st, p.mod, p.N, p.rot, p.rqs, p.db, p.acc, p.dim, p.nl, p.L, p.G,
+                       p.ng, p.nblk, p.q0, p.Qt);
+}
 // an instantiation's name as rocprofv3 prints it (namespaces dropped), which is what the byte ledger records; QW only where the form
 // has batches
 template <class F>
 static std::string stream_name(const char *policy, int bpp, int qw, int nw) {
     char n[96];
-    if (F::batch) snprintf(n, sizeof n, "k_hydia_%s<%s, %d, %d, %d>", F::name, policy, bpp, qw, nw);
+    if (!F::bpp_arg) snprintf(n, sizeof n, "k_hydia_%s<%s, %d, %d>", F::name, policy, qw, nw);
+    else if (F::batch) snprintf(n, sizeof n, "k_hydia_%s<%s, %d, %d, %d>", F::name, policy, bpp, qw, nw);
     else snprintf(n, sizeof n, "k_hydia_%s<%s, %d, %d>", F::name, policy, bpp, nw);
     return n;
 }
@@ -1820,16 +1966,22 @@ static void stream_nw(hipStream_t st, int nw, dim3 grid, const LoopB &p, int j0,
 template <class F, int KS>
 static void split_qw(hipStream_t st, int qw, dim3 grid, const LoopB &p, double bytes) {
     ledger_add(split_name<F>(KS, qw).c_str(), bytes);
+    if constexpr (F::max_qw >= 4)
+        if (qw == 4) return launch_split<KS, 4>(F{}, st, grid, p);
     if constexpr (F::batch)
         if (qw == 2) return launch_split<KS, 2>(F{}, st, grid, p);
+    if (qw != 1) throw std::logic_error("hydia: no loop B kernel for this batch width");
     launch_split<KS, 1>(F{}, st, grid, p);
 }
-// Loop B of every form: Q queries (one unless the form has batches and bpp = TENSOR_BATCH) against G blocks of dim diagonals
+// Loop B of every form: Q queries (one unless the form has batches and bpp = TENSOR_BATCH) against G blocks of dim diagonals; width =
+// queries per pass of a batch (a power of two up to F::max_qw; what is left over takes the narrower widths, a last odd query QW = 1)
 template <class F>
 static void loop_b(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G, int dim,
-                   int nl, const DbLayout &L, int ng, int bpp, int nw) {
+                   int nl, const DbLayout &L, int ng, int bpp, int nw, int width = MQ_QW) {
     const bool batch = F::batch && bpp == TENSOR_BATCH;
     if (Q < 1 || (!batch && Q != 1) || G < 1 || dim < 2 || (ng > 0 && G % ng)) throw std::logic_error("hydia: loop B with a bad shape");
+    if (!batch) width = 1;
+    if (width < 1 || width > F::max_qw || (width & (width - 1))) throw std::logic_error("hydia: loop B with a batch width that is not instantiated");
     if (L.bits46 && !(L.packed && L.seq && dim <= 4096)) throw std::logic_error("hydia: 46-bit database outside the 24-bit-halves loop B");
     if (L.seq && (G != L.blocks || dim != L.bd || G % L.seq || G <= 8 || L.seq % L.seq_bpp || (L.seq & (L.seq - 1)) || L.seq > 8))
         throw std::logic_error("hydia: loop B launched against a group-sequential database with another shape");
@@ -1849,8 +2001,9 @@ static void loop_b(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_
     // ledger bytes per limb: the resident database (dp polynomials per entry; 6- or 8-byte residues, 5.75 for 46-bit) + the QW rotation
     // sets (qp polynomials per rotation) once + QW x G accumulators of `comps` components
     const double per_lp8 = LP_BYTES(N), per_lp6 = (double)N * (L.bits46 ? 5.75 : 6.0);
-    for (p.q0 = 0; p.q0 < Q; p.q0 += MQ_QW) {  // one pass over the database per QW queries (an odd last one alone)
-        const int QW = Q - p.q0 >= MQ_QW ? MQ_QW : 1;
+    int QW = 1;
+    for (p.q0 = 0; p.q0 < Q; p.q0 += QW) {  // one pass over the database per QW queries (an odd last one alone)
+        for (QW = width; QW > Q - p.q0; QW >>= 1) {}
         auto bytes = [&](int limbs, double per_lp) {
             return limbs * ((double)G * dim * F::dp * per_lp + QW * ((double)dim * F::qp + (double)G * F::comps) * per_lp8);
         };
@@ -1858,6 +2011,8 @@ static void loop_b(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_
             typedef typename std::remove_pointer<decltype(policy)>::type A;
             const dim3 grid((N / 128) * p.Gq, limbs);
             const double by = bytes(limbs, j0 ? per_lp6 : per_lp8);
+            if constexpr (F::max_qw >= 4)
+                if (QW == 4) return stream_nw<F, A, 1, 4>(st, W, grid, p, j0, by);
             if constexpr (F::batch)
                 if (QW == 2) return stream_nw<F, A, 1, 2>(st, W, grid, p, j0, by);  // (a batch has B = 1)
             if (B == 2) stream_nw<F, A, 2, 1>(st, W, grid, p, j0, by);
@@ -1899,6 +2054,13 @@ void hydia_pq_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot,
                          const DbLayout &L, int ng, int bpp, int nw) {
     if (L.plain) throw std::logic_error("hydia: plain-query loop B launched against a plain gallery");
     loop_b<FormPlainCt>(st, mod, N, rot, 0, db, acc, 1, G, dim, nl, L, ng, bpp, nw);
+}
+// A batch of plain queries over the same routine, with the encrypted batch's choices (workgroup = the layout's group or 4 / 2 / 1 waves
+// by divisibility of G, limb 0 on the split kernel for few ciphertext-major blocks, its arithmetic per layout)
+void hydia_pq_accumulate_multi(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G,
+                               int dim, int nl, const DbLayout &L, int ng, int width) {
+    if (L.plain) throw std::logic_error("hydia: plain-query loop B launched against a plain gallery");
+    loop_b<FormPlainCtMq>(st, mod, N, rot, rqs, db, acc, Q, G, dim, nl, L, ng, TENSOR_BATCH, 0, width > 0 ? width : hydia_pq_mq_width(L));
 }
 void automorph_batch(hipStream_t st, int logN, const u64 *m, u64 *out, int nl, int R, const unsigned *galois) {
     ledger_add("k_automorph_batch", (1.0 + R) * nl * LP_BYTES(1 << logN));

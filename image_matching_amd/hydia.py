@@ -107,6 +107,10 @@ def load_library():
         "hydia_compute_similarity_pq": (i32, [vp, vp, pp]),
         "hydia_index_scenario_pq": (i32, [vp, vp, pp]),
         "hydia_membership_scenario_pq": (i32, [vp, vp, pp]),
+        "hydia_compute_similarity_pq_multi": (i32, [vp, vp, u32, vp]),
+        "hydia_index_scenario_pq_multi": (i32, [vp, vp, u32, vp]),
+        "hydia_membership_scenario_pq_multi": (i32, [vp, vp, u32, vp]),
+        "hydia_set_pq_batch_width": (i32, [vp, u32]),
         "hydia_db_import_ct": (i32, [vp, sz, vp]),
         "hydia_db_export_ct": (i32, [vp, sz, vp]),
         "hydia_db_fill_random": (i32, [vp, sz, u64]),
@@ -733,6 +737,12 @@ class Context:
         return a.value, b.value, c.value
 
     # ---- measurement
+    def set_pq_batch_width(self, width):
+        """UNSTABLE (hydia_set_pq_batch_width: measurements and tests only).  Queries one database pass of a plain-query batch serves
+        on this context: 1, 2 or 4; 0 = the library's measured choice.  No result depends on it (tools/bench_plain_query.py --batch
+        compares the widths with it)"""
+        _chk(self.L.hydia_set_pq_batch_width(self.h, int(width)))
+
     def kernel_time(self, name):
         ms, n = C.c_double(), C.c_uint64()
         _chk(self.L.hydia_kernel_time(self.h, name.encode(), C.byref(ms), C.byref(n)))
@@ -893,6 +903,38 @@ class DiagonalSender:
 
     def membershipScenarioMulti(self, query_ciphers):
         return self._multi("hydia_membership_scenario_multi", query_ciphers)
+
+    # ---- several PLAIN queries in one pass over the database (names of their own: the *Multi methods above keep refusing a Plaintext).
+    # A list of Plaintext in, a list out: per query exactly what the single-query method returns
+    def encodeQueries(self, matrix):
+        """one Plaintext per row of `matrix` (k x vector_dim), each what encodeQuery makes of that row"""
+        if not isinstance(self.cc, Context):
+            raise HydiaError(-2, "hydia: a plain query is not served on a sharded context")
+        matrix = np.ascontiguousarray(matrix, dtype=np.float64)
+        assert matrix.ndim == 2 and matrix.shape[1] == self.cc.dim
+        return [self.encodeQuery(row) for row in matrix]
+
+    def _plain_multi(self, fn, plaintexts):
+        qs = list(plaintexts)
+        if any(not isinstance(q, Plaintext) for q in qs):
+            raise HydiaError(-1, "hydia: a *PlainMulti method takes Plaintexts (encodeQuery); encrypted queries go to the *Multi methods")
+        if not isinstance(self.cc, Context):
+            raise HydiaError(-2, "hydia: a plain query is not served on a sharded context")
+        fn = getattr(self.cc.L, fn)
+        n = len(qs)
+        hs = (C.c_void_p * max(n, 1))(*[q.h for q in qs])
+        out = (C.c_void_p * max(n, 1))()
+        _chk(fn(self.cc.h, hs, n, out))
+        return [Ciphertext(self.cc, C.c_void_p(out[i])) for i in range(n)]
+
+    def computeSimilarityPlainMulti(self, plaintexts):
+        return self._plain_multi("hydia_compute_similarity_pq_multi", plaintexts)
+
+    def indexScenarioPlainMulti(self, plaintexts):
+        return self._plain_multi("hydia_index_scenario_pq_multi", plaintexts)
+
+    def membershipScenarioPlainMulti(self, plaintexts):
+        return self._plain_multi("hydia_membership_scenario_pq_multi", plaintexts)
 
     # ---- loop A split over the GPUs of a node (sender_diag.cpp:23-26 cut into ranges; image_matching_amd.sharding)
     def rotateQueryRange(self, query_cipher, first, count):

@@ -354,7 +354,12 @@ int hydia_membership_scenario_multi(hydia_ctx *ctx, const hydia_ct *const *queri
  * any work is enqueued: the relinearisation key (the comparator of the scenarios), a giant-step key B g (kind 6), a power-of-two key
  * (the EvalSum of membership).
  * Served on kinds 5 and 6 only.  A plain gallery (kind 7 / 8) answers HYDIA_ERR_STATE: with both sides in the clear nothing would be
- * private.  No database, or kinds 1 / 3 / 4: HYDIA_ERR_STATE.  NOT served: batches, caller-supplied rotations, hydia_group_*. */
+ * private.  No database, or kinds 1 / 3 / 4: HYDIA_ERR_STATE.  NOT served: caller-supplied rotations, hydia_group_*.
+ * The *_pq_multi entries serve n_queries plain queries in one pass over the database, with the output convention of hydia_*_multi:
+ * out[q] receives exactly what the single *_pq entry returns for queries[q], bit for bit, and is freed on its own; on any error every
+ * out[q] is NULL.  Every refusal is made for every query before any work is enqueued and leaves the database as it was: an empty
+ * batch, a NULL handle, a plaintext not at full level, unequal scales: HYDIA_ERR_ARG; what the single entry refuses (a plain gallery,
+ * no database or another kind, a missing key): HYDIA_ERR_STATE with the single entry's message. */
 typedef struct hydia_pt hydia_pt;
 int hydia_encode_query(hydia_ctx *ctx, const double *query /* vector_dim */, hydia_pt **out);
 int hydia_pt_import(hydia_ctx *ctx, const uint64_t *data /* [n_q][N] */, double scale, hydia_pt **out);
@@ -363,6 +368,13 @@ void hydia_pt_free(hydia_pt *pt);
 int hydia_compute_similarity_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out);
 int hydia_index_scenario_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out);
 int hydia_membership_scenario_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out);
+int hydia_compute_similarity_pq_multi(hydia_ctx *ctx, const hydia_pt *const *queries, uint32_t n_queries, hydia_ct **out);
+int hydia_index_scenario_pq_multi(hydia_ctx *ctx, const hydia_pt *const *queries, uint32_t n_queries, hydia_ct **out);
+int hydia_membership_scenario_pq_multi(hydia_ctx *ctx, const hydia_pt *const *queries, uint32_t n_queries, hydia_ct **out);
+/* UNSTABLE, for measurements and tests only (tools/bench_plain_query.py --batch): not part of the interface an integration should
+ * rely on, and it may change or go without notice.  The queries one database pass of a *_pq_multi call serves on this context, 1, 2
+ * or 4; 0 = the library's measured choice (the default).  The results do not depend on it.  Another value: HYDIA_ERR_ARG. */
+int hydia_set_pq_batch_width(hydia_ctx *ctx, uint32_t width);
 /* OpenFHEWrapper::chebyshevCompare (src/openFHE_wrapper.cpp:143-185) on every ciphertext of the batch */
 int hydia_chebyshev_compare(hydia_ctx *ctx, const hydia_ct *in, double delta, size_t sign_depth, hydia_ct **out);
 /* multi-GPU membership tail: sum the batch into one ciphertext, then EvalSum over all slots (:46-47) */

@@ -314,8 +314,43 @@ class DiagonalSender : public Sender {
         hydia_ct *out = run_pq(query, hydia_index_scenario_pq, "indexScenario");
         return out ? split_batch(cc, out) : std::vector<Ciphertext>{};
     }
+    // Several plain queries in one pass over the database (names of their own: the *Multi methods take ciphertexts).  One Plaintext
+    // per query in; per query exactly what the single-query overload returns.  Not on a sharded context: an error, empty.
+    std::vector<std::vector<Ciphertext>> computeSimilarityPlainMulti(const std::vector<Plaintext> &queries) {
+        std::vector<std::vector<Ciphertext>> r;
+        for (hydia_ct *h : run_pq_multi(queries, hydia_compute_similarity_pq_multi, "computeSimilarityPlainMulti")) r.push_back(split_batch(cc, h));
+        return r;
+    }
+    std::vector<Ciphertext> membershipScenarioPlainMulti(const std::vector<Plaintext> &queries) {
+        std::vector<Ciphertext> r;
+        for (hydia_ct *h : run_pq_multi(queries, hydia_membership_scenario_pq_multi, "membershipScenarioPlainMulti")) r.push_back(split_batch(cc, h)[0]);
+        return r;
+    }
+    std::vector<std::vector<Ciphertext>> indexScenarioPlainMulti(const std::vector<Plaintext> &queries) {
+        std::vector<std::vector<Ciphertext>> r;
+        for (hydia_ct *h : run_pq_multi(queries, hydia_index_scenario_pq_multi, "indexScenarioPlainMulti")) r.push_back(split_batch(cc, h));
+        return r;
+    }
 
   private:
+    std::vector<hydia_ct *> run_pq_multi(const std::vector<Plaintext> &qs,
+                                         int (*multi)(hydia_ctx *, const hydia_pt *const *, uint32_t, hydia_ct **), const char *what) {
+        if (cc->group) {
+            std::cerr << "Error: " << what << ": a plain query is not served on a sharded context" << std::endl;
+            return {};
+        }
+        std::vector<const hydia_pt *> in;
+        for (auto &q : qs) {
+            if (!q) {
+                std::cerr << "Error: " << what << ": empty plain query" << std::endl;
+                return {};
+            }
+            in.push_back(q.pt->h);
+        }
+        std::vector<hydia_ct *> out(in.size(), nullptr);
+        if (!cc->check(multi(cc->h, in.data(), (uint32_t)in.size(), out.data()), what)) return {};
+        return out;
+    }
     hydia_ct *run_pq(const Plaintext &q, int (*one)(hydia_ctx *, const hydia_pt *, hydia_ct **), const char *what) {
         if (!q || cc->group) {
             std::cerr << "Error: " << what << ": " << (q ? "a plain query is not served on a sharded context" : "empty plain query") << std::endl;
