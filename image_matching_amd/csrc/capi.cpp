@@ -1026,6 +1026,42 @@ int hydia_set_pq_batch_width(hydia_ctx *ctx, uint32_t width) {
     return HYDIA_OK;
     API_END
 }
+// a batch of encrypted queries against a plain gallery (kinds 7 / 8): the output convention of scenario_multi_call
+static int scenario_gallery_multi_call(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out, int what) {
+    if (out)
+        for (uint32_t q = 0; q < n_queries; q++) out[q] = nullptr;
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && queries && out, "null argument");
+    REQUIRE(n_queries >= 1, "a batch of queries needs at least one query");
+    std::vector<const Ct *> qs(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) {
+        REQUIRE(queries[q], "null query in the batch");
+        qs[q] = &queries[q]->c;
+    }
+    if (ctx->in_group) throw StateError("hydia: a plain gallery (kind 7 / 8) is not served on a shard of a group: neither are its batches");
+    std::vector<Ct> r = ctx->cx.scenario_gallery_multi(qs, what);
+    for (uint32_t q = 0; q < n_queries; q++) out[q] = wrap(ctx, std::move(r[q]));  // compact and owning: no copy, cannot fail
+    return HYDIA_OK;
+    API_END
+}
+int hydia_compute_similarity_gallery_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out) {
+    return scenario_gallery_multi_call(ctx, queries, n_queries, out, 0);
+}
+int hydia_index_scenario_gallery_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out) {
+    return scenario_gallery_multi_call(ctx, queries, n_queries, out, 1);
+}
+int hydia_membership_scenario_gallery_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out) {
+    return scenario_gallery_multi_call(ctx, queries, n_queries, out, 2);
+}
+int hydia_set_gallery_batch_width(hydia_ctx *ctx, uint32_t width) {
+    API_BEGIN
+    REQUIRE(ctx, "null argument");
+    REQUIRE(width == 0 || width == 1 || width == 2 || width == 4, "a plain gallery's batch serves 1, 2 or 4 queries per pass (0 = the default)");
+    ctx->cx.plain_mq_width = (int)width;
+    return HYDIA_OK;
+    API_END
+}
 int hydia_chebyshev_compare(hydia_ctx *ctx, const hydia_ct *query, double delta, size_t sign_depth, hydia_ct **out) {
     SENDER_CALL(ctx->cx.chebyshev_compare(query->c, delta, (int)sign_depth))
 }

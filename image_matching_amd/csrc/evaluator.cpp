@@ -1668,10 +1668,13 @@ void Context::check_multi(const std::vector<const Ct *> &qs) const {
 // and the allocator's trim-and-retry made it 7x slower than 8 single calls), never fewer than one — a batch of one needs what a
 // single-query call needs
 int Context::multi_batch(int Q, bool plain_queries) {
-    const int dim = prm.dim, R = db_kind == 6 ? db_babies : dim, NG = db_kind == 6 ? dim / db_babies : 1, G = (int)(db_cts / dim);
+    const bool bsgs = db_kind == 6 || db_kind == 8;
+    const int dim = prm.dim, R = bsgs ? db_babies : dim, NG = bsgs ? dim / db_babies : 1, G = (int)(db_cts / dim);
     const double lp = (double)nQ * N * 8;
-    // a plain query's rotations are one polynomial each and its accumulators have two components; the comparator's share is the same
-    const double per_query = (double)R * (plain_queries ? 1 : 2) * lp + (double)G * NG * (plain_queries ? 2 : 3) * lp + (double)G * 48 * 2 * lp;
+    // a plain query's rotations are one polynomial each and its accumulators have two components; a plain gallery's batch (kinds 7 / 8)
+    // has 2-polynomial rotations and 2-component accumulators; the comparator's share is the same
+    const double per_query =
+        (double)R * (plain_queries ? 1 : 2) * lp + (double)G * NG * (plain_queries || db_plain() ? 2 : 3) * lp + (double)G * 48 * 2 * lp;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 1;
     const double avail = 0.85 * ((double)free_b + (double)pool.bytes_cached);
@@ -1786,6 +1789,67 @@ std::vector<Ct> Context::scenario_pq_multi(const std::vector<const Ct *> &pts, i
             timer_end("hydia_pq_multi");
         }
         if (db_kind == 6) acc = giant_step_sum(acc, NG);  // slot (giant g, query q, block) = (g Qb + q) G + block
+        tails_multi(acc, Qb, what, res);
+        q0 += Qb;
+    }
+    return res;
+}
+// ------------------------------------------------------------------ a batch of ENCRYPTED queries against a PLAIN gallery (kinds 7 / 8)
+// in shared passes over the gallery: loop A per query into one [Qb][R][2][nQ][N] buffer, ONE batched loop B (k_hydia_plain_mq: the
+// launcher's passes of plain_mq_width queries and what is left over), for kind 8 the giant steps on the 2-component [NG][Qb G]
+// accumulators, then the batch's tails.  Per query exactly what the single call returns.  The query checks are check_multi's, the
+// state and key checks the single call's with its messages, all made before anything is enqueued
+void Context::check_gallery_multi(const std::vector<const Ct *> &qs, int what) const {
+    if (qs.empty()) throw std::runtime_error("hydia: a batch of queries needs at least one query");
+    for (const Ct *q : qs)
+        if (!q || q->X != 1 || q->npoly != 2 || q->nl != nQ || !q->compact() || q->scale != qs[0]->scale)
+            throw std::runtime_error("hydia: every query of a batch must be one fresh 2-component ciphertext at full level");
+    if (d_db && db_cts > 0 && (db_kind == 5 || db_kind == 6))
+        throw StateError("hydia: a ciphertext database (kind 5 / 6) is resident: its batches are served by hydia_*_multi");
+    if (!d_db || db_cts == 0 || !db_plain() || !db_lay.plain) throw StateError("hydia: no plain gallery resident (kind 7 or 8)");
+    const int dim = prm.dim, B = db_babies;
+    if (db_kind == 8 && (B < 1 || dim % B)) throw StateError("hydia: the resident database carries no valid baby count");
+    // the keys in the order the single call asks for them: the giant steps' (build_giants), loop A's (build_rotptrs), the comparator's,
+    // EvalSum's
+    if (db_kind == 8)
+        for (int g = 1; g < dim / B; g++)
+            if (!rot_keys.count(g * B)) throw StateError("hydia: rotation key " + std::to_string(g * B) + " not loaded");
+    if (!rotptrs_valid)
+        for (int i = 1; i < dim; i++)
+            if (!rot_keys.count(i)) throw StateError("hydia: rotation key " + std::to_string(i) + " not loaded");
+    if (what >= 1 && !relin_key.d) throw StateError("hydia: relinearisation key not loaded");
+    if (what == 2)
+        for (int r = 1; r < slots; r <<= 1)
+            if (!rot_keys.count(r)) throw StateError("hydia: rotation key " + std::to_string(r) + " not loaded");
+}
+std::vector<Ct> Context::scenario_gallery_multi(const std::vector<const Ct *> &qs, int what) {
+    check_gallery_multi(qs, what);
+    const int Q = (int)qs.size(), dim = prm.dim, nl = nQ, G = (int)(db_cts / dim);
+    const int R = db_kind == 8 ? db_babies : dim, NG = dim / R;
+    std::vector<Ct> res;
+    res.reserve(Q);
+    for (int q0 = 0; q0 < Q;) {
+        const int Qb = multi_batch(Q - q0);
+        if (db_kind == 8) build_giants(Qb * G);  // one table entry per (giant step, query, block)
+        const double scale = qs[q0]->scale;
+        Ct acc(this, Qb * G * NG, 2, nl, scale * delta);
+        {
+            Ct rot(this, Qb * R, 2, nl, scale);
+            const size_t rqs = (size_t)R * rot.ct_elems();
+            for (int q = 0; q < Qb; q++) rotate_query_range(*qs[q0 + q], 0, R, rot.d + (size_t)q * rqs);
+            const int w = plain_mq_width > 0 ? plain_mq_width : hk::hydia_plain_mq_width(db_lay);
+            int passes = 0;
+            for (int left = Qb, qw = w; left > 0; passes++) {  // the launcher's schedule: the widest width that still fits what is left
+                while (qw > left) qw >>= 1;
+                left -= qw;
+            }
+            op_bytes("op:loop_b_plain_multi", N, 0,
+                     (double)passes * db_cts * (double)db_lay.ct_bytes + ((double)Qb * R * 2 + (double)Qb * G * NG * 2) * nl * N * 8);
+            timer_begin("hydia_plain_multi");
+            hk::hydia_plain_accumulate_multi(stream, d_mod, N, rot.d, rqs, d_db, acc.d, Qb, G * NG, R, nl, db_lay, db_kind == 8 ? NG : 0, w);
+            timer_end("hydia_plain_multi");
+        }
+        if (db_kind == 8) acc = giant_step_sum(acc, NG);  // slot (giant g, query q, block) = (g Qb + q) G + block
         tails_multi(acc, Qb, what, res);
         q0 += Qb;
     }

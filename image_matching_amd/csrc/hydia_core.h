@@ -469,6 +469,12 @@ struct Context : HostParams {
     // query passes pq_check and all carry one scale (runtime_error otherwise) before anything is enqueued
     std::vector<Ct> scenario_pq_multi(const std::vector<const Ct *> &pts, int what);
     int pq_mq_width = 0;  // queries per pass of a plain-query batch (1, 2, 4); 0 = hk::hydia_pq_mq_width, the measured choice
+    // a batch of ENCRYPTED queries against a PLAIN gallery (kinds 7 / 8) in shared passes over the gallery: one result per query, each
+    // exactly what the single call returns.  check_gallery_multi: check_multi's query checks (runtime_error), then the single call's
+    // state and key checks with its messages (StateError), before anything is enqueued
+    std::vector<Ct> scenario_gallery_multi(const std::vector<const Ct *> &qs, int what);
+    void check_gallery_multi(const std::vector<const Ct *> &qs, int what) const;
+    int plain_mq_width = 0;  // queries per pass of a plain gallery's batch (1, 2, 4); 0 = hk::hydia_plain_mq_width
     Ct giant_step_sum(Ct &acc, int NG);  // BSGS giant steps on [NG X0] giant-major accumulators -> [X0][2][nQ][N] (relinearises a 3-component acc)
     Ct batch_slice(const Ct &b, int q, int per);
     // ---- HERS sender (approach 4, src/sender/sender_hers.cpp): q = dim query ciphertexts

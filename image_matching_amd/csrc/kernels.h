@@ -435,6 +435,12 @@ void hydia_pq_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot,
 void hydia_pq_accumulate_multi(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G,
                                int dim, int nl, const DbLayout &L, int ng, int width = 0);
 int hydia_pq_mq_width(const DbLayout &L);  // queries one pass serves for this form
+// A BATCH of Q encrypted queries against a PLAIN gallery (L.plain): rot holds the queries' rotation sets [dim][2][nl][N], rqs elements
+// apart; acc [Q G][2][nl][N] with the batch slot map of hydia_tensor_accumulate.  Every accumulator equals hydia_plain_accumulate's for
+// that query, bit for bit.  width: queries per pass (1, 2 or 4); 0 = hydia_plain_mq_width(L)
+void hydia_plain_accumulate_multi(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G,
+                                  int dim, int nl, const DbLayout &L, int ng, int width = 0);
+int hydia_plain_mq_width(const DbLayout &L);  // queries one pass serves for this form
 // out[i][j][c] = m[j][perm_{galois[i]}(c)], i < R, in one launch (m [nl][N], out [R][nl][N]; galois: device [R], 1 = identity)
 void automorph_batch(hipStream_t st, int logN, const u64 *m, u64 *out, int nl, int R, const unsigned *galois);
 

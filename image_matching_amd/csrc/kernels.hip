@@ -11,6 +11,7 @@
 //   k_hydia_pq            the same sums for a PLAIN query against the encrypted database (one encoded polynomial per rotation; no
 //                         counterpart in the reference), k_automorph_batch: the rotations of that plaintext
 //   k_hydia_pq_mq         the same for a BATCH of plain queries: QW probes per pass over the database
+//   k_hydia_plain_mq      a BATCH of encrypted queries against a PLAIN gallery: QW queries per pass over the gallery
 //   k_rescale_*           RescaleInPlace (sender_diag.cpp:80)
 //   k_tensor, k_lincomb*  ct x ct products and Chebyshev/f4 leaves of chebyshevCompare (src/openFHE_wrapper.cpp:143-185)
 //   k_batch_sum           HERS: sum of the per-dimension products (src/sender/sender_hers.cpp:60-87)
@@ -916,8 +917,20 @@ struct FormPlainCtMq : FormPlainCt {
     static constexpr int max_qw = 4;
 };
 
-// The streaming kernels.  k_hydia_tensor, k_hydia_plain, k_hydia_pq and k_hydia_pq_mq hold the SAME pipeline (tile map, db_walk, rotating operand
-// sets with the clamped re-fetch, one s_barrier per diagonal, fold, reduction, mq_slot store): a change to it is made in all four.
+// A BATCH of encrypted queries against a plain gallery (k_hydia_plain_mq, k_hydia_plain_mq_sk): FormCtPlain's products for QW queries per
+// pass, every query with its own rotation set (rqs elements apart) and its OWN two sums.  The bounds are FormPlain's, unchanged: a sum
+// still takes one product of two canonical residues per diagonal, however many queries sit beside it.  A tag of its own, as
+// FormPlainCtMq is, so that FormCtPlain (batch = false), k_hydia_plain / k_hydia_plain_sk, their names and their code stay what they
+// are; one block per wave, no BPP in the streaming kernel's template list
+struct FormCtPlainMq : FormCtPlain {
+    static constexpr const char *name = "plain_mq";
+    static constexpr bool batch = true, bpp_arg = false;
+    static constexpr int max_qw = 4;
+};
+
+// The streaming kernels.  k_hydia_tensor, k_hydia_plain, k_hydia_pq, k_hydia_pq_mq and k_hydia_plain_mq hold the SAME pipeline (tile map,
+// db_walk, rotating operand sets with the clamped re-fetch, one s_barrier per diagonal, fold, reduction, mq_slot store): a change to
+// it is made in all five.
 // It is written out in each entry point on purpose.  Called as one device function the pipeline is optimised twice, alone and again
 // after inlining, and the second pass orders the multiply-accumulates differently: k_hydia_tensor<Halves24<true>, 1, 2, *> took 186 /
 // 188 VGPRs instead of 164 (2 waves per SIMD instead of 3), k_hydia_pq<Halves24<true>, 2, *> 151 instead of 120 (3 instead of 4),
@@ -1456,6 +1469,117 @@ __global__ __launch_bounds__(64 * KS) void k_hydia_pq_mq_sk(const ModC *__restri
                                                             DbLayout L, int G, int ng, int nblk, int q0, int Qt) {
     loop_b_split<FormPlainCtMq, KS, QW>(mod, N, rot, rqs, db, acc, dim, nl, L, G, ng, nblk, q0, Qt);
 }
+// ------------------------------------------------------------------------------------------------ loop B for a batch on a plain gallery
+// k_hydia_plain's pipeline with the query dimension k_hydia_pq_mq has, at ONE block per wave: rot holds the queries' rotation sets
+// [R][2][nl][N], rqs elements apart, from query q0 on.  The gallery operand (one polynomial) is loaded and cut once per diagonal, with
+// the first query, and shared by the QW queries; each query's two operands are loaded once.  Every query has its own two sums, so the
+// bounds are FormPlain's, unchanged.  The store goes through mq_slot into [slot][2][nl][N] (Qt = queries of the whole batch).  QW = 4
+// on eight-wave workgroups asks for one workgroup per CU, as k_hydia_pq_mq does
+template <class A, int QW, int NW>
+__global__ __launch_bounds__(64 * NW, (QW >= 4 && NW >= 8) ? 1 : 2) void k_hydia_plain_mq(
+    const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs, const unsigned char *__restrict__ db, u64 *__restrict__ acc,
+    int dim, int nl, int Gq, int xcd_map, DbLayout L, int j0, int G, int ng, int nblk, int q0, int Qt) {
+    typedef typename A::T T;
+    const int j = blockIdx.y + j0;
+    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
+    const int gq = xcd_map ? k % Gq : blockIdx.x % Gq;
+    const int tile = xcd_map ? xcd + 8 * (k / Gq) : blockIdx.x / Gq;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const ModC M = mod[j];
+    const size_t c = (size_t)tile * 128 + lane * 2;
+    const size_t ps = (size_t)nl * N, cs = 2 * ps;  // rot / acc poly stride, ciphertext stride (elements)
+    const int g = gq * NW + wv;                     // the wave's block
+    const u64 *ra = rot + (size_t)q0 * rqs + (size_t)j * N + c;
+    const DbWalk dw = db_walk(L, N, dim, j, tile, lane, g, gq, wv);
+    const unsigned char *da = db + dw.base;
+    const A ar(M, dim, lane);
+    typename A::Sum s[QW][2][2];  // [query][component][coefficient of the lane's pair]
+#pragma unroll
+    for (int q = 0; q < QW; q++)
+#pragma unroll
+        for (int p = 0; p < 2; p++) s[q][p][0] = s[q][p][1] = typename A::Sum{};
+    struct Operands {
+        ulonglong2 a0[QW], a1[QW];
+        typename A::Raw b;
+    };
+    auto fetch = [&](Operands &o, int i) {
+#pragma unroll
+        for (int q = 0; q < QW; q++) {
+            o.a0[q] = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs);
+            o.a1[q] = *reinterpret_cast<const ulonglong2 *>(ra + q * rqs + (size_t)i * cs + ps);
+        }
+        o.b.template load<true>(da + (size_t)i * dw.si);
+    };
+    auto accumulate = [&](const Operands &o) {
+        T b[2];
+#pragma unroll
+        for (int q = 0; q < QW; q++) {
+            const T a[2][2] = {{A::rot(o.a0[q].x), A::rot(o.a0[q].y)}, {A::rot(o.a1[q].x), A::rot(o.a1[q].y)}};
+            if (q == 0) ar.cut(o.b, b);  // (k_hydia_tensor's nesting: the block's operand is cut with the first query)
+#pragma unroll
+            for (int p = 0; p < 2; p++)
+#pragma unroll
+                for (int e = 0; e < 2; e++) A::mac(s[q][p][e], a[p][e], b[e]);
+        }
+    };
+    if constexpr (A::depth == 3) {
+        Operands S0, S1, S2;
+        fetch(S0, 0);
+        fetch(S1, 1);
+        int i = 0;
+        for (; i + 2 < dim; i += 3) {  // branch-free inside: clamped re-fetches of the last diagonal are never accumulated
+            fetch(S2, i + 2);
+            accumulate(S0);
+            if (NW > 1) __builtin_amdgcn_s_barrier();  // keep the waves on the same diagonal (no memory wait implied)
+            fetch(S0, i + 3 < dim ? i + 3 : dim - 1);
+            accumulate(S1);
+            if (NW > 1) __builtin_amdgcn_s_barrier();
+            fetch(S1, i + 4 < dim ? i + 4 : dim - 1);
+            accumulate(S2);
+            if (NW > 1) __builtin_amdgcn_s_barrier();
+        }
+        if (i < dim) accumulate(S0);
+        if (i + 1 < dim) accumulate(S1);
+    } else {
+        Operands cur, nxt;
+        fetch(cur, 0);
+        for (int i0 = 0; i0 < dim; i0 += ar.chunk) {
+            const int i1 = i0 + ar.chunk < dim ? i0 + ar.chunk : dim;
+            for (int i = i0; i < i1; i += 2) {  // dim and every chunk are even (k_hydia_tensor)
+                fetch(nxt, i + 1);
+                accumulate(cur);
+                if (NW > 1) __builtin_amdgcn_s_barrier();
+                fetch(cur, i + 2 < dim ? i + 2 : i + 1);
+                accumulate(nxt);
+                if (NW > 1) __builtin_amdgcn_s_barrier();
+            }
+            if (i1 < dim) {
+#pragma unroll
+                for (int q = 0; q < QW; q++)
+#pragma unroll
+                    for (int p = 0; p < 2; p++) {
+                        A::fold(s[q][p][0], M);
+                        A::fold(s[q][p][1], M);
+                    }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < QW; q++) {
+        u64 *o = acc + (mq_slot(q0 + q, g, G, ng, nblk, Qt) * 2 * nl + j) * N + c;
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+            *reinterpret_cast<ulonglong2 *>(o + p * ps) = make_ulonglong2(A::reduce(s[q][p][0], M), A::reduce(s[q][p][1], M));
+    }
+}
+// its split-diagonal entry (limb 0 of small ciphertext-major galleries), on the batch's own tag, so that loop_b_split<FormCtPlain, KS, 1>
+// keeps k_hydia_plain_sk as its only caller and that kernel's code stays what it is
+template <int KS, int QW>
+__global__ __launch_bounds__(64 * KS) void k_hydia_plain_mq_sk(const ModC *__restrict__ mod, int N, const u64 *__restrict__ rot, size_t rqs,
+                                                               const unsigned char *__restrict__ db, u64 *__restrict__ acc, int dim, int nl,
+                                                               DbLayout L, int G, int ng, int nblk, int q0, int Qt) {
+    loop_b_split<FormCtPlainMq, KS, QW>(mod, N, rot, rqs, db, acc, dim, nl, L, G, ng, nblk, q0, Qt);
+}
 // The R rotations of a plaintext in ONE launch: out[i][j][co] = m[j][perm_{g_i}(co)] (the gather form of the evaluation-form
 // automorphism, k_moddown_combine's index map), galois[i] = 5^i mod 2N, identity for g = 1 (rotation 0).  grid (N/256, nl, R)
 __global__ __launch_bounds__(256) void k_automorph_batch(int logN, const u64 *__restrict__ m, u64 *__restrict__ out, int nl,
@@ -1874,6 +1998,12 @@ int hydia_tensor_mq_width(const DbLayout &) { return MQ_QW; }
 // launcher serves what is left with the narrower widths
 constexpr int PQ_MQ_QW = 4;
 int hydia_pq_mq_width(const DbLayout &) { return PQ_MQ_QW; }
+// A batch on a plain gallery: both widths build without scratch, and batches of four or more take QW = 4 — the measured
+// choice: at 2^20 vectors it beats QW = 2 by more than the repeats spread, 10.1 against 10.7 ms of loop B per query
+// (profiles/plain_gallery_batch/README.md).  Two or three queries take QW = 2 (and 1): the launcher serves what is left with the
+// narrower widths
+constexpr int PLAIN_MQ_QW = 4;
+int hydia_plain_mq_width(const DbLayout &) { return PLAIN_MQ_QW; }
 // what every loop-B entry point takes, in the launcher's words (a plain form ignores rqs, q0 and Qt)
 struct LoopB {
     const ModC *mod;
@@ -1926,6 +2056,19 @@ static void launch_stream(FormPlainCtMq, hipStream_t st, dim3 grid, const LoopB 
 template <int KS, int QW>
 static void launch_split(FormPlainCtMq, hipStream_t st, dim3 grid, const LoopB &p) {
     hipLaunchKernelGGL((k_hydia_pq_mq_sk<KS, QW>), grid, dim3(64 * KS), 0, st, p.mod, p.N, p.rot, p.rqs, p.db, p.acc, p.dim, p.nl, p.L, p.G,
+                       p.ng, p.nblk, p.q0, p.Qt);
+}
+template <class A, int BPP, int QW, int NW>
+static void launch_stream(FormCtPlainMq, hipStream_t st, dim3 grid, const LoopB &p, int j0) {
+    // (Halves24<false> is not instantiated for this family either: a batch keeps the 128-bit sums there, see loop_b)
+    if constexpr (BPP == 1 && !std::is_same<A, Halves24<false>>::value)
+        hipLaunchKernelGGL((k_hydia_plain_mq<A, QW, NW>), grid, dim3(64 * NW), 0, st, p.mod, p.N, p.rot, p.rqs, p.db, p.acc, p.dim, p.nl, p.Gq,
+                           p.xm, p.L, j0, p.G, p.ng, p.nblk, p.q0, p.Qt);
+    else throw std::logic_error("hydia: no such kernel for a batch on a plain gallery (one block per wave; 128-bit sums or 46-bit halves)");
+}
+template <int KS, int QW>
+static void launch_split(FormCtPlainMq, hipStream_t st, dim3 grid, const LoopB &p) {
+    hipLaunchKernelGGL((k_hydia_plain_mq_sk<KS, QW>), grid, dim3(64 * KS), 0, st, p.mod, p.N, p.rot, p.rqs, p.db, p.acc, p.dim, p.nl, p.L, p.G,
                        p.ng, p.nblk, p.q0, p.Qt);
 }
 // an instantiation's name as rocprofv3 prints it (namespaces dropped), which is what the byte ledger records; QW only where the form
@@ -2061,6 +2204,13 @@ void hydia_pq_accumulate_multi(hipStream_t st, const ModC *mod, int N, const u64
                                int dim, int nl, const DbLayout &L, int ng, int width) {
     if (L.plain) throw std::logic_error("hydia: plain-query loop B launched against a plain gallery");
     loop_b<FormPlainCtMq>(st, mod, N, rot, rqs, db, acc, Q, G, dim, nl, L, ng, TENSOR_BATCH, 0, width > 0 ? width : hydia_pq_mq_width(L));
+}
+// A batch of encrypted queries on a plain gallery over the same routine, with the other batches' choices (workgroup = the layout's group
+// or 4 / 2 / 1 waves by divisibility of G, limb 0 on the split kernel for few ciphertext-major blocks, the arithmetic per layout)
+void hydia_plain_accumulate_multi(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G,
+                                  int dim, int nl, const DbLayout &L, int ng, int width) {
+    if (!L.plain) throw std::logic_error("hydia: plain loop B launched against a ciphertext database");
+    loop_b<FormCtPlainMq>(st, mod, N, rot, rqs, db, acc, Q, G, dim, nl, L, ng, TENSOR_BATCH, 0, width > 0 ? width : hydia_plain_mq_width(L));
 }
 void automorph_batch(hipStream_t st, int logN, const u64 *m, u64 *out, int nl, int R, const unsigned *galois) {
     ledger_add("k_automorph_batch", (1.0 + R) * nl * LP_BYTES(1 << logN));

@@ -111,6 +111,10 @@ def load_library():
         "hydia_index_scenario_pq_multi": (i32, [vp, vp, u32, vp]),
         "hydia_membership_scenario_pq_multi": (i32, [vp, vp, u32, vp]),
         "hydia_set_pq_batch_width": (i32, [vp, u32]),
+        "hydia_compute_similarity_gallery_multi": (i32, [vp, vp, u32, vp]),
+        "hydia_index_scenario_gallery_multi": (i32, [vp, vp, u32, vp]),
+        "hydia_membership_scenario_gallery_multi": (i32, [vp, vp, u32, vp]),
+        "hydia_set_gallery_batch_width": (i32, [vp, u32]),
         "hydia_db_import_ct": (i32, [vp, sz, vp]),
         "hydia_db_export_ct": (i32, [vp, sz, vp]),
         "hydia_db_fill_random": (i32, [vp, sz, u64]),
@@ -743,6 +747,12 @@ class Context:
         compares the widths with it)"""
         _chk(self.L.hydia_set_pq_batch_width(self.h, int(width)))
 
+    def set_gallery_batch_width(self, width):
+        """UNSTABLE (hydia_set_gallery_batch_width: measurements and tests only).  Queries one pass over a plain gallery serves in a
+        *GalleryMulti batch on this context: 1, 2 or 4; 0 = the library's choice.  No result depends on it
+        (tools/bench_plain_gallery.py --batch compares the widths with it)"""
+        _chk(self.L.hydia_set_gallery_batch_width(self.h, int(width)))
+
     def kernel_time(self, name):
         ms, n = C.c_double(), C.c_uint64()
         _chk(self.L.hydia_kernel_time(self.h, name.encode(), C.byref(ms), C.byref(n)))
@@ -935,6 +945,30 @@ class DiagonalSender:
 
     def membershipScenarioPlainMulti(self, plaintexts):
         return self._plain_multi("hydia_membership_scenario_pq_multi", plaintexts)
+
+    # ---- several ENCRYPTED queries against a PLAIN gallery (kinds 7 / 8) in shared passes over it (names of their own: the *Multi
+    # methods keep refusing a plain gallery).  A list of Ciphertext in, a list out: per query exactly what the single method returns
+    def _gallery_multi(self, fn, query_ciphers):
+        qs = list(query_ciphers)
+        if any(not isinstance(q, Ciphertext) or isinstance(q, Plaintext) for q in qs):
+            raise HydiaError(-1, "hydia: a *GalleryMulti method takes encrypted queries (Ciphertext): a plain gallery under a plain query would keep nothing private")
+        if not isinstance(self.cc, Context):
+            raise HydiaError(-2, "hydia: a plain gallery (kind 7 / 8) is not served on a sharded context")
+        fn = getattr(self.cc.L, fn)
+        n = len(qs)
+        hs = (C.c_void_p * max(n, 1))(*[q.h for q in qs])
+        out = (C.c_void_p * max(n, 1))()
+        _chk(fn(self.cc.h, hs, n, out))
+        return [Ciphertext(self.cc, C.c_void_p(out[i])) for i in range(n)]
+
+    def computeSimilarityGalleryMulti(self, query_ciphers):
+        return self._gallery_multi("hydia_compute_similarity_gallery_multi", query_ciphers)
+
+    def indexScenarioGalleryMulti(self, query_ciphers):
+        return self._gallery_multi("hydia_index_scenario_gallery_multi", query_ciphers)
+
+    def membershipScenarioGalleryMulti(self, query_ciphers):
+        return self._gallery_multi("hydia_membership_scenario_gallery_multi", query_ciphers)
 
     # ---- loop A split over the GPUs of a node (sender_diag.cpp:23-26 cut into ranges; image_matching_amd.sharding)
     def rotateQueryRange(self, query_cipher, first, count):

@@ -278,7 +278,8 @@ int hydia_db_export_ct(hydia_ctx *ctx, size_t t, uint64_t *data);
  *                             HYDIA_ERR_ARG); every plaintext starts as the zero polynomial
  *   hydia_plain_db_import_pt  a residue at or above its q_j: HYDIA_ERR_ARG, nothing written; without a plain gallery HYDIA_ERR_STATE
  * Served on a plain gallery, by dispatch on the resident kind: hydia_compute_similarity, hydia_index_scenario,
- * hydia_membership_scenario, hydia_rotate_query, hydia_db_kind / _babies / _stats / _group / _residue_bits.
+ * hydia_membership_scenario, hydia_rotate_query, hydia_db_kind / _babies / _stats / _group / _residue_bits; batches of queries by
+ * entry points of their own, hydia_*_gallery_multi (below, after hydia_*_multi).
  * NOT served yet — each answers HYDIA_ERR_STATE with a message naming the plain gallery, before any work is enqueued and with the
  * gallery untouched: hydia_*_multi, hydia_*_rotated, hydia_rotate_query_range*, hydia_db_update*, hydia_db_save, hydia_db_import_ct,
  * hydia_db_export_ct, hydia_db_set_babies; there is no hydia_group_* enrolment of a plain gallery, and hydia_plain_db_enroll /
@@ -335,6 +336,19 @@ int hydia_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **
 int hydia_compute_similarity_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out);
 int hydia_index_scenario_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out);
 int hydia_membership_scenario_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out);
+/* The same for a PLAIN GALLERY (database kinds 7 / 8; hydia_*_multi above keep answering HYDIA_ERR_STATE on one): n_queries encrypted
+ * queries share passes over the gallery, out[q] receives exactly what the single-query entry returns for queries[q] on that gallery,
+ * bit for bit, and is freed on its own.  On any error every out[q] is NULL, nothing has been enqueued and the gallery is as it was:
+ * an empty batch, a NULL handle, a query that is not one fresh 2-component ciphertext at full level, unequal scales: HYDIA_ERR_ARG;
+ * a ciphertext database of kind 5 / 6 (its batches are hydia_*_multi's), any other kind, no database, a shard context of a group, a
+ * key the scenario needs that is not loaded (the single entry's message): HYDIA_ERR_STATE. */
+int hydia_compute_similarity_gallery_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out);
+int hydia_index_scenario_gallery_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out);
+int hydia_membership_scenario_gallery_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out);
+/* UNSTABLE, for measurements and tests only (tools/bench_plain_gallery.py --batch).  The queries one pass over the gallery of a
+ * *_gallery_multi call serves on this context, 1, 2 or 4; 0 = the library's choice (the default).  The results do not depend on it.
+ * Another value: HYDIA_ERR_ARG. */
+int hydia_set_gallery_batch_width(hydia_ctx *ctx, uint32_t width);
 /* ---- plain query: a KNOWN probe against the ENCRYPTED database (kinds 5 / 6).  An extension with no counterpart in the reference,
  * for the deployment where the operator of the sender produces the probe itself (it runs the cameras or the door) and the gallery
  * belongs to someone else (an agency's watchlist, another company's staff list).  TRUST MODEL:

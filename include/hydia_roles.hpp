@@ -288,6 +288,23 @@ class DiagonalSender : public Sender {
         for (hydia_ct *h : run_multi(queryCiphers, hydia_index_scenario_multi, "indexScenarioMulti")) r.push_back(split_batch(cc, h));
         return r;
     }
+    // The same against a PLAIN gallery (PlainEnroller, database kinds 7 / 8; the *Multi methods above keep refusing one): the queries
+    // share passes over the gallery; per query exactly what the single-query method returns.  Not on a sharded context: an error, empty.
+    std::vector<std::vector<Ciphertext>> computeSimilarityGalleryMulti(std::vector<std::vector<Ciphertext>> &queryCiphers) {
+        std::vector<std::vector<Ciphertext>> r;
+        for (hydia_ct *h : run_multi(queryCiphers, hydia_compute_similarity_gallery_multi, "computeSimilarityGalleryMulti")) r.push_back(split_batch(cc, h));
+        return r;
+    }
+    std::vector<Ciphertext> membershipScenarioGalleryMulti(std::vector<std::vector<Ciphertext>> &queryCiphers) {
+        std::vector<Ciphertext> r;
+        for (hydia_ct *h : run_multi(queryCiphers, hydia_membership_scenario_gallery_multi, "membershipScenarioGalleryMulti")) r.push_back(split_batch(cc, h)[0]);
+        return r;
+    }
+    std::vector<std::vector<Ciphertext>> indexScenarioGalleryMulti(std::vector<std::vector<Ciphertext>> &queryCiphers) {
+        std::vector<std::vector<Ciphertext>> r;
+        for (hydia_ct *h : run_multi(queryCiphers, hydia_index_scenario_gallery_multi, "indexScenarioGalleryMulti")) r.push_back(split_batch(cc, h));
+        return r;
+    }
     // A plain query (an extension; hydia.h): the sender knows the probe, the database (kinds 5 / 6) stays encrypted and so does every
     // result.  encodeQuery makes exactly the plaintext DiagonalReceiver::encryptQuery encrypts — no seed, no key; the overloads return
     // what the ciphertext methods return.  No rotation key 1 .. vector_dim-1 is needed.  Not on a sharded context: an error, empty.
