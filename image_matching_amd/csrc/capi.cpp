@@ -559,7 +559,7 @@ int hydia_db_update_shard(hydia_ctx *ctx, size_t first_vector, double *rows, siz
     REQUIRE(ctx, "null argument");
     use_device(ctx);
     Context &cx = ctx->cx;
-    if (cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: it is not updated in place yet (enrol it again)");
+    if (cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: it is updated in place by hydia_plain_db_update (no seed: nothing is encrypted)");
     if (!cx.d_db || cx.db_cts == 0 || (cx.db_kind != 5 && cx.db_kind != 6))
         return fail(HYDIA_ERR_STATE, "hydia: no diagonal database resident (an update needs kind 5 or 6: hydia_db_enroll, hydia_db_load or an import)");
     REQUIRE(seed, "null argument");
@@ -696,6 +696,40 @@ int hydia_plain_db_export_pt(hydia_ctx *ctx, size_t t, uint64_t *data) {
     cx.sync();
     HIP_CHECK(hipMemcpy(data, tmp, e * sizeof(u64), hipMemcpyDeviceToHost));
     cx.pool.put(tmp);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_plain_db_update(hydia_ctx *ctx, size_t first_vector, double *rows, size_t n, int normalise) {
+    API_BEGIN
+    REQUIRE(ctx, "null argument");
+    use_device(ctx);
+    Context &cx = ctx->cx;
+    if (cx.d_db && cx.db_cts && (cx.db_kind == 5 || cx.db_kind == 6))
+        return fail(HYDIA_ERR_STATE, "hydia: a ciphertext database (kind 5 / 6) is resident: it is updated in place by hydia_db_update (with a seed)");
+    if (!cx.d_db || cx.db_cts == 0 || !cx.db_plain())
+        return fail(HYDIA_ERR_STATE, "hydia: no plain gallery resident (an update needs kind 7 or 8: hydia_plain_db_enroll, hydia_plain_db_alloc or hydia_plain_db_load)");
+    REQUIRE(first_vector <= cx.db_vectors, "first_vector lies past the end of the gallery (an update leaves no holes)");
+    REQUIRE(n <= SIZE_MAX / sizeof(double) / (size_t)cx.prm.dim && first_vector + n >= first_vector, "row count out of range");
+    if (n == 0) return HYDIA_OK;
+    REQUIRE(rows, "null rows");
+    client_plain_db_update(cx, first_vector, rows, n, normalise);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_plain_db_save(hydia_ctx *ctx, const char *path) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && path, "null argument");
+    ctx->cx.plain_db_save(path);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_plain_db_load(hydia_ctx *ctx, const char *path) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && path, "null argument");
+    if (ctx->in_group) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is not loaded on a shard of a group: the sharded senders do not serve it yet");
+    ctx->cx.plain_db_load(path);
     return HYDIA_OK;
     API_END
 }

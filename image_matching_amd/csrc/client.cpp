@@ -379,6 +379,37 @@ void client_db_update(Context &cx, size_t first_vector, double *rows, size_t n, 
     cx.pool.put((u64 *)d_rows);
 }
 
+// In-place update of a resident PLAIN gallery (kind 7 / 8): client_db_update's loop with encode_device in place of encrypt_device —
+// no seed, no nonce.  Per touched block the sparse diagonal image of the rows at their slots is ENCODED as client_plain_enroll
+// encodes (E_t) and added to a block that existed ((old_t + E_t) mod q_j, canonical) or stored as a new one — a new block is bit
+// for bit that block of client_plain_enroll on the same rows.  The encoder rounds once per update, and symmetrically:
+// encode(-x) + encode(x) = 0 in every residue, so the negated rows restore an existing block exactly.  Form and kind stay.
+void client_plain_db_update(Context &cx, size_t first_vector, double *rows, size_t n, int normalise) {
+    if (n == 0) return;
+    const int dim = cx.prm.dim, Nh = cx.slots, babies = cx.db_babies;
+    if (normalise)
+        for (size_t v = 0; v < n; v++) normalize(rows + v * dim, dim);
+    const size_t G_old = cx.db_cts / dim, pt_elems = (size_t)cx.nQ * cx.N;
+    const size_t n_new = std::max(cx.db_vectors, first_vector + n), G_new = (n_new + (size_t)Nh - 1) / (size_t)Nh;
+    cx.db_grow(n_new, G_new * (size_t)dim);  // (throws before anything is touched when a larger gallery does not fit)
+    double *d_rows = (double *)cx.pool.get(sizeof(double) * (size_t)Nh * dim);
+    double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)dim * Nh);
+    u64 *d_pts = cx.pool.get(sizeof(u64) * (size_t)dim * pt_elems);
+    const size_t end = first_vector + n;
+    for (size_t g = first_vector / (size_t)Nh; g * (size_t)Nh < end; g++) {
+        const size_t lo = std::max(first_vector, g * (size_t)Nh), hi = std::min(end, (g + 1) * (size_t)Nh);
+        HIP_CHECK(hipMemcpyAsync(d_rows, rows + (lo - first_vector) * dim, sizeof(double) * (hi - lo) * dim, hipMemcpyHostToDevice, cx.stream));
+        hc::diag_pack(cx.stream, d_rows, (long long)(hi - lo), dim, Nh, d_slots, (babies > 0 && babies < dim) ? babies : 0, (int)(lo - g * (size_t)Nh));
+        encode_device(cx, d_slots, dim, d_pts);
+        if (g < G_old) cx.db_accumulate(g * dim, d_pts, dim);
+        else cx.db_store(g * dim, d_pts, dim);
+    }
+    cx.sync();
+    cx.pool.put(d_pts);
+    cx.pool.put((u64 *)d_slots);
+    cx.pool.put((u64 *)d_rows);
+}
+
 #define HY_HERS_NONCE_BASE (1ull << 37)
 // HersEnroller::serializeDB (/root/reference/src/enroller/enroller_hers.cpp:40-93): normalise in place, then per matrix of
 // `slots` vectors one ciphertext per dimension holding that coordinate of every vector

@@ -28,6 +28,8 @@ void client_plain_enroll(Context &cx, double *db, size_t n, int babies);
 // a plain query: the plaintext client_encrypt_query encrypts, encoded and not encrypted ([1][1][nQ][N])
 Ct client_encode_query(Context &cx, const double *query);
 void client_db_update(Context &cx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32], size_t first_block = 0);
+// resident kind 7 / 8 gallery += the ENCODED sparse diagonal image of rows[n][dim] at vectors first_vector .. (no seed, no nonce)
+void client_plain_db_update(Context &cx, size_t first_vector, double *rows, size_t n, int normalise);
 // HERS (approach 4): column-packed enrolment and the vector_dim broadcast query ciphertexts
 void client_hers_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32]);
 Ct client_hers_encrypt_query(Context &cx, const double *query, const uint8_t seed[32], uint64_t nonce0);

@@ -649,12 +649,14 @@ void Context::db_relayout(int form) {
 // call fails with a DeviceError BEFORE anything is touched.
 void Context::db_grow(size_t n_vectors, size_t cts) {
     if (!d_db || db_cts == 0) throw StateError("hydia: no database resident");
-    if (db_plain()) throw StateError("hydia: a plain gallery (kind 7 / 8) is not updated in place");
     if (cts <= db_cts) {
         db_vectors = n_vectors;
         return;
     }
-    const DbLayout want = db_layout_for(cts, db_babies);
+    // a plain gallery (kinds 7 / 8, client_plain_db_update) grows the same way with one polynomial per entry
+    const bool plain = db_plain();
+    const size_t np = plain ? 1 : 2;
+    const DbLayout want = db_layout_for(cts, db_babies, plain);
     sync_all();
     struct Scratch {
         Context *c;
@@ -675,15 +677,15 @@ void Context::db_grow(size_t n_vectors, size_t cts) {
     if (e != hipSuccess) {
         s.fresh = nullptr;
         (void)hipGetLastError();
-        throw DeviceError("hydia: growing the resident database needs a second buffer of " + std::to_string(bytes >> 20) +
-                          " MiB, which does not fit in device memory (" + hipGetErrorString(e) +
-                          "); the database is unchanged — enrol it as a whole, or shard it over more GPUs");
+        throw DeviceError(std::string("hydia: growing the resident ") + (plain ? "plain gallery" : "database") + " needs a second buffer of " +
+                          std::to_string(bytes >> 20) + " MiB, which does not fit in device memory (" + hipGetErrorString(e) + "); the " +
+                          (plain ? "gallery is unchanged — enrol it as a whole" : "database is unchanged — enrol it as a whole, or shard it over more GPUs"));
     }
     if (!want.seq && !db_lay.seq && want.ct_bytes == db_lay.ct_bytes) {
         HIP_CHECK(hipMemcpyAsync(s.fresh, d_db, db_cts * db_lay.ct_bytes, hipMemcpyDeviceToDevice, stream));
     } else {
         const size_t chunk = 16;
-        s.plain = pool.get(chunk * 2 * nQ * N * sizeof(u64));
+        s.plain = pool.get(chunk * np * nQ * N * sizeof(u64));
         for (size_t t0 = 0; t0 < db_cts; t0 += chunk) {
             const int cnt = (int)std::min(chunk, db_cts - t0);
             hk::db_unpack(stream, N, nQ, s.plain, d_db, t0, cnt, db_lay);
@@ -735,7 +737,7 @@ struct DbConv {
 }  // namespace
 void Context::db_save(const char *path) {
     if (!d_db || db_cts == 0) throw StateError("hydia: no database resident");
-    if (db_plain()) throw StateError("hydia: a plain gallery (kind 7 / 8) is not saved: the file format holds ciphertexts");
+    if (db_plain()) throw StateError("hydia: a plain gallery (kind 7 / 8) is not saved by hydia_db_save, whose files hold ciphertexts: use hydia_plain_db_save");
     if (db_kind == 1) throw StateError("hydia: a row-packed database (approach 1) is not saved: the file format describes the context's packing, not kind 1's plain residues");
     if (db_kind == 3) throw StateError("hydia: a chunk-packed database (approach 3) is not saved: the file format describes the context's packing, not kind 3's plain residues");
     sync_all();
@@ -749,17 +751,21 @@ void Context::db_save(const char *path) {
     h.n_vectors = db_vectors; h.n_cts = db_cts; h.ct_bytes = ctm.ct_bytes;
     for (int j = 0; j < nQ; j++) h.moduli[j] = q[j];
     if (fwrite(&h, sizeof h, 1, fc.f) != 1) throw std::runtime_error("hydia: write failed (header)");
+    db_write_payload(fc.f, ctm);
+}
+// the entries in order, ciphertext-major (`ctm`: two polynomials per entry, or one for a plain gallery), after the header
+void Context::db_write_payload(FILE *f, const DbLayout &ctm) {
     const size_t total = db_cts * ctm.ct_bytes;
     if (!db_lay.seq) {
         PinnedBuf buf(std::min(total, DB_IO_CHUNK));
         for (size_t off = 0; off < total; off += DB_IO_CHUNK) {
             const size_t n = std::min(DB_IO_CHUNK, total - off);
             HIP_CHECK(hipMemcpy(buf.p, d_db + off, n, hipMemcpyDeviceToHost));
-            if (fwrite(buf.p, 1, n, fc.f) != n) throw std::runtime_error("hydia: write failed (disk full?)");
+            if (fwrite(buf.p, 1, n, f) != n) throw std::runtime_error("hydia: write failed (disk full?)");
         }
         return;
     }
-    // group-sequential resident layout: DB_CONV_CTS ciphertexts at a time through plain residues into a ciphertext-major staging image
+    // group-sequential resident layout: DB_CONV_CTS entries at a time through plain residues into a ciphertext-major staging image
     DbConv cv(this, ctm);
     PinnedBuf buf(DB_CONV_CTS * ctm.ct_bytes);
     for (size_t t0 = 0; t0 < db_cts; t0 += DB_CONV_CTS) {
@@ -768,8 +774,92 @@ void Context::db_save(const char *path) {
         hk::db_pack(stream, N, nQ, cv.plain, cv.image, 0, (int)cnt, ctm);
         HIP_CHECK(hipMemcpyAsync(buf.p, cv.image, cnt * ctm.ct_bytes, hipMemcpyDeviceToHost, stream));
         sync();
-        if (fwrite(buf.p, 1, cnt * ctm.ct_bytes, fc.f) != cnt * ctm.ct_bytes) throw std::runtime_error("hydia: write failed (disk full?)");
+        if (fwrite(buf.p, 1, cnt * ctm.ct_bytes, f) != cnt * ctm.ct_bytes) throw std::runtime_error("hydia: write failed (disk full?)");
     }
+}
+// hydia_plain_db_save: a plain gallery (kinds 7 / 8) in db_save's streaming format — the same header with kind 7 / 8, n_cts = the
+// number of plaintexts and ct_bytes = the bytes of ONE plaintext in the ciphertext-major layout of the context's packing; then the
+// plaintexts in order, ciphertext-major
+void Context::plain_db_save(const char *path) {
+    if (!d_db || db_cts == 0 || !db_plain()) throw StateError("hydia: no plain gallery resident (hydia_plain_db_enroll, hydia_plain_db_alloc or hydia_plain_db_load); a ciphertext database is saved by hydia_db_save");
+    sync_all();
+    FileCloser fc{fopen(path, "wb")};
+    if (!fc.f) throw std::runtime_error(std::string("hydia: cannot open ") + path + " for writing");
+    DbFileHeader h{};
+    memcpy(h.magic, "HYDIADB1", 8);
+    h.logN = (uint32_t)prm.logN; h.nQ = (uint32_t)nQ; h.dim = (uint32_t)prm.dim; h.packed = db_packed ? 1 : 0; h.kind = (uint32_t)db_kind;
+    h.babies = (uint32_t)db_babies;
+    const DbLayout ctm = hk::db_layout(N, nQ, db_packed ? 1 : 0, true);
+    h.n_vectors = db_vectors; h.n_cts = db_cts; h.ct_bytes = ctm.ct_bytes;
+    for (int j = 0; j < nQ; j++) h.moduli[j] = q[j];
+    if (fwrite(&h, sizeof h, 1, fc.f) != 1) throw std::runtime_error("hydia: write failed (header)");
+    db_write_payload(fc.f, ctm);
+}
+// hydia_plain_db_load.  Every header check (parameters, prime chain, packing, kind, baby count, plaintext count, exact file size)
+// comes before anything is allocated or the resident database is touched.  The file is untrusted and nothing authenticates a
+// plaintext, while loop B's bounds and the 46-bit fields assume canonical residues: every chunk's unpacked residues are checked ON THE
+// DEVICE (k_db_check_canonical) before they are stored.  A residue at or above its modulus, like a short read, is found in mid-load:
+// it throws (HYDIA_ERR_ARG) and leaves NO database resident (kind 0, zero counts).  The gallery takes the form the file declares.
+void Context::plain_db_load(const char *path) {
+    FileCloser fc{fopen(path, "rb")};
+    if (!fc.f) throw std::runtime_error(std::string("hydia: cannot open ") + path);
+    DbFileHeader h{};
+    if (fread(&h, sizeof h, 1, fc.f) != 1 || memcmp(h.magic, "HYDIADB1", 8) != 0) throw std::runtime_error("hydia: not a hydia database file");
+    if ((int)h.logN != prm.logN || (int)h.nQ != nQ || (int)h.dim != prm.dim) throw std::runtime_error("hydia: database file was written for other parameters");
+    for (int j = 0; j < nQ; j++)
+        if (h.moduli[j] != q[j]) throw std::runtime_error("hydia: database file was written on another prime chain");
+    if (h.kind == 4 || h.kind == 5 || h.kind == 6)
+        throw std::runtime_error("hydia: the file holds a ciphertext database (kind " + std::to_string(h.kind) + "), not a plain gallery: load it with hydia_db_load");
+    if (h.kind != 7 && h.kind != 8) throw std::runtime_error("hydia: database file has an unknown packing kind");
+    const DbLayout ctm = hk::db_layout(N, nQ, db_packed ? 1 : 0, true);
+    if ((h.packed != 0) != db_packed || h.ct_bytes != ctm.ct_bytes)
+        throw std::runtime_error("hydia: database file layout (48-bit packed / 8-byte) differs from this context's");
+    if (h.kind == 8 && (h.babies < 2 || h.babies >= (uint32_t)prm.dim || (h.babies & (h.babies - 1)) || prm.dim % h.babies))
+        throw std::runtime_error("hydia: database file carries an invalid baby count");
+    if (h.kind == 7 && h.babies != (uint32_t)prm.dim) throw std::runtime_error("hydia: database file header is inconsistent (kind 7 with a baby count other than vector_dim)");
+    if (h.n_vectors < 1 || h.n_cts < 1) throw std::runtime_error("hydia: database file header declares an empty database");
+    const uint64_t dim = (uint64_t)prm.dim, S = (uint64_t)slots;
+    if (h.n_vectors > (UINT64_MAX - S) || h.n_cts != ((h.n_vectors + S - 1) / S) * dim)
+        throw std::runtime_error("hydia: database file header is inconsistent (plaintext count does not match the vector count)");
+    {
+        struct stat sb {};
+        if (fstat(fileno(fc.f), &sb) != 0) throw std::runtime_error("hydia: cannot stat the database file");
+        const unsigned __int128 need = (unsigned __int128)h.n_cts * h.ct_bytes + sizeof h;
+        if ((unsigned __int128)sb.st_size < need) throw std::runtime_error("hydia: database file is truncated");
+        if ((unsigned __int128)sb.st_size > need) throw std::runtime_error("hydia: database file has trailing bytes");
+    }
+    sync_all();  // an earlier, still asynchronous query may be reading the resident database this load overwrites
+    db_kind = 0;
+    db_resize(h.n_vectors, h.n_cts, (int)h.babies, true);
+    struct Flag {
+        unsigned *d = nullptr;
+        Flag() { HIP_CHECK(hipMalloc((void **)&d, sizeof(unsigned))); }
+        ~Flag() { (void)hipFree(d); }
+    } flag;
+    HIP_CHECK(hipMemsetAsync(flag.d, 0, sizeof(unsigned), stream));
+    DbConv cv(this, ctm);
+    PinnedBuf buf(DB_CONV_CTS * ctm.ct_bytes);
+    for (size_t t0 = 0; t0 < db_cts; t0 += DB_CONV_CTS) {
+        const size_t cnt = std::min(DB_CONV_CTS, db_cts - t0);
+        if (fread(buf.p, 1, cnt * ctm.ct_bytes, fc.f) != cnt * ctm.ct_bytes) {
+            db_vectors = db_cts = 0;  // nothing usable is resident
+            throw std::runtime_error("hydia: database file is truncated");
+        }
+        HIP_CHECK(hipMemcpyAsync(cv.image, buf.p, cnt * ctm.ct_bytes, hipMemcpyHostToDevice, stream));
+        hk::db_unpack(stream, N, nQ, cv.plain, cv.image, 0, (int)cnt, ctm);
+        hk::db_check_canonical(stream, d_mod, N, nQ, cv.plain, (int)cnt, flag.d);
+        db_store(t0, cv.plain, (int)cnt);
+        unsigned bad = 0;
+        HIP_CHECK(hipMemcpyAsync(&bad, flag.d, sizeof bad, hipMemcpyDeviceToHost, stream));
+        sync();  // the pinned buffer is refilled next
+        if (bad) {
+            db_vectors = db_cts = 0;
+            throw std::runtime_error("hydia: the plain gallery file holds a residue at or above its modulus (plaintexts " + std::to_string(t0) + " .. " +
+                                     std::to_string(t0 + cnt - 1) + "); no database is resident");
+        }
+    }
+    db_kind = (int)h.kind;
+    db_babies = (int)h.babies;
 }
 void Context::db_load(const char *path) {
     FileCloser fc{fopen(path, "rb")};
@@ -779,6 +869,8 @@ void Context::db_load(const char *path) {
     if ((int)h.logN != prm.logN || (int)h.nQ != nQ || (int)h.dim != prm.dim) throw std::runtime_error("hydia: database file was written for other parameters");
     for (int j = 0; j < nQ; j++)
         if (h.moduli[j] != q[j]) throw std::runtime_error("hydia: database file was written on another prime chain");
+    if (h.kind == 7 || h.kind == 8)  // (looked at before the ct_bytes comparison: a plaintext has half a ciphertext's bytes)
+        throw std::runtime_error("hydia: the file holds a plain gallery (kind " + std::to_string(h.kind) + "), not a ciphertext database: load it with hydia_plain_db_load");
     const DbLayout ctm = hk::db_layout(N, nQ, db_packed ? 1 : 0);
     if ((h.packed != 0) != db_packed || h.ct_bytes != ctm.ct_bytes)
         throw std::runtime_error("hydia: database file layout (48-bit packed / 8-byte) differs from this context's");

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <exception>
 #include <map>
 #include <mutex>
@@ -211,13 +212,18 @@ struct Context : HostParams {
     void db_resize(size_t n_vectors, size_t cts, int form, bool plain = false);
     void db_resize_rows(size_t n_vectors, size_t cts);  // kind 1: `cts` ciphertexts as plain [ct][2][nQ][N] residues
     void db_relayout(int form);  // the same ciphertexts laid out for another form (a second buffer for the duration)
-    void db_grow(size_t n_vectors, size_t cts);  // kind 5 / 6: room for more blocks, old ciphertexts kept (a second buffer for the duration)
+    void db_grow(size_t n_vectors, size_t cts);  // kind 5 / 6 / 7 / 8: room for more blocks, old entries kept (a second buffer for the duration)
     // persistence of the resident database (own streaming format: header + the ciphertext-major layout verbatim, so a restart does
     // not re-enrol from plaintext; the reference keeps serial/db_diagonal/index<t>.bin, enroller_diag.cpp:158-166)
     void db_save(const char *path);
     void db_load(const char *path);
+    // the same for a plain gallery (kinds 7 / 8): the same header with ct_bytes = ONE ciphertext-major polynomial; the load checks every
+    // residue on the device (< q_j) and leaves no database resident when one is not
+    void plain_db_save(const char *path);
+    void plain_db_load(const char *path);
+    void db_write_payload(FILE *f, const DbLayout &ctm);  // the entries in order, ciphertext-major (db_save / plain_db_save)
     void db_store(size_t t0, const u64 *d_plain, int X);  // [X][2][nQ][N] device residues -> ciphertexts t0..t0+X-1 ([X][nQ][N] -> plaintexts of a plain gallery)
-    void db_accumulate(size_t t0, const u64 *d_plain, int X);  // ciphertexts t0..t0+X-1 += [X][2][nQ][N] device residues, in place
+    void db_accumulate(size_t t0, const u64 *d_plain, int X);  // ciphertexts t0..t0+X-1 += [X][2][nQ][N] device residues, in place (plaintexts of a plain gallery += [X][nQ][N])
     void db_fetch(size_t t0, u64 *d_plain, int X);
     // kinds 4 / 5 / 6: every resident ciphertext key-switched in place with the caller's switching key (host memory, [dnum][2][nT][N]:
     // client_keygen_switch) — (c0, c1) := (c0 + ks0, ks1); layout, form, kind, scale and order stay.  In chunks sized from free device

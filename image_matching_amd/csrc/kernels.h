@@ -268,8 +268,11 @@ DbLayout db_layout_seq(int N, int nQ, int packed, int bd, int blocks, int bpp, i
 // ciphertexts t0 .. t0+X-1 of the database at `db` <-> plain [X][np][nQ][N] residues, np = db_polys(L)
 void db_pack(hipStream_t st, int N, int nQ, const u64 *plain, void *db, size_t t0, int X, const DbLayout &L);
 void db_unpack(hipStream_t st, int N, int nQ, u64 *plain, const void *db, size_t t0, int X, const DbLayout &L);
-// ciphertexts t0 .. t0+X-1 of the database += plain [X][2][nQ][N] residues mod q_j, in place (db_accum.h; mod = the context's table)
+// ciphertexts t0 .. t0+X-1 of the database += plain [X][2][nQ][N] residues mod q_j, in place (db_accum.h; mod = the context's table);
+// a plain gallery (L.plain): plaintexts t0 .. t0+X-1 += plain [X][nQ][N], through k_plain_db_accumulate / k_plain_db_accumulate46
 void db_accumulate(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *plain, void *db, size_t t0, int X, const DbLayout &L);
+// loading a plain gallery: *flag := 1 when a residue of plain [X][nQ][N] is at or above its modulus (never cleared here)
+void db_check_canonical(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *plain, int X, unsigned *flag);
 // re-keying (Context::db_rekey): polynomial 1 of ciphertexts t0 .. t0+X-1 -> out [X][nQ][N] residues (the key switch's operand), and the
 // key switch's output ks [X][2][nQ][N] back in place: (c0, c1) := (c0 + ks0 mod q_j, ks1)
 void db_gather_poly(hipStream_t st, int N, int nQ, u64 *out, const void *db, size_t t0, int X, const DbLayout &L);

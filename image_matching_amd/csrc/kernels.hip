@@ -1686,6 +1686,42 @@ __global__ __launch_bounds__(256) void k_db_accumulate46(const ModC *__restrict_
     }
     db_accumulate_granule46(reinterpret_cast<unsigned *>(db + db_offset(L, N, t0 + x, p, j, c)), a, mod[j].q);
 }
+// In-place update of a PLAIN gallery (one polynomial per entry): plaintexts t0 .. t0+X-1 += fresh [X][nQ][N] residues, mod q_j, on the
+// same thread-to-bytes map and with the same arithmetic (db_accum.h).  Kernels of their own, so the ciphertext kernels above keep their
+// code.  grid (N/512, nQ or 1, X)
+__global__ __launch_bounds__(256) void k_plain_db_accumulate(const ModC *__restrict__ mod, int N, int nQ, const u64 *__restrict__ plain,
+                                                             unsigned char *__restrict__ db, DbLayout L, size_t t0) {
+    const int j = blockIdx.y, x = blockIdx.z;
+    const size_t c = (size_t)(blockIdx.x * 256 + threadIdx.x) * 2;
+    const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(plain + ((size_t)x * nQ + j) * N + c);
+    db_accumulate_pair(db + db_offset(L, N, t0 + x, 0, j, c), L.packed && j > 0, a.x, a.y, mod[j].q);
+}
+// ... the 46-bit limbs of a bits46 gallery.  grid (N/4096, nQ - 1, X): limb j = blockIdx.y + 1
+__global__ __launch_bounds__(256) void k_plain_db_accumulate46(const ModC *__restrict__ mod, int N, int nQ, const u64 *__restrict__ plain,
+                                                               unsigned char *__restrict__ db, DbLayout L, size_t t0) {
+    const int j = blockIdx.y + 1, x = blockIdx.z;
+    const size_t c = (size_t)(blockIdx.x * 256 + threadIdx.x) * 16;
+    if (c >= (size_t)N) return;
+    const u64 *pl = plain + ((size_t)x * nQ + j) * N + c;
+    u64 a[16];
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+        const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(pl + r);
+        a[r] = v.x;
+        a[r + 1] = v.y;
+    }
+    db_accumulate_granule46(reinterpret_cast<unsigned *>(db + db_offset(L, N, t0 + x, 0, j, c)), a, mod[j].q);
+}
+// Loading a plain gallery from an untrusted file: are the unpacked residues plain [X][nQ][N] canonical (< q_j)?  A flag reduction: a
+// workgroup that saw a residue at or above its modulus sets *flag (never cleared here).  grid (N/512, nQ, X)
+__global__ __launch_bounds__(256) void k_db_check_canonical(const ModC *__restrict__ mod, int N, int nQ, const u64 *__restrict__ plain,
+                                                            unsigned *__restrict__ flag) {
+    const int j = blockIdx.y, x = blockIdx.z;
+    const size_t c = (size_t)(blockIdx.x * 256 + threadIdx.x) * 2;
+    const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(plain + ((size_t)x * nQ + j) * N + c);
+    const u64 q = mod[j].q;
+    if (__syncthreads_or(a.x >= q || a.y >= q) && threadIdx.x == 0) *flag = 1u;
+}
 
 // Re-keying the resident database (Context::db_rekey): polynomial 1 ALONE of ciphertexts t0 .. t0+X-1 out of the resident layout into
 // out [X][nQ][N] u64 — the key switch's c1 operand — on k_db_repack<false>'s thread-to-bytes map; polynomial 0 is never unpacked (the
@@ -2259,10 +2295,22 @@ void db_unpack(hipStream_t st, int N, int nQ, u64 *plain, const void *db, size_t
 // ciphertexts t0 .. t0+X-1 of the database at `db` += plain [X][2][nQ][N] residues (mod q_j): the launch shapes of db_pack
 void db_accumulate(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *plain, void *db, size_t t0, int X, const DbLayout &L) {
     const bool b46 = L.bits46 && L.seq && L.packed && nQ > 1;
+    if (L.plain) {  // a plain gallery: plain [X][nQ][N], one polynomial read and written + nQ N 8 fresh bytes read per entry
+        ledger_add("k_plain_db_accumulate", (double)X * (2.0 * L.ct_bytes + 1.0 * nQ * N * 8));
+        hipLaunchKernelGGL(k_plain_db_accumulate, dim3(N / 512, b46 ? 1 : nQ, X), dim3(256), 0, st, mod, N, nQ, plain, (unsigned char *)db, L, t0);
+        if (b46)
+            hipLaunchKernelGGL(k_plain_db_accumulate46, dim3((N / 16 + 255) / 256, nQ - 1, X), dim3(256), 0, st, mod, N, nQ, plain, (unsigned char *)db, L, t0);
+        return;
+    }
     ledger_add("k_db_accumulate", (double)X * (2.0 * L.ct_bytes + 2.0 * nQ * N * 8));  // resident bytes read and written + the fresh ones read
     hipLaunchKernelGGL(k_db_accumulate, dim3(N / 512, b46 ? 1 : nQ, X * 2), dim3(256), 0, st, mod, N, nQ, plain, (unsigned char *)db, L, t0);
     if (b46)
         hipLaunchKernelGGL(k_db_accumulate46, dim3((N / 16 + 255) / 256, nQ - 1, X * 2), dim3(256), 0, st, mod, N, nQ, plain, (unsigned char *)db, L, t0);
+}
+// *flag |= (some residue of plain [X][nQ][N] is at or above its modulus); the caller clears the flag and reads it back
+void db_check_canonical(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *plain, int X, unsigned *flag) {
+    ledger_add("k_db_check_canonical", (double)X * nQ * N * 8);
+    hipLaunchKernelGGL(k_db_check_canonical, dim3(N / 512, nQ, X), dim3(256), 0, st, mod, N, nQ, plain, flag);
 }
 // polynomial 1 of ciphertexts t0 .. t0+X-1 -> out [X][nQ][N] residues: the launch shapes of db_unpack, one polynomial per ciphertext
 void db_gather_poly(hipStream_t st, int N, int nQ, u64 *out, const void *db, size_t t0, int X, const DbLayout &L) {

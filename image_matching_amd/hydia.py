@@ -100,6 +100,9 @@ def load_library():
         "hydia_plain_db_alloc": (i32, [vp, sz, i32]),
         "hydia_plain_db_import_pt": (i32, [vp, sz, vp]),
         "hydia_plain_db_export_pt": (i32, [vp, sz, vp]),
+        "hydia_plain_db_update": (i32, [vp, sz, vp, sz, i32]),
+        "hydia_plain_db_save": (i32, [vp, C.c_char_p]),
+        "hydia_plain_db_load": (i32, [vp, C.c_char_p]),
         "hydia_encode_query": (i32, [vp, vp, pp]),
         "hydia_pt_import": (i32, [vp, vp, dbl, pp]),
         "hydia_pt_export": (i32, [vp, vp, vp]),
@@ -665,6 +668,22 @@ class Context:
         _chk(self.L.hydia_plain_db_export_pt(self.h, t, _p(out)))
         return out
 
+    def plain_db_update(self, first_vector, rows, normalise=True):
+        """hydia_plain_db_update: add the ENCODED sparse image of `rows` (k x vector_dim float64, normalised IN PLACE when `normalise`),
+        placed at vectors first_vector .., to the resident plain gallery — db_update without a seed.  Append: first_vector =
+        db_stats()[0]; remove: the negated template (the same rows negated restore an existing block bit for bit); replace:
+        new_normalised - old_normalised with normalise=False."""
+        assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.ndim == 2 and rows.shape[1] == self.dim
+        _chk(self.L.hydia_plain_db_update(self.h, first_vector, _p(rows), rows.shape[0], 1 if normalise else 0))
+
+    def plain_db_save(self, path):
+        """write the resident plain gallery to `path` (db_save's format, one polynomial per entry)"""
+        _chk(self.L.hydia_plain_db_save(self.h, str(path).encode()))
+
+    def plain_db_load(self, path):
+        """load a plain gallery file; every residue is checked on the device, and a bad one leaves no database resident"""
+        _chk(self.L.hydia_plain_db_load(self.h, str(path).encode()))
+
     def db_update(self, first_vector, rows, normalise=True, seed=None, first_block=0):
         """hydia_db_update[_shard]: add a FRESH encryption of `rows` (k x vector_dim float64, normalised IN PLACE when `normalise`),
         placed at vectors first_vector .., to the resident kind-5 / kind-6 database.  Append: first_vector = db_stats()[0]; remove:
@@ -821,6 +840,16 @@ class PlainEnroller:
         assert database.dtype == np.float64 and database.flags.c_contiguous
         assert database.shape == (self.numVectors, self.cc.dim)
         _chk(self.cc.L.hydia_plain_db_enroll(self.cc.h, _p(database), self.numVectors))
+
+    def updateRows(self, first_vector, rows, normalise=True):
+        """In-place update (Context.plain_db_update): the encoded image of `rows` at vectors first_vector .. is added to the blocks
+        they touch.  numVectors follows the gallery; a DiagonalSender / DiagonalReceiver built for the old count is rebuilt by the caller."""
+        self.cc.plain_db_update(first_vector, rows, normalise)
+        self.numVectors = max(self.numVectors, first_vector + rows.shape[0])
+
+    def appendDB(self, rows):
+        """append `rows` (normalised in place) after the last enrolled vector"""
+        self.updateRows(self.numVectors, rows, True)
 
 
 class DiagonalReceiver:

@@ -280,15 +280,53 @@ int hydia_db_export_ct(hydia_ctx *ctx, size_t t, uint64_t *data);
  * Served on a plain gallery, by dispatch on the resident kind: hydia_compute_similarity, hydia_index_scenario,
  * hydia_membership_scenario, hydia_rotate_query, hydia_db_kind / _babies / _stats / _group / _residue_bits; batches of queries by
  * entry points of their own, hydia_*_gallery_multi (below, after hydia_*_multi).
+ * In-place updates and files have entry points of their own: hydia_plain_db_update, hydia_plain_db_save / hydia_plain_db_load (below).
  * NOT served yet — each answers HYDIA_ERR_STATE with a message naming the plain gallery, before any work is enqueued and with the
- * gallery untouched: hydia_*_multi, hydia_*_rotated, hydia_rotate_query_range*, hydia_db_update*, hydia_db_save, hydia_db_import_ct,
- * hydia_db_export_ct, hydia_db_set_babies; there is no hydia_group_* enrolment of a plain gallery, and hydia_plain_db_enroll /
- * hydia_plain_db_alloc on a context that is a shard of a group (hydia_group_ctx) answer HYDIA_ERR_STATE the same way.  hydia_db_load of a ciphertext
- * file, like any enrolment, replaces the gallery. */
+ * gallery untouched: hydia_*_multi, hydia_*_rotated, hydia_rotate_query_range*, hydia_db_import_ct, hydia_db_export_ct,
+ * hydia_db_set_babies, and the ciphertext database's hydia_db_update* and hydia_db_save (their messages name hydia_plain_db_update /
+ * hydia_plain_db_save); there is no hydia_group_* enrolment of a plain gallery, and hydia_plain_db_enroll / hydia_plain_db_alloc /
+ * hydia_plain_db_load on a context that is a shard of a group (hydia_group_ctx) answer HYDIA_ERR_STATE the same way.  hydia_db_load of a
+ * ciphertext file, like any enrolment, replaces the gallery. */
 int hydia_plain_db_enroll(hydia_ctx *ctx, double *db /* n x vector_dim row-major */, size_t n);
 int hydia_plain_db_alloc(hydia_ctx *ctx, size_t n_vectors, int babies);
 int hydia_plain_db_import_pt(hydia_ctx *ctx, size_t t, const uint64_t *data /* [n_q][N] */);
 int hydia_plain_db_export_pt(hydia_ctx *ctx, size_t t, uint64_t *data);
+/* In-place update of a resident plain gallery: hydia_db_update's one primitive without seed and nonce.  With n_old the resident vector
+ * count: normalise != 0 normalises every row IN PLACE like hydia_plain_db_enroll, 0 takes the rows as given; first_vector <= n_old (no
+ * holes); afterwards the gallery holds max(n_old, first_vector + n) vectors.  Per block touched by vectors first_vector ..
+ * first_vector + n - 1 the sparse slot image of the rows at their slots (pre-rotated when hydia_db_babies < vector_dim) is encoded as
+ * hydia_plain_db_enroll encodes, giving E_t for plaintext t = block * vector_dim + diagonal:
+ *   a block that existed:        plaintext t := (old_t + E_t) mod q_j, residue by residue, stored canonical;
+ *   a block the update creates:  plaintext t := E_t — bit for bit that block of hydia_plain_db_enroll on the same rows;
+ *   every other block is neither read nor written.
+ * Append: first_vector = n_old, normalise = 1.  Remove: the negated template at its index.  Replace: new_normalised - old_normalised
+ * with normalise = 0.  Kind and form stay; the gallery lies afterwards where an enrolment of the new size in that form would put it
+ * (growing a hoisted gallery past 8 blocks moves it from ciphertext-major 48-bit to group-sequential 46-bit residues, a grown
+ * group-sequential gallery may get another group size, a pre-rotated gallery counts (block, giant step) pairs).  Growth needs a second
+ * buffer for its duration: when it does not fit the call answers HYDIA_ERR_DEVICE before anything is touched.
+ * ROUNDING: the encoder rounds once per update.  encode(a) + encode(b) differs from encode(a + b) by at most 1 per coefficient before
+ * the transform — about 2^-45 of the scale per update — so an updated existing block is NOT bit-identical to a fresh enrolment of the
+ * same rows.
+ * THE EXACT INVERSE: the encoder rounds symmetrically, encode(-x) + encode(x) = 0 mod q_j in every residue.  The same rows negated, at
+ * the same first_vector with the same normalise, restore every plaintext of a block that existed bit for bit; blocks the first call
+ * created become zero polynomials, and the vector count stays grown.  Removing one row out of several added in one call leaves at
+ * most the rounding residue above.
+ * Errors, all before any launch and with the gallery untouched: no database resident or a ciphertext database: HYDIA_ERR_STATE (for
+ * kinds 5 / 6 the message names hydia_db_update); first_vector > n_old, null rows with n > 0, or a row count that overflows:
+ * HYDIA_ERR_ARG; n == 0: HYDIA_OK and nothing changes.  It orders itself against queries in flight as hydia_db_update does. */
+int hydia_plain_db_update(hydia_ctx *ctx, size_t first_vector, double *rows /* n x vector_dim row-major */, size_t n, int normalise);
+/* Persistence of a plain gallery in hydia_db_save's streaming format: the same header with kind 7 / 8 and the baby count, n_cts = the
+ * number of plaintexts, ct_bytes = the bytes of ONE plaintext in the ciphertext-major layout of the context's packing; then the
+ * plaintexts in order, ciphertext-major (a group-sequential gallery is converted on the way).  hydia_plain_db_save without a plain
+ * gallery: HYDIA_ERR_STATE.  hydia_plain_db_load checks the header before anything is allocated or the resident database is touched,
+ * each failure HYDIA_ERR_ARG: parameters, prime chain, packing, a valid baby count for kind 8, n_cts equal to what n_vectors implies,
+ * the exact file size (neither truncated nor with trailing bytes); a ciphertext file is refused with a message naming hydia_db_load, as
+ * hydia_db_load refuses a plain-gallery file naming hydia_plain_db_load.  The file is UNTRUSTED and nothing authenticates a plaintext:
+ * every residue is checked on the device while the file streams in, and a residue at or above its q_j — found in mid-load, like a
+ * short read — answers HYDIA_ERR_ARG and leaves NO database resident (kind 0, zero counts): the load is not transactional.  A loaded
+ * gallery takes the form the file declares, whatever hydia_set_matvec says.  On a shard of a group: HYDIA_ERR_STATE. */
+int hydia_plain_db_save(hydia_ctx *ctx, const char *path);
+int hydia_plain_db_load(hydia_ctx *ctx, const char *path);
 /* Persistence of the enrolled database (the reference keeps one serial/db_diagonal/index<t>.bin per ciphertext,
  * src/enroller/enroller_diag.cpp:158-166, and re-reads them every query; here the database stays in HBM and a file is only
  * what a server restart needs).  Own streaming format: a header (parameters, prime chain, packing) + the ciphertexts in order, each

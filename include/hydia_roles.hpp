@@ -612,6 +612,28 @@ class PlainEnroller {
         for (size_t i = 0; i < numVectors && i < database.size(); i++)
             for (size_t j = 0; j < dim && j < database[i].size(); j++) database[i][j] = flat[i * dim + j];
     }
+    // In-place update of the gallery (hydia_plain_db_update): DiagonalEnroller::updateRows without the seed — the ENCODED image of
+    // `rows` placed at vectors first_vector .. is added to the resident blocks they touch.  append: appendDB; remove: the negated
+    // template with normalise = true (the same rows negated restore an existing block bit for bit); replace: new_normalised -
+    // old_normalised with normalise = false.  Normalised rows are written back like serializeDB's.  numVectors follows the gallery;
+    // senders and receivers constructed for the old count are rebuilt by the caller.
+    bool updateRows(size_t first_vector, std::vector<std::vector<double>> &rows, bool normalise = true) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: updateRows: a plain gallery (kind 7 / 8) is not served on a sharded context" << std::endl;
+            return false;
+        }
+        const size_t dim = cc->info.vector_dim;
+        std::vector<double> flat(rows.size() * dim, 0.0);
+        for (size_t i = 0; i < rows.size(); i++)
+            for (size_t j = 0; j < dim && j < rows[i].size(); j++) flat[i * dim + j] = rows[i][j];
+        if (!cc->check(hydia_plain_db_update(cc->h, first_vector, flat.data(), rows.size(), normalise ? 1 : 0), "updateRows")) return false;
+        for (size_t i = 0; i < rows.size(); i++)
+            for (size_t j = 0; j < dim && j < rows[i].size(); j++) rows[i][j] = flat[i * dim + j];
+        if (first_vector + rows.size() > numVectors) numVectors = first_vector + rows.size();
+        return true;
+    }
+    bool appendDB(std::vector<std::vector<double>> &rows) { return updateRows(numVectors, rows, true); }
     size_t size() const { return numVectors; }
 
   private:
