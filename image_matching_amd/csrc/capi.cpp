@@ -995,6 +995,131 @@ void hydia_pt_free(hydia_pt *pt) {
     delete pt;
     if (owner && owner->refs.fetch_sub(1) == 1) delete owner;
 }
+// ------------------------------------------------------------------ templates already in device memory (hydia_dev_rows)
+// every check of a descriptor, before anything is launched: HYDIA_OK, or the code recorded with its message.  A context that is a shard
+// of a group is refused (the group enrols and serves its shards' databases), then the descriptor itself is looked at
+static int check_dev_rows(hydia_ctx *ctx, const hydia_dev_rows *rows, DevRows &out) {
+    if (ctx->in_group) return fail(HYDIA_ERR_STATE, "hydia: rows in device memory are not taken on a shard of a group: the group enrols and serves its shards");
+    REQUIRE((int)rows->dtype >= (int)HYDIA_F64 && (int)rows->dtype <= (int)HYDIA_BF16, "element type outside HYDIA_F64 / HYDIA_F32 / HYDIA_F16 / HYDIA_BF16");
+    const size_t dim = (size_t)ctx->cx.prm.dim, esz = rows->dtype == HYDIA_F64 ? 8 : rows->dtype == HYDIA_F32 ? 4 : 2;
+    REQUIRE(rows->row_stride >= dim, "row_stride is smaller than vector_dim");
+    REQUIRE(rows->n <= SIZE_MAX / 8 / rows->row_stride, "row count out of range");
+    out = DevRows{rows->ptr, (int)rows->dtype, rows->n, rows->row_stride, (hipStream_t)rows->stream};
+    if (rows->n == 0) return HYDIA_OK;
+    REQUIRE(rows->ptr, "null rows");
+    REQUIRE((uintptr_t)rows->ptr % esz == 0, "rows pointer is not aligned to its element type");
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, rows->ptr) != hipSuccess) {
+        (void)hipGetLastError();  // (an address the runtime has never seen: not an error of the device)
+        return fail(HYDIA_ERR_ARG, "hydia: rows pointer is not device memory (host rows go to the host entry point)");
+    }
+    REQUIRE(at.type == hipMemoryTypeDevice, "rows pointer is not device memory (host rows go to the host entry point)");
+    REQUIRE(at.device == ctx->cx.device, "rows lie in the memory of another GPU than the context's");
+    return HYDIA_OK;
+}
+#define CHECK_DEV_ROWS(r)                              \
+    REQUIRE(ctx && rows, "null argument");             \
+    use_device(ctx);                                   \
+    DevRows r;                                         \
+    if (int code_ = check_dev_rows(ctx, rows, r)) return code_;
+
+int hydia_rows_widen_device(hydia_ctx *ctx, const hydia_dev_rows *rows, int normalise, double *dev_dst) {
+    API_BEGIN
+    CHECK_DEV_ROWS(r)
+    if (r.n == 0) return HYDIA_OK;
+    REQUIRE(dev_dst, "null argument");
+    client_rows_widen(ctx->cx, r, normalise, dev_dst);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_db_enroll_device(hydia_ctx *ctx, const hydia_dev_rows *rows, const uint8_t seed[32]) {
+    API_BEGIN
+    CHECK_DEV_ROWS(r)
+    REQUIRE(seed && r.n >= 1, "bad argument");
+    Context &cx = ctx->cx;
+    if (!cx.d_pk) return fail(HYDIA_ERR_STATE, "hydia: public key not loaded");
+    const size_t G = (r.n + (size_t)cx.slots - 1) / (size_t)cx.slots;
+    const int B = cx.babies_for(G, 0);
+    cx.db_kind = 0;
+    cx.db_resize(r.n, hydia_db_num_cts(ctx, r.n), B);
+    client_enroll_device(cx, r, seed, 0, B);
+    cx.db_kind = B < cx.prm.dim ? 6 : 5;
+    cx.db_babies = B;
+    return HYDIA_OK;
+    API_END
+}
+int hydia_plain_db_enroll_device(hydia_ctx *ctx, const hydia_dev_rows *rows) {
+    API_BEGIN
+    CHECK_DEV_ROWS(r)
+    REQUIRE(r.n >= 1, "bad argument");
+    Context &cx = ctx->cx;
+    const size_t G = (r.n + (size_t)cx.slots - 1) / (size_t)cx.slots;
+    const int B = cx.babies_for(G, 0);
+    cx.db_kind = 0;
+    cx.db_resize(r.n, hydia_db_num_cts(ctx, r.n), B, true);
+    client_plain_enroll_device(cx, r, B);
+    cx.db_kind = B < cx.prm.dim ? 8 : 7;
+    cx.db_babies = B;
+    return HYDIA_OK;
+    API_END
+}
+int hydia_db_update_device(hydia_ctx *ctx, size_t first_vector, const hydia_dev_rows *rows, int normalise, const uint8_t seed[32]) {
+    API_BEGIN
+    CHECK_DEV_ROWS(r)
+    Context &cx = ctx->cx;
+    if (cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: it is updated in place by hydia_plain_db_update (no seed: nothing is encrypted)");
+    if (!cx.d_db || cx.db_cts == 0 || (cx.db_kind != 5 && cx.db_kind != 6))
+        return fail(HYDIA_ERR_STATE, "hydia: no diagonal database resident (an update needs kind 5 or 6: hydia_db_enroll, hydia_db_load or an import)");
+    REQUIRE(seed, "null argument");
+    REQUIRE(first_vector <= cx.db_vectors, "first_vector lies past the end of the database (an update leaves no holes)");
+    REQUIRE(first_vector + r.n >= first_vector, "row count out of range");
+    if (r.n == 0) return HYDIA_OK;
+    if (!cx.d_pk) return fail(HYDIA_ERR_STATE, "hydia: public key not loaded");
+    client_db_update_device(cx, first_vector, r, normalise, seed, 0);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_plain_db_update_device(hydia_ctx *ctx, size_t first_vector, const hydia_dev_rows *rows, int normalise) {
+    API_BEGIN
+    CHECK_DEV_ROWS(r)
+    Context &cx = ctx->cx;
+    if (cx.d_db && cx.db_cts && (cx.db_kind == 5 || cx.db_kind == 6))
+        return fail(HYDIA_ERR_STATE, "hydia: a ciphertext database (kind 5 / 6) is resident: it is updated in place by hydia_db_update (with a seed)");
+    if (!cx.d_db || cx.db_cts == 0 || !cx.db_plain())
+        return fail(HYDIA_ERR_STATE, "hydia: no plain gallery resident (an update needs kind 7 or 8: hydia_plain_db_enroll, hydia_plain_db_alloc or hydia_plain_db_load)");
+    REQUIRE(first_vector <= cx.db_vectors, "first_vector lies past the end of the gallery (an update leaves no holes)");
+    REQUIRE(first_vector + r.n >= first_vector, "row count out of range");
+    if (r.n == 0) return HYDIA_OK;
+    client_plain_db_update_device(cx, first_vector, r, normalise);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_encrypt_queries_device(hydia_ctx *ctx, const hydia_dev_rows *rows, const uint8_t seed[32], uint64_t nonce0, hydia_ct **out) {
+    if (out && rows)
+        for (size_t q = 0; q < rows->n; q++) out[q] = nullptr;
+    API_BEGIN
+    CHECK_DEV_ROWS(r)
+    REQUIRE(seed && out, "null argument");
+    REQUIRE(r.n >= 1, "a batch of probes needs at least one row");
+    REQUIRE(nonce0 < HYDIA_NONCE_LIMIT && r.n <= HYDIA_NONCE_LIMIT - nonce0, "nonce must be below 2^40");
+    if (!ctx->cx.d_pk) return fail(HYDIA_ERR_STATE, "hydia: public key not loaded");
+    std::vector<Ct> cts = client_encrypt_queries_device(ctx->cx, r, seed, nonce0);
+    for (size_t q = 0; q < r.n; q++) out[q] = wrap(ctx, std::move(cts[q]));  // compact and owning: no copy, cannot fail
+    return HYDIA_OK;
+    API_END
+}
+int hydia_encode_queries_device(hydia_ctx *ctx, const hydia_dev_rows *rows, hydia_pt **out) {
+    if (out && rows)
+        for (size_t q = 0; q < rows->n; q++) out[q] = nullptr;
+    API_BEGIN
+    CHECK_DEV_ROWS(r)
+    REQUIRE(out, "null argument");
+    REQUIRE(r.n >= 1, "a batch of probes needs at least one row");
+    std::vector<Ct> pts = client_encode_queries_device(ctx->cx, r);
+    for (size_t q = 0; q < r.n; q++) out[q] = wrap_pt(ctx, std::move(pts[q]));
+    return HYDIA_OK;
+    API_END
+}
 int hydia_compute_similarity_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out) { SENDER_CALL(ctx->cx.similarity_pq(query->c)) }
 int hydia_index_scenario_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out) { SENDER_CALL(ctx->cx.index_scenario_pq(query->c)) }
 int hydia_membership_scenario_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out) { SENDER_CALL(ctx->cx.membership_scenario_pq(query->c)) }

@@ -15,6 +15,7 @@
 
 #include "../../include/hydia.h"  // HY_EVK_ID_SWITCH
 #include "client_kernels.h"
+#include "rows_norm.h"
 
 namespace hydia {
 
@@ -223,13 +224,8 @@ void client_encode_plain(Context &cx, const double *slots, int nl, u64 *pt) {
 }
 
 // VectorUtils::plaintextNormalize (vector_utils.cpp:42-51): divide by the L2 norm, zero vector passes through
-static void normalize(double *x, int dim) {
-    double m = 0.0;
-    for (int i = 0; i < dim; i++) m += x[i] * x[i];
-    m = std::sqrt(m);
-    if (m != 0)
-        for (int i = 0; i < dim; i++) x[i] = x[i] / m;
-}
+// (the arithmetic lives in rows_norm.h, where k_rows_widen and the host check share it)
+static void normalize(double *x, int dim) { rn_normalise_row(x, dim); }
 
 Ct client_encrypt_query(Context &cx, const double *query, const uint8_t seed[32], uint64_t nonce) {
     const int dim = cx.prm.dim;
@@ -290,125 +286,230 @@ Ct client_encode_query(Context &cx, const double *query) {
     cx.sync();  // `batch` is host memory of this call
     return out;
 }
-// PlainEnroller::serializeDB — a gallery the sender may see (database kinds 7 / 8): normalise IN PLACE and pack the generalised
-// diagonals exactly as client_enroll does, then ENCODE the vector_dim slot vectors of each block (one polynomial each) into the resident
-// layout.  Plaintext t is the slot image of client_enroll's ciphertext t.
-void client_plain_enroll(Context &cx, double *db, size_t n, int babies) {
-    const int dim = cx.prm.dim, Nh = cx.slots;
-    for (size_t v = 0; v < n; v++) normalize(db + v * dim, dim);
-    const size_t G = cx.db_cts / dim, pt_elems = (size_t)cx.nQ * cx.N;
-    double *d_rows = (double *)cx.pool.get(sizeof(double) * (size_t)Nh * dim);
-    double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)dim * Nh);
-    u64 *d_pts = cx.pool.get(sizeof(u64) * (size_t)dim * pt_elems);
-    for (size_t g = 0; g < G; g++) {
-        const size_t first = g * (size_t)Nh;
-        const size_t rows = n > first ? std::min((size_t)Nh, n - first) : 0;
-        if (rows)
-            HIP_CHECK(hipMemcpyAsync(d_rows, db + first * dim, sizeof(double) * rows * dim, hipMemcpyHostToDevice, cx.stream));
-        hc::diag_pack(cx.stream, d_rows, (long long)rows, dim, Nh, d_slots, (babies > 0 && babies < dim) ? babies : 0);
-        encode_device(cx, d_slots, dim, d_pts);
-        cx.db_store(g * dim, d_pts, dim);
+// ---- where the rows of a block loop come from: the caller's host array (normalised up front by the host entry point, copied block by
+// block) or rows already in device memory (hydia_dev_rows: widened and normalised by ONE k_rows_widen launch per block on that block's
+// slice).  Either way d_rows holds dense normalised doubles afterwards, and everything behind it is shared
+struct RowSource {
+    const double *host = nullptr;
+    const DevRows *dev = nullptr;
+    int normalise = 0;  // device rows only
+    // rows first .. first + count - 1 of the source -> d_rows[count][dim], on the context's stream
+    void stage(Context &cx, size_t first, size_t count, double *d_rows) const {
+        const int dim = cx.prm.dim;
+        if (dev)
+            hc::rows_widen(cx.stream, (const char *)dev->ptr + first * dev->stride * hc::rows_elem_size(dev->dtype), dev->dtype, count, dim,
+                           dev->stride, normalise, d_rows);
+        else
+            HIP_CHECK(hipMemcpyAsync(d_rows, host + first * dim, sizeof(double) * count * dim, hipMemcpyHostToDevice, cx.stream));
     }
+};
+// the context's stream waits for what the producer stream has enqueued so far (no host synchronisation); NULL: the caller guarantees
+// that the rows are complete
+static void wait_for_producer(Context &cx, hipStream_t producer) {
+    if (!producer) return;
+    hipEvent_t ev;
+    HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, producer);
+    if (e == hipSuccess) e = hipStreamWaitEvent(cx.stream, ev, 0);
+    (void)hipEventDestroy(ev);  // (released once the recorded work has completed)
+    HIP_CHECK(e);
+}
+void client_rows_widen(Context &cx, const DevRows &rows, int normalise, double *dev_dst) {
+    wait_for_producer(cx, rows.stream);
+    hc::rows_widen(cx.stream, rows.ptr, rows.dtype, rows.n, cx.prm.dim, rows.stride, normalise, dev_dst);
     cx.sync();
-    cx.pool.put(d_pts);
-    cx.pool.put((u64 *)d_slots);
-    cx.pool.put((u64 *)d_rows);
 }
 
 #define HY_DB_NONCE_BASE (1ull << 36)
 #define HY_NONCE_LIMIT (1ull << 40)
-// DiagonalEnroller::serializeDB: normalise IN PLACE (enroller_diag.cpp:32-35), then per group of `slots` rows: pack the
-// generalised diagonals (:37-45) and encrypt the vector_dim slot vectors (:48-52) into the resident HBM layout.
-void client_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32], size_t first_block, int babies) {
+// The block loop of an enrolment.  key != nullptr: DiagonalEnroller::serializeDB — per group of `slots` rows pack the generalised
+// diagonals (enroller_diag.cpp:37-45) and encrypt the vector_dim slot vectors (:48-52) into the resident HBM layout.  key == nullptr:
+// PlainEnroller::serializeDB — the same slot vectors ENCODED (one polynomial each): plaintext t is the slot image of ciphertext t
+static void enroll_blocks(Context &cx, const RowSource &src, size_t n, const ChaChaKey *key, size_t first_block, int babies) {
     const int dim = cx.prm.dim, Nh = cx.slots;
-    for (long long v = 0; v < (long long)n; v++) normalize(db + (size_t)v * dim, dim);
-    const ChaChaKey key = make_key(seed);
-    const size_t G = cx.db_cts / dim, ct_elems = (size_t)2 * cx.nQ * cx.N;
-    // nonces are a 40-bit field of the sampler stream id: block first_block + g uses HY_DB_NONCE_BASE + (first_block + g) dim ..
-    if (first_block > (HY_NONCE_LIMIT - HY_DB_NONCE_BASE) / (size_t)dim || G > (HY_NONCE_LIMIT - HY_DB_NONCE_BASE) / (size_t)dim - first_block)
-        throw std::runtime_error("hydia: first_block + number of blocks exceeds the 2^40 nonce space of the encryption sampler");
+    const size_t G = cx.db_cts / dim, out_elems = (size_t)(key ? 2 : 1) * cx.nQ * cx.N;
     double *d_rows = (double *)cx.pool.get(sizeof(double) * (size_t)Nh * dim);
     double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)dim * Nh);
-    u64 *d_cts = cx.pool.get(sizeof(u64) * (size_t)dim * ct_elems);  // one group of fresh ciphertexts before packing
+    u64 *d_out = cx.pool.get(sizeof(u64) * (size_t)dim * out_elems);  // one group of fresh ciphertexts / plaintexts before packing
     for (size_t g = 0; g < G; g++) {
         const size_t first = g * (size_t)Nh;
         const size_t rows = n > first ? std::min((size_t)Nh, n - first) : 0;
-        if (rows)
-            HIP_CHECK(hipMemcpyAsync(d_rows, db + first * dim, sizeof(double) * rows * dim, hipMemcpyHostToDevice, cx.stream));
+        if (rows) src.stage(cx, first, rows, d_rows);
         hc::diag_pack(cx.stream, d_rows, (long long)rows, dim, Nh, d_slots, (babies > 0 && babies < dim) ? babies : 0);
-        encrypt_device(cx, d_slots, dim, key, HY_DB_NONCE_BASE + (first_block + g) * dim, d_cts);
-        cx.db_store(g * dim, d_cts, dim);
+        if (key) encrypt_device(cx, d_slots, dim, *key, HY_DB_NONCE_BASE + (first_block + g) * dim, d_out);
+        else encode_device(cx, d_slots, dim, d_out);
+        cx.db_store(g * dim, d_out, dim);
     }
     cx.sync();
-    cx.pool.put(d_cts);
+    cx.pool.put(d_out);
     cx.pool.put((u64 *)d_slots);
     cx.pool.put((u64 *)d_rows);
 }
-
-// In-place update of a resident diagonal database (kind 5 / 6): a FRESH encryption of the sparse diagonal image of `rows` at vectors
-// first_vector .. first_vector + n - 1 is added to the blocks they touch (append: first_vector = the vector count — the padding slots
-// hold encryptions of zero; remove: the negated template; replace: new - old, normalise = 0).  Per touched block: diag_pack with the
-// rows' first slot, encrypt_device with the enrolment's nonces, then db_accumulate for a block that existed or db_store for a new
-// one — a new block is bit-identical to that block of client_enroll on the same rows with the same seed.  Form and kind stay.
-void client_db_update(Context &cx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32], size_t first_block) {
-    if (n == 0) return;
-    const int dim = cx.prm.dim, Nh = cx.slots, babies = cx.db_babies;
-    if (normalise)
-        for (size_t v = 0; v < n; v++) normalize(rows + v * dim, dim);
-    const ChaChaKey key = make_key(seed);
-    const size_t G_old = cx.db_cts / dim, ct_elems = (size_t)2 * cx.nQ * cx.N;
-    const size_t n_new = std::max(cx.db_vectors, first_vector + n), G_new = (n_new + (size_t)Nh - 1) / (size_t)Nh;
-    if (first_block > (HY_NONCE_LIMIT - HY_DB_NONCE_BASE) / (size_t)dim || G_new > (HY_NONCE_LIMIT - HY_DB_NONCE_BASE) / (size_t)dim - first_block)
+// nonces are a 40-bit field of the sampler stream id: block first_block + g uses HY_DB_NONCE_BASE + (first_block + g) dim ..
+static void check_db_nonces(size_t first_block, size_t blocks, int dim) {
+    if (first_block > (HY_NONCE_LIMIT - HY_DB_NONCE_BASE) / (size_t)dim || blocks > (HY_NONCE_LIMIT - HY_DB_NONCE_BASE) / (size_t)dim - first_block)
         throw std::runtime_error("hydia: first_block + number of blocks exceeds the 2^40 nonce space of the encryption sampler");
+}
+// PlainEnroller::serializeDB — a gallery the sender may see (database kinds 7 / 8): normalise IN PLACE and pack the generalised
+// diagonals exactly as client_enroll does, then ENCODE the vector_dim slot vectors of each block (one polynomial each) into the resident
+// layout.  Plaintext t is the slot image of client_enroll's ciphertext t.
+void client_plain_enroll(Context &cx, double *db, size_t n, int babies) {
+    const int dim = cx.prm.dim;
+    for (size_t v = 0; v < n; v++) normalize(db + v * dim, dim);
+    RowSource src;
+    src.host = db;
+    enroll_blocks(cx, src, n, nullptr, 0, babies);
+}
+// the same from rows in device memory: every row is normalised by the kernel, the source is not written
+void client_plain_enroll_device(Context &cx, const DevRows &rows, int babies) {
+    RowSource src;
+    src.dev = &rows;
+    src.normalise = 1;
+    wait_for_producer(cx, rows.stream);
+    enroll_blocks(cx, src, rows.n, nullptr, 0, babies);
+}
+
+// DiagonalEnroller::serializeDB: normalise IN PLACE (enroller_diag.cpp:32-35), then the block loop above.
+void client_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32], size_t first_block, int babies) {
+    const int dim = cx.prm.dim;
+    for (long long v = 0; v < (long long)n; v++) normalize(db + (size_t)v * dim, dim);
+    const ChaChaKey key = make_key(seed);
+    check_db_nonces(first_block, cx.db_cts / dim, dim);
+    RowSource src;
+    src.host = db;
+    enroll_blocks(cx, src, n, &key, first_block, babies);
+}
+void client_enroll_device(Context &cx, const DevRows &rows, const uint8_t seed[32], size_t first_block, int babies) {
+    const int dim = cx.prm.dim;
+    const ChaChaKey key = make_key(seed);
+    check_db_nonces(first_block, cx.db_cts / dim, dim);
+    RowSource src;
+    src.dev = &rows;
+    src.normalise = 1;
+    wait_for_producer(cx, rows.stream);
+    enroll_blocks(cx, src, rows.n, &key, first_block, babies);
+}
+
+// The block loop of an in-place update of a resident diagonal database (kind 5 / 6, key != nullptr) or plain gallery (kind 7 / 8,
+// key == nullptr): the sparse diagonal image of the n source rows at vectors first_vector .. first_vector + n - 1, freshly ENCRYPTED
+// with the enrolment's nonces or ENCODED, is added to the blocks they touch.  Per touched block: diag_pack with the rows' first slot,
+// encrypt_device / encode_device, then db_accumulate for a block that existed or db_store for a new one — a new block is bit-identical
+// to that block of an enrolment of the same rows (with the same seed).  Form and kind stay.
+static void update_blocks(Context &cx, size_t first_vector, const RowSource &src, size_t n, const ChaChaKey *key, size_t first_block) {
+    const int dim = cx.prm.dim, Nh = cx.slots, babies = cx.db_babies;
+    const size_t G_old = cx.db_cts / dim, out_elems = (size_t)(key ? 2 : 1) * cx.nQ * cx.N;
+    const size_t n_new = std::max(cx.db_vectors, first_vector + n), G_new = (n_new + (size_t)Nh - 1) / (size_t)Nh;
+    if (key) check_db_nonces(first_block, G_new, dim);
     cx.db_grow(n_new, G_new * (size_t)dim);  // (throws before anything is touched when a larger database does not fit)
     double *d_rows = (double *)cx.pool.get(sizeof(double) * (size_t)Nh * dim);
     double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)dim * Nh);
-    u64 *d_cts = cx.pool.get(sizeof(u64) * (size_t)dim * ct_elems);
+    u64 *d_out = cx.pool.get(sizeof(u64) * (size_t)dim * out_elems);
     const size_t end = first_vector + n;
     for (size_t g = first_vector / (size_t)Nh; g * (size_t)Nh < end; g++) {
         const size_t lo = std::max(first_vector, g * (size_t)Nh), hi = std::min(end, (g + 1) * (size_t)Nh);
-        HIP_CHECK(hipMemcpyAsync(d_rows, rows + (lo - first_vector) * dim, sizeof(double) * (hi - lo) * dim, hipMemcpyHostToDevice, cx.stream));
+        src.stage(cx, lo - first_vector, hi - lo, d_rows);
         hc::diag_pack(cx.stream, d_rows, (long long)(hi - lo), dim, Nh, d_slots, (babies > 0 && babies < dim) ? babies : 0, (int)(lo - g * (size_t)Nh));
-        encrypt_device(cx, d_slots, dim, key, HY_DB_NONCE_BASE + (first_block + g) * dim, d_cts);
-        if (g < G_old) cx.db_accumulate(g * dim, d_cts, dim);
-        else cx.db_store(g * dim, d_cts, dim);
+        if (key) encrypt_device(cx, d_slots, dim, *key, HY_DB_NONCE_BASE + (first_block + g) * dim, d_out);
+        else encode_device(cx, d_slots, dim, d_out);
+        if (g < G_old) cx.db_accumulate(g * dim, d_out, dim);
+        else cx.db_store(g * dim, d_out, dim);
     }
     cx.sync();
-    cx.pool.put(d_cts);
+    cx.pool.put(d_out);
     cx.pool.put((u64 *)d_slots);
     cx.pool.put((u64 *)d_rows);
 }
-
-// In-place update of a resident PLAIN gallery (kind 7 / 8): client_db_update's loop with encode_device in place of encrypt_device —
-// no seed, no nonce.  Per touched block the sparse diagonal image of the rows at their slots is ENCODED as client_plain_enroll
-// encodes (E_t) and added to a block that existed ((old_t + E_t) mod q_j, canonical) or stored as a new one — a new block is bit
-// for bit that block of client_plain_enroll on the same rows.  The encoder rounds once per update, and symmetrically:
-// encode(-x) + encode(x) = 0 in every residue, so the negated rows restore an existing block exactly.  Form and kind stay.
-void client_plain_db_update(Context &cx, size_t first_vector, double *rows, size_t n, int normalise) {
+// In-place update of a resident diagonal database (kind 5 / 6): a FRESH encryption of the sparse diagonal image of `rows` at vectors
+// first_vector .. first_vector + n - 1 is added to the blocks they touch (append: first_vector = the vector count — the padding slots
+// hold encryptions of zero; remove: the negated template; replace: new - old, normalise = 0).
+void client_db_update(Context &cx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32], size_t first_block) {
     if (n == 0) return;
-    const int dim = cx.prm.dim, Nh = cx.slots, babies = cx.db_babies;
+    const int dim = cx.prm.dim;
     if (normalise)
         for (size_t v = 0; v < n; v++) normalize(rows + v * dim, dim);
-    const size_t G_old = cx.db_cts / dim, pt_elems = (size_t)cx.nQ * cx.N;
-    const size_t n_new = std::max(cx.db_vectors, first_vector + n), G_new = (n_new + (size_t)Nh - 1) / (size_t)Nh;
-    cx.db_grow(n_new, G_new * (size_t)dim);  // (throws before anything is touched when a larger gallery does not fit)
-    double *d_rows = (double *)cx.pool.get(sizeof(double) * (size_t)Nh * dim);
-    double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)dim * Nh);
-    u64 *d_pts = cx.pool.get(sizeof(u64) * (size_t)dim * pt_elems);
-    const size_t end = first_vector + n;
-    for (size_t g = first_vector / (size_t)Nh; g * (size_t)Nh < end; g++) {
-        const size_t lo = std::max(first_vector, g * (size_t)Nh), hi = std::min(end, (g + 1) * (size_t)Nh);
-        HIP_CHECK(hipMemcpyAsync(d_rows, rows + (lo - first_vector) * dim, sizeof(double) * (hi - lo) * dim, hipMemcpyHostToDevice, cx.stream));
-        hc::diag_pack(cx.stream, d_rows, (long long)(hi - lo), dim, Nh, d_slots, (babies > 0 && babies < dim) ? babies : 0, (int)(lo - g * (size_t)Nh));
-        encode_device(cx, d_slots, dim, d_pts);
-        if (g < G_old) cx.db_accumulate(g * dim, d_pts, dim);
-        else cx.db_store(g * dim, d_pts, dim);
+    const ChaChaKey key = make_key(seed);
+    RowSource src;
+    src.host = rows;
+    update_blocks(cx, first_vector, src, n, &key, first_block);
+}
+void client_db_update_device(Context &cx, size_t first_vector, const DevRows &rows, int normalise, const uint8_t seed[32], size_t first_block) {
+    if (rows.n == 0) return;
+    const ChaChaKey key = make_key(seed);
+    RowSource src;
+    src.dev = &rows;
+    src.normalise = normalise;
+    wait_for_producer(cx, rows.stream);
+    update_blocks(cx, first_vector, src, rows.n, &key, first_block);
+}
+
+// In-place update of a resident PLAIN gallery (kind 7 / 8): the update loop with encode_device in place of encrypt_device — no seed,
+// no nonce.  The encoder rounds once per update, and symmetrically: encode(-x) + encode(x) = 0 in every residue, so the negated rows
+// restore an existing block exactly.
+void client_plain_db_update(Context &cx, size_t first_vector, double *rows, size_t n, int normalise) {
+    if (n == 0) return;
+    const int dim = cx.prm.dim;
+    if (normalise)
+        for (size_t v = 0; v < n; v++) normalize(rows + v * dim, dim);
+    RowSource src;
+    src.host = rows;
+    update_blocks(cx, first_vector, src, n, nullptr, 0);
+}
+void client_plain_db_update_device(Context &cx, size_t first_vector, const DevRows &rows, int normalise) {
+    if (rows.n == 0) return;
+    RowSource src;
+    src.dev = &rows;
+    src.normalise = normalise;
+    wait_for_producer(cx, rows.stream);
+    update_blocks(cx, first_vector, src, rows.n, nullptr, 0);
+}
+
+// Probes in device memory, as encrypted queries (key != nullptr: query i is client_encrypt_query(row i, seed, nonce0 + i), bit for
+// bit) or as plain queries (client_encode_query(row i)): per pass ONE k_rows_widen launch normalises the probes, ONE k_query_tile tiles
+// them over all slots, ONE encrypt_device / encode_device over the whole pass makes the polynomials (encrypt_device steps the nonce
+// per batch element), and each query gets a handle of its own.  A pass takes what free HBM holds of the encoder's and the
+// encryption's temporaries
+static std::vector<Ct> queries_device(Context &cx, const DevRows &rows, const ChaChaKey *key, u64 nonce0) {
+    if (key && !cx.d_pk) throw StateError("hydia: public key not loaded");
+    const int dim = cx.prm.dim, Nh = cx.slots, np = key ? 2 : 1;
+    const size_t poly = (size_t)cx.nQ * cx.N * sizeof(u64), elems = (size_t)np * cx.nQ * cx.N;
+    // per probe: slots + complex work + coefficients (4 N doubles' worth), three sampled polynomials and their limbs, the output twice
+    const double per_query = 32.0 * cx.N + (key ? 12.0 * cx.N + 3.0 * poly : 0.0) + 2.0 * np * poly + 8.0 * dim;
+    size_t free_b = 0, total_b = 0;
+    size_t pass = 1;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        pass = (size_t)std::max(1.0, std::floor(0.5 * ((double)free_b + (double)cx.pool.bytes_cached) / per_query));
+    pass = std::min({pass, rows.n, (size_t)4096});
+    wait_for_producer(cx, rows.stream);
+    double *d_q = (double *)cx.pool.get(sizeof(double) * pass * dim);
+    double *d_slots = (double *)cx.pool.get(sizeof(double) * pass * Nh);
+    u64 *d_out = cx.pool.get(sizeof(u64) * pass * elems);
+    std::vector<Ct> out;
+    out.reserve(rows.n);
+    RowSource src;
+    src.dev = &rows;
+    src.normalise = 1;
+    for (size_t q0 = 0; q0 < rows.n; q0 += pass) {
+        const int Q = (int)std::min(pass, rows.n - q0);
+        src.stage(cx, q0, (size_t)Q, d_q);
+        hc::query_tile(cx.stream, d_q, Q, dim, Nh, d_slots);
+        if (key) encrypt_device(cx, d_slots, Q, *key, nonce0 + q0, d_out);
+        else encode_device(cx, d_slots, Q, d_out);
+        for (int q = 0; q < Q; q++) {
+            out.emplace_back(&cx, 1, np, cx.nQ, cx.delta);
+            HIP_CHECK(hipMemcpyAsync(out.back().d, d_out + (size_t)q * elems, sizeof(u64) * elems, hipMemcpyDeviceToDevice, cx.stream));
+        }
     }
     cx.sync();
-    cx.pool.put(d_pts);
+    cx.pool.put(d_out);
     cx.pool.put((u64 *)d_slots);
-    cx.pool.put((u64 *)d_rows);
+    cx.pool.put((u64 *)d_q);
+    return out;
 }
+std::vector<Ct> client_encrypt_queries_device(Context &cx, const DevRows &rows, const uint8_t seed[32], uint64_t nonce0) {
+    const ChaChaKey key = make_key(seed);
+    return queries_device(cx, rows, &key, nonce0);
+}
+std::vector<Ct> client_encode_queries_device(Context &cx, const DevRows &rows) { return queries_device(cx, rows, nullptr, 0); }
 
 #define HY_HERS_NONCE_BASE (1ull << 37)
 // HersEnroller::serializeDB (/root/reference/src/enroller/enroller_hers.cpp:40-93): normalise in place, then per matrix of

@@ -30,6 +30,25 @@ Ct client_encode_query(Context &cx, const double *query);
 void client_db_update(Context &cx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32], size_t first_block = 0);
 // resident kind 7 / 8 gallery += the ENCODED sparse diagonal image of rows[n][dim] at vectors first_vector .. (no seed, no nonce)
 void client_plain_db_update(Context &cx, size_t first_vector, double *rows, size_t n, int normalise);
+// ---- rows that already lie in device memory (include/hydia.h, hydia_dev_rows; the C-ABI has checked pointer, type, stride and state):
+// n rows of vector_dim elements of `dtype` (hydia_dtype), `stride` elements apart, produced on `stream` (nullptr: complete already).
+// The context's stream waits for an event recorded on `stream` — no host synchronisation on the way in; every call is synchronous on
+// return.  The rows are never written.  Each *_device entry runs the block loop of its host twin from d_rows on (one k_rows_widen
+// launch per block in place of the host normalisation and the copy), so the resident database comes out bit-identical
+struct DevRows {
+    const void *ptr;
+    int dtype;
+    size_t n, stride;
+    hipStream_t stream;
+};
+void client_rows_widen(Context &cx, const DevRows &rows, int normalise, double *dev_dst /* [n][vector_dim] */);
+void client_enroll_device(Context &cx, const DevRows &rows, const uint8_t seed[32], size_t first_block, int babies);
+void client_plain_enroll_device(Context &cx, const DevRows &rows, int babies);
+void client_db_update_device(Context &cx, size_t first_vector, const DevRows &rows, int normalise, const uint8_t seed[32], size_t first_block = 0);
+void client_plain_db_update_device(Context &cx, size_t first_vector, const DevRows &rows, int normalise);
+// one handle per probe: query i = client_encrypt_query(row i, seed, nonce0 + i) / client_encode_query(row i), bit for bit
+std::vector<Ct> client_encrypt_queries_device(Context &cx, const DevRows &rows, const uint8_t seed[32], uint64_t nonce0);
+std::vector<Ct> client_encode_queries_device(Context &cx, const DevRows &rows);
 // HERS (approach 4): column-packed enrolment and the vector_dim broadcast query ciphertexts
 void client_hers_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32]);
 Ct client_hers_encrypt_query(Context &cx, const double *query, const uint8_t seed[32], uint64_t nonce0);

@@ -44,4 +44,15 @@ void row_pack(hipStream_t st, const double *dbg, long long elems_left, int Nh, d
 void chunk_pack(hipStream_t st, const double *rows, long long rows_left, int dim, int chunk, int Nh, double *slots);
 void chunk_tile(hipStream_t st, const double *q, int dim, int chunk, int Nh, double *slots);
 void broadcast_rows(hipStream_t st, const double *vals, int dim, int Nh, double *slots);
+// templates in device memory: n rows of dim elements of type `dtype` (the values of hydia_dtype), `stride` elements apart (>= dim, dim
+// a power of two), widened exactly to dense doubles dst[n][dim] — diag_pack's input — and with normalise != 0 divided by their L2
+// norm bit for bit as the host normalises (rows_norm.h).  src is never written and needs only its element's alignment
+#define HC_ROWS_F64 0
+#define HC_ROWS_F32 1
+#define HC_ROWS_F16 2
+#define HC_ROWS_BF16 3
+size_t rows_elem_size(int dtype);
+void rows_widen(hipStream_t st, const void *src, int dtype, size_t n, int dim, size_t stride, int normalise, double *dst);
+// slots[q][i] = rows[q][i mod dim] for Q probes (Q <= 65535): the tiling of DiagonalReceiver::encryptQuery
+void query_tile(hipStream_t st, const double *rows, int Q, int dim, int Nh, double *slots);
 }  // namespace hc

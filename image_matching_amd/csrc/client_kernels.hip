@@ -1,6 +1,6 @@
 // image_matching_amd/csrc/client_kernels.hip — gfx950 kernels of the receiver / enroller / key-generation side:
 // ChaCha20-addressed samplers, the canonical-embedding FFT (CKKS encode/decode), public-key encryption, decryption
-// and the diagonal packing of DiagonalEnroller.
+// the diagonal packing of DiagonalEnroller, and the widening / normalisation of templates that arrive in device memory.
 //
 // Replaces, on the GPU: MakeCKKSPackedPlaintext + Encrypt (/root/reference/src/openFHE_wrapper.cpp:74-77), Decrypt +
 // GetRealPackedValue (:81-85), KeyGen/EvalMultKeyGen/EvalRotateKeyGen (/root/reference/src/main.cpp:184-206) and the
@@ -8,7 +8,11 @@
 // Floating point here is compiled with -ffp-contract=off and uses the same operation order as the specification in
 // DESIGN.md, so encodings are reproducible bit for bit.
 #include "client_kernels.h"
+
+#include <stdexcept>
+
 #include "gauss_cdt.h"
+#include "rows_norm.h"
 
 namespace {
 
@@ -303,6 +307,64 @@ __global__ __launch_bounds__(256) void k_broadcast_rows(const double *__restrict
     slots[(size_t)blockIdx.y * Nh + blockIdx.x * 256 + threadIdx.x] = vals[blockIdx.y];
 }
 
+// ---- templates that are already in device memory (f64 / f32 / f16 / bf16 rows, `stride` elements apart): dense double rows
+// dst[n][dim], the d_rows buffer k_diag_pack reads — widened exactly and, with normalise != 0, divided by their L2 norm bit for bit
+// as normalize() in client.cpp does it on the host (rows_norm.h: the squared sum runs in index order, so ONE thread owns a row's
+// sum).  src is only ever read, element by element: nothing but the element's own alignment is assumed.
+// A workgroup takes a tile of RW_ROWS rows.  Pass 1 (normalise only): RW_COLS columns at a time are loaded by all 256 threads —
+// consecutive threads take consecutive elements of a row, so a wave reads whole runs of a row — widened and parked in LDS; lane r of
+// wave 0 then walks row r there.  The row pitch is odd in doubles: at one column the 32 lanes of a ds_read_b64 group hit the 32
+// different even banks.  Pass 2: all threads read the tile again (from cache), divide by the row's norm and write dst coalesced.
+// dim is a power of two.  grid ((n + RW_ROWS - 1) / RW_ROWS), 256 threads
+#define RW_ROWS 64
+#define RW_COLS 64
+#define RW_PITCH (RW_COLS + 1)
+struct bf16_bits {
+    unsigned short b;
+};
+DEV double rw_widen(double v) { return v; }
+DEV double rw_widen(float v) { return rn_widen_f32_bits(__builtin_bit_cast(unsigned, v)); }
+DEV double rw_widen(_Float16 v) { return rn_widen_f16_bits(__builtin_bit_cast(unsigned short, v)); }
+DEV double rw_widen(bf16_bits v) { return rn_widen_bf16_bits(v.b); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_rows_widen(const T *__restrict__ src, long long n, int log_dim, long long stride, int normalise,
+                                                    double *__restrict__ dst) {
+    __shared__ double tile[RW_ROWS * RW_PITCH];
+    __shared__ double norm[RW_ROWS];
+    const int t = threadIdx.x, dim = 1 << log_dim;
+    const long long row0 = (long long)blockIdx.x * RW_ROWS;
+    const int rows = (int)(n - row0 < RW_ROWS ? n - row0 : RW_ROWS);
+    if (normalise) {
+        const int log_cols = log_dim < 6 ? log_dim : 6, cols = 1 << log_cols;  // min(dim, RW_COLS)
+        double m = 0.0;
+        for (int c0 = 0; c0 < dim; c0 += cols) {
+            for (int e = t; e < rows << log_cols; e += 256) {
+                const int r = e >> log_cols, c = e & (cols - 1);
+                tile[r * RW_PITCH + c] = rw_widen(src[(row0 + r) * stride + c0 + c]);
+            }
+            __syncthreads();
+            if (t < rows)
+                for (int c = 0; c < cols; c++) m = rn_sq_step(m, tile[t * RW_PITCH + c]);
+            __syncthreads();
+        }
+        if (t < RW_ROWS) norm[t] = rn_norm(m);
+        __syncthreads();
+    }
+    for (int e = t; e < rows << log_dim; e += 256) {
+        const int r = e >> log_dim, c = e & (dim - 1);
+        double v = rw_widen(src[(row0 + r) * stride + c]);
+        if (normalise) v = rn_quot(v, norm[r]);
+        dst[((row0 + r) << log_dim) + c] = v;
+    }
+}
+// DiagonalReceiver::encryptQuery's tiling (/root/reference/src/receiver/receiver_diag.cpp:18-21) for Q probes at once: slot image q =
+// row q of rows[Q][dim] (k_rows_widen's output) repeated over all slots.  dim is a power of two.  grid (Nh/256, Q)
+__global__ __launch_bounds__(256) void k_query_tile(const double *__restrict__ rows, int dim, int Nh, double *__restrict__ slots) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    slots[(size_t)blockIdx.y * Nh + s] = rows[(size_t)blockIdx.y * dim + (s & (dim - 1))];
+}
+
 }  // namespace
 
 namespace hc {
@@ -381,6 +443,26 @@ void broadcast_rows(hipStream_t st, const double *vals, int dim, int Nh, double 
 }
 void diag_pack(hipStream_t st, const double *dbg, long long rows_left, int dim, int Nh, double *slots, int babies, int row0) {
     hipLaunchKernelGGL(k_diag_pack, dim3(Nh / 256, dim), dim3(256), 0, st, dbg, rows_left, dim, Nh, slots, babies, row0);
+}
+size_t rows_elem_size(int dtype) { return dtype == HC_ROWS_F64 ? 8 : dtype == HC_ROWS_F32 ? 4 : 2; }
+void rows_widen(hipStream_t st, const void *src, int dtype, size_t n, int dim, size_t stride, int normalise, double *dst) {
+    if (n == 0) return;
+    int log_dim = 0;
+    while ((1 << log_dim) < dim) log_dim++;
+    if ((1 << log_dim) != dim || stride < (size_t)dim || n > (size_t)0x7FFFFFFF * RW_ROWS)
+        throw std::runtime_error("hydia: rows_widen takes a power-of-two dimension, a row stride of at least it and fewer than 2^37 rows");
+    const dim3 grid((unsigned)((n + RW_ROWS - 1) / RW_ROWS)), block(256);
+    const long long nn = (long long)n, ss = (long long)stride;
+    switch (dtype) {
+        case HC_ROWS_F64: hipLaunchKernelGGL(k_rows_widen<double>, grid, block, 0, st, (const double *)src, nn, log_dim, ss, normalise, dst); break;
+        case HC_ROWS_F32: hipLaunchKernelGGL(k_rows_widen<float>, grid, block, 0, st, (const float *)src, nn, log_dim, ss, normalise, dst); break;
+        case HC_ROWS_F16: hipLaunchKernelGGL(k_rows_widen<_Float16>, grid, block, 0, st, (const _Float16 *)src, nn, log_dim, ss, normalise, dst); break;
+        case HC_ROWS_BF16: hipLaunchKernelGGL(k_rows_widen<bf16_bits>, grid, block, 0, st, (const bf16_bits *)src, nn, log_dim, ss, normalise, dst); break;
+        default: throw std::runtime_error("hydia: rows_widen: element type outside f64 / f32 / f16 / bf16");
+    }
+}
+void query_tile(hipStream_t st, const double *rows, int Q, int dim, int Nh, double *slots) {
+    hipLaunchKernelGGL(k_query_tile, dim3(Nh / 256, Q), dim3(256), 0, st, rows, dim, Nh, slots);
 }
 
 }  // namespace hc

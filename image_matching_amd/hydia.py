@@ -27,6 +27,10 @@ class _Params(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("log_n", "mult_depth", "scale_bits", "first_mod_bits", "dnum", "vector_dim")]
 
 
+class _DevRows(C.Structure):  # hydia_dev_rows
+    _fields_ = [("ptr", C.c_void_p), ("dtype", C.c_int), ("n", C.c_size_t), ("row_stride", C.c_size_t), ("stream", C.c_void_p)]
+
+
 class _Info(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("log_n", "n", "slots", "n_q", "n_p", "dnum", "alpha", "vector_dim")] + [
         ("delta", C.c_double)]
@@ -114,6 +118,13 @@ def load_library():
         "hydia_index_scenario_pq_multi": (i32, [vp, vp, u32, vp]),
         "hydia_membership_scenario_pq_multi": (i32, [vp, vp, u32, vp]),
         "hydia_set_pq_batch_width": (i32, [vp, u32]),
+        "hydia_rows_widen_device": (i32, [vp, C.POINTER(_DevRows), i32, vp]),
+        "hydia_db_enroll_device": (i32, [vp, C.POINTER(_DevRows), vp]),
+        "hydia_plain_db_enroll_device": (i32, [vp, C.POINTER(_DevRows)]),
+        "hydia_db_update_device": (i32, [vp, sz, C.POINTER(_DevRows), i32, vp]),
+        "hydia_plain_db_update_device": (i32, [vp, sz, C.POINTER(_DevRows), i32]),
+        "hydia_encrypt_queries_device": (i32, [vp, C.POINTER(_DevRows), vp, u64, vp]),
+        "hydia_encode_queries_device": (i32, [vp, C.POINTER(_DevRows), vp]),
         "hydia_compute_similarity_gallery_multi": (i32, [vp, vp, u32, vp]),
         "hydia_index_scenario_gallery_multi": (i32, [vp, vp, u32, vp]),
         "hydia_membership_scenario_gallery_multi": (i32, [vp, vp, u32, vp]),
@@ -243,6 +254,33 @@ def _seed(x):
     else:
         b = int(x).to_bytes(32, "little")
     return np.frombuffer(b, dtype=np.uint8).copy()
+
+
+def _is_device_tensor(x):
+    """a tensor in device memory, by duck typing: torch is not imported unless the caller already hands one in"""
+    return all(hasattr(x, a) for a in ("data_ptr", "is_cuda", "dtype", "stride"))
+
+
+_DTYPES = {"torch.float64": 0, "torch.float32": 1, "torch.float16": 2, "torch.bfloat16": 3}  # hydia_dtype
+
+
+def _dev_rows(cc, t):
+    """hydia_dev_rows of a 2-D tensor (1-D: one row) of f64 / f32 / f16 / bf16 on the context's GPU whose last dimension has stride 1;
+    the producer stream is torch's current stream of the tensor's device.  The tensor is only read.  That the memory lies on the
+    context's GPU is checked by the library (HydiaError(-1))."""
+    import torch
+    if t.dim() == 1:
+        t = t[None]
+    code = _DTYPES.get(str(t.dtype))
+    if not t.is_cuda or code is None or t.dim() != 2 or t.shape[1] != cc.dim or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise HydiaError(-1, "hydia: device rows are a tensor [n][vector_dim] of float64 / float32 / float16 / bfloat16 in device "
+                             "memory whose last dimension has stride 1")
+    n = t.shape[0]
+    stream = torch.cuda.current_stream(t.device)
+    handle = stream.cuda_stream or None
+    if handle is None:
+        stream.synchronize()  # the null stream: nothing to record an event on that the context's non-blocking stream would wait for
+    return _DevRows(t.data_ptr() or None, code, n, t.stride(0) if n > 1 else cc.dim, handle)
 
 
 def byte_ledger(enable=-1):
@@ -692,6 +730,31 @@ class Context:
         assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.ndim == 2 and rows.shape[1] == self.dim
         _chk(self.L.hydia_db_update_shard(self.h, first_vector, _p(rows), rows.shape[0], 1 if normalise else 0, _p(_seed(seed)), first_block))
 
+    # ---- templates already in device memory (include/hydia.h, hydia_dev_rows): `rows` is a tensor on this context's GPU, only read
+    def rows_widen_device(self, rows, normalise=True):
+        """hydia_rows_widen_device: the rows widened exactly to float64 (and divided by their L2 norm), as a new tensor [n][vector_dim]"""
+        import torch
+        d = _dev_rows(self, rows)
+        out = torch.empty((d.n, self.dim), dtype=torch.float64, device=rows.device)
+        _chk(self.L.hydia_rows_widen_device(self.h, C.byref(d), 1 if normalise else 0, C.c_void_p(out.data_ptr() or None)))
+        return out
+
+    def db_update_device(self, first_vector, rows, normalise=True, seed=None):
+        """db_update from rows in device memory (normalised on the device, never written)"""
+        d = _dev_rows(self, rows)
+        _chk(self.L.hydia_db_update_device(self.h, first_vector, C.byref(d), 1 if normalise else 0, _p(_seed(seed))))
+
+    def plain_db_update_device(self, first_vector, rows, normalise=True):
+        """plain_db_update from rows in device memory (normalised on the device, never written)"""
+        d = _dev_rows(self, rows)
+        _chk(self.L.hydia_plain_db_update_device(self.h, first_vector, C.byref(d), 1 if normalise else 0))
+
+    def _queries_device(self, fn, cls, rows, *args):
+        d = _dev_rows(self, rows)
+        out = (C.c_void_p * max(d.n, 1))()
+        _chk(fn(self.h, C.byref(d), *args, out))
+        return [cls(self, C.c_void_p(out[i])) for i in range(d.n)]
+
     def db_rekey(self, key, chunk=0):
         """hydia_db_rekey: key-switch every ciphertext of the resident kind-4 / 5 / 6 database in place with `key` (keygen_switch of
         the NEW receiver's context).  Layout, form, kind and order stay; afterwards import the new receiver's evaluation and public
@@ -801,7 +864,19 @@ class DiagonalEnroller:
         """DiagonalEnroller::serializeDB (src/enroller/enroller_diag.cpp:12-53).  Normalises `database` IN PLACE like
         the reference; the ciphertexts go straight into HBM instead of serial/db_diagonal/index<t>.bin.  first_block > 0:
         `database` is one shard (a contiguous range of 16384-vector blocks) of a larger database.  matvec: None = the context's
-        policy (Context.set_matvec), or "hoisted" / "bsgs" / a baby count (a sharded enrolment passes one decision to every shard)."""
+        policy (Context.set_matvec), or "hoisted" / "bsgs" / a baby count (a sharded enrolment passes one decision to every shard).
+        A tensor on the context's GPU (f64 / f32 / f16 / bf16) is enrolled where it lies (hydia_db_enroll_device): normalised on the
+        device and never written; the form follows Context.set_matvec."""
+        if _is_device_tensor(database):
+            if not isinstance(self.cc, Context):
+                raise HydiaError(-2, "hydia: rows in device memory are not taken on a sharded context")
+            if first_block or matvec is not None:
+                raise HydiaError(-1, "hydia: rows in device memory are enrolled whole, in the form of Context.set_matvec")
+            d = _dev_rows(self.cc, database)
+            if d.n != self.numVectors:
+                raise HydiaError(-1, "hydia: the tensor holds another number of rows than the enroller was built for")
+            _chk(self.cc.L.hydia_db_enroll_device(self.cc.h, C.byref(d), _p(_seed(seed))))
+            return
         assert database.dtype == np.float64 and database.flags.c_contiguous
         assert database.shape == (self.numVectors, self.cc.dim)
         mv = 0 if matvec is None else self.cc._matvec_code(matvec)
@@ -809,8 +884,12 @@ class DiagonalEnroller:
 
     def updateRows(self, first_vector, rows, normalise=True, seed=None):
         """In-place update (Context.db_update): a fresh encryption of `rows` at vectors first_vector .. is added to the blocks they
-        touch.  numVectors follows the database; a DiagonalSender / DiagonalReceiver built for the old count is rebuilt by the caller."""
-        self.cc.db_update(first_vector, rows, normalise, seed)
+        touch.  numVectors follows the database; a DiagonalSender / DiagonalReceiver built for the old count is rebuilt by the caller.
+        `rows` may be a tensor on the context's GPU (Context.db_update_device)."""
+        if _is_device_tensor(rows):
+            self.cc.db_update_device(first_vector, rows, normalise, seed)
+        else:
+            self.cc.db_update(first_vector, rows, normalise, seed)
         self.numVectors = max(self.numVectors, first_vector + rows.shape[0])
 
     def appendDB(self, rows, seed=None):
@@ -836,15 +915,26 @@ class PlainEnroller:
         self.cc, self.numVectors = cc, num_vectors
 
     def serializeDB(self, database):
-        """normalises `database` IN PLACE like DiagonalEnroller.serializeDB; the form follows Context.set_matvec"""
+        """normalises `database` IN PLACE like DiagonalEnroller.serializeDB; the form follows Context.set_matvec.  A tensor on the
+        context's GPU is enrolled where it lies (hydia_plain_db_enroll_device): normalised on the device and never written"""
+        if _is_device_tensor(database):
+            d = _dev_rows(self.cc, database)
+            if d.n != self.numVectors:
+                raise HydiaError(-1, "hydia: the tensor holds another number of rows than the enroller was built for")
+            _chk(self.cc.L.hydia_plain_db_enroll_device(self.cc.h, C.byref(d)))
+            return
         assert database.dtype == np.float64 and database.flags.c_contiguous
         assert database.shape == (self.numVectors, self.cc.dim)
         _chk(self.cc.L.hydia_plain_db_enroll(self.cc.h, _p(database), self.numVectors))
 
     def updateRows(self, first_vector, rows, normalise=True):
         """In-place update (Context.plain_db_update): the encoded image of `rows` at vectors first_vector .. is added to the blocks
-        they touch.  numVectors follows the gallery; a DiagonalSender / DiagonalReceiver built for the old count is rebuilt by the caller."""
-        self.cc.plain_db_update(first_vector, rows, normalise)
+        they touch.  numVectors follows the gallery; a DiagonalSender / DiagonalReceiver built for the old count is rebuilt by the caller.
+        `rows` may be a tensor on the context's GPU (Context.plain_db_update_device)."""
+        if _is_device_tensor(rows):
+            self.cc.plain_db_update_device(first_vector, rows, normalise)
+        else:
+            self.cc.plain_db_update(first_vector, rows, normalise)
         self.numVectors = max(self.numVectors, first_vector + rows.shape[0])
 
     def appendDB(self, rows):
@@ -859,9 +949,26 @@ class DiagonalReceiver:
         self.cc, self.numVectors = cc, num_vectors
 
     def encryptQuery(self, query, seed=None, nonce=1):
+        """a 1-D tensor on the context's GPU is encrypted where it lies (the one-row case of encryptQueries)"""
+        if _is_device_tensor(query):
+            if query.dim() != 1:
+                raise HydiaError(-1, "hydia: encryptQuery takes one probe (encryptQueries takes a matrix)")
+            return self.encryptQueries(query, seed, nonce)[0]
         query = np.ascontiguousarray(query, dtype=np.float64)
         assert query.shape == (self.cc.dim,)
         return self.cc._out(self.cc.L.hydia_encrypt_query, _p(query), _p(_seed(seed)), nonce)
+
+    def encryptQueries(self, matrix, seed=None, nonce0=1):
+        """one Ciphertext per row of `matrix` (k x vector_dim): row i is what encryptQuery(row i, seed, nonce0 + i) makes.  A tensor on
+        the context's GPU is ONE library call (hydia_encrypt_queries_device): normalised, tiled, encoded and encrypted as a batch"""
+        if _is_device_tensor(matrix):
+            if not isinstance(self.cc, Context):
+                raise HydiaError(-2, "hydia: rows in device memory are not taken on a sharded context")
+            return self.cc._queries_device(self.cc.L.hydia_encrypt_queries_device, Ciphertext, matrix, _p(_seed(seed)), nonce0)
+        matrix = np.ascontiguousarray(matrix, dtype=np.float64)
+        assert matrix.ndim == 2 and matrix.shape[1] == self.cc.dim
+        key = _seed(seed)  # ONE key for the batch: the nonces tell the probes apart
+        return [self.encryptQuery(row, bytes(key), nonce0 + i) for i, row in enumerate(matrix)]
 
     def genSwitchKey(self, old_secret, seed=None):
         """the switching key from the OLD receiver's secret (its Context.export_secret_key()) to this receiver's
@@ -892,6 +999,10 @@ class DiagonalSender:
         """exactly the plaintext DiagonalReceiver.encryptQuery encrypts, encoded and not encrypted: no seed, no nonce, no public key"""
         if not isinstance(self.cc, Context):
             raise HydiaError(-2, "hydia: a plain query is not served on a sharded context")
+        if _is_device_tensor(query):  # a 1-D tensor on the context's GPU: the one-row case of encodeQueries
+            if query.dim() != 1:
+                raise HydiaError(-1, "hydia: encodeQuery takes one probe (encodeQueries takes a matrix)")
+            return self.encodeQueries(query)[0]
         query = np.ascontiguousarray(query, dtype=np.float64)
         assert query.shape == (self.cc.dim,)
         h = C.c_void_p()
@@ -946,9 +1057,12 @@ class DiagonalSender:
     # ---- several PLAIN queries in one pass over the database (names of their own: the *Multi methods above keep refusing a Plaintext).
     # A list of Plaintext in, a list out: per query exactly what the single-query method returns
     def encodeQueries(self, matrix):
-        """one Plaintext per row of `matrix` (k x vector_dim), each what encodeQuery makes of that row"""
+        """one Plaintext per row of `matrix` (k x vector_dim), each what encodeQuery makes of that row.  A tensor on the context's GPU
+        is ONE library call (hydia_encode_queries_device): the probes are normalised, tiled and encoded as a batch where they lie"""
         if not isinstance(self.cc, Context):
             raise HydiaError(-2, "hydia: a plain query is not served on a sharded context")
+        if _is_device_tensor(matrix):
+            return self.cc._queries_device(self.cc.L.hydia_encode_queries_device, Plaintext, matrix)
         matrix = np.ascontiguousarray(matrix, dtype=np.float64)
         assert matrix.ndim == 2 and matrix.shape[1] == self.cc.dim
         return [self.encodeQuery(row) for row in matrix]

@@ -427,6 +427,44 @@ int hydia_membership_scenario_pq_multi(hydia_ctx *ctx, const hydia_pt *const *qu
  * rely on, and it may change or go without notice.  The queries one database pass of a *_pq_multi call serves on this context, 1, 2
  * or 4; 0 = the library's measured choice (the default).  The results do not depend on it.  Another value: HYDIA_ERR_ARG. */
 int hydia_set_pq_batch_width(hydia_ctx *ctx, uint32_t width);
+/* ---- templates already in device memory (an extension; no counterpart in the reference).  A template usually leaves an embedding
+ * network as an f16 / bf16 / f32 tensor on the GPU that will enrol or match it; these entries take it where it lies.  A
+ * hydia_dev_rows describes n rows of vector_dim elements, row_stride elements apart (row_stride >= vector_dim; elements of a row are
+ * contiguous).  The rows are widened exactly to doubles and normalised on the device, bit for bit as the host entry points normalise
+ * (divide by the L2 norm, squared sum in index order, a zero row passes through), so each *_device entry leaves exactly what its host
+ * twin leaves when handed the widened rows: the same ciphertexts under the same seed, the same plaintexts, the same form
+ * (hydia_set_matvec).  NaN and infinite elements follow IEEE arithmetic as on the host.
+ * Ordering and lifetime: `stream` is the hipStream_t on which the rows were produced.  The library records an event on it and makes
+ * its own stream wait — no host synchronisation on the way in; whatever is enqueued on `stream` AFTER the call begins is not waited
+ * for.  stream == NULL: the caller guarantees that the rows are complete.  The rows are only ever read, never written (a host entry
+ * point normalises its array in place; these do not), must stay valid and unchanged during the call, and may be reused or freed when
+ * it returns: every call is synchronous on return.
+ * Refusals, all made before anything is launched and leaving the resident database as it was: ptr is not device memory, or lies on
+ * another GPU than the context's, or is not aligned to its element type; row_stride < vector_dim; a dtype out of range: HYDIA_ERR_ARG.
+ * A context that is a shard of a hydia_group: HYDIA_ERR_STATE.  Otherwise what the host twin refuses, with its message (no public key;
+ * an update with no database or the wrong kind resident).  n == 0: an enrolment answers HYDIA_ERR_ARG and an update HYDIA_OK, as the
+ * host entries do; the two query entries answer HYDIA_ERR_ARG.
+ *   hydia_rows_widen_device       the kernel alone: dev_dst [n][vector_dim] doubles in device memory of the same GPU
+ *   hydia_encrypt_queries_device  out[i] = hydia_encrypt_query(row i, seed, nonce0 + i), bit for bit; nonce0 + n <= 2^40
+ *   hydia_encode_queries_device   out[i] = hydia_encode_query(row i), bit for bit
+ * Both make all n queries with one encoder / encryption pass per batch (batches sized from free device memory) and return n handles,
+ * each freed on its own; on any error every out[i] is NULL.
+ * NOT served: approaches 1 - 4, hydia_db_enroll_shard* and hydia_group_*, integer templates. */
+typedef enum { HYDIA_F64 = 0, HYDIA_F32 = 1, HYDIA_F16 = 2, HYDIA_BF16 = 3 } hydia_dtype;
+typedef struct {
+    const void *ptr;    /* device memory of the context's GPU; never written */
+    hydia_dtype dtype;
+    size_t n;           /* rows */
+    size_t row_stride;  /* elements between rows, >= vector_dim */
+    void *stream;       /* hipStream_t that produced the rows, or NULL */
+} hydia_dev_rows;
+int hydia_rows_widen_device(hydia_ctx *ctx, const hydia_dev_rows *rows, int normalise, double *dev_dst /* [n][vector_dim] */);
+int hydia_db_enroll_device(hydia_ctx *ctx, const hydia_dev_rows *rows, const uint8_t seed[32]);
+int hydia_plain_db_enroll_device(hydia_ctx *ctx, const hydia_dev_rows *rows);
+int hydia_db_update_device(hydia_ctx *ctx, size_t first_vector, const hydia_dev_rows *rows, int normalise, const uint8_t seed[32]);
+int hydia_plain_db_update_device(hydia_ctx *ctx, size_t first_vector, const hydia_dev_rows *rows, int normalise);
+int hydia_encrypt_queries_device(hydia_ctx *ctx, const hydia_dev_rows *rows, const uint8_t seed[32], uint64_t nonce0, hydia_ct **out /* n handles */);
+int hydia_encode_queries_device(hydia_ctx *ctx, const hydia_dev_rows *rows, hydia_pt **out /* n handles */);
 /* OpenFHEWrapper::chebyshevCompare (src/openFHE_wrapper.cpp:143-185) on every ciphertext of the batch */
 int hydia_chebyshev_compare(hydia_ctx *ctx, const hydia_ct *in, double delta, size_t sign_depth, hydia_ct **out);
 /* multi-GPU membership tail: sum the batch into one ciphertext, then EvalSum over all slots (:46-47) */

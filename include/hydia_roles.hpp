@@ -188,6 +188,14 @@ struct Plaintext {
     std::shared_ptr<PtHandle> pt;
     explicit operator bool() const { return pt && pt->h; }
 };
+// templates already in device memory (hydia.h, hydia_dev_rows): n rows of vector_dim elements of `dtype`, rowStride elements apart,
+// on the context's GPU, produced on `stream` (a hipStream_t; nullptr: complete already).  The rows are only read, and may be reused
+// when the call that takes them returns.  The overloads that take one do what their std::vector twins do, bit for bit
+struct DeviceRows {
+    hydia_dev_rows d;
+    DeviceRows(const void *ptr, hydia_dtype dtype, size_t n, size_t rowStride, void *stream = nullptr) : d{ptr, dtype, n, rowStride, stream} {}
+    size_t size() const { return d.n; }
+};
 inline std::vector<Ciphertext> split_batch(const CryptoContext &cc, hydia_ct *h) {
     std::vector<Ciphertext> v;
     if (!h) return v;
@@ -318,6 +326,19 @@ class DiagonalSender : public Sender {
         hydia_pt *h = nullptr;
         if (!cc->check(hydia_encode_query(cc->h, query.data(), &h), "encodeQuery")) return {};
         return Plaintext{std::make_shared<PtHandle>(cc, h)};
+    }
+    // one Plaintext per probe of `rows`, each what encodeQuery makes of that row: ONE library call (hydia_encode_queries_device)
+    std::vector<Plaintext> encodeQueries(const DeviceRows &rows) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: encodeQueries: a plain query is not served on a sharded context" << std::endl;
+            return {};
+        }
+        std::vector<hydia_pt *> h(rows.size() ? rows.size() : 1, nullptr);
+        if (!cc->check(hydia_encode_queries_device(cc->h, &rows.d, h.data()), "encodeQueries")) return {};
+        std::vector<Plaintext> r;
+        for (size_t i = 0; i < rows.size(); i++) r.push_back(Plaintext{std::make_shared<PtHandle>(cc, h[i])});
+        return r;
     }
     std::vector<Ciphertext> computeSimilarity(const Plaintext &query) {
         hydia_ct *out = run_pq(query, hydia_compute_similarity_pq, "computeSimilarity");
@@ -470,6 +491,21 @@ class DiagonalReceiver : public HersReceiver {
         if (!cc->check(hydia_encrypt_query(cc->h, query.data(), seed, ++nonce, &out), "encryptQuery")) return {};
         return split_batch(cc, out);
     }
+    // one queryCipher per probe of `rows` (hydia_encrypt_queries_device: ONE library call), each what encryptQuery makes of that row;
+    // the probes take the next rows.size() nonces of this receiver.  Not on a sharded context: an error, empty
+    std::vector<std::vector<Ciphertext>> encryptQueries(const DeviceRows &rows) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: encryptQueries: rows in device memory are not taken on a sharded context" << std::endl;
+            return {};
+        }
+        std::vector<hydia_ct *> h(rows.size() ? rows.size() : 1, nullptr);
+        if (!cc->check(hydia_encrypt_queries_device(cc->h, &rows.d, seed, nonce + 1, h.data()), "encryptQueries")) return {};
+        nonce += rows.size();
+        std::vector<std::vector<Ciphertext>> r;
+        for (size_t i = 0; i < rows.size(); i++) r.push_back(split_batch(cc, h[i]));
+        return r;
+    }
     // The switching key of a re-keyed database (hydia_keygen_switch; no counterpart in the reference): from the OLD receiver's secret
     // (oldSecret, [n_q+n_p][N] as hydia_export_secret_key gives it) to THIS receiver's, for DiagonalEnroller::rekeyDB.  Treat it like an
     // evaluation key.  seed32 == nullptr draws a fresh sampler key from the OS (use a fresh one per switching key).  Empty on failure.
@@ -570,6 +606,21 @@ class DiagonalEnroller : public EnrollerBase {
         return true;
     }
     bool appendDB(std::vector<std::vector<double>> &rows, const uint8_t *seed32 = nullptr) { return updateRows(numVectors, rows, true, seed32); }
+    // The same from rows in device memory (hydia_db_enroll_device / hydia_db_update_device): normalised on the device, never written.
+    // Not on a sharded context
+    void serializeDB(const DeviceRows &database) {
+        if (!device_rows_ok("serializeDB", database.size() == numVectors) || !next_seed("serializeDB")) return;
+        cc->check(hydia_db_enroll_device(cc->h, &database.d, seed), "serializeDB");
+    }
+    bool updateRows(size_t first_vector, const DeviceRows &rows, bool normalise = true, const uint8_t *seed32 = nullptr) {
+        if (!device_rows_ok("updateRows", true)) return false;
+        uint8_t s[32];
+        role_seed(s, seed32);
+        if (!cc->check(hydia_db_update_device(cc->h, first_vector, &rows.d, normalise ? 1 : 0, s), "updateRows")) return false;
+        if (first_vector + rows.size() > numVectors) numVectors = first_vector + rows.size();
+        return true;
+    }
+    bool appendDB(const DeviceRows &rows, const uint8_t *seed32 = nullptr) { return updateRows(numVectors, rows, true, seed32); }
     // Re-key the enrolled database in place under a new receiver key (hydia_db_rekey; no counterpart in the reference, which re-enrols):
     // every resident ciphertext is key-switched with `key`, the NEW receiver's DiagonalReceiver::genSwitchKey.  Afterwards the caller
     // imports the new receiver's evaluation and public keys; later updateRows / appendDB calls encrypt under the new public key.
@@ -587,6 +638,17 @@ class DiagonalEnroller : public EnrollerBase {
         return cc->check(hydia_db_rekey(cc->h, key.data()), "rekeyDB");
     }
     size_t size() const { return numVectors; }
+
+  private:
+    bool device_rows_ok(const char *what, bool count_ok) {
+        if (cc->group || !count_ok) {
+            cc->last_status = cc->group ? HYDIA_ERR_STATE : HYDIA_ERR_ARG;
+            std::cerr << "Error: " << what << ": "
+                      << (cc->group ? "rows in device memory are not taken on a sharded context" : "the rows are not the enroller's number of vectors") << std::endl;
+            return false;
+        }
+        return true;
+    }
 };
 
 // ---- a plain gallery (database kinds 7 / 8; an extension with no counterpart in the reference): the operator of the sender owns the
@@ -634,9 +696,31 @@ class PlainEnroller {
         return true;
     }
     bool appendDB(std::vector<std::vector<double>> &rows) { return updateRows(numVectors, rows, true); }
+    // The same from rows in device memory (hydia_plain_db_enroll_device / hydia_plain_db_update_device): normalised on the device,
+    // never written
+    void serializeDB(const DeviceRows &database) {
+        if (!device_rows_ok("serializeDB", database.size() == numVectors)) return;
+        cc->check(hydia_plain_db_enroll_device(cc->h, &database.d), "serializeDB");
+    }
+    bool updateRows(size_t first_vector, const DeviceRows &rows, bool normalise = true) {
+        if (!device_rows_ok("updateRows", true)) return false;
+        if (!cc->check(hydia_plain_db_update_device(cc->h, first_vector, &rows.d, normalise ? 1 : 0), "updateRows")) return false;
+        if (first_vector + rows.size() > numVectors) numVectors = first_vector + rows.size();
+        return true;
+    }
+    bool appendDB(const DeviceRows &rows) { return updateRows(numVectors, rows, true); }
     size_t size() const { return numVectors; }
 
   private:
+    bool device_rows_ok(const char *what, bool count_ok) {
+        if (cc->group || !count_ok) {
+            cc->last_status = cc->group ? HYDIA_ERR_STATE : HYDIA_ERR_ARG;
+            std::cerr << "Error: " << what << ": "
+                      << (cc->group ? "a plain gallery (kind 7 / 8) is not served on a sharded context" : "the rows are not the enroller's number of vectors") << std::endl;
+            return false;
+        }
+        return true;
+    }
     CryptoContext cc;
     size_t numVectors;
 };
