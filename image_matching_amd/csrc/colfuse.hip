@@ -130,6 +130,12 @@ DEV CfSum cf_mac_row(const u64 (&y)[NS][NR], int k, const CfConstN<NS> &f) {
 // H (2^60 mod q) by one exact FP64 product with its quotient, the top dword of L times 2^32 with one quotient, the low dword as it is —
 // |operand| <= 1.4 q (H < 2^50: the quotient estimate is off by at most 3/8, so the first term stays below 0.875 q; the second below
 // 0.5 q; 1.9 q with the dropped limb's centred residue).  The canonical results after pass 2 are the same residues.
+// Both figures take q >> 2^32 (the low dword) and a dropped limb about as large as the target (its centred residue adds q_l / 2) for
+// granted.  Where either fails — a target below 2^40, or q_l > (1 + 1/32) q: a 48-bit limb dropped beside 45-bit targets — cf_fp_wide
+// says so and the operands of that target are re-centred after the conversion, |operand| <= (q + 1) / 2: an exact step on integral
+// doubles below 2^52, the same residues.  The test is workgroup-uniform (one scalar branch per target) and false for every target of a
+// chain whose scaling primes lie within 3 % of each other, the default chain among them (1.375 q + 0.516 q + 2^32 < 1.9 q there).
+DEV bool cf_fp_wide(const ModC &M, u64 ql) { return M.q < (1ull << 40) || ql > M.q + (M.q >> 5); }
 DEV double cf_fold(const FpA &ar, const CfSum a, double c60) {
     const double t1 = ar.mulmod2(FpA::u2d(a.H), c60);
     const double h = (double)(unsigned)(a.L >> 32) * 4294967296.0;  // exact
@@ -230,7 +236,7 @@ DEV void cf_convert(const IntP ar, const ModC &M, const CfConstN<NS> &f, const u
 }
 template <bool MDR, int NR, int NS>
 DEV void cf_convert(const FpA ar, const ModC &M, const CfConstN<NS> &f, const u64 (&y)[NS][NR], const u64 *um /* [k * 256] */,
-                    unsigned neg, double c60, double (&v)[NR], bool nosrc) {
+                    unsigned neg, double c60, double (&v)[NR], bool nosrc, u64 ql /* MDR: the dropped limb's modulus */) {
 #pragma unroll
     for (int k = 0; k < NR; k++) {
         double r = nosrc ? 0.0 : cf_fold(ar, cf_mac_row(y, k, f), c60);
@@ -239,6 +245,10 @@ DEV void cf_convert(const FpA ar, const ModC &M, const CfConstN<NS> &f, const u6
             r += ((neg >> k) & 1u) ? -c : c;
         }
         v[k] = r;
+    }
+    if (cf_fp_wide(M, MDR ? ql : 0)) {
+#pragma unroll
+        for (int k = 0; k < NR; k++) ar.recentre(v[k]);
     }
 }
 
@@ -363,7 +373,7 @@ __global__ __launch_bounds__(256, 2) void k_ntt15_colfuse(NttTables T, const u64
         if (fp) {
             const FpA ar(M);
             double v[16];
-            cf_convert<MDR, 16>(ar, M, f, y, umem, neg, FpA::u2d(cf.t60[tt]), v, MDR && cf.nk == 0);
+            cf_convert<MDR, 16>(ar, M, f, y, umem, neg, FpA::u2d(cf.t60[tt]), v, MDR && cf.nk == 0, cf.lM.q);
             CF_STORE_LTW();
             cf_forward<FpA>(ar, tw, ltw, lds, g, col, v, d);
         } else if ((T.pm_mask >> m) & 1u) {
@@ -611,7 +621,7 @@ __global__ __launch_bounds__(256, NS > HY_CF_SRC ? 2 : 3) void k_ntt15_colfuse8(
         if (fp) {
             const FpA ar(M);
             double v[8];
-            cf_convert<MDR, 8>(ar, M, f, y, umem, neg, FpA::u2d(cf.t60[tt]), v, MDR && cf.nk == 0);
+            cf_convert<MDR, 8>(ar, M, f, y, umem, neg, FpA::u2d(cf.t60[tt]), v, MDR && cf.nk == 0, cf.lM.q);
             ltw[t & 127] = ltv;
             cf_forward8<FpA>(ar, tw, ltw, lds, g, col, v, d);
         } else if ((T.pm_mask >> m) & 1u) {
@@ -690,6 +700,10 @@ __global__ __launch_bounds__(256, MDR ? 2 : 4) void k_ntt15_conv_p1(NttTables T,
             double r = cf_fold(ar, a, c60);
             if (MDR) r += ng ? -FpA::u2d(mag) : FpA::u2d(mag);
             v[k] = r;
+        }
+        if (cf_fp_wide(M, MDR ? Ml.q : 0)) {
+#pragma unroll
+            for (int k = 0; k < 16; k++) ar.recentre(v[k]);
         }
         cf_forward<FpA>(ar, tw, ltw, lds, g, col, v, d);
     } else {
@@ -782,6 +796,10 @@ __global__ __launch_bounds__(256, 4) void k_ntt15_conv_p1_8(NttTables T, const u
             if (MDR) r += ng ? -FpA::u2d(mag) : FpA::u2d(mag);
             v[k] = r;
         }
+        if (cf_fp_wide(M, MDR ? Ml.q : 0)) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) ar.recentre(v[k]);
+        }
         cf_forward8<FpA>(ar, tw, ltw, lds, g, col, v, d);
     } else {
         const bool pm = (T.pm_mask >> m) & 1u;
@@ -863,12 +881,17 @@ void ntt15_colfuse(hipStream_t st, const NttTables &T, const u64 *src, size_t so
         else (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ntt15_colfuse<false>), hipFuncAttributeMaxDynamicSharedMemorySize, CF_LDS_BYTES);
         attr_done[dev][mdr] = true;
     }
-    int nt_max = 0;
+    int nt_max = 0, nk_max = 0;
     double rows = 0;  // sources in, targets out, each once
     for (int i = 0; i < ncf; i++) {
         nt_max = std::max(nt_max, h_cf[i].nt);
+        nk_max = std::max(nk_max, h_cf[i].nk);
         rows += h_cf[i].nk + (h_cf[i].mdr ? 1 : 0) + h_cf[i].nt;
     }
+    // five sources exist in the narrow kernel's five-source instantiation only: the small-launch kernels hold four (CfConst, cf_mac4)
+    // and would drop the fifth without a word
+    if (nk_max > HY_CF_SRC_MAX || (pre && nk_max > HY_CF_SRC))
+        throw std::logic_error("hydia: column-fused conversion with more than four sources in the small-launch form");
     if (pre && !T.cf_wide) {  // small launch: one target per workgroup, 16-column tiles
         ledger_add(mdr ? "k_ntt15_conv_p1_8<true>" : "k_ntt15_conv_p1_8<false>", rows * XP * 262144.0);
         if (mdr) hipLaunchKernelGGL((k_ntt15_conv_p1_8<true>), dim3(16, XP, ncf * nt_max), dim3(256), 0, st, T, src, so, dst, dso, d_cf, nt_max);
@@ -881,10 +904,7 @@ void ntt15_colfuse(hipStream_t st, const NttTables &T, const u64 *src, size_t so
         else hipLaunchKernelGGL((k_ntt15_conv_p1<false>), dim3(8, XP, ncf * nt_max), dim3(256), 0, st, T, src, so, dst, dso, d_cf, nt_max);
         return;
     }
-    int nk_max = 0;
-    for (int i = 0; i < ncf; i++) nk_max = std::max(nk_max, h_cf[i].nk);
     if (nk_max > HY_CF_SRC) {  // five sources (special primes below 2^48; cf_plan_* vouches): the narrow kernel's five-source instantiation only
-        if (pre || nk_max > HY_CF_SRC_MAX) throw std::logic_error("hydia: column-fused conversion with more than four sources in the small-launch form");
         ledger_add(mdr ? "k_ntt15_colfuse8<true, 5>" : "k_ntt15_colfuse8<false, 5>", rows * XP * 262144.0);
         if (mdr) hipLaunchKernelGGL((k_ntt15_colfuse8<true, 5>), dim3(16, XP, ncf), dim3(256), CF8_LDS_BYTES, st, T, src, so, dst, dso, d_cf, 1, nt_max);
         else hipLaunchKernelGGL((k_ntt15_colfuse8<false, 5>), dim3(16, XP, ncf), dim3(256), CF8_LDS_BYTES, st, T, src, so, dst, dso, d_cf, 1, nt_max);

@@ -44,7 +44,9 @@ missing term — sat / uniform and uniform / sat carry that.
 
 NOT reached: the extended limbs of a digit are base-conversion outputs; their joint worst case with a saturated key (every extended
 residue at q - 1 together with the key) is not constructed — only the own-digit terms are (q - 1)^2 by construction.  The
-conversions' own inputs are the business of the column-fused tests.  The sharded contexts' borrowed keys are not re-keyed here.
+conversions' own inputs are the business of the column-fused tests: tests/test_gpu_colfuse_edges.py lays the patterns on the
+conversion SOURCES, in coefficient form, for the ModUp, the ModDown and the merged ModDown + Rescale (helpers in tests/colfuse_ref.py,
+the host side in tests/test_colfuse_edges_cpu.py).  The sharded contexts' borrowed keys are not re-keyed here.
 
 Nothing of the issue's list was dropped.  Measured on one MI355X: the whole file (about 200 cases) takes a quarter of a minute.  A
 relinearize or eval_rotate case (both batches) 0.07 s, a loop A case on the default engine 0.3 s (it computes the oracle's fifteen
