@@ -3,6 +3,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include <sys/random.h>
@@ -30,9 +31,129 @@ Params hydia_to_params(const hydia_params *p) {
     r.dim = (int)p->vector_dim;
     return r;
 }
+static void copy_moduli(const HostParams &h, uint64_t *moduli, uint64_t *roots) {
+    for (int m = 0; m < h.nT; m++) {
+        if (moduli) moduli[m] = h.q[m];
+        if (roots) roots[m] = h.psi[m];
+    }
+}
+// HYDIA_OK when `device` is a HIP device of this machine, else the code recorded with its message
+static int check_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(HYDIA_ERR_DEVICE, "hydia: no HIP device visible — libhydia has no CPU fallback");
+    REQUIRE(device >= 0, "bad device index");
+    if (device >= ndev)  // a device this machine does not have (a shard list written for a bigger node): a device error, not a typo
+        return fail(HYDIA_ERR_DEVICE, "hydia: device index " + std::to_string(device) + " but only " + std::to_string(ndev) + " HIP device(s) visible");
+    return HYDIA_OK;
+}
 static void fill_info(const HostParams &h, hydia_info *o) {
     o->log_n = h.prm.logN; o->n = h.N; o->slots = h.slots; o->n_q = h.nQ; o->n_p = h.nP; o->dnum = h.prm.dnum;
     o->alpha = h.alpha; o->vector_dim = h.prm.dim; o->delta = h.delta;
+}
+// ---- what several entry points below do alike, once
+template <class H>
+static void free_handle(H *h) {
+    if (!h) return;
+    hydia_ctx *owner = h->owner;
+    use_device(owner);  // the buffer goes back to the pool (or the context goes away) under the context's own GPU
+    delete h;
+    if (owner && owner->refs.fetch_sub(1) == 1) delete owner;
+}
+// kind and baby count of a resident diagonal database (ciphertexts: kinds 5 / 6, a plain gallery: 7 / 8) in the form of B babies
+static void set_diagonal_form(Context &cx, bool plain, int B) {
+    cx.db_kind = (plain ? 7 : 5) + (B < cx.prm.dim ? 1 : 0);
+    cx.db_babies = B;
+}
+// the frame of every diagonal enrolment of n vectors: the baby count from the blocks (matvec: hydia_db_enroll_shard_ex), no kind while
+// the database is rebuilt, room for it, enrol(B), then the kind and babies it now has
+template <class Enrol>
+static void enroll_diagonal(hydia_ctx *ctx, size_t n, bool plain, int matvec, Enrol enrol) {
+    Context &cx = ctx->cx;
+    const size_t G = (n + (size_t)cx.slots - 1) / (size_t)cx.slots;
+    const int B = cx.babies_for(G, matvec);
+    cx.db_kind = 0;
+    cx.db_resize(n, hydia_db_num_cts(ctx, n), B, plain);
+    enrol(B);
+    set_diagonal_form(cx, plain, B);
+}
+// a DECLARED form: vector_dim (hoisted) or a power of two >= 2 dividing it — never 0 / 1, which mean "auto" / "hoisted" only in
+// hydia_set_matvec's policy and would silently mark an imported hoisted database as pre-rotated
+static int check_declared_babies(const Context &cx, int babies) {
+    const int dim = cx.prm.dim;
+    REQUIRE(babies == dim || (babies >= 2 && babies < dim && (babies & (babies - 1)) == 0 && dim % babies == 0),
+            "the declared baby count must be vector_dim or a power of two >= 2 dividing it");
+    return HYDIA_OK;
+}
+// loop B's bounds and the packed layouts (46 / 48 bits of a residue) assume canonical residues: one encoded polynomial [n_q][N] is
+// checked before anything is created or written
+static int check_canonical(const Context &cx, const uint64_t *data) {
+    for (int j = 0; j < cx.nQ; j++)
+        for (int c = 0; c < cx.N; c++)
+            REQUIRE(data[(size_t)j * cx.N + c] < cx.q[j], "plaintext residue at or above its modulus");
+    return HYDIA_OK;
+}
+// entry t of the resident database from / to host memory through a pooled staging buffer: `polys` polynomials [n_q][N] (a ciphertext
+// two, a plaintext of a plain gallery one)
+static void db_entry_in(Context &cx, size_t t, const uint64_t *data, int polys) {
+    const size_t e = (size_t)polys * cx.nQ * cx.N;
+    u64 *tmp = cx.pool.get(e * sizeof(u64));
+    cx.sync();
+    HIP_CHECK(hipMemcpy(tmp, data, e * sizeof(u64), hipMemcpyHostToDevice));
+    cx.db_store(t, tmp, 1);  // (a row-packed database, kind 1, is addressed the same way: its layout is the unpacked ciphertext-major one)
+    cx.sync();
+    cx.pool.put(tmp);
+}
+static void db_entry_out(Context &cx, size_t t, uint64_t *data, int polys) {
+    const size_t e = (size_t)polys * cx.nQ * cx.N;
+    u64 *tmp = cx.pool.get(e * sizeof(u64));
+    cx.db_fetch(t, tmp, 1);
+    cx.sync();
+    HIP_CHECK(hipMemcpy(data, tmp, e * sizeof(u64), hipMemcpyDeviceToHost));
+    cx.pool.put(tmp);
+}
+// what every in-place update checks before any work, in this order: the other kind resident, nothing resident, a null seed (ciphertext
+// target only), first_vector past the end, the row count.  HYDIA_OK, or the code recorded with its message
+static int check_update(const Context &cx, bool plain, size_t first_vector, size_t n, const uint8_t *seed) {
+    if (plain) {
+        if (cx.d_db && cx.db_cts && (cx.db_kind == 5 || cx.db_kind == 6))
+            return fail(HYDIA_ERR_STATE, "hydia: a ciphertext database (kind 5 / 6) is resident: it is updated in place by hydia_db_update (with a seed)");
+        if (!cx.d_db || cx.db_cts == 0 || !cx.db_plain())
+            return fail(HYDIA_ERR_STATE, "hydia: no plain gallery resident (an update needs kind 7 or 8: hydia_plain_db_enroll, hydia_plain_db_alloc or hydia_plain_db_load)");
+        REQUIRE(first_vector <= cx.db_vectors, "first_vector lies past the end of the gallery (an update leaves no holes)");
+    } else {
+        if (cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: it is updated in place by hydia_plain_db_update (no seed: nothing is encrypted)");
+        if (!cx.d_db || cx.db_cts == 0 || (cx.db_kind != 5 && cx.db_kind != 6))
+            return fail(HYDIA_ERR_STATE, "hydia: no diagonal database resident (an update needs kind 5 or 6: hydia_db_enroll, hydia_db_load or an import)");
+        REQUIRE(seed, "null argument");
+        REQUIRE(first_vector <= cx.db_vectors, "first_vector lies past the end of the database (an update leaves no holes)");
+    }
+    // (rows in device memory arrive with n already inside this bound: check_dev_rows, row_stride >= vector_dim)
+    REQUIRE(n <= SIZE_MAX / sizeof(double) / (size_t)cx.prm.dim && first_vector + n >= first_vector, "row count out of range");
+    return HYDIA_OK;
+}
+// a batch of queries (H: hydia_ct, or hydia_pt for plain queries) in shared passes over the database, run = the Context's scenario of
+// the batch's form: out[q] = the single-query result for queries[q]; on any error every out[q] is NULL.  gallery: a plain gallery's
+// batch, refused on a shard of a group
+template <class H>
+static int batch_call(hydia_ctx *ctx, const H *const *queries, uint32_t n_queries, hydia_ct **out, int what,
+                      std::vector<Ct> (Context::*run)(const std::vector<const Ct *> &, int), bool gallery = false) {
+    if (out)
+        for (uint32_t q = 0; q < n_queries; q++) out[q] = nullptr;
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && queries && out, "null argument");
+    REQUIRE(n_queries >= 1, (std::is_same<H, hydia_pt>::value ? "a batch of plain queries needs at least one query" : "a batch of queries needs at least one query"));
+    std::vector<const Ct *> qs(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) {
+        REQUIRE(queries[q], "null query in the batch");
+        qs[q] = &queries[q]->c;
+    }
+    if (gallery && ctx->in_group) throw StateError("hydia: a plain gallery (kind 7 / 8) is not served on a shard of a group: neither are its batches");
+    std::vector<Ct> r = (ctx->cx.*run)(qs, what);
+    for (uint32_t q = 0; q < n_queries; q++) out[q] = wrap(ctx, std::move(r[q]));  // compact and owning: no copy, cannot fail
+    return HYDIA_OK;
+    API_END
 }
 extern "C" {
 
@@ -107,22 +228,14 @@ int hydia_params_describe(const hydia_params *p, hydia_info *info, uint64_t *mod
     REQUIRE(p, "null params");
     HostParams h(hydia_to_params(p));
     if (info) fill_info(h, info);
-    for (int m = 0; m < h.nT; m++) {
-        if (moduli) moduli[m] = h.q[m];
-        if (roots) roots[m] = h.psi[m];
-    }
+    copy_moduli(h, moduli, roots);
     return HYDIA_OK;
     API_END
 }
 int hydia_ctx_create(const hydia_params *p, int device, hydia_ctx **out) {
     API_BEGIN
     REQUIRE(p && out, "null argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(HYDIA_ERR_DEVICE, "hydia: no HIP device visible — libhydia has no CPU fallback");
-    REQUIRE(device >= 0, "bad device index");
-    if (device >= ndev)  // a device this machine does not have (a shard list written for a bigger node): a device error, not a typo
-        return fail(HYDIA_ERR_DEVICE, "hydia: device index " + std::to_string(device) + " but only " + std::to_string(ndev) + " HIP device(s) visible");
+    if (int code = check_device(device)) return code;
     *out = new hydia_ctx(hydia_to_params(p), device);
     return HYDIA_OK;
     API_END
@@ -132,12 +245,7 @@ int hydia_ctx_create_custom(const hydia_params *p, const uint64_t *moduli, const
     API_BEGIN
     REQUIRE(p && out && moduli, "null argument");
     REQUIRE(n_q >= 2 && n_p >= 1 && n_q + n_p <= HY_MAX_MODS, "bad limb counts");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(HYDIA_ERR_DEVICE, "hydia: no HIP device visible — libhydia has no CPU fallback");
-    REQUIRE(device >= 0, "bad device index");
-    if (device >= ndev)  // a device this machine does not have (a shard list written for a bigger node): a device error, not a typo
-        return fail(HYDIA_ERR_DEVICE, "hydia: device index " + std::to_string(device) + " but only " + std::to_string(ndev) + " HIP device(s) visible");
+    if (int code = check_device(device)) return code;
     Params prm = hydia_to_params(p);
     prm.mult_depth = (int)n_q - 1;
     prm.custom_q.assign(moduli, moduli + n_q + n_p);
@@ -159,10 +267,7 @@ int hydia_get_info(const hydia_ctx *ctx, hydia_info *out) {
 }
 int hydia_get_moduli(const hydia_ctx *ctx, uint64_t *moduli, uint64_t *roots) {
     REQUIRE(ctx, "null ctx");
-    for (int m = 0; m < ctx->cx.nT; m++) {
-        if (moduli) moduli[m] = ctx->cx.q[m];
-        if (roots) roots[m] = ctx->cx.psi[m];
-    }
+    copy_moduli(ctx->cx, moduli, roots);
     return HYDIA_OK;
 }
 int hydia_sync(hydia_ctx *ctx) {
@@ -271,25 +376,21 @@ int hydia_import_secret_key(hydia_ctx *ctx, const uint64_t *data) {
     return import_buf(ctx->cx, &ctx->cx.d_sk, data, (size_t)ctx->cx.nT * ctx->cx.N);
     API_END
 }
-int hydia_export_public_key(hydia_ctx *ctx, uint64_t *data) {
+static int export_buf(hydia_ctx *ctx, u64 *Context::*key, size_t polys, uint64_t *data, const char *missing) {
     API_BEGIN
     use_device(ctx);
     REQUIRE(ctx && data, "null argument");
-    if (!ctx->cx.d_pk) return fail(HYDIA_ERR_STATE, "hydia: public key not loaded");
+    if (!(ctx->cx.*key)) return fail(HYDIA_ERR_STATE, missing);
     ctx->cx.sync();
-    HIP_CHECK(hipMemcpy(data, ctx->cx.d_pk, (size_t)2 * ctx->cx.nQ * ctx->cx.N * sizeof(u64), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(data, ctx->cx.*key, polys * ctx->cx.N * sizeof(u64), hipMemcpyDeviceToHost));
     return HYDIA_OK;
     API_END
 }
+int hydia_export_public_key(hydia_ctx *ctx, uint64_t *data) {
+    return export_buf(ctx, &Context::d_pk, ctx ? (size_t)2 * ctx->cx.nQ : 0, data, "hydia: public key not loaded");
+}
 int hydia_export_secret_key(hydia_ctx *ctx, uint64_t *data) {
-    API_BEGIN
-    use_device(ctx);
-    REQUIRE(ctx && data, "null argument");
-    if (!ctx->cx.d_sk) return fail(HYDIA_ERR_STATE, "hydia: secret key not loaded");
-    ctx->cx.sync();
-    HIP_CHECK(hipMemcpy(data, ctx->cx.d_sk, (size_t)ctx->cx.nT * ctx->cx.N * sizeof(u64), hipMemcpyDeviceToHost));
-    return HYDIA_OK;
-    API_END
+    return export_buf(ctx, &Context::d_sk, ctx ? (size_t)ctx->cx.nT : 0, data, "hydia: secret key not loaded");
 }
 
 // ------------------------------------------------------------------ ciphertext handles
@@ -388,13 +489,7 @@ int hydia_ct_limb_prefix(hydia_ctx *ctx, const hydia_ct *ct, uint32_t n_limbs, h
     return HYDIA_OK;
     API_END
 }
-void hydia_ct_free(hydia_ct *ct) {
-    if (!ct) return;
-    hydia_ctx *owner = ct->owner;
-    use_device(owner);  // the buffer goes back to the pool (or the context goes away) under the context's own GPU
-    delete ct;
-    if (owner && owner->refs.fetch_sub(1) == 1) delete owner;
-}
+void hydia_ct_free(hydia_ct *ct) { free_handle(ct); }
 
 // ------------------------------------------------------------------ receiver
 int hydia_encrypt_query(hydia_ctx *ctx, const double *query, const uint8_t seed[32], uint64_t nonce, hydia_ct **out) {
@@ -467,8 +562,7 @@ int hydia_db_alloc(hydia_ctx *ctx, size_t n_vectors) {
     use_device(ctx);
     REQUIRE(ctx && n_vectors >= 1, "bad argument");
     ctx->cx.db_resize(n_vectors, hydia_db_num_cts(ctx, n_vectors), ctx->cx.prm.dim);
-    ctx->cx.db_kind = 5;
-    ctx->cx.db_babies = ctx->cx.prm.dim;
+    set_diagonal_form(ctx->cx, false, ctx->cx.prm.dim);
     return HYDIA_OK;
     API_END
 }
@@ -480,17 +574,8 @@ int hydia_db_import_ct(hydia_ctx *ctx, size_t t, const uint64_t *data) {
     if (!cx.d_db) return fail(HYDIA_ERR_STATE, "hydia: no database resident (call hydia_db_alloc)");
     if (cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: it holds plaintexts (hydia_plain_db_import_pt), not ciphertexts");
     REQUIRE(t < cx.db_cts, "ciphertext index out of range");
-    const size_t e = (size_t)2 * cx.nQ * cx.N;
-    u64 *tmp = cx.pool.get(e * sizeof(u64));
-    cx.sync();
-    HIP_CHECK(hipMemcpy(tmp, data, e * sizeof(u64), hipMemcpyHostToDevice));
-    cx.db_store(t, tmp, 1);  // (a row-packed database, kind 1, is addressed the same way: its layout is the unpacked ciphertext-major one)
-    cx.sync();
-    cx.pool.put(tmp);
-    if (cx.db_kind == 0) {
-        cx.db_kind = 5;
-        cx.db_babies = cx.prm.dim;
-    }
+    db_entry_in(cx, t, data, 2);
+    if (cx.db_kind == 0) set_diagonal_form(cx, false, cx.prm.dim);
     return HYDIA_OK;
     API_END
 }
@@ -502,12 +587,7 @@ int hydia_db_export_ct(hydia_ctx *ctx, size_t t, uint64_t *data) {
     if (!cx.d_db) return fail(HYDIA_ERR_STATE, "hydia: no database resident");
     if (cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: it holds plaintexts (hydia_plain_db_export_pt), not ciphertexts");
     REQUIRE(t < cx.db_cts, "ciphertext index out of range");
-    const size_t e = (size_t)2 * cx.nQ * cx.N;
-    u64 *tmp = cx.pool.get(e * sizeof(u64));
-    cx.db_fetch(t, tmp, 1);
-    cx.sync();
-    HIP_CHECK(hipMemcpy(data, tmp, e * sizeof(u64), hipMemcpyDeviceToHost));
-    cx.pool.put(tmp);
+    db_entry_out(cx, t, data, 2);
     return HYDIA_OK;
     API_END
 }
@@ -528,8 +608,7 @@ int hydia_db_fill_random(hydia_ctx *ctx, size_t n_vectors, uint64_t seed) {
     }
     cx.sync();
     cx.pool.put(tmp);
-    cx.db_babies = babies;
-    cx.db_kind = cx.db_babies < cx.prm.dim ? 6 : 5;
+    set_diagonal_form(cx, false, babies);
     return HYDIA_OK;
     API_END
 }
@@ -539,14 +618,7 @@ int hydia_db_enroll_shard_ex(hydia_ctx *ctx, double *db, size_t n, const uint8_t
     API_BEGIN
     use_device(ctx);
     REQUIRE(ctx && db && seed && n >= 1 && matvec >= 0, "bad argument");
-    Context &cx = ctx->cx;
-    const size_t G = (n + (size_t)cx.slots - 1) / (size_t)cx.slots;
-    const int B = cx.babies_for(G, matvec);
-    cx.db_kind = 0;
-    cx.db_resize(n, hydia_db_num_cts(ctx, n), B);
-    client_enroll(cx, db, n, seed, first_block, B);
-    cx.db_kind = B < cx.prm.dim ? 6 : 5;
-    cx.db_babies = B;
+    enroll_diagonal(ctx, n, false, matvec, [&](int B) { client_enroll(ctx->cx, db, n, seed, first_block, B); });
     return HYDIA_OK;
     API_END
 }
@@ -559,12 +631,7 @@ int hydia_db_update_shard(hydia_ctx *ctx, size_t first_vector, double *rows, siz
     REQUIRE(ctx, "null argument");
     use_device(ctx);
     Context &cx = ctx->cx;
-    if (cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: it is updated in place by hydia_plain_db_update (no seed: nothing is encrypted)");
-    if (!cx.d_db || cx.db_cts == 0 || (cx.db_kind != 5 && cx.db_kind != 6))
-        return fail(HYDIA_ERR_STATE, "hydia: no diagonal database resident (an update needs kind 5 or 6: hydia_db_enroll, hydia_db_load or an import)");
-    REQUIRE(seed, "null argument");
-    REQUIRE(first_vector <= cx.db_vectors, "first_vector lies past the end of the database (an update leaves no holes)");
-    REQUIRE(n <= SIZE_MAX / sizeof(double) / (size_t)cx.prm.dim && first_vector + n >= first_vector, "row count out of range");
+    if (int code = check_update(cx, false, first_vector, n, seed)) return code;
     if (n == 0) return HYDIA_OK;
     REQUIRE(rows, "null rows");
     client_db_update(cx, first_vector, rows, n, normalise, seed, first_block);
@@ -608,16 +675,10 @@ int hydia_db_set_babies(hydia_ctx *ctx, int babies) {
     Context &cx = ctx->cx;
     if (cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: its form is declared at allocation (hydia_plain_db_alloc)");
     if (!cx.d_db || cx.db_cts == 0 || (cx.db_kind != 5 && cx.db_kind != 6)) return fail(HYDIA_ERR_STATE, "hydia: no diagonal database resident");
-    // a DECLARED form: vector_dim (hoisted) or a power of two >= 2 dividing it — never 0 / 1, which mean "auto" / "hoisted" only in
-    // hydia_set_matvec's policy and would silently mark an imported hoisted database as pre-rotated
-    const int dim = cx.prm.dim;
-    REQUIRE(babies == dim || (babies >= 2 && babies < dim && (babies & (babies - 1)) == 0 && dim % babies == 0),
-            "the declared baby count must be vector_dim or a power of two >= 2 dividing it");
-    const int B = babies;
+    if (int code = check_declared_babies(cx, babies)) return code;
     use_device(ctx);
-    cx.db_relayout(B);  // no-op unless the resident order was chosen for another form (hydia_db_alloc assumes the hoisted one)
-    cx.db_babies = B;
-    cx.db_kind = cx.db_babies < cx.prm.dim ? 6 : 5;
+    cx.db_relayout(babies);  // no-op unless the resident order was chosen for another form (hydia_db_alloc assumes the hoisted one)
+    set_diagonal_form(cx, false, babies);
     return HYDIA_OK;
     API_END
 }
@@ -633,14 +694,7 @@ int hydia_plain_db_enroll(hydia_ctx *ctx, double *db, size_t n) {
     use_device(ctx);
     REQUIRE(ctx && db && n >= 1, "bad argument");
     if (ctx->in_group) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is not enrolled on a shard of a group: the sharded senders do not serve it yet");
-    Context &cx = ctx->cx;
-    const size_t G = (n + (size_t)cx.slots - 1) / (size_t)cx.slots;
-    const int B = cx.babies_for(G, 0);
-    cx.db_kind = 0;
-    cx.db_resize(n, hydia_db_num_cts(ctx, n), B, true);
-    client_plain_enroll(cx, db, n, B);
-    cx.db_kind = B < cx.prm.dim ? 8 : 7;
-    cx.db_babies = B;
+    enroll_diagonal(ctx, n, true, 0, [&](int B) { client_plain_enroll(ctx->cx, db, n, B); });
     return HYDIA_OK;
     API_END
 }
@@ -650,15 +704,12 @@ int hydia_plain_db_alloc(hydia_ctx *ctx, size_t n_vectors, int babies) {
     REQUIRE(ctx && n_vectors >= 1, "bad argument");
     if (ctx->in_group) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is not enrolled on a shard of a group: the sharded senders do not serve it yet");
     Context &cx = ctx->cx;
-    const int dim = cx.prm.dim;
-    REQUIRE(babies == dim || (babies >= 2 && babies < dim && (babies & (babies - 1)) == 0 && dim % babies == 0),
-            "the declared baby count must be vector_dim or a power of two >= 2 dividing it");
+    if (int code = check_declared_babies(cx, babies)) return code;
     cx.db_kind = 0;
     cx.db_resize(n_vectors, hydia_db_num_cts(ctx, n_vectors), babies, true);
     HIP_CHECK(hipMemsetAsync(cx.d_db, 0, cx.db_alloc_bytes, cx.stream));  // plaintexts never imported are zero polynomials
     cx.sync();
-    cx.db_kind = babies < dim ? 8 : 7;
-    cx.db_babies = babies;
+    set_diagonal_form(cx, true, babies);
     return HYDIA_OK;
     API_END
 }
@@ -669,17 +720,8 @@ int hydia_plain_db_import_pt(hydia_ctx *ctx, size_t t, const uint64_t *data) {
     Context &cx = ctx->cx;
     if (!cx.d_db || !cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: no plain gallery resident (call hydia_plain_db_alloc)");
     REQUIRE(t < cx.db_cts, "plaintext index out of range");
-    // the packed layouts keep 46 / 48 bits of a residue and loop B's bounds assume canonical ones: checked before anything is written
-    for (int j = 0; j < cx.nQ; j++)
-        for (int c = 0; c < cx.N; c++)
-            REQUIRE(data[(size_t)j * cx.N + c] < cx.q[j], "plaintext residue at or above its modulus");
-    const size_t e = (size_t)cx.nQ * cx.N;
-    u64 *tmp = cx.pool.get(e * sizeof(u64));
-    cx.sync();
-    HIP_CHECK(hipMemcpy(tmp, data, e * sizeof(u64), hipMemcpyHostToDevice));
-    cx.db_store(t, tmp, 1);
-    cx.sync();
-    cx.pool.put(tmp);
+    if (int code = check_canonical(cx, data)) return code;
+    db_entry_in(cx, t, data, 1);
     return HYDIA_OK;
     API_END
 }
@@ -690,12 +732,7 @@ int hydia_plain_db_export_pt(hydia_ctx *ctx, size_t t, uint64_t *data) {
     Context &cx = ctx->cx;
     if (!cx.d_db || !cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: no plain gallery resident");
     REQUIRE(t < cx.db_cts, "plaintext index out of range");
-    const size_t e = (size_t)cx.nQ * cx.N;
-    u64 *tmp = cx.pool.get(e * sizeof(u64));
-    cx.db_fetch(t, tmp, 1);
-    cx.sync();
-    HIP_CHECK(hipMemcpy(data, tmp, e * sizeof(u64), hipMemcpyDeviceToHost));
-    cx.pool.put(tmp);
+    db_entry_out(cx, t, data, 1);
     return HYDIA_OK;
     API_END
 }
@@ -704,12 +741,7 @@ int hydia_plain_db_update(hydia_ctx *ctx, size_t first_vector, double *rows, siz
     REQUIRE(ctx, "null argument");
     use_device(ctx);
     Context &cx = ctx->cx;
-    if (cx.d_db && cx.db_cts && (cx.db_kind == 5 || cx.db_kind == 6))
-        return fail(HYDIA_ERR_STATE, "hydia: a ciphertext database (kind 5 / 6) is resident: it is updated in place by hydia_db_update (with a seed)");
-    if (!cx.d_db || cx.db_cts == 0 || !cx.db_plain())
-        return fail(HYDIA_ERR_STATE, "hydia: no plain gallery resident (an update needs kind 7 or 8: hydia_plain_db_enroll, hydia_plain_db_alloc or hydia_plain_db_load)");
-    REQUIRE(first_vector <= cx.db_vectors, "first_vector lies past the end of the gallery (an update leaves no holes)");
-    REQUIRE(n <= SIZE_MAX / sizeof(double) / (size_t)cx.prm.dim && first_vector + n >= first_vector, "row count out of range");
+    if (int code = check_update(cx, true, first_vector, n, nullptr)) return code;
     if (n == 0) return HYDIA_OK;
     REQUIRE(rows, "null rows");
     client_plain_db_update(cx, first_vector, rows, n, normalise);
@@ -946,20 +978,12 @@ int hydia_compute_similarity_rotated(hydia_ctx *ctx, const hydia_ct *query, hydi
 int hydia_index_scenario_rotated(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.index_scenario_rot(query->c)) }
 int hydia_index_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.index_scenario(query->c)) }
 int hydia_membership_scenario(hydia_ctx *ctx, const hydia_ct *query, hydia_ct **out) { SENDER_CALL(ctx->cx.membership_scenario(query->c)) }
-// a batch of queries in one pass over the database: out[q] = the single-query result for queries[q]; on any error every out[q] is NULL
 // ------------------------------------------------------------------ plain query (the sender knows the probe; kinds 5 / 6 only)
-static hydia_pt *wrap_pt(hydia_ctx *owner, Ct &&c) {
-    hydia_pt *h = new hydia_pt;
-    h->c = std::move(c);
-    h->owner = owner;
-    owner->refs.fetch_add(1);
-    return h;
-}
 int hydia_encode_query(hydia_ctx *ctx, const double *query, hydia_pt **out) {
     API_BEGIN
     use_device(ctx);
     REQUIRE(ctx && query && out, "null argument");
-    *out = wrap_pt(ctx, client_encode_query(ctx->cx, query));
+    *out = wrap<hydia_pt>(ctx, client_encode_query(ctx->cx, query));
     return HYDIA_OK;
     API_END
 }
@@ -968,14 +992,11 @@ int hydia_pt_import(hydia_ctx *ctx, const uint64_t *data, double scale, hydia_pt
     use_device(ctx);
     REQUIRE(ctx && data && out, "null argument");
     Context &cx = ctx->cx;
-    // loop B's bounds and the packed halves assume canonical residues: checked before anything is created
-    for (int j = 0; j < cx.nQ; j++)
-        for (int c = 0; c < cx.N; c++)
-            REQUIRE(data[(size_t)j * cx.N + c] < cx.q[j], "plaintext residue at or above its modulus");
+    if (int code = check_canonical(cx, data)) return code;
     Ct c(&cx, 1, 1, cx.nQ, scale);
     cx.sync();
     HIP_CHECK(hipMemcpy(c.d, data, c.bytes(), hipMemcpyHostToDevice));
-    *out = wrap_pt(ctx, std::move(c));
+    *out = wrap<hydia_pt>(ctx, std::move(c));
     return HYDIA_OK;
     API_END
 }
@@ -988,13 +1009,7 @@ int hydia_pt_export(hydia_ctx *ctx, const hydia_pt *pt, uint64_t *data) {
     return HYDIA_OK;
     API_END
 }
-void hydia_pt_free(hydia_pt *pt) {
-    if (!pt) return;
-    hydia_ctx *owner = pt->owner;
-    use_device(owner);
-    delete pt;
-    if (owner && owner->refs.fetch_sub(1) == 1) delete owner;
-}
+void hydia_pt_free(hydia_pt *pt) { free_handle(pt); }
 // ------------------------------------------------------------------ templates already in device memory (hydia_dev_rows)
 // every check of a descriptor, before anything is launched: HYDIA_OK, or the code recorded with its message.  A context that is a shard
 // of a group is refused (the group enrols and serves its shards' databases), then the descriptor itself is looked at
@@ -1038,13 +1053,7 @@ int hydia_db_enroll_device(hydia_ctx *ctx, const hydia_dev_rows *rows, const uin
     REQUIRE(seed && r.n >= 1, "bad argument");
     Context &cx = ctx->cx;
     if (!cx.d_pk) return fail(HYDIA_ERR_STATE, "hydia: public key not loaded");
-    const size_t G = (r.n + (size_t)cx.slots - 1) / (size_t)cx.slots;
-    const int B = cx.babies_for(G, 0);
-    cx.db_kind = 0;
-    cx.db_resize(r.n, hydia_db_num_cts(ctx, r.n), B);
-    client_enroll_device(cx, r, seed, 0, B);
-    cx.db_kind = B < cx.prm.dim ? 6 : 5;
-    cx.db_babies = B;
+    enroll_diagonal(ctx, r.n, false, 0, [&](int B) { client_enroll_device(cx, r, seed, 0, B); });
     return HYDIA_OK;
     API_END
 }
@@ -1052,14 +1061,7 @@ int hydia_plain_db_enroll_device(hydia_ctx *ctx, const hydia_dev_rows *rows) {
     API_BEGIN
     CHECK_DEV_ROWS(r)
     REQUIRE(r.n >= 1, "bad argument");
-    Context &cx = ctx->cx;
-    const size_t G = (r.n + (size_t)cx.slots - 1) / (size_t)cx.slots;
-    const int B = cx.babies_for(G, 0);
-    cx.db_kind = 0;
-    cx.db_resize(r.n, hydia_db_num_cts(ctx, r.n), B, true);
-    client_plain_enroll_device(cx, r, B);
-    cx.db_kind = B < cx.prm.dim ? 8 : 7;
-    cx.db_babies = B;
+    enroll_diagonal(ctx, r.n, true, 0, [&](int B) { client_plain_enroll_device(ctx->cx, r, B); });
     return HYDIA_OK;
     API_END
 }
@@ -1067,12 +1069,7 @@ int hydia_db_update_device(hydia_ctx *ctx, size_t first_vector, const hydia_dev_
     API_BEGIN
     CHECK_DEV_ROWS(r)
     Context &cx = ctx->cx;
-    if (cx.db_plain()) return fail(HYDIA_ERR_STATE, "hydia: a plain gallery (kind 7 / 8) is resident: it is updated in place by hydia_plain_db_update (no seed: nothing is encrypted)");
-    if (!cx.d_db || cx.db_cts == 0 || (cx.db_kind != 5 && cx.db_kind != 6))
-        return fail(HYDIA_ERR_STATE, "hydia: no diagonal database resident (an update needs kind 5 or 6: hydia_db_enroll, hydia_db_load or an import)");
-    REQUIRE(seed, "null argument");
-    REQUIRE(first_vector <= cx.db_vectors, "first_vector lies past the end of the database (an update leaves no holes)");
-    REQUIRE(first_vector + r.n >= first_vector, "row count out of range");
+    if (int code = check_update(cx, false, first_vector, r.n, seed)) return code;
     if (r.n == 0) return HYDIA_OK;
     if (!cx.d_pk) return fail(HYDIA_ERR_STATE, "hydia: public key not loaded");
     client_db_update_device(cx, first_vector, r, normalise, seed, 0);
@@ -1083,12 +1080,7 @@ int hydia_plain_db_update_device(hydia_ctx *ctx, size_t first_vector, const hydi
     API_BEGIN
     CHECK_DEV_ROWS(r)
     Context &cx = ctx->cx;
-    if (cx.d_db && cx.db_cts && (cx.db_kind == 5 || cx.db_kind == 6))
-        return fail(HYDIA_ERR_STATE, "hydia: a ciphertext database (kind 5 / 6) is resident: it is updated in place by hydia_db_update (with a seed)");
-    if (!cx.d_db || cx.db_cts == 0 || !cx.db_plain())
-        return fail(HYDIA_ERR_STATE, "hydia: no plain gallery resident (an update needs kind 7 or 8: hydia_plain_db_enroll, hydia_plain_db_alloc or hydia_plain_db_load)");
-    REQUIRE(first_vector <= cx.db_vectors, "first_vector lies past the end of the gallery (an update leaves no holes)");
-    REQUIRE(first_vector + r.n >= first_vector, "row count out of range");
+    if (int code = check_update(cx, true, first_vector, r.n, nullptr)) return code;
     if (r.n == 0) return HYDIA_OK;
     client_plain_db_update_device(cx, first_vector, r, normalise);
     return HYDIA_OK;
@@ -1116,7 +1108,7 @@ int hydia_encode_queries_device(hydia_ctx *ctx, const hydia_dev_rows *rows, hydi
     REQUIRE(out, "null argument");
     REQUIRE(r.n >= 1, "a batch of probes needs at least one row");
     std::vector<Ct> pts = client_encode_queries_device(ctx->cx, r);
-    for (size_t q = 0; q < r.n; q++) out[q] = wrap_pt(ctx, std::move(pts[q]));
+    for (size_t q = 0; q < r.n; q++) out[q] = wrap<hydia_pt>(ctx, std::move(pts[q]));
     return HYDIA_OK;
     API_END
 }
@@ -1124,58 +1116,23 @@ int hydia_compute_similarity_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct 
 int hydia_index_scenario_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out) { SENDER_CALL(ctx->cx.index_scenario_pq(query->c)) }
 int hydia_membership_scenario_pq(hydia_ctx *ctx, const hydia_pt *query, hydia_ct **out) { SENDER_CALL(ctx->cx.membership_scenario_pq(query->c)) }
 
-static int scenario_multi_call(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out, int what) {
-    if (out)
-        for (uint32_t q = 0; q < n_queries; q++) out[q] = nullptr;
-    API_BEGIN
-    use_device(ctx);
-    REQUIRE(ctx && queries && out, "null argument");
-    REQUIRE(n_queries >= 1, "a batch of queries needs at least one query");
-    std::vector<const Ct *> qs(n_queries);
-    for (uint32_t q = 0; q < n_queries; q++) {
-        REQUIRE(queries[q], "null query in the batch");
-        qs[q] = &queries[q]->c;
-    }
-    std::vector<Ct> r = ctx->cx.scenario_multi(qs, what);
-    for (uint32_t q = 0; q < n_queries; q++) out[q] = wrap(ctx, std::move(r[q]));  // compact and owning: no copy, cannot fail
-    return HYDIA_OK;
-    API_END
-}
 int hydia_compute_similarity_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out) {
-    return scenario_multi_call(ctx, queries, n_queries, out, 0);
+    return batch_call(ctx, queries, n_queries, out, 0, &Context::scenario_multi);
 }
 int hydia_index_scenario_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out) {
-    return scenario_multi_call(ctx, queries, n_queries, out, 1);
+    return batch_call(ctx, queries, n_queries, out, 1, &Context::scenario_multi);
 }
 int hydia_membership_scenario_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out) {
-    return scenario_multi_call(ctx, queries, n_queries, out, 2);
-}
-// a batch of plain queries: the output convention of scenario_multi_call
-static int scenario_pq_multi_call(hydia_ctx *ctx, const hydia_pt *const *queries, uint32_t n_queries, hydia_ct **out, int what) {
-    if (out)
-        for (uint32_t q = 0; q < n_queries; q++) out[q] = nullptr;
-    API_BEGIN
-    use_device(ctx);
-    REQUIRE(ctx && queries && out, "null argument");
-    REQUIRE(n_queries >= 1, "a batch of plain queries needs at least one query");
-    std::vector<const Ct *> qs(n_queries);
-    for (uint32_t q = 0; q < n_queries; q++) {
-        REQUIRE(queries[q], "null query in the batch");
-        qs[q] = &queries[q]->c;
-    }
-    std::vector<Ct> r = ctx->cx.scenario_pq_multi(qs, what);
-    for (uint32_t q = 0; q < n_queries; q++) out[q] = wrap(ctx, std::move(r[q]));  // compact and owning: no copy, cannot fail
-    return HYDIA_OK;
-    API_END
+    return batch_call(ctx, queries, n_queries, out, 2, &Context::scenario_multi);
 }
 int hydia_compute_similarity_pq_multi(hydia_ctx *ctx, const hydia_pt *const *queries, uint32_t n_queries, hydia_ct **out) {
-    return scenario_pq_multi_call(ctx, queries, n_queries, out, 0);
+    return batch_call(ctx, queries, n_queries, out, 0, &Context::scenario_pq_multi);
 }
 int hydia_index_scenario_pq_multi(hydia_ctx *ctx, const hydia_pt *const *queries, uint32_t n_queries, hydia_ct **out) {
-    return scenario_pq_multi_call(ctx, queries, n_queries, out, 1);
+    return batch_call(ctx, queries, n_queries, out, 1, &Context::scenario_pq_multi);
 }
 int hydia_membership_scenario_pq_multi(hydia_ctx *ctx, const hydia_pt *const *queries, uint32_t n_queries, hydia_ct **out) {
-    return scenario_pq_multi_call(ctx, queries, n_queries, out, 2);
+    return batch_call(ctx, queries, n_queries, out, 2, &Context::scenario_pq_multi);
 }
 int hydia_set_pq_batch_width(hydia_ctx *ctx, uint32_t width) {
     API_BEGIN
@@ -1185,33 +1142,15 @@ int hydia_set_pq_batch_width(hydia_ctx *ctx, uint32_t width) {
     return HYDIA_OK;
     API_END
 }
-// a batch of encrypted queries against a plain gallery (kinds 7 / 8): the output convention of scenario_multi_call
-static int scenario_gallery_multi_call(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out, int what) {
-    if (out)
-        for (uint32_t q = 0; q < n_queries; q++) out[q] = nullptr;
-    API_BEGIN
-    use_device(ctx);
-    REQUIRE(ctx && queries && out, "null argument");
-    REQUIRE(n_queries >= 1, "a batch of queries needs at least one query");
-    std::vector<const Ct *> qs(n_queries);
-    for (uint32_t q = 0; q < n_queries; q++) {
-        REQUIRE(queries[q], "null query in the batch");
-        qs[q] = &queries[q]->c;
-    }
-    if (ctx->in_group) throw StateError("hydia: a plain gallery (kind 7 / 8) is not served on a shard of a group: neither are its batches");
-    std::vector<Ct> r = ctx->cx.scenario_gallery_multi(qs, what);
-    for (uint32_t q = 0; q < n_queries; q++) out[q] = wrap(ctx, std::move(r[q]));  // compact and owning: no copy, cannot fail
-    return HYDIA_OK;
-    API_END
-}
+// a batch of encrypted queries against a plain gallery (kinds 7 / 8)
 int hydia_compute_similarity_gallery_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out) {
-    return scenario_gallery_multi_call(ctx, queries, n_queries, out, 0);
+    return batch_call(ctx, queries, n_queries, out, 0, &Context::scenario_gallery_multi, true);
 }
 int hydia_index_scenario_gallery_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out) {
-    return scenario_gallery_multi_call(ctx, queries, n_queries, out, 1);
+    return batch_call(ctx, queries, n_queries, out, 1, &Context::scenario_gallery_multi, true);
 }
 int hydia_membership_scenario_gallery_multi(hydia_ctx *ctx, const hydia_ct *const *queries, uint32_t n_queries, hydia_ct **out) {
-    return scenario_gallery_multi_call(ctx, queries, n_queries, out, 2);
+    return batch_call(ctx, queries, n_queries, out, 2, &Context::scenario_gallery_multi, true);
 }
 int hydia_set_gallery_batch_width(hydia_ctx *ctx, uint32_t width) {
     API_BEGIN

@@ -46,9 +46,11 @@ int hydia_fail(int code, const std::string &msg);  // records the calling thread
 #define REQUIRE(cond, msg) \
     if (!(cond)) return hydia_fail(HYDIA_ERR_ARG, msg)
 
-// handles that cross the C-ABI are always compact ([count][poly][limb][N], nl == lstride) and owning
-inline hydia_ct *wrap(hydia_ctx *owner, hydia::Ct &&c) {
-    hydia_ct *h = new hydia_ct;
+// handles that cross the C-ABI (H: hydia_ct, or hydia_pt for a plain query) are always compact ([count][poly][limb][N], nl == lstride)
+// and owning
+template <class H = hydia_ct>
+inline H *wrap(hydia_ctx *owner, hydia::Ct &&c) {
+    H *h = new H;
     if (c.view || !c.compact()) h->c = c.ctx->clone(c);
     else h->c = std::move(c);
     h->owner = owner;

@@ -1597,12 +1597,8 @@ void Context::pq_check(const Ct &pt, int what) {
     const int dim = prm.dim, B = db_babies;
     if (db_kind == 6 && (B < 1 || dim % B)) throw StateError("hydia: the resident database carries no valid baby count");
     if (what >= 1 && !relin_key.d) throw StateError("hydia: relinearisation key not loaded");
-    if (db_kind == 6)
-        for (int g = 1; g < dim / B; g++)
-            if (!rot_keys.count(g * B)) throw StateError("hydia: rotation key " + std::to_string(g * B) + " not loaded");
-    if (what == 2)
-        for (int r = 1; r < slots; r <<= 1)
-            if (!rot_keys.count(r)) throw StateError("hydia: rotation key " + std::to_string(r) + " not loaded");
+    if (db_kind == 6) require_rot_keys(B, dim, B);
+    if (what == 2) require_rot_keys(1, slots, 0);
 }
 const unsigned *Context::pq_galois_table(int R) {
     auto it = pq_galois.find(R);
@@ -1651,57 +1647,49 @@ Ct Context::membership_scenario_pq(const Ct &pt) {
     Ct s = relin_compare_lanes(acc, 0.44, 10);
     return sum_and_evalsum(s);
 }
-// ------------------------------------------------------------------ a batch of queries in one pass over the database (an extension:
-// the reference serves one query per call).  Loop A runs per query into one [Q][R][2][nQ][N] rotation buffer; loop B is ONE multi-query
-// launch set (ceil(Q / QW) passes over the database); the per-block tails run once on the [Q G] batch.  Every ciphertext is what the
+// ------------------------------------------------------------------ a batch of queries in shared passes over the database (an extension:
+// the reference serves one query per call).  Three forms — encrypted queries against an encrypted database, plain queries against it,
+// encrypted queries against a plain gallery — through one driver (scenario_batch).  The rotations are made per query into one
+// [Qb][R][qpolys][nQ][N] buffer; loop B is ONE multi-query launch set (hk::loop_b_passes passes over the database); for a BSGS kind the
+// giant steps run on the [NG][Qb G] accumulators; the per-block tails run once on the [Qb G] batch.  Every ciphertext is what the
 // single-query call returns for its query, bit for bit: each step computes every ciphertext of a batch as it would alone.
-void Context::check_multi(const std::vector<const Ct *> &qs) const {
+static void loop_a_rotations(Context &cx, const Ct &q, int R, u64 *out) { cx.rotate_query_range(q, 0, R, out); }
+static const Context::BatchForm batch_ct = {  // kinds 5 / 6: loop A per query, k_hydia_tensor_mq
+    2, 3, 6, nullptr, hk::hydia_tensor_mq_width, "op:loop_b_multi", "hydia_tensor_multi", loop_a_rotations,
+    [](hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G, int dim, int nl,
+       const DbLayout &L, int ng, int) { hk::hydia_tensor_accumulate(st, mod, N, rot, rqs, db, acc, Q, G, dim, nl, L, ng, hk::TENSOR_BATCH, 0); }};
+static const Context::BatchForm batch_pq = {  // kinds 5 / 6, known probes: one k_automorph_batch launch per query, no key looked at
+    1, 2, 6, &Context::pq_mq_width, hk::hydia_pq_mq_width, "op:loop_b_pq_multi", "hydia_pq_multi",
+    [](Context &cx, const Ct &pt, int R, u64 *out) { hk::automorph_batch(cx.stream, cx.prm.logN, pt.d, out, pt.nl, R, cx.pq_galois_table(R)); },
+    hk::hydia_pq_accumulate_multi};
+static const Context::BatchForm batch_gallery = {  // kinds 7 / 8: loop A per query, k_hydia_plain_mq
+    2, 2, 8, &Context::plain_mq_width, hk::hydia_plain_mq_width, "op:loop_b_plain_multi", "hydia_plain_multi",
+    loop_a_rotations, hk::hydia_plain_accumulate_multi};
+
+void Context::check_fresh_batch(const std::vector<const Ct *> &qs) const {
     if (qs.empty()) throw std::runtime_error("hydia: a batch of queries needs at least one query");
     for (const Ct *q : qs)
         if (!q || q->X != 1 || q->npoly != 2 || q->nl != nQ || !q->compact() || q->scale != qs[0]->scale)
             throw std::runtime_error("hydia: every query of a batch must be one fresh 2-component ciphertext at full level");
-    if (db_plain()) throw StateError("hydia: a plain gallery (kind 7 / 8) is resident: batches of queries are not served on it yet");
-    if (!d_db || db_cts == 0 || (db_kind != 5 && db_kind != 6)) throw StateError("hydia: no database resident (diagonal packing)");
+}
+void Context::require_rot_keys(int first, int end, int step) const {
+    for (int r = first; r < end; r = step ? r + step : r * 2)
+        if (!rot_keys.count(r)) throw StateError("hydia: rotation key " + std::to_string(r) + " not loaded");
 }
 // queries one batch takes: what free HBM (plus the pool's cache) holds of a query's rotation set, accumulators and comparator
 // temporaries (48 full-level ciphertexts per block: at 2^20 vectors a batch of 8 with 24 per block ran out of HBM inside the comparator
 // and the allocator's trim-and-retry made it 7x slower than 8 single calls), never fewer than one — a batch of one needs what a
 // single-query call needs
-int Context::multi_batch(int Q, bool plain_queries) {
-    const bool bsgs = db_kind == 6 || db_kind == 8;
+int Context::multi_batch(int Q, const BatchForm &f) {
+    const bool bsgs = db_kind == f.bsgs_kind;
     const int dim = prm.dim, R = bsgs ? db_babies : dim, NG = bsgs ? dim / db_babies : 1, G = (int)(db_cts / dim);
     const double lp = (double)nQ * N * 8;
-    // a plain query's rotations are one polynomial each and its accumulators have two components; a plain gallery's batch (kinds 7 / 8)
-    // has 2-polynomial rotations and 2-component accumulators; the comparator's share is the same
-    const double per_query =
-        (double)R * (plain_queries ? 1 : 2) * lp + (double)G * NG * (plain_queries || db_plain() ? 2 : 3) * lp + (double)G * 48 * 2 * lp;
+    // the form's rotations and accumulators; the comparator's share is the same for every form
+    const double per_query = (double)R * f.qpolys * lp + (double)G * NG * f.comps * lp + (double)G * 48 * 2 * lp;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 1;
     const double avail = 0.85 * ((double)free_b + (double)pool.bytes_cached);
     return (int)std::max(1.0, std::min((double)Q, std::floor(avail / per_query)));
-}
-// loop A + loop B (+ for BSGS the relinearisation and the giant steps) of queries q0 .. q0+Qb-1: kind 5 the [Qb G][3][nQ]
-// accumulators, kind 6 the relinearised [Qb G][2][nQ] sums (what similarity_accumulate / similarity_bsgs_sum return, query-major)
-Ct Context::loop_b_multi(const std::vector<const Ct *> &qs, int q0, int Qb) {
-    const int dim = prm.dim, nl = nQ;
-    const int B = db_kind == 6 ? db_babies : dim, NG = (dim + B - 1) / B, G = (int)(db_cts / dim);
-    if (db_kind == 6 && (B < 1 || dim % B)) throw StateError("hydia: the resident database carries no valid baby count");
-    if (db_kind == 6) build_giants(Qb * G);  // one table entry per (giant step, query, block)
-    const double scale = qs[q0]->scale;
-    Ct acc(this, Qb * G * NG, 3, nl, scale * delta);
-    {
-        Ct rot(this, Qb * B, 2, nl, scale);
-        const size_t rqs = (size_t)B * rot.ct_elems();
-        for (int q = 0; q < Qb; q++) rotate_query_range(*qs[q0 + q], 0, B, rot.d + (size_t)q * rqs);
-        const int passes = (Qb + hk::hydia_tensor_mq_width(db_lay) - 1) / hk::hydia_tensor_mq_width(db_lay);
-        op_bytes("op:loop_b_multi", N, 0, (double)passes * db_cts * (double)db_lay.ct_bytes + ((double)Qb * B * 2 + (double)Qb * G * NG * 3) * nl * N * 8);
-        timer_begin("hydia_tensor_multi");
-        hk::hydia_tensor_accumulate(stream, d_mod, N, rot.d, rqs, d_db, acc.d, Qb, G * NG, B, nl, db_lay, db_kind == 6 ? NG : 0,
-                                    hk::TENSOR_BATCH, 0);
-        timer_end("hydia_tensor_multi");
-    }
-    if (db_kind == 5) return acc;
-    return giant_step_sum(acc, NG);  // slot (giant g, query q, block) = (g Qb + q) G + block
 }
 // ciphertexts q*per .. q*per+per-1 of a batch, compact and owning
 Ct Context::batch_slice(const Ct &b, int q, int per) {
@@ -1709,15 +1697,33 @@ Ct Context::batch_slice(const Ct &b, int q, int per) {
     hk::copy_limbs(stream, N, b.d + (size_t)q * per * b.ct_elems(), o.d, b.poly_elems(), o.poly_elems(), per * b.npoly, b.nl);
     return o;
 }
-// 0 similarity, 1 index scenario, 2 membership scenario
-std::vector<Ct> Context::scenario_multi(const std::vector<const Ct *> &qs, int what) {
-    check_multi(qs);
-    const int Q = (int)qs.size();
+// The sub-batch loop of every form, after the form's own checks.  Per sub-batch: the giant steps' tables (one entry per giant step,
+// query and block), the accumulators, the rotations (released before the giant steps and the tails run: multi_batch's budget assumes
+// that), loop B, for a BSGS kind the giant steps (slot (giant g, query q, block) = (g Qb + q) G + block), then the tails
+std::vector<Ct> Context::scenario_batch(const BatchForm &f, const std::vector<const Ct *> &qs, int what) {
+    const int Q = (int)qs.size(), dim = prm.dim, nl = nQ, G = (int)(db_cts / dim);
+    const bool bsgs = db_kind == f.bsgs_kind;
+    const int R = bsgs ? db_babies : dim, NG = dim / R;
     std::vector<Ct> res;
     res.reserve(Q);
     for (int q0 = 0; q0 < Q;) {
-        const int Qb = multi_batch(Q - q0);
-        Ct acc = loop_b_multi(qs, q0, Qb);  // [Qb G]: 3 components (hoisted) : 2 (BSGS, relinearised)
+        const int Qb = multi_batch(Q - q0, f);
+        if (bsgs) build_giants(Qb * G);
+        const double scale = qs[q0]->scale;
+        Ct acc(this, Qb * G * NG, f.comps, nl, scale * delta);
+        {
+            Ct rot(this, Qb * R, f.qpolys, nl, scale);
+            const size_t rqs = (size_t)R * rot.ct_elems();
+            for (int q = 0; q < Qb; q++) f.rotations(*this, *qs[q0 + q], R, rot.d + (size_t)q * rqs);
+            const int w = f.width && this->*f.width > 0 ? this->*f.width : f.default_width(db_lay);
+            op_bytes(f.op, N, 0,
+                     (double)hk::loop_b_passes(Qb, w) * db_cts * (double)db_lay.ct_bytes +
+                         ((double)Qb * R * f.qpolys + (double)Qb * G * NG * f.comps) * nl * N * 8);
+            timer_begin(f.timer);
+            f.launch(stream, d_mod, N, rot.d, rqs, d_db, acc.d, Qb, G * NG, R, nl, db_lay, bsgs ? NG : 0, w);
+            timer_end(f.timer);
+        }
+        if (bsgs) acc = giant_step_sum(acc, NG);  // 2 components (relinearised where the form has three)
         tails_multi(acc, Qb, what, res);
         q0 += Qb;
     }
@@ -1753,10 +1759,16 @@ void Context::tails_multi(Ct &acc, int Qb, int what, std::vector<Ct> &res) {
         for (int q = 0; q < Qb; q++) res.push_back(batch_slice(r, q, G));
     }
 }
-// ------------------------------------------------------------------ a batch of PLAIN queries in one pass over the database: per query
-// one k_automorph_batch launch into one [Qb][R][nQ][N] buffer, ONE batched loop B (ceil(Qb / width) passes), for kind 6 the giant steps
-// on the 2-component [NG][Qb G] accumulators, then the batch's tails.  Every refusal is the single call's, made for every query before
-// anything is enqueued
+// encrypted queries against the encrypted database.  A missing rotation key is found by the first sub-batch (build_giants,
+// build_rotptrs), a missing relinearisation key by its tails.  what: 0 similarity, 1 index scenario, 2 membership scenario
+std::vector<Ct> Context::scenario_multi(const std::vector<const Ct *> &qs, int what) {
+    check_fresh_batch(qs);
+    if (db_plain()) throw StateError("hydia: a plain gallery (kind 7 / 8) is resident: batches of queries are not served on it yet");
+    if (!d_db || db_cts == 0 || (db_kind != 5 && db_kind != 6)) throw StateError("hydia: no database resident (diagonal packing)");
+    if (db_kind == 6 && (db_babies < 1 || prm.dim % db_babies)) throw StateError("hydia: the resident database carries no valid baby count");
+    return scenario_batch(batch_ct, qs, what);
+}
+// PLAIN queries against the encrypted database.  Every refusal is the single call's, made for every query before anything is enqueued
 std::vector<Ct> Context::scenario_pq_multi(const std::vector<const Ct *> &pts, int what) {
     if (pts.empty()) throw std::runtime_error("hydia: a batch of plain queries needs at least one query");
     for (const Ct *pt : pts) {
@@ -1764,46 +1776,12 @@ std::vector<Ct> Context::scenario_pq_multi(const std::vector<const Ct *> &pts, i
         pq_check(*pt, what);
         if (pt->scale != pts[0]->scale) throw std::runtime_error("hydia: every plain query of a batch must carry the same scale");
     }
-    const int Q = (int)pts.size(), dim = prm.dim, nl = nQ, G = (int)(db_cts / dim);
-    const int R = db_kind == 6 ? db_babies : dim, NG = dim / R;
-    std::vector<Ct> res;
-    res.reserve(Q);
-    for (int q0 = 0; q0 < Q;) {
-        const int Qb = multi_batch(Q - q0, true);
-        if (db_kind == 6) build_giants(Qb * G);  // one table entry per (giant step, query, block)
-        Ct acc(this, Qb * G * NG, 2, nl, pts[q0]->scale * delta);
-        {
-            const unsigned *gal = pq_galois_table(R);
-            Ct rot(this, Qb * R, 1, nl, pts[q0]->scale);
-            const size_t rqs = (size_t)R * rot.ct_elems();
-            for (int q = 0; q < Qb; q++) hk::automorph_batch(stream, prm.logN, pts[q0 + q]->d, rot.d + (size_t)q * rqs, nl, R, gal);
-            const int w = pq_mq_width > 0 ? pq_mq_width : hk::hydia_pq_mq_width(db_lay);
-            int passes = 0;
-            for (int left = Qb, qw = w; left > 0; passes++) {  // the launcher's schedule: the widest width that still fits what is left
-                while (qw > left) qw >>= 1;
-                left -= qw;
-            }
-            op_bytes("op:loop_b_pq_multi", N, 0, (double)passes * db_cts * (double)db_lay.ct_bytes + ((double)Qb * R + (double)Qb * G * NG * 2) * nl * N * 8);
-            timer_begin("hydia_pq_multi");
-            hk::hydia_pq_accumulate_multi(stream, d_mod, N, rot.d, rqs, d_db, acc.d, Qb, G * NG, R, nl, db_lay, db_kind == 6 ? NG : 0, w);
-            timer_end("hydia_pq_multi");
-        }
-        if (db_kind == 6) acc = giant_step_sum(acc, NG);  // slot (giant g, query q, block) = (g Qb + q) G + block
-        tails_multi(acc, Qb, what, res);
-        q0 += Qb;
-    }
-    return res;
+    return scenario_batch(batch_pq, pts, what);
 }
-// ------------------------------------------------------------------ a batch of ENCRYPTED queries against a PLAIN gallery (kinds 7 / 8)
-// in shared passes over the gallery: loop A per query into one [Qb][R][2][nQ][N] buffer, ONE batched loop B (k_hydia_plain_mq: the
-// launcher's passes of plain_mq_width queries and what is left over), for kind 8 the giant steps on the 2-component [NG][Qb G]
-// accumulators, then the batch's tails.  Per query exactly what the single call returns.  The query checks are check_multi's, the
-// state and key checks the single call's with its messages, all made before anything is enqueued
-void Context::check_gallery_multi(const std::vector<const Ct *> &qs, int what) const {
-    if (qs.empty()) throw std::runtime_error("hydia: a batch of queries needs at least one query");
-    for (const Ct *q : qs)
-        if (!q || q->X != 1 || q->npoly != 2 || q->nl != nQ || !q->compact() || q->scale != qs[0]->scale)
-            throw std::runtime_error("hydia: every query of a batch must be one fresh 2-component ciphertext at full level");
+// ENCRYPTED queries against a PLAIN gallery (kinds 7 / 8).  The query checks are the encrypted batch's, the state and key checks the
+// single call's with its messages, all made before anything is enqueued
+std::vector<Ct> Context::scenario_gallery_multi(const std::vector<const Ct *> &qs, int what) {
+    check_fresh_batch(qs);
     if (d_db && db_cts > 0 && (db_kind == 5 || db_kind == 6))
         throw StateError("hydia: a ciphertext database (kind 5 / 6) is resident: its batches are served by hydia_*_multi");
     if (!d_db || db_cts == 0 || !db_plain() || !db_lay.plain) throw StateError("hydia: no plain gallery resident (kind 7 or 8)");
@@ -1811,49 +1789,11 @@ void Context::check_gallery_multi(const std::vector<const Ct *> &qs, int what) c
     if (db_kind == 8 && (B < 1 || dim % B)) throw StateError("hydia: the resident database carries no valid baby count");
     // the keys in the order the single call asks for them: the giant steps' (build_giants), loop A's (build_rotptrs), the comparator's,
     // EvalSum's
-    if (db_kind == 8)
-        for (int g = 1; g < dim / B; g++)
-            if (!rot_keys.count(g * B)) throw StateError("hydia: rotation key " + std::to_string(g * B) + " not loaded");
-    if (!rotptrs_valid)
-        for (int i = 1; i < dim; i++)
-            if (!rot_keys.count(i)) throw StateError("hydia: rotation key " + std::to_string(i) + " not loaded");
+    if (db_kind == 8) require_rot_keys(B, dim, B);
+    if (!rotptrs_valid) require_rot_keys(1, dim, 1);
     if (what >= 1 && !relin_key.d) throw StateError("hydia: relinearisation key not loaded");
-    if (what == 2)
-        for (int r = 1; r < slots; r <<= 1)
-            if (!rot_keys.count(r)) throw StateError("hydia: rotation key " + std::to_string(r) + " not loaded");
-}
-std::vector<Ct> Context::scenario_gallery_multi(const std::vector<const Ct *> &qs, int what) {
-    check_gallery_multi(qs, what);
-    const int Q = (int)qs.size(), dim = prm.dim, nl = nQ, G = (int)(db_cts / dim);
-    const int R = db_kind == 8 ? db_babies : dim, NG = dim / R;
-    std::vector<Ct> res;
-    res.reserve(Q);
-    for (int q0 = 0; q0 < Q;) {
-        const int Qb = multi_batch(Q - q0);
-        if (db_kind == 8) build_giants(Qb * G);  // one table entry per (giant step, query, block)
-        const double scale = qs[q0]->scale;
-        Ct acc(this, Qb * G * NG, 2, nl, scale * delta);
-        {
-            Ct rot(this, Qb * R, 2, nl, scale);
-            const size_t rqs = (size_t)R * rot.ct_elems();
-            for (int q = 0; q < Qb; q++) rotate_query_range(*qs[q0 + q], 0, R, rot.d + (size_t)q * rqs);
-            const int w = plain_mq_width > 0 ? plain_mq_width : hk::hydia_plain_mq_width(db_lay);
-            int passes = 0;
-            for (int left = Qb, qw = w; left > 0; passes++) {  // the launcher's schedule: the widest width that still fits what is left
-                while (qw > left) qw >>= 1;
-                left -= qw;
-            }
-            op_bytes("op:loop_b_plain_multi", N, 0,
-                     (double)passes * db_cts * (double)db_lay.ct_bytes + ((double)Qb * R * 2 + (double)Qb * G * NG * 2) * nl * N * 8);
-            timer_begin("hydia_plain_multi");
-            hk::hydia_plain_accumulate_multi(stream, d_mod, N, rot.d, rqs, d_db, acc.d, Qb, G * NG, R, nl, db_lay, db_kind == 8 ? NG : 0, w);
-            timer_end("hydia_plain_multi");
-        }
-        if (db_kind == 8) acc = giant_step_sum(acc, NG);  // slot (giant g, query q, block) = (g Qb + q) G + block
-        tails_multi(acc, Qb, what, res);
-        q0 += Qb;
-    }
-    return res;
+    if (what == 2) require_rot_keys(1, slots, 0);
+    return scenario_batch(batch_gallery, qs, what);
 }
 
 // Cross-shard membership reduction: partial sums of the shards are added as plain 64-bit integers (what an RCCL

@@ -451,14 +451,29 @@ struct Context : HostParams {
     void eval_sum_inplace(Ct &m);     // EvalSum on every ciphertext of the batch
     void add_raw_inplace(Ct &a, const u64 *other /* compact, same shape, this device */);  // integer sum, no reduction
     void mod_reduce_inplace(Ct &a);   // every 64-bit value -> canonical residue of its limb
-    // ---- a batch of queries in one pass over the database (an extension; evaluator.cpp): one result per query, each exactly what
+    // ---- a batch of queries in shared passes over the database (an extension; evaluator.cpp): one result per query, each exactly what
     // the single-query call returns.  what: 0 similarity, 1 index scenario, 2 membership scenario.  The batch is split where free HBM
-    // does not hold it (multi_batch); the split changes no result
+    // does not hold it (multi_batch); the split changes no result.  The three forms of a batch differ in what a BatchForm holds and
+    // in their checks; scenario_batch runs the sub-batch loop of any of them
+    struct BatchForm {
+        int qpolys, comps;     // polynomials per rotation of a query, components per accumulator
+        int bsgs_kind;         // the database kind that takes giant steps (its hoisted kind needs none)
+        int Context::*width;   // the context's override of the queries per pass (nullptr: the form has none), 0 = default_width
+        int (*default_width)(const DbLayout &);
+        const char *op, *timer;  // names in the byte ledger and of the loop-B timer
+        void (*rotations)(Context &cx, const Ct &q, int R, u64 *out);  // rotations 0 .. R-1 of one query -> out [R][qpolys][nQ][N]
+        void (*launch)(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G, int dim,
+                       int nl, const DbLayout &L, int ng, int width);
+    };
+    std::vector<Ct> scenario_batch(const BatchForm &f, const std::vector<const Ct *> &qs, int what);  // after the form's checks
+    int multi_batch(int Q, const BatchForm &f);  // queries one sub-batch takes, from free HBM and the form's per-query bytes
+    void tails_multi(Ct &acc, int Qb, int what, std::vector<Ct> &res);  // the tails of [Qb G] accumulators, shared by every form
+    // runtime_error unless every query is one fresh 2-component ciphertext at full level and all carry one scale
+    void check_fresh_batch(const std::vector<const Ct *> &qs) const;
+    // StateError naming the first rotation key of first, first + step, .. (step 0: first, 2 first, 4 first, ..) below end that is not loaded
+    void require_rot_keys(int first, int end, int step) const;
+    // encrypted queries against the encrypted database (kinds 5 / 6).  runtime_error: a query is not fresh; StateError: no diagonal database
     std::vector<Ct> scenario_multi(const std::vector<const Ct *> &qs, int what);
-    void check_multi(const std::vector<const Ct *> &qs) const;  // runtime_error: a query is not fresh; StateError: no diagonal database
-    int multi_batch(int Q, bool plain_queries = false);  // queries one batch takes, from free HBM and the form's per-query bytes
-    void tails_multi(Ct &acc, int Qb, int what, std::vector<Ct> &res);  // the tails of [Qb G] accumulators, shared by both batch kinds
-    Ct loop_b_multi(const std::vector<const Ct *> &qs, int q0, int Qb);
     // ---- a PLAIN QUERY (an extension; evaluator.cpp): the sender knows the probe, the database (kinds 5 / 6) stays encrypted.  pt is
     // ONE encoded polynomial [1][1][nQ][N] (canonical residues, evaluation form).  Bit for bit the encrypted-query path on the trivial
     // ciphertext (pt, 0): rotating a plaintext is a permutation, pt x ct has two components — no rotation key 1 .. R-1 is looked at
@@ -471,15 +486,12 @@ struct Context : HostParams {
     Ct similarity_pq(const Ct &pt);
     Ct index_scenario_pq(const Ct &pt);
     Ct membership_scenario_pq(const Ct &pt);
-    // a batch of plain queries in one pass over the database: one result per query, each exactly what the single call returns.  Every
-    // query passes pq_check and all carry one scale (runtime_error otherwise) before anything is enqueued
+    // a batch of plain queries: every query passes pq_check and all carry one scale (runtime_error otherwise) before anything is enqueued
     std::vector<Ct> scenario_pq_multi(const std::vector<const Ct *> &pts, int what);
     int pq_mq_width = 0;  // queries per pass of a plain-query batch (1, 2, 4); 0 = hk::hydia_pq_mq_width, the measured choice
-    // a batch of ENCRYPTED queries against a PLAIN gallery (kinds 7 / 8) in shared passes over the gallery: one result per query, each
-    // exactly what the single call returns.  check_gallery_multi: check_multi's query checks (runtime_error), then the single call's
-    // state and key checks with its messages (StateError), before anything is enqueued
+    // a batch of ENCRYPTED queries against a PLAIN gallery (kinds 7 / 8): check_fresh_batch's query checks (runtime_error), then the
+    // single call's state and key checks with its messages (StateError), before anything is enqueued
     std::vector<Ct> scenario_gallery_multi(const std::vector<const Ct *> &qs, int what);
-    void check_gallery_multi(const std::vector<const Ct *> &qs, int what) const;
     int plain_mq_width = 0;  // queries per pass of a plain gallery's batch (1, 2, 4); 0 = hk::hydia_plain_mq_width
     Ct giant_step_sum(Ct &acc, int NG);  // BSGS giant steps on [NG X0] giant-major accumulators -> [X0][2][nQ][N] (relinearises a 3-component acc)
     Ct batch_slice(const Ct &b, int q, int per);

@@ -421,6 +421,14 @@ constexpr int TENSOR_BATCH = 0;
 void hydia_tensor_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, size_t rqs, const void *db, u64 *acc, int Q, int G,
                              int dim, int nl, const DbLayout &L, int ng, int bpp, int nw);
 int hydia_tensor_mq_width(const DbLayout &L);  // queries one pass over the database serves
+// passes over the database a batch of Q queries takes at `width` queries per pass — the launcher's schedule: every pass takes the
+// widest power of two up to width that still fits what is left (5 queries at width 4: 4 + 1; at width 2: 2 + 2 + 1)
+inline int loop_b_passes(int Q, int width) {
+    int passes = 0;
+    for (int left = Q, qw = width; left > 0; left -= qw, passes++)
+        while (qw > left) qw >>= 1;
+    return passes;
+}
 // Loop B over a plain gallery (database kinds 7 / 8, L.plain): acc [G][2][nl][N] (slot map as above with a batch of one),
 // acc[slot][p] = sum_i rot[i].c_p * m[g][i] mod q_j — no third component, nothing to relinearise.  bpp, nw: split caps (tensor_split)
 void hydia_plain_accumulate(hipStream_t st, const ModC *mod, int N, const u64 *rot, const void *db, u64 *acc, int G, int dim, int nl,

@@ -1035,15 +1035,18 @@ class DiagonalSender:
 
     # ---- several queries in one pass over the database (an extension: the reference serves one query per call).  A list of query
     # ciphertexts in, a list out: per query exactly what the single-query method returns
-    def _multi(self, fn, query_ciphers):
-        qs = list(query_ciphers)
-        self._no_plain("a *Multi method", *qs)
-        fn = getattr(self.cc.L, fn)
+    def _batch_call(self, fn, qs):
+        """the C call of every batch method: the handles of `qs` in, one owning Ciphertext per query out"""
         n = len(qs)
         hs = (C.c_void_p * max(n, 1))(*[q.h for q in qs])
         out = (C.c_void_p * max(n, 1))()
-        _chk(fn(self.cc.h, hs, n, out))
+        _chk(getattr(self.cc.L, fn)(self.cc.h, hs, n, out))
         return [Ciphertext(self.cc, C.c_void_p(out[i])) for i in range(n)]
+
+    def _multi(self, fn, query_ciphers):
+        qs = list(query_ciphers)
+        self._no_plain("a *Multi method", *qs)
+        return self._batch_call(fn, qs)
 
     def computeSimilarityMulti(self, query_ciphers):
         return self._multi("hydia_compute_similarity_multi", query_ciphers)
@@ -1073,12 +1076,7 @@ class DiagonalSender:
             raise HydiaError(-1, "hydia: a *PlainMulti method takes Plaintexts (encodeQuery); encrypted queries go to the *Multi methods")
         if not isinstance(self.cc, Context):
             raise HydiaError(-2, "hydia: a plain query is not served on a sharded context")
-        fn = getattr(self.cc.L, fn)
-        n = len(qs)
-        hs = (C.c_void_p * max(n, 1))(*[q.h for q in qs])
-        out = (C.c_void_p * max(n, 1))()
-        _chk(fn(self.cc.h, hs, n, out))
-        return [Ciphertext(self.cc, C.c_void_p(out[i])) for i in range(n)]
+        return self._batch_call(fn, qs)
 
     def computeSimilarityPlainMulti(self, plaintexts):
         return self._plain_multi("hydia_compute_similarity_pq_multi", plaintexts)
@@ -1097,12 +1095,7 @@ class DiagonalSender:
             raise HydiaError(-1, "hydia: a *GalleryMulti method takes encrypted queries (Ciphertext): a plain gallery under a plain query would keep nothing private")
         if not isinstance(self.cc, Context):
             raise HydiaError(-2, "hydia: a plain gallery (kind 7 / 8) is not served on a sharded context")
-        fn = getattr(self.cc.L, fn)
-        n = len(qs)
-        hs = (C.c_void_p * max(n, 1))(*[q.h for q in qs])
-        out = (C.c_void_p * max(n, 1))()
-        _chk(fn(self.cc.h, hs, n, out))
-        return [Ciphertext(self.cc, C.c_void_p(out[i])) for i in range(n)]
+        return self._batch_call(fn, qs)
 
     def computeSimilarityGalleryMulti(self, query_ciphers):
         return self._gallery_multi("hydia_compute_similarity_gallery_multi", query_ciphers)

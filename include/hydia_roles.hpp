@@ -371,6 +371,14 @@ class DiagonalSender : public Sender {
     }
 
   private:
+    // the C call of every batch method: one result handle per query, or nothing after an error (reported by check)
+    template <class H>
+    std::vector<hydia_ct *> batch_call(const std::vector<const H *> &in, int (*multi)(hydia_ctx *, const H *const *, uint32_t, hydia_ct **),
+                                       const char *what) {
+        std::vector<hydia_ct *> out(in.size(), nullptr);
+        if (!cc->check(multi(cc->h, in.data(), (uint32_t)in.size(), out.data()), what)) return {};
+        return out;
+    }
     std::vector<hydia_ct *> run_pq_multi(const std::vector<Plaintext> &qs,
                                          int (*multi)(hydia_ctx *, const hydia_pt *const *, uint32_t, hydia_ct **), const char *what) {
         if (cc->group) {
@@ -385,9 +393,7 @@ class DiagonalSender : public Sender {
             }
             in.push_back(q.pt->h);
         }
-        std::vector<hydia_ct *> out(in.size(), nullptr);
-        if (!cc->check(multi(cc->h, in.data(), (uint32_t)in.size(), out.data()), what)) return {};
-        return out;
+        return batch_call(in, multi, what);
     }
     hydia_ct *run_pq(const Plaintext &q, int (*one)(hydia_ctx *, const hydia_pt *, hydia_ct **), const char *what) {
         if (!q || cc->group) {
@@ -411,9 +417,7 @@ class DiagonalSender : public Sender {
             }
             in.push_back(q[0].batch->h);
         }
-        std::vector<hydia_ct *> out(in.size(), nullptr);
-        if (!cc->check(multi(cc->h, in.data(), (uint32_t)in.size(), out.data()), what)) return {};
-        return out;
+        return batch_call(in, multi, what);
     }
     hydia_ct *run(std::vector<Ciphertext> &q, int (*one)(hydia_ctx *, const hydia_ct *, hydia_ct **),
                   int (*sharded)(hydia_group *, const hydia_ct *, hydia_ct **), const char *what) {
