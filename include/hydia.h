@@ -142,7 +142,11 @@ void hydia_ct_free(hydia_ct *ct);
 /* Receiver::encryptQuery, src/receiver/receiver_diag.cpp:13-26: normalise, tile to all slots, encode, encrypt */
 int hydia_encrypt_query(hydia_ctx *ctx, const double *query /* vector_dim */, const uint8_t seed[32], uint64_t nonce,
                         hydia_ct **out);
-/* OpenFHEWrapper::encryptFromVector, src/openFHE_wrapper.cpp:74-77 (count vectors of `slots` doubles each) */
+/* OpenFHEWrapper::encryptFromVector, src/openFHE_wrapper.cpp:74-77 (count vectors of `slots` doubles each).
+ * The encoder's range: the coefficients of the encoded polynomial are 64-bit integers, each the slot values' transform times
+ * 2^scale_bits rounded half to even.  max|slot| * 2^scale_bits < 2^63 is sufficient: a coefficient is at most the mean absolute slot
+ * value times the scale.  Beyond that range the residues are unspecified (the device conversion saturates where the CPU oracle's llrint
+ * is undefined); no fault occurs */
 int hydia_encrypt(hydia_ctx *ctx, const double *slots, uint32_t count, const uint8_t seed[32], uint64_t nonce0,
                   hydia_ct **out);
 /* OpenFHEWrapper::decryptToVector, src/openFHE_wrapper.cpp:81-85: out = count * slots doubles */
@@ -651,7 +655,8 @@ int hydia_level_reduce(hydia_ctx *ctx, hydia_ct *ct, uint32_t n_limbs);
 /* helpers of approach 1 (src/openFHE_wrapper.cpp), on every ciphertext of the batch:
  * EvalMult(ct, MakeCKKSPackedPlaintext(slots)) + RescaleInPlace under FIXEDMANUAL (:235-237): `slots` (slots doubles) encoded at scale
  * 2^scale_bits on the ciphertext's current limbs, multiplied residue-wise in evaluation form (scale ct.scale * 2^scale_bits), then
- * rescaled — out has one limb less */
+ * rescaled — out has one limb less.  `slots` is in the encoder's range stated at hydia_encrypt: max|slot| * 2^scale_bits < 2^63 is
+ * sufficient, beyond it the plaintext's residues are unspecified, and no fault occurs */
 int hydia_eval_mult_plain(hydia_ctx *ctx, const hydia_ct *ct, const double *slots, hydia_ct **out);
 /* OpenFHEWrapper::binaryRotate (:103-128): the greedy signed power-of-two decomposition of `factor` (round(log2 |f|), largest first),
  * applied in that order; every step needs the key of its rotation mod slots */

@@ -1,6 +1,7 @@
 """GPU parity of the receiver / enroller / key-generation side (run with -m gpu): ChaCha20-addressed sampling, CKKS
 encode/decode, encryption, decryption and DiagonalEnroller packing on the GPU against the CPU oracle — bit exact on
-ciphertext residues; decoded doubles are compared exactly as well (same IEEE operation order, no contraction)."""
+ciphertext residues; decoded doubles are compared exactly as well (same IEEE operation order, no contraction).  The data here is
+generated; the edges of decryption, decoding, the threshold and the encoder's rounding are in tests/test_gpu_client_edges.py."""
 import os
 
 import numpy as np
