@@ -5,7 +5,7 @@ the thin Python host mirror of the reference's role classes over that C-ABI; it 
 raises if the HIP library is missing.
 """
 from .hydia import (Context, Ciphertext, DiagonalEnroller, DiagonalReceiver, DiagonalSender, HydiaError,  # noqa: F401
-                    PlainEnroller, Plaintext,
+                    PlainEnroller, Plaintext, SeededKeys, SeededQuery,
                     HersEnroller, HersReceiver, HersSender, BaseEnroller, BaseReceiver, BaseSender, base_rotations,
                     GroteReceiver, GroteSender, grote_row_length, BlindEnroller, BlindReceiver, BlindSender, BLIND_CHUNK_LEN,
                     byte_ledger, default_params, describe_params, compute_required_depth, lib_path, load_library,

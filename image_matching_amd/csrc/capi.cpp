@@ -295,18 +295,99 @@ int hydia_keygen(hydia_ctx *ctx, const uint8_t seed[32]) {
     return HYDIA_OK;
     API_END
 }
-int hydia_keygen_rotations(hydia_ctx *ctx, const uint8_t seed[32], const int32_t *rots, uint32_t n) {
-    API_BEGIN
-    use_device(ctx);
-    REQUIRE(ctx && seed && (rots || n == 0), "null argument");
-    const long S = ctx->cx.slots;
-    std::vector<int> set;
+// the rotation list of a key generation as key ids: each r mod slots in [1, slots), duplicates dropped, in the caller's order
+static int rotation_set(const Context &cx, const int32_t *rots, uint32_t n, std::vector<int> &set) {
+    const long S = cx.slots;
     for (uint32_t i = 0; i < n; i++) {
         const int r = (int)((((long)rots[i] % S) + S) % S);  // HY_STREAM carries the key id as an unsigned field: never negative
         REQUIRE(r != 0, "a rotation of 0 mod slots has no key");
         if (std::find(set.begin(), set.end(), r) == set.end()) set.push_back(r);
     }
+    return HYDIA_OK;
+}
+int hydia_keygen_rotations(hydia_ctx *ctx, const uint8_t seed[32], const int32_t *rots, uint32_t n) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && seed && (rots || n == 0), "null argument");
+    std::vector<int> set;
+    if (int code = rotation_set(ctx->cx, rots, n, set)) return code;
     client_keygen_rotations(ctx->cx, seed, set);
+    return HYDIA_OK;
+    API_END
+}
+// ---- seeded keys and queries: the uniform halves travel as the 32-byte public seed they are the expansion of
+// a_seed == seed would publish the seed of the secret key (and of every error): refused before anything is touched
+#define REQUIRE_PUBLIC_SEED(seed, a_seed) REQUIRE(std::memcmp(seed, a_seed, 32) != 0, "a_seed equals seed: the public expansion seed must be independent of the secret one")
+int hydia_keygen_seeded(hydia_ctx *ctx, const uint8_t seed[32], const uint8_t a_seed[32]) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && seed && a_seed, "null argument");
+    REQUIRE_PUBLIC_SEED(seed, a_seed);
+    client_keygen(ctx->cx, seed, a_seed);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_keygen_rotations_seeded(hydia_ctx *ctx, const uint8_t seed[32], const uint8_t a_seed[32], const int32_t *rots, uint32_t n) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && seed && a_seed && (rots || n == 0), "null argument");
+    REQUIRE_PUBLIC_SEED(seed, a_seed);
+    std::vector<int> set;
+    if (int code = rotation_set(ctx->cx, rots, n, set)) return code;
+    client_keygen_rotations(ctx->cx, seed, set, a_seed);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_get_key_seed(const hydia_ctx *ctx, uint8_t out[32]) {
+    REQUIRE(ctx && out, "null argument");
+    if (!ctx->cx.has_key_seed) return fail(HYDIA_ERR_STATE, "hydia: no seeded key set was generated on this context (hydia_keygen_seeded)");
+    std::memcpy(out, ctx->cx.key_seed, 32);
+    return HYDIA_OK;
+}
+size_t hydia_eval_key_seeded_words(const hydia_ctx *ctx) { return ctx ? (size_t)ctx->cx.prm.dnum * ctx->cx.nT * ctx->cx.N : 0; }
+int hydia_export_eval_key_seeded(hydia_ctx *ctx, int rot, uint64_t *b_out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && b_out, "null argument");
+    Context &cx = ctx->cx;
+    const Context::EvalKey *k = nullptr;
+    if (rot == 0) k = &cx.relin_key;
+    else if (cx.rot_keys.count(rot)) k = &cx.rot_keys[rot];
+    if (!k || !k->d) return fail(HYDIA_ERR_STATE, "hydia: evaluation key not loaded");
+    if (!cx.has_key_seed || !k->seeded)
+        return fail(HYDIA_ERR_STATE, "hydia: this evaluation key is not covered by the context's key seed (hydia_keygen_seeded makes such keys; export it whole)");
+    const size_t half = (size_t)cx.nT * cx.N * sizeof(u64);
+    cx.sync();
+    HIP_CHECK(hipMemcpy2D(b_out, half, k->d, 2 * half, half, (size_t)cx.prm.dnum, hipMemcpyDeviceToHost));
+    return HYDIA_OK;
+    API_END
+}
+int hydia_export_public_key_seeded(hydia_ctx *ctx, uint64_t *b_out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && b_out, "null argument");
+    Context &cx = ctx->cx;
+    if (!cx.d_pk) return fail(HYDIA_ERR_STATE, "hydia: public key not loaded");
+    if (!cx.has_key_seed || !cx.pk_seeded)
+        return fail(HYDIA_ERR_STATE, "hydia: the public key is not covered by the context's key seed (hydia_keygen_seeded makes such a key; export it whole)");
+    cx.sync();
+    HIP_CHECK(hipMemcpy(b_out, cx.d_pk, (size_t)cx.nQ * cx.N * sizeof(u64), hipMemcpyDeviceToHost));
+    return HYDIA_OK;
+    API_END
+}
+int hydia_import_eval_key_seeded(hydia_ctx *ctx, int rot, const uint64_t *b, const uint8_t a_seed[32]) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && b && a_seed && rot >= 0 && rot < ctx->cx.slots, "bad argument");
+    client_import_eval_key_seeded(ctx->cx, rot, (const u64 *)b, a_seed);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_import_public_key_seeded(hydia_ctx *ctx, const uint64_t *b, const uint8_t a_seed[32]) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && b && a_seed, "null argument");
+    client_import_public_key_seeded(ctx->cx, (const u64 *)b, a_seed);
     return HYDIA_OK;
     API_END
 }
@@ -360,6 +441,7 @@ static int import_buf(Context &cx, u64 **slot, const uint64_t *data, size_t elem
     if (cx.keys_borrowed) throw StateError("hydia: this context borrows its keys from another context (re-key the owner)");
     if (!*slot) HIP_CHECK(hipMalloc((void **)slot, elems * sizeof(u64)));
     HIP_CHECK(hipMemcpy(*slot, data, elems * sizeof(u64), hipMemcpyHostToDevice));
+    if (slot == &cx.d_pk) cx.pk_seeded = false;  // an imported public key is whatever the caller sent: no seed covers it
     return HYDIA_OK;
 }
 int hydia_import_public_key(hydia_ctx *ctx, const uint64_t *data) {
@@ -1097,6 +1179,55 @@ int hydia_encrypt_queries_device(hydia_ctx *ctx, const hydia_dev_rows *rows, con
     if (!ctx->cx.d_pk) return fail(HYDIA_ERR_STATE, "hydia: public key not loaded");
     std::vector<Ct> cts = client_encrypt_queries_device(ctx->cx, r, seed, nonce0);
     for (size_t q = 0; q < r.n; q++) out[q] = wrap(ctx, std::move(cts[q]));  // compact and owning: no copy, cannot fail
+    return HYDIA_OK;
+    API_END
+}
+// ---- seeded secret-key queries: the receiver sends c0 and (a_seed, nonce0); the sender expands c1
+// what the three encrypting entries check alike before any work: the seeds and the nonce range (probe i takes nonce0 + i)
+static int check_seeded(const uint8_t *seed, const uint8_t *a_seed, uint64_t nonce0, size_t count) {
+    REQUIRE(seed && a_seed, "null argument");
+    REQUIRE_PUBLIC_SEED(seed, a_seed);
+    REQUIRE(nonce0 <= HYDIA_NONCE_LIMIT && count <= HYDIA_NONCE_LIMIT - nonce0, "nonce0 + count must not exceed 2^40");
+    return HYDIA_OK;
+}
+int hydia_encrypt_queries_seeded(hydia_ctx *ctx, const double *queries, size_t count, const uint8_t seed[32], const uint8_t a_seed[32],
+                                 uint64_t nonce0, uint64_t *c0_out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx, "null argument");
+    if (int code = check_seeded(seed, a_seed, nonce0, count)) return code;
+    if (count == 0) return HYDIA_OK;
+    REQUIRE(queries && c0_out, "null argument");
+    REQUIRE(count <= SIZE_MAX / sizeof(double) / (size_t)ctx->cx.prm.dim, "probe count out of range");
+    client_encrypt_queries_seeded(ctx->cx, queries, count, seed, a_seed, nonce0, (u64 *)c0_out);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_encrypt_query_seeded(hydia_ctx *ctx, const double *query, const uint8_t seed[32], const uint8_t a_seed[32], uint64_t nonce,
+                               uint64_t *c0_out) {
+    return hydia_encrypt_queries_seeded(ctx, query, 1, seed, a_seed, nonce, c0_out);
+}
+int hydia_encrypt_queries_seeded_device(hydia_ctx *ctx, const hydia_dev_rows *rows, const uint8_t seed[32], const uint8_t a_seed[32],
+                                        uint64_t nonce0, uint64_t *c0_out) {
+    API_BEGIN
+    CHECK_DEV_ROWS(r)
+    if (int code = check_seeded(seed, a_seed, nonce0, r.n)) return code;
+    if (r.n == 0) return HYDIA_OK;
+    REQUIRE(c0_out, "null argument");
+    client_encrypt_queries_seeded_device(ctx->cx, r, seed, a_seed, nonce0, (u64 *)c0_out);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_ct_expand_seeded(hydia_ctx *ctx, const uint64_t *c0, size_t count, const uint8_t a_seed[32], uint64_t nonce0, hydia_ct **out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && a_seed, "null argument");
+    REQUIRE(nonce0 <= HYDIA_NONCE_LIMIT && count <= HYDIA_NONCE_LIMIT - nonce0, "nonce0 + count must not exceed 2^40");
+    if (count == 0) return HYDIA_OK;
+    REQUIRE(c0 && out, "null argument");
+    for (size_t q = 0; q < count; q++) out[q] = nullptr;  // (what a device error below leaves behind)
+    std::vector<Ct> cts = client_expand_seeded(ctx->cx, (const u64 *)c0, count, a_seed, nonce0);
+    for (size_t q = 0; q < count; q++) out[q] = wrap(ctx, std::move(cts[q]));  // compact and owning: no copy, cannot fail
     return HYDIA_OK;
     API_END
 }

@@ -59,12 +59,22 @@ static u64 inv_mod_pow2(u64 g, u64 M) {
 }
 
 // hybrid switching key from secret s_from (Q limbs) to secret s_enc (Q u P limbs), written to evk [dnum][2][nT][N] (device memory);
-// key_id addresses the sampler streams
-static void gen_evk(Context &cx, const ChaChaKey &key, u64 key_id, const u64 *s_enc, const u64 *s_from, u64 *evk) {
+// key_id addresses the sampler streams.  The uniform halves are sampled under akey (a seeded key set: the PUBLIC expansion seed; every
+// other caller passes akey == key), the Gaussian errors under key.
+// evk_sample_a / pk_sample_a: the ONE launch each that draws the uniform halves — key generation and the import of a half key share it
+static void evk_sample_a(Context &cx, const ChaChaKey &akey, u64 key_id, u64 *evk) {
+    const int N = cx.N, nT = cx.nT;
+    hc::sample_uniform(cx.stream, akey, cx.d_mod, N, HY_STREAM(HY_DOM_EVK_A, key_id, 0, 0), 1ull, 1ull << 8,
+                       evk + (size_t)nT * N, (size_t)N, (size_t)2 * nT * N, cx.sel_range(0, nT), cx.prm.dnum);
+}
+static void pk_sample_a(Context &cx, const ChaChaKey &akey, u64 *pk) {
+    hc::sample_uniform(cx.stream, akey, cx.d_mod, cx.N, HY_STREAM(HY_DOM_PK_A, 0, 0, 0), 1ull, 0, pk + (size_t)cx.nQ * cx.N,
+                       (size_t)cx.N, 0, cx.sel_q(cx.nQ), 1);
+}
+static void gen_evk(Context &cx, const ChaChaKey &key, const ChaChaKey &akey, u64 key_id, const u64 *s_enc, const u64 *s_from, u64 *evk) {
     const int N = cx.N, nT = cx.nT, dnum = cx.prm.dnum;
     const LimbSel all = cx.sel_range(0, nT);
-    hc::sample_uniform(cx.stream, key, cx.d_mod, N, HY_STREAM(HY_DOM_EVK_A, key_id, 0, 0), 1ull, 1ull << 8,
-                       evk + (size_t)nT * N, (size_t)N, (size_t)2 * nT * N, all, dnum);
+    evk_sample_a(cx, akey, key_id, evk);
     int *e32 = (int *)cx.pool.get(sizeof(int) * (size_t)dnum * N);
     hc::sample_gauss(cx.stream, key, N, HY_STREAM(HY_DOM_EVK_E, key_id, 0, 0), 1ull << 8, e32, dnum);
     u64 *e = cx.pool.get(sizeof(u64) * (size_t)dnum * nT * N);
@@ -77,15 +87,15 @@ static void gen_evk(Context &cx, const ChaChaKey &key, u64 key_id, const u64 *s_
     cx.pool.put((u64 *)e32);
 }
 
-static void keygen_impl(Context &cx, const uint8_t seed[32], const std::vector<int> &rots);
-void client_keygen(Context &cx, const uint8_t seed[32]) {
+static void keygen_impl(Context &cx, const uint8_t seed[32], const uint8_t *a_seed, const std::vector<int> &rots);
+void client_keygen(Context &cx, const uint8_t seed[32], const uint8_t *a_seed) {
     // rotation keys {1..dim-1} u {dim, 2 dim, ... < slots}
     std::vector<int> rots;
     for (int i = 1; i < cx.prm.dim; i++) rots.push_back(i);
     for (int i = cx.prm.dim; i < cx.slots; i <<= 1) rots.push_back(i);
-    keygen_impl(cx, seed, rots);
+    keygen_impl(cx, seed, a_seed, rots);
 }
-void client_keygen_rotations(Context &cx, const uint8_t seed[32], const std::vector<int> &rots) {
+void client_keygen_rotations(Context &cx, const uint8_t seed[32], const std::vector<int> &rots, const uint8_t *a_seed) {
     for (int r : rots)
         if (r < 1 || r >= cx.slots) throw std::runtime_error("hydia: rotation keys are indexed by r mod slots in [1, slots)");
     if (cx.keys_borrowed) throw StateError("hydia: this context borrows its keys from another context (re-key the owner)");
@@ -101,11 +111,13 @@ void client_keygen_rotations(Context &cx, const uint8_t seed[32], const std::vec
         it = cx.rot_keys.erase(it);
     }
     cx.rotptrs_valid = cx.giants_valid = false;
-    keygen_impl(cx, seed, rots);
+    keygen_impl(cx, seed, a_seed, rots);
 }
-static void keygen_impl(Context &cx, const uint8_t seed[32], const std::vector<int> &rots) {
+// a_seed != nullptr: the seeded key set — every uniform half under a_seed (the caller has refused a_seed == seed), which the context
+// then remembers, and every key written here marked as covered by it
+static void keygen_impl(Context &cx, const uint8_t seed[32], const uint8_t *a_seed, const std::vector<int> &rots) {
     const int N = cx.N, nT = cx.nT, nQ = cx.nQ;
-    const ChaChaKey key = make_key(seed);
+    const ChaChaKey key = make_key(seed), akey = a_seed ? make_key(a_seed) : key;
     const LimbSel all = cx.sel_range(0, nT), qsel = cx.sel_q(nQ);
     if (cx.keys_borrowed) throw StateError("hydia: this context borrows its keys from another context (re-key the owner)");
     if (!cx.d_sk) HIP_CHECK(hipMalloc((void **)&cx.d_sk, sizeof(u64) * (size_t)nT * N));
@@ -115,8 +127,7 @@ static void keygen_impl(Context &cx, const uint8_t seed[32], const std::vector<i
     hc::small_to_limbs(cx.stream, cx.d_mod, N, s32, nullptr, cx.d_sk, 0, 1, all);
     cx.ntt_fwd(cx.d_sk, 0, 1, all);
     // public key (b, a) = (-a s + e, a)
-    hc::sample_uniform(cx.stream, key, cx.d_mod, N, HY_STREAM(HY_DOM_PK_A, 0, 0, 0), 1ull, 0, cx.d_pk + (size_t)nQ * N,
-                       (size_t)N, 0, qsel, 1);
+    pk_sample_a(cx, akey, cx.d_pk);
     hc::sample_gauss(cx.stream, key, N, HY_STREAM(HY_DOM_PK_E, 0, 0, 0), 0, s32, 1);
     hc::small_to_limbs(cx.stream, cx.d_mod, N, s32, nullptr, cx.d_pk, 0, 1, qsel);
     cx.ntt_fwd(cx.d_pk, 0, 1, qsel);
@@ -125,17 +136,47 @@ static void keygen_impl(Context &cx, const uint8_t seed[32], const std::vector<i
     // relinearisation key: s^2 -> s
     u64 *tmp = cx.pool.get(sizeof(u64) * (size_t)nT * N);
     hc::mul(cx.stream, cx.d_mod, N, cx.d_sk, cx.d_sk, tmp, qsel);
-    gen_evk(cx, key, 0, cx.d_sk, tmp, cx.eval_key_storage(0));
+    gen_evk(cx, key, akey, 0, cx.d_sk, tmp, cx.eval_key_storage(0));
     // rotation keys: key r switches s -> sigma_g^{-1}(s), g = 5^r, so EvalFastRotation needs a single automorphism at the very end
     // (see evaluator.cpp, rotate_query); the sampler streams are addressed by r, whatever set r belongs to
     const u64 M = 2ull * N;
     for (int r : rots) {
         const u64 ginv = inv_mod_pow2(cx.galois_elt(r), M);
         hc::automorph(cx.stream, cx.prm.logN, cx.d_sk, tmp, (unsigned)ginv, nT);
-        gen_evk(cx, key, (u64)r, tmp, cx.d_sk, cx.eval_key_storage(r));
+        gen_evk(cx, key, akey, (u64)r, tmp, cx.d_sk, cx.eval_key_storage(r));
     }
     cx.pool.put(tmp);
     cx.sync();
+    // (eval_key_storage has cleared the mark of every key written above)
+    cx.pk_seeded = a_seed != nullptr;
+    if (!a_seed) return;
+    if (cx.has_key_seed && std::memcmp(cx.key_seed, a_seed, 32) != 0)  // keys an earlier seeded set left behind are another seed's
+        for (auto &kv : cx.rot_keys) kv.second.seeded = false;
+    std::memcpy(cx.key_seed, a_seed, 32);
+    cx.has_key_seed = true;
+    cx.relin_key.seeded = true;
+    for (int r : rots) cx.rot_keys[r].seeded = true;
+}
+// The sender's side of a half key: b (host, the [d][0] halves [dnum][nT][N] of key `rot`, or the public key's [nQ][N]) into its strided
+// place, and the a halves expanded on the GPU by the launch key generation makes.  Residues are not range-checked.  The key is NOT
+// marked seeded here (eval_key_storage clears the mark; the importing context made no key set)
+void client_import_eval_key_seeded(Context &cx, int rot, const u64 *b, const uint8_t a_seed[32]) {
+    const size_t half = (size_t)cx.nT * cx.N;
+    u64 *dst = cx.eval_key_storage(rot);
+    cx.sync();
+    HIP_CHECK(hipMemcpy2D(dst, 2 * half * sizeof(u64), b, half * sizeof(u64), half * sizeof(u64), (size_t)cx.prm.dnum, hipMemcpyHostToDevice));
+    evk_sample_a(cx, make_key(a_seed), (u64)rot, dst);
+    cx.sync();
+}
+void client_import_public_key_seeded(Context &cx, const u64 *b, const uint8_t a_seed[32]) {
+    if (cx.keys_borrowed) throw StateError("hydia: this context borrows its keys from another context (re-key the owner)");
+    const size_t half = (size_t)cx.nQ * cx.N;
+    if (!cx.d_pk) HIP_CHECK(hipMalloc((void **)&cx.d_pk, 2 * half * sizeof(u64)));
+    cx.sync();
+    HIP_CHECK(hipMemcpy(cx.d_pk, b, half * sizeof(u64), hipMemcpyHostToDevice));
+    pk_sample_a(cx, make_key(a_seed), cx.d_pk);
+    cx.sync();
+    cx.pk_seeded = false;
 }
 
 // The switching key of a re-keyed database (Context::db_rekey): from the OLD receiver's secret (old_secret, host memory, [nT][N] in
@@ -147,7 +188,8 @@ void client_keygen_switch(Context &cx, const u64 *old_secret, const uint8_t seed
     u64 *d_old = cx.pool.get(sk_elems * sizeof(u64)), *d_key = cx.pool.get(key_elems * sizeof(u64));
     cx.sync();
     HIP_CHECK(hipMemcpy(d_old, old_secret, sk_elems * sizeof(u64), hipMemcpyHostToDevice));
-    gen_evk(cx, make_key(seed), HY_EVK_ID_SWITCH, cx.d_sk, d_old, d_key);
+    const ChaChaKey key = make_key(seed);
+    gen_evk(cx, key, key, HY_EVK_ID_SWITCH, cx.d_sk, d_old, d_key);
     cx.sync();
     HIP_CHECK(hipMemcpy(out, d_key, key_elems * sizeof(u64), hipMemcpyDeviceToHost));
     cx.pool.put(d_key);
@@ -181,6 +223,29 @@ static void encrypt_device(Context &cx, const double *d_slots, int X, const ChaC
     hc::enc_combine(cx.stream, cx.d_mod, N, nQ, cx.d_pk, U, T0, T1, dst, X);
     for (void *p : {(void *)work, (void *)coeffs, (void *)u32, (void *)e0, (void *)e1, (void *)U, (void *)T0, (void *)T1})
         cx.pool.put((u64 *)p);
+}
+
+// encode + encrypt X slot vectors under the SECRET key with a seeded c1: c0 = NTT(e0 + m) - a s, where e0 is encrypt_device's (the
+// stream (ENC_E0, nonce) under the secret `key`) and a limb j is the uniform stream (SYM_A, nonce, 0, j) under the PUBLIC akey, drawn
+// inside k_enc_sym.  One sampled polynomial and one transform batch where encrypt_device takes three of each.  Writes c0 [X][nQ][N] at
+// c0 and, when c1 != nullptr, a [X][nQ][N] at c1
+static void encrypt_sym_device(Context &cx, const double *d_slots, int X, const ChaChaKey &key, const ChaChaKey &akey, u64 nonce0, u64 *c0,
+                               u64 *c1 = nullptr) {
+    if (!cx.d_sk) throw StateError("hydia: secret key not loaded (seeded encryption is the secret-key holder's; hydia_encrypt_query takes the public key)");
+    ensure_embedding_tables(cx);
+    const int N = cx.N, nQ = cx.nQ, Nh = cx.slots;
+    const LimbSel qsel = cx.sel_q(nQ);
+    double2 *work = (double2 *)cx.pool.get(sizeof(double2) * (size_t)X * Nh);
+    long long *coeffs = (long long *)cx.pool.get(sizeof(long long) * (size_t)X * N);
+    hc::encode(cx.stream, d_slots, work, coeffs, N, X, cx.delta, cx.d_rot_group, (const double2 *)cx.d_ksi);
+    int *e0 = (int *)cx.pool.get(sizeof(int) * (size_t)X * N);
+    hc::sample_gauss(cx.stream, key, N, HY_STREAM(HY_DOM_ENC_E0, nonce0, 0, 0), 1ull << 16, e0, X);
+    const size_t pe = (size_t)nQ * N;
+    u64 *T0 = cx.pool.get(sizeof(u64) * X * pe);
+    hc::small_to_limbs(cx.stream, cx.d_mod, N, e0, coeffs, T0, pe, X, qsel);
+    cx.ntt_fwd(T0, pe, X, qsel);
+    hc::enc_sym(cx.stream, akey, cx.d_mod, N, nQ, HY_STREAM(HY_DOM_SYM_A, nonce0, 0, 0), T0, cx.d_sk, c0, c1, X);
+    for (void *p : {(void *)work, (void *)coeffs, (void *)e0, (void *)T0}) cx.pool.put((u64 *)p);
 }
 
 Ct client_encrypt(Context &cx, const double *slots, int count, const uint8_t seed[32], uint64_t nonce0) {
@@ -510,6 +575,68 @@ std::vector<Ct> client_encrypt_queries_device(Context &cx, const DevRows &rows, 
     return queries_device(cx, rows, &key, nonce0);
 }
 std::vector<Ct> client_encode_queries_device(Context &cx, const DevRows &rows) { return queries_device(cx, rows, nullptr, 0); }
+
+// Seeded queries: n probes (src: normalised host rows, or rows in device memory that k_rows_widen normalises) -> their c0 halves in
+// host memory, c0_out [n][nQ][N]; probe i takes nonce0 + i.  queries_device's passes — ONE k_query_tile and ONE encrypt_sym_device over
+// what free HBM holds of the encoder's temporaries, one sampled polynomial, its limbs and the output — then one copy out per pass
+static void queries_seeded(Context &cx, const RowSource &src, size_t n, const ChaChaKey &key, const ChaChaKey &akey, u64 nonce0, u64 *c0_out) {
+    if (!cx.d_sk) throw StateError("hydia: secret key not loaded (seeded encryption is the secret-key holder's; hydia_encrypt_query takes the public key)");
+    const int dim = cx.prm.dim, Nh = cx.slots;
+    const size_t elems = (size_t)cx.nQ * cx.N, poly = elems * sizeof(u64);
+    const double per_query = 32.0 * cx.N + 4.0 * cx.N + 2.0 * poly + 8.0 * dim;
+    size_t free_b = 0, total_b = 0, pass = 1;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        pass = (size_t)std::max(1.0, std::floor(0.5 * ((double)free_b + (double)cx.pool.bytes_cached) / per_query));
+    pass = std::min({pass, n, (size_t)4096});
+    double *d_q = (double *)cx.pool.get(sizeof(double) * pass * dim);
+    double *d_slots = (double *)cx.pool.get(sizeof(double) * pass * Nh);
+    u64 *d_out = cx.pool.get(pass * poly);
+    for (size_t q0 = 0; q0 < n; q0 += pass) {
+        const int Q = (int)std::min(pass, n - q0);
+        src.stage(cx, q0, (size_t)Q, d_q);
+        hc::query_tile(cx.stream, d_q, Q, dim, Nh, d_slots);
+        encrypt_sym_device(cx, d_slots, Q, key, akey, nonce0 + q0, d_out);
+        HIP_CHECK(hipMemcpyAsync(c0_out + q0 * elems, d_out, (size_t)Q * poly, hipMemcpyDeviceToHost, cx.stream));
+        cx.sync();  // d_out is written again by the next pass; the caller's rows and c0_out are host memory
+    }
+    cx.pool.put(d_out);
+    cx.pool.put((u64 *)d_slots);
+    cx.pool.put((u64 *)d_q);
+}
+void client_encrypt_queries_seeded(Context &cx, const double *queries, size_t n, const uint8_t seed[32], const uint8_t a_seed[32], uint64_t nonce0,
+                                   u64 *c0_out) {
+    const int dim = cx.prm.dim;
+    std::vector<double> qn(queries, queries + n * (size_t)dim);
+    for (size_t v = 0; v < n; v++) normalize(qn.data() + v * dim, dim);
+    RowSource src;
+    src.host = qn.data();
+    queries_seeded(cx, src, n, make_key(seed), make_key(a_seed), nonce0, c0_out);
+}
+void client_encrypt_queries_seeded_device(Context &cx, const DevRows &rows, const uint8_t seed[32], const uint8_t a_seed[32], uint64_t nonce0,
+                                          u64 *c0_out) {
+    RowSource src;
+    src.dev = &rows;
+    src.normalise = 1;
+    wait_for_producer(cx, rows.stream);
+    queries_seeded(cx, src, rows.n, make_key(seed), make_key(a_seed), nonce0, c0_out);
+}
+// the sender's side: handle i = (c0[i], a) with a limb j = the uniform stream (SYM_A, nonce0 + i, 0, j) under a_seed — the launch of
+// sample_uniform whose thread k_enc_sym repeats — an ordinary fresh ciphertext [1][2][nQ][N] at scale 2^scale_bits
+std::vector<Ct> client_expand_seeded(Context &cx, const u64 *c0, size_t n, const uint8_t a_seed[32], uint64_t nonce0) {
+    const size_t elems = (size_t)cx.nQ * cx.N;
+    const ChaChaKey akey = make_key(a_seed);
+    const LimbSel qsel = cx.sel_q(cx.nQ);
+    std::vector<Ct> out;
+    out.reserve(n);
+    for (size_t i = 0; i < n; i++) {
+        out.emplace_back(&cx, 1, 2, cx.nQ, cx.delta);
+        HIP_CHECK(hipMemcpyAsync(out.back().d, c0 + i * elems, elems * sizeof(u64), hipMemcpyHostToDevice, cx.stream));
+        hc::sample_uniform(cx.stream, akey, cx.d_mod, cx.N, HY_STREAM(HY_DOM_SYM_A, nonce0 + i, 0, 0), 1ull, 0, out.back().d + elems,
+                           (size_t)cx.N, 0, qsel, 1);
+    }
+    cx.sync();  // c0 is caller memory
+    return out;
+}
 
 #define HY_HERS_NONCE_BASE (1ull << 37)
 // HersEnroller::serializeDB (/root/reference/src/enroller/enroller_hers.cpp:40-93): normalise in place, then per matrix of

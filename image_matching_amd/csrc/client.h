@@ -4,10 +4,23 @@
 #include "hydia_core.h"
 
 namespace hydia {
-void client_keygen(Context &cx, const uint8_t seed[32]);
+// a_seed != nullptr (both key generations): the SEEDED key set — every uniform half (the public key's a, every evk[d][1]) is sampled
+// under the public a_seed at the unchanged stream addresses, the secret and every Gaussian error stay under seed; the context
+// remembers a_seed and marks the keys it wrote.  The caller refuses a_seed == seed.  nullptr: not a bit changes
+void client_keygen(Context &cx, const uint8_t seed[32], const uint8_t *a_seed = nullptr);
 // sk, pk and relinearisation key exactly as client_keygen, rotation keys for exactly `rots` (each in [1, slots)); every other
 // rotation key is released.  A key that client_keygen also makes comes out bit-identical (same sampler streams).
-void client_keygen_rotations(Context &cx, const uint8_t seed[32], const std::vector<int> &rots);
+void client_keygen_rotations(Context &cx, const uint8_t seed[32], const std::vector<int> &rots, const uint8_t *a_seed = nullptr);
+// half keys on the importing side: b = the [d][0] halves [dnum][nT][N] (the public key: [nQ][N]) from host memory into their strided
+// places, the a halves expanded on the GPU under a_seed by key generation's own sample_uniform launch.  Not range-checked, not marked
+void client_import_eval_key_seeded(Context &cx, int rot, const u64 *b, const uint8_t a_seed[32]);
+void client_import_public_key_seeded(Context &cx, const u64 *b, const uint8_t a_seed[32]);
+// seeded secret-key queries (k_enc_sym): c0 = NTT(e0 + m) - a s of probe i (normalised, tiled, encoded as client_encrypt_query does;
+// e0 under seed, a under the public a_seed, nonce nonce0 + i) into HOST memory c0_out [n][nQ][N].  StateError without a secret key
+void client_encrypt_queries_seeded(Context &cx, const double *queries /* n x vector_dim */, size_t n, const uint8_t seed[32],
+                                   const uint8_t a_seed[32], uint64_t nonce0, u64 *c0_out);
+// and the sender's expansion: handle i = (c0[i], a(a_seed, nonce0 + i)), an ordinary [1][2][nQ][N] ciphertext at scale 2^scale_bits
+std::vector<Ct> client_expand_seeded(Context &cx, const u64 *c0, size_t n, const uint8_t a_seed[32], uint64_t nonce0);
 // the switching key of Context::db_rekey: old_secret (host, [nT][N], evaluation form) -> this context's secret, into out (host,
 // [dnum][2][nT][N]); sampler streams of key id HY_EVK_ID_SWITCH.  StateError without a secret; the context's own keys are untouched
 void client_keygen_switch(Context &cx, const u64 *old_secret, const uint8_t seed[32], u64 *out);
@@ -49,6 +62,9 @@ void client_plain_db_update_device(Context &cx, size_t first_vector, const DevRo
 // one handle per probe: query i = client_encrypt_query(row i, seed, nonce0 + i) / client_encode_query(row i), bit for bit
 std::vector<Ct> client_encrypt_queries_device(Context &cx, const DevRows &rows, const uint8_t seed[32], uint64_t nonce0);
 std::vector<Ct> client_encode_queries_device(Context &cx, const DevRows &rows);
+// client_encrypt_queries_seeded from rows in device memory (one k_rows_widen and one k_query_tile per pass); c0_out is host memory
+void client_encrypt_queries_seeded_device(Context &cx, const DevRows &rows, const uint8_t seed[32], const uint8_t a_seed[32], uint64_t nonce0,
+                                          u64 *c0_out);
 // HERS (approach 4): column-packed enrolment and the vector_dim broadcast query ciphertexts
 void client_hers_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32]);
 Ct client_hers_encrypt_query(Context &cx, const double *query, const uint8_t seed[32], uint64_t nonce0);

@@ -14,6 +14,7 @@ struct ChaChaKey {
 #define HY_DOM_ENC_U 6ull
 #define HY_DOM_ENC_E0 7ull
 #define HY_DOM_ENC_E1 8ull
+#define HY_DOM_SYM_A 9ull  // c1 = a of a seeded secret-key query, under the PUBLIC expansion seed: (9, nonce, 0, limb)
 #define HY_STREAM(dom, a, b, c) (((u64)(dom) << 56) | ((u64)(a) << 16) | ((u64)(b) << 8) | (u64)(c))
 
 namespace hc {
@@ -30,6 +31,10 @@ void evk_combine(hipStream_t st, const ModC *mod, int N, int nT, int nQ, int alp
                  const u64 *s_enc, const u64 *s_from, const ScaleSel &pmodq);
 void enc_combine(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *pk, const u64 *u, const u64 *t0, const u64 *t1,
                  u64 *ct, int X);
+// seeded secret-key encryption of X polynomials (X <= 65535): c0[x][j] = t0[x][j] - a s[j] with a = sample_uniform(akey, sbase, step_y
+// 1, step_z 1 << 16) limb j of element x, drawn inside the kernel; a is also written to c1 [X][nQ][N] when c1 != nullptr
+void enc_sym(hipStream_t st, const ChaChaKey &akey, const ModC *mod, int N, int nQ, u64 sbase, const u64 *t0, const u64 *s, u64 *c0,
+             u64 *c1, int X);
 void dec_dot(hipStream_t st, const ModC *mod, int N, int npoly, int nl, const u64 *ct, const u64 *s, u64 *t, int nu, int X);
 void encode(hipStream_t st, const double *slots, double2 *work, long long *coeffs, int N, int X, double scale,
             const unsigned *rot_group, const double2 *ksi);

@@ -154,6 +154,39 @@ __global__ __launch_bounds__(256) void k_enc_combine(const ModC *__restrict__ mo
     ct[(((size_t)x * 2 + 0) * nQ + j) * N + c] = addmod(mulmod(pk[(size_t)j * N + c], uu, M), t0[i], M.q);
     ct[(((size_t)x * 2 + 1) * nQ + j) * N + c] = addmod(mulmod(pk[((size_t)nQ + j) * N + c], uu, M), t1[i], M.q);
 }
+// seeded secret-key encryption: c0[x][j] = t0[x][j] - a s[j], a = the uniform residues of stream sbase + j + (x << 16) under the PUBLIC
+// key `akey` — k_sample_uniform's thread (one ChaCha block = 4 residues, the same reduce128) fused with the combine, so `a` reaches
+// memory only when c1 is given.  t0, c0, c1 [X][nQ][N]; s [>= nQ][N].  16-byte loads and stores.  grid (N/4/256 rounded up, nQ, X)
+__global__ __launch_bounds__(256) void k_enc_sym(ChaChaKey akey, const ModC *__restrict__ mod, int N, int nQ, u64 sbase,
+                                                 const u64 *__restrict__ t0, const u64 *__restrict__ s, u64 *__restrict__ c0,
+                                                 u64 *__restrict__ c1) {
+    const int blk = blockIdx.x * 256 + threadIdx.x;
+    if (blk * 4 >= N) return;
+    const int j = blockIdx.y, x = blockIdx.z;
+    const ModC M = mod[j];
+    unsigned w[16];
+    chacha_block(akey, sbase + (u64)j + ((u64)x << 16), (u64)blk, w);
+    u64 a[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const u64 lo = (u64)w[4 * t] | ((u64)w[4 * t + 1] << 32);
+        const u64 hi = (u64)w[4 * t + 2] | ((u64)w[4 * t + 3] << 32);
+        a[t] = reduce128(((u128)hi << 64) | lo, M);
+    }
+    const size_t is = (size_t)j * N + (size_t)blk * 4, i = (size_t)x * nQ * N + is;
+    const ulonglong2 *tp = (const ulonglong2 *)(t0 + i), *sp = (const ulonglong2 *)(s + is);
+    ulonglong2 *op = (ulonglong2 *)(c0 + i);
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const ulonglong2 tv = tp[h], sv = sp[h];
+        op[h] = make_ulonglong2(submod(tv.x, mulmod(a[2 * h], sv.x, M), M.q), submod(tv.y, mulmod(a[2 * h + 1], sv.y, M), M.q));
+    }
+    if (c1) {
+        ulonglong2 *ap = (ulonglong2 *)(c1 + i);
+        ap[0] = make_ulonglong2(a[0], a[1]);
+        ap[1] = make_ulonglong2(a[2], a[3]);
+    }
+}
 // decryption dot product on the first nu limbs: t[x][j] = c0 + s (c1 + s c2 ...). grid (N/256, nu, X)
 __global__ __launch_bounds__(256) void k_dec_dot(const ModC *__restrict__ mod, int N, int npoly, int nl,
                                                  const u64 *__restrict__ ct, const u64 *__restrict__ s, u64 *__restrict__ t,
@@ -402,6 +435,11 @@ void evk_combine(hipStream_t st, const ModC *mod, int N, int nT, int nQ, int alp
 void enc_combine(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *pk, const u64 *u, const u64 *t0, const u64 *t1,
                  u64 *ct, int X) {
     hipLaunchKernelGGL(k_enc_combine, dim3(N / 256, nQ, X), dim3(256), 0, st, mod, N, nQ, pk, u, t0, t1, ct);
+}
+void enc_sym(hipStream_t st, const ChaChaKey &akey, const ModC *mod, int N, int nQ, u64 sbase, const u64 *t0, const u64 *s, u64 *c0,
+             u64 *c1, int X) {
+    if (X < 1 || X > 65535) throw std::runtime_error("hydia: enc_sym takes 1 .. 65535 polynomials per launch");
+    hipLaunchKernelGGL(k_enc_sym, dim3((N / 4 + 255) / 256, nQ, X), dim3(256), 0, st, akey, mod, N, nQ, sbase, t0, s, c0, c1);
 }
 void dec_dot(hipStream_t st, const ModC *mod, int N, int npoly, int nl, const u64 *ct, const u64 *s, u64 *t, int nu, int X) {
     hipLaunchKernelGGL(k_dec_dot, dim3(N / 256, nu, X), dim3(256), 0, st, mod, N, npoly, nl, ct, s, t, nu);

@@ -173,7 +173,8 @@ Ct Ct::alias(int nl_) const {
 
 // ------------------------------------------------------------------ context
 HostParams::HostParams(const Params &p) : prm(p) {
-    if (p.logN < 11 || p.logN > 16) throw std::runtime_error("hydia: log_n must be in [11,16]");
+    // (log_n 10 is the receiver's side only: keys, encryption, decryption, handles.  Key switching and the resident database start at 2^11)
+    if (p.logN < 10 || p.logN > 16) throw std::runtime_error("hydia: log_n must be in [10,16]");
     if (p.dnum < 1 || p.mult_depth < 1) throw std::runtime_error("hydia: bad dnum / depth");
     N = 1 << p.logN;
     slots = N / 2;
@@ -508,9 +509,11 @@ void Context::adopt_keys(Context &src) {
     src.sync_all();
     relin_key = src.relin_key;
     relin_key.borrowed = true;
+    relin_key.seeded = false;  // (the owner exports the halves of its seeded keys)
     for (auto &kv : src.rot_keys) {
         EvalKey k = kv.second;
         k.borrowed = true;
+        k.seeded = false;
         rot_keys[kv.first] = k;
     }
     d_sk = src.d_sk;
@@ -547,6 +550,7 @@ u64 *Context::eval_key_storage(int rot) {
     // every caller is about to WRITE this key (import, key generation, random fill): loop A's pointer table and its packed
     // shadow of rotations 1..dim-1 are rebuilt from the new contents before the next query
     if (rot >= 1 && rot < prm.dim) rotptrs_valid = giants_valid = false;
+    k.seeded = false;  // (client_keygen_seeded marks the key again once it has written it)
     return k.d;
 }
 void Context::load_eval_key(int rot, const u64 *host) {
@@ -568,6 +572,7 @@ DbLayout Context::db_layout_for(size_t cts, int form, bool plain) const {
     return hk::db_layout_seq(N, nQ, 1, form, (int)(cts / (size_t)form), plain ? hk::PLAIN_BPP : tensor_bpp, tensor_nw, b46, plain);
 }
 void Context::db_resize(size_t n_vectors, size_t cts, int form, bool plain) {
+    if (cts && prm.logN < 11) throw std::runtime_error("hydia: a resident database needs log_n >= 11 (a 2^10 ring serves the receiver's side only)");
     const DbLayout want = db_layout_for(cts, form, plain);
     const size_t bytes = db_alloc_size(want, cts);  // (+ the tail a lane's last 16-byte load may touch: db_layout.h)
     if (d_db) sync_all();  // the layout may change under a still asynchronous query

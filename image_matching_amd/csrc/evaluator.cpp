@@ -37,6 +37,7 @@ void Context::ntt_inv(const u64 *src, u64 *dst, size_t so, size_t dso, int X, co
 }
 
 const Context::ModUpPlan &Context::modup_plan(int nl) {
+    if (prm.logN < 11) throw std::runtime_error("hydia: key switching needs log_n >= 11 (a 2^10 ring serves the receiver's side only)");
     auto it = modup_plans.find(nl);
     if (it != modup_plans.end()) return it->second;
     const int nE = nl + nP, nd = (nl + alpha - 1) / alpha;

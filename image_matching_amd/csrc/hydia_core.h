@@ -136,7 +136,12 @@ struct Context : HostParams {
         const u64 **d_cell = nullptr;
         unsigned *d_gal = nullptr;   // [0] = Galois element g, [1] = g^{-1} mod 2N
         bool borrowed = false;       // storage belongs to another context on the same GPU (adopt_keys)
+        bool seeded = false;         // its a halves are the expansion of key_seed (client_keygen_seeded); eval_key_storage clears it
     };
+    // the PUBLIC seed the uniform halves of the keys marked `seeded` (and of the public key, pk_seeded) were sampled under: what the
+    // half-key exports ship in place of those halves.  Any other writer of a key clears that key's mark
+    unsigned char key_seed[32] = {};
+    bool has_key_seed = false, pk_seeded = false;
     EvalKey relin_key;
     std::map<int, EvalKey> rot_keys;
     const u64 **d_rotptrs = nullptr;   // device array: key pointers of rotations 1..dim-1 (hoisted loop A)

@@ -82,17 +82,19 @@ __global__ __launch_bounds__(256) void k_ntt_strided(NttTables T, int logN, cons
     }
 }
 
-template <bool INV>
+// CH: the coefficients a workgroup owns, 2048, or 1024 for the one ring that is smaller than that (N = 2^10: one workgroup per limb)
+template <bool INV, int CH = 2048>
 __global__ __launch_bounds__(256) void k_ntt_contig(NttTables T, int logN, const u64 *__restrict__ src,
                                                     u64 *__restrict__ dst, size_t so, size_t dso, LimbSel sel) {
-    __shared__ u64 lds[2048];
+    static_assert(CH == 2048 || CH == 1024, "a chunk is a whole number of 512-coefficient loads and holds 256-coefficient blocks");
+    __shared__ u64 lds[CH];
     const int N = 1 << logN;
     const int y = blockIdx.y, x = y / sel.n, slot = y - x * sel.n, m = sel.mod[slot];
     const u64 q = T.mod[m].q;
-    const int B0 = blockIdx.x * 2048, tid = threadIdx.x;
+    const int B0 = blockIdx.x * CH, tid = threadIdx.x;
     const u64 *s = src + (size_t)x * so + (size_t)slot * N + B0;
     u64 *d = dst + (size_t)x * dso + (size_t)slot * N + B0;
-    for (int k = 0; k < 4; k++) {
+    for (int k = 0; k < CH / 512; k++) {
         const int idx = 2 * tid + 512 * k;
         const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(s + idx);
         lds[idx] = v.x;
@@ -105,7 +107,7 @@ __global__ __launch_bounds__(256) void k_ntt_contig(NttTables T, int logN, const
         const int lt = INV ? st : 7 - st;  // log2 of the stride inside the chunk
         const int base = (INV ? (N >> (lt + 1)) : (N >> (lt + 1))) + (B0 >> (lt + 1));
         // forward stage with stride t uses block mm = N/(2t); inverse stage with stride t uses block h = N/(2t)
-        for (int e = tid; e < 1024; e += 256) {
+        for (int e = tid; e < CH / 2; e += 256) {
             const int i = e >> lt, o = e & ((1 << lt) - 1);
             const int l0 = (i << (lt + 1)) + o, l1 = l0 + (1 << lt);
             const u64 W = tw[base + i], Ws = tws[base + i];
@@ -121,7 +123,7 @@ __global__ __launch_bounds__(256) void k_ntt_contig(NttTables T, int logN, const
         }
         __syncthreads();
     }
-    for (int k = 0; k < 4; k++) {
+    for (int k = 0; k < CH / 512; k++) {
         const int idx = 2 * tid + 512 * k;
         ulonglong2 v;
         v.x = lds[idx];
@@ -1858,14 +1860,16 @@ void ntt_forward(hipStream_t st, const NttTables &T, int logN, const u64 *src, u
     ScaleSel dummy = {};
     hipLaunchKernelGGL(k_ntt_strided<false>, dim3(8, X * sel.n), dim3(256), (size_t)R * 32 * 8, st, T, logN, src, dst, so,
                        dso, sel, dummy);
-    hipLaunchKernelGGL(k_ntt_contig<false>, dim3(N / 2048, X * sel.n), dim3(256), 0, st, T, logN, dst, dst, dso, dso, sel);
+    if (N < 2048) hipLaunchKernelGGL((k_ntt_contig<false, 1024>), dim3(N / 1024, X * sel.n), dim3(256), 0, st, T, logN, dst, dst, dso, dso, sel);
+    else hipLaunchKernelGGL(k_ntt_contig<false>, dim3(N / 2048, X * sel.n), dim3(256), 0, st, T, logN, dst, dst, dso, dso, sel);
 }
 void ntt_inverse(hipStream_t st, const NttTables &T, int logN, const u64 *src, u64 *dst, size_t so, size_t dso, int X,
                  const LimbSel &sel, const ScaleSel &scale) {
     if (logN == 15 && !T.generic) return ntt15_inverse(st, T, src, dst, so, dso, X, sel, scale);
     if (logN == 16 && T.ntt16 && !T.generic) return ntt16_inverse(st, T, src, dst, so, dso, X, sel, scale);
     const int N = 1 << logN, R = N >> 8;
-    hipLaunchKernelGGL(k_ntt_contig<true>, dim3(N / 2048, X * sel.n), dim3(256), 0, st, T, logN, src, dst, so, dso, sel);
+    if (N < 2048) hipLaunchKernelGGL((k_ntt_contig<true, 1024>), dim3(N / 1024, X * sel.n), dim3(256), 0, st, T, logN, src, dst, so, dso, sel);
+    else hipLaunchKernelGGL(k_ntt_contig<true>, dim3(N / 2048, X * sel.n), dim3(256), 0, st, T, logN, src, dst, so, dso, sel);
     hipLaunchKernelGGL(k_ntt_strided<true>, dim3(8, X * sel.n), dim3(256), (size_t)R * 32 * 8, st, T, logN, dst, dst, dso,
                        dso, sel, scale);
 }

@@ -125,6 +125,18 @@ def load_library():
         "hydia_plain_db_update_device": (i32, [vp, sz, C.POINTER(_DevRows), i32]),
         "hydia_encrypt_queries_device": (i32, [vp, C.POINTER(_DevRows), vp, u64, vp]),
         "hydia_encode_queries_device": (i32, [vp, C.POINTER(_DevRows), vp]),
+        "hydia_keygen_seeded": (i32, [vp, vp, vp]),
+        "hydia_keygen_rotations_seeded": (i32, [vp, vp, vp, vp, u32]),
+        "hydia_get_key_seed": (i32, [vp, vp]),
+        "hydia_eval_key_seeded_words": (sz, [vp]),
+        "hydia_export_eval_key_seeded": (i32, [vp, i32, vp]),
+        "hydia_export_public_key_seeded": (i32, [vp, vp]),
+        "hydia_import_eval_key_seeded": (i32, [vp, i32, vp, vp]),
+        "hydia_import_public_key_seeded": (i32, [vp, vp, vp]),
+        "hydia_encrypt_query_seeded": (i32, [vp, vp, vp, vp, u64, vp]),
+        "hydia_encrypt_queries_seeded": (i32, [vp, vp, sz, vp, vp, u64, vp]),
+        "hydia_encrypt_queries_seeded_device": (i32, [vp, C.POINTER(_DevRows), vp, vp, u64, vp]),
+        "hydia_ct_expand_seeded": (i32, [vp, vp, sz, vp, u64, vp]),
         "hydia_compute_similarity_gallery_multi": (i32, [vp, vp, u32, vp]),
         "hydia_index_scenario_gallery_multi": (i32, [vp, vp, u32, vp]),
         "hydia_membership_scenario_gallery_multi": (i32, [vp, vp, u32, vp]),
@@ -465,6 +477,44 @@ class Context:
         """keygen with rotation keys for exactly `rotations` (each taken mod slots; include/hydia.h hydia_keygen_rotations)."""
         rots = np.ascontiguousarray(list(rotations), dtype=np.int32)
         _chk(self.L.hydia_keygen_rotations(self.h, _p(_seed(seed)), _p(rots) if rots.size else None, rots.size))
+
+    # ---- seeded keys (include/hydia.h): the uniform halves are the expansion of the PUBLIC a_seed; only the b halves travel
+    def keygen_seeded(self, seed=None, a_seed=None):
+        """hydia_keygen_seeded: keygen(seed) with every uniform half under the public `a_seed` (None: fresh OS entropy; read it back
+        with key_seed()).  a_seed == seed is refused (HydiaError -1)."""
+        _chk(self.L.hydia_keygen_seeded(self.h, _p(_seed(seed)), _p(_seed(a_seed))))
+
+    def keygen_rotations_seeded(self, rotations, seed=None, a_seed=None):
+        rots = np.ascontiguousarray(list(rotations), dtype=np.int32)
+        _chk(self.L.hydia_keygen_rotations_seeded(self.h, _p(_seed(seed)), _p(_seed(a_seed)), _p(rots) if rots.size else None, rots.size))
+
+    def key_seed(self):
+        """the 32 bytes of the public seed the context's seeded keys were made under (HydiaError -2 when there is none)"""
+        out = np.zeros(32, dtype=np.uint8)
+        _chk(self.L.hydia_get_key_seed(self.h, _p(out)))
+        return out.tobytes()
+
+    def export_eval_key_seeded(self, rot):
+        """the b halves [dnum][n_q+n_p][N] of a key key_seed() covers (HydiaError -2 for any other key)"""
+        out = np.zeros((self.dnum, self.nT, self.N), dtype=np.uint64)
+        assert out.size == self.L.hydia_eval_key_seeded_words(self.h)
+        _chk(self.L.hydia_export_eval_key_seeded(self.h, rot, _p(out)))
+        return out
+
+    def import_eval_key_seeded(self, rot, b, a_seed):
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        assert b.size == self.dnum * self.nT * self.N
+        _chk(self.L.hydia_import_eval_key_seeded(self.h, rot, _p(b), _p(_seed(a_seed))))
+
+    def export_public_key_seeded(self):
+        out = np.zeros((self.nQ, self.N), dtype=np.uint64)
+        _chk(self.L.hydia_export_public_key_seeded(self.h, _p(out)))
+        return out
+
+    def import_public_key_seeded(self, b, a_seed):
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        assert b.size == self.nQ * self.N
+        _chk(self.L.hydia_import_public_key_seeded(self.h, _p(b), _p(_seed(a_seed))))
 
     def import_eval_key(self, rot, data):
         data = np.ascontiguousarray(data, dtype=np.uint64)
@@ -942,11 +992,78 @@ class PlainEnroller:
         self.updateRows(self.numVectors, rows, True)
 
 
+class SeededQuery:
+    """What the receiver sends for `count` seeded queries (include/hydia.h): c0 [count][n_q][N] uint64, the PUBLIC a_seed (32 bytes)
+    and nonce0 (query i was made with nonce0 + i).  The sender expands c1 (DiagonalSender.expandQueries)."""
+
+    def __init__(self, c0, a_seed, nonce0):
+        self.c0, self.a_seed, self.nonce0 = c0, bytes(a_seed), int(nonce0)
+
+    def __len__(self):
+        return self.c0.shape[0]
+
+    @property
+    def nbytes(self):
+        """bytes on the wire: the c0 halves, the seed and the nonce"""
+        return int(self.c0.nbytes) + 32 + 8
+
+
+class SeededKeys:
+    """The receiver's seeded key set as it travels: a_seed (32 bytes, public), the public key's b half [n_q][N] and, per key id (0 = the
+    relinearisation key), the b halves [dnum][n_q+n_p][N]."""
+
+    def __init__(self, a_seed, public_key, eval_keys):
+        self.a_seed, self.public_key, self.eval_keys = bytes(a_seed), public_key, eval_keys
+
+    @property
+    def nbytes(self):
+        return 32 + int(self.public_key.nbytes) + sum(int(b.nbytes) for b in self.eval_keys.values())
+
+
 class DiagonalReceiver:
     """include/receiver_diag.h:7-16 + inherited HersReceiver::decrypt* (src/receiver/receiver_hers.cpp:26-54)."""
 
     def __init__(self, cc, num_vectors):
         self.cc, self.numVectors = cc, num_vectors
+
+    # ---- seeded secret-key queries (include/hydia.h): half the bytes of encryptQuery's ciphertext; needs the secret key
+    def encryptQuerySeeded(self, query, seed=None, a_seed=None, nonce=1):
+        """one probe (a host vector, or a 1-D tensor on the context's GPU) -> SeededQuery of count 1"""
+        if _is_device_tensor(query):
+            if query.dim() != 1:
+                raise HydiaError(-1, "hydia: encryptQuerySeeded takes one probe (encryptQueriesSeeded takes a matrix)")
+            return self.encryptQueriesSeeded(query, seed, a_seed, nonce)
+        query = np.ascontiguousarray(query, dtype=np.float64)
+        assert query.shape == (self.cc.dim,)
+        return self.encryptQueriesSeeded(query[None], seed, a_seed, nonce)
+
+    def encryptQueriesSeeded(self, matrix, seed=None, a_seed=None, nonce0=1):
+        """k probes (k x vector_dim host array, or a tensor on the context's GPU) -> ONE SeededQuery; probe i takes nonce0 + i.
+        seed=None and a_seed=None each draw fresh OS entropy per call; a pair (a_seed, nonce) must never encrypt two queries."""
+        if not isinstance(self.cc, Context):
+            raise HydiaError(-2, "hydia: seeded queries are not made on a sharded context")
+        L, key, akey = self.cc.L, _seed(seed), _seed(a_seed)
+        if _is_device_tensor(matrix):
+            d = _dev_rows(self.cc, matrix)
+            c0 = np.zeros((d.n, self.cc.nQ, self.cc.N), dtype=np.uint64)
+            _chk(L.hydia_encrypt_queries_seeded_device(self.cc.h, C.byref(d), _p(key), _p(akey), nonce0, _p(c0)))
+        else:
+            matrix = np.ascontiguousarray(matrix, dtype=np.float64)
+            assert matrix.ndim == 2 and matrix.shape[1] == self.cc.dim
+            c0 = np.zeros((matrix.shape[0], self.cc.nQ, self.cc.N), dtype=np.uint64)
+            _chk(L.hydia_encrypt_queries_seeded(self.cc.h, _p(matrix), matrix.shape[0], _p(key), _p(akey), nonce0, _p(c0)))
+        return SeededQuery(c0, akey.tobytes(), nonce0)
+
+    def exportKeysSeeded(self, rotations=None):
+        """the seeded key set of Context.keygen_seeded as SeededKeys: the public key and every evaluation key the context holds (or
+        the relinearisation key and `rotations`).  At the default parameters the full set is 6.5 GB of host memory in place of
+        13 GB; a caller short of it loops over Context.export_eval_key_seeded key by key."""
+        cc = self.cc
+        if rotations is None:
+            ids = [r for r in range(cc.slots) if cc.has_eval_key(r)]
+        else:
+            ids = [0] + [int(r) % cc.slots for r in rotations]
+        return SeededKeys(cc.key_seed(), cc.export_public_key_seeded(), {r: cc.export_eval_key_seeded(r) for r in ids})
 
     def encryptQuery(self, query, seed=None, nonce=1):
         """a 1-D tensor on the context's GPU is encrypted where it lies (the one-row case of encryptQueries)"""
@@ -1008,6 +1125,30 @@ class DiagonalSender:
         h = C.c_void_p()
         _chk(self.cc.L.hydia_encode_query(self.cc.h, _p(query), C.byref(h)))
         return Plaintext(self.cc, h)
+
+    # ---- seeded keys and queries (include/hydia.h): the sender regenerates the uniform halves on its GPU from the public seed
+    def importKeysSeeded(self, keys):
+        """DiagonalReceiver.exportKeysSeeded's SeededKeys into this context: the full public key and evaluation keys, bit for bit"""
+        self.cc.import_public_key_seeded(keys.public_key, keys.a_seed)
+        for r, b in keys.eval_keys.items():
+            self.cc.import_eval_key_seeded(r, b, keys.a_seed)
+
+    def expandQueries(self, seeded):
+        """a SeededQuery -> one ordinary Ciphertext per probe (hydia_ct_expand_seeded): what every method below takes"""
+        if not isinstance(self.cc, Context):
+            raise HydiaError(-2, "hydia: seeded queries are expanded on one context (hand the handles to the sharded sender)")
+        n = len(seeded)
+        c0 = np.ascontiguousarray(seeded.c0, dtype=np.uint64)
+        assert c0.shape == (n, self.cc.nQ, self.cc.N)
+        out = (C.c_void_p * max(n, 1))()
+        _chk(self.cc.L.hydia_ct_expand_seeded(self.cc.h, _p(c0), n, _p(_seed(seeded.a_seed)), seeded.nonce0, out))
+        return [Ciphertext(self.cc, C.c_void_p(out[i])) for i in range(n)]
+
+    def expandQuery(self, seeded):
+        """a SeededQuery of one probe -> its Ciphertext"""
+        if len(seeded) != 1:
+            raise HydiaError(-1, "hydia: expandQuery takes one probe (expandQueries takes a batch)")
+        return self.expandQueries(seeded)[0]
 
     @staticmethod
     def _no_plain(what, *queries):

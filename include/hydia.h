@@ -40,7 +40,9 @@ typedef enum {
 
 /* CKKS parameters — the knobs of /root/reference/src/main.cpp:169-173 plus VECTOR_DIM (include/config.h:30). */
 typedef struct {
-    uint32_t log_n;          /* 15  (HEStd_128_classic at this modulus size) */
+    uint32_t log_n;          /* 15  (HEStd_128_classic at this modulus size); 10 .. 16.  The small rings exist for tests.  At 10 a
+                              * context serves the receiver's side only — keys, encryption, decryption, ciphertext handles — and
+                              * key switching and a resident database answer HYDIA_ERR_ARG: they start at 11 */
     uint32_t mult_depth;     /* 11  = OpenFHEWrapper::computeRequiredDepth(5), src/openFHE_wrapper.cpp:37-40 */
     uint32_t scale_bits;     /* 45  SetScalingModSize */
     uint32_t first_mod_bits; /* 60  OpenFHE default first modulus */
@@ -469,6 +471,65 @@ int hydia_db_update_device(hydia_ctx *ctx, size_t first_vector, const hydia_dev_
 int hydia_plain_db_update_device(hydia_ctx *ctx, size_t first_vector, const hydia_dev_rows *rows, int normalise);
 int hydia_encrypt_queries_device(hydia_ctx *ctx, const hydia_dev_rows *rows, const uint8_t seed[32], uint64_t nonce0, hydia_ct **out /* n handles */);
 int hydia_encode_queries_device(hydia_ctx *ctx, const hydia_dev_rows *rows, hydia_pt **out /* n handles */);
+/* ---- seeded keys and queries (an extension; no counterpart in the reference): the uniform half of every key and of every query
+ * travels as the 32-byte seed it is the expansion of.  Half of an evaluation key (every [d][1] row), of the public key (a) and of a
+ * ciphertext made by the holder of the secret (c1) is uniform; the sampler is addressed by (seed, stream, block), so the other side
+ * regenerates those halves on its GPU, bit for bit.  At the default parameters an evaluation key shrinks from 25 165 824 to
+ * 12 582 912 bytes and a query from 6 291 456 to 3 145 728 (+ 32 bytes of seed and the nonce).
+ * CONTRACT
+ *   a_seed is PUBLIC and travels with the data.  Draw it from hydia_random_seed, independently of `seed`: a_seed == seed (32 equal
+ *     bytes) would publish the seed of the secret key and of every error term, and is refused with HYDIA_ERR_ARG before anything is
+ *     touched.
+ *   For one secret key a pair (a_seed, nonce) MUST NEVER ENCRYPT TWO QUERIES: the two c0 would differ by exactly the plaintext
+ *     difference plus noise.  This is the (seed, nonce) rule above, applied to the public seed as well.
+ *   One a_seed may cover a whole key set (the streams are addressed by key id), and it may also be the one used for queries (the
+ *     stream domains differ).
+ *   Seeded encryption needs the SECRET key: it is for the receiver of the reference's roles.  A client of a plain gallery that holds
+ *     only the public key keeps hydia_encrypt_query.
+ *   Noise: one fresh Gaussian (e0), lower than the public-key path's (e0 + e1 s + u e_pk).  No circuit privacy is claimed, as before.
+ * KEYS, receiver side
+ *   hydia_keygen_seeded / hydia_keygen_rotations_seeded   exactly hydia_keygen / hydia_keygen_rotations, except that every uniform
+ *     half is sampled under a_seed at the unchanged stream addresses; the secret and every Gaussian error stay under seed, so the
+ *     secret key is the one hydia_keygen(seed) makes.  The context remembers a_seed (hydia_get_key_seed; HYDIA_ERR_STATE when no
+ *     seeded set was made) and marks every key generated this way; any other writer of a key (hydia_import_eval_key,
+ *     hydia_import_public_key, hydia_fill_eval_keys_random, hydia_keygen, hydia_keygen_rotations, the *_seeded imports below) clears
+ *     that key's mark.
+ *   hydia_export_eval_key_seeded    the [d][0] halves of key `rot`, [dnum][n_q+n_p][N] (hydia_eval_key_seeded_words() words)
+ *   hydia_export_public_key_seeded  b, [n_q][N].  Both answer HYDIA_ERR_STATE for a key that is not marked.
+ * KEYS, sender side
+ *   hydia_import_eval_key_seeded / hydia_import_public_key_seeded   upload the b halves into their places and expand the a halves on
+ *     the GPU under a_seed; afterwards hydia_export_eval_key / hydia_export_public_key give the receiver's full key bit for bit, and
+ *     everything that follows a key write follows as for hydia_import_eval_key.  Residues are NOT range-checked, as in
+ *     hydia_import_eval_key.  The imported key is not marked seeded on the importing context.
+ * QUERIES
+ *   hydia_encrypt_query_seeded             c0 = NTT(e0 + m) - a s into HOST memory c0_out [n_q][N].  m is exactly the plaintext
+ *     hydia_encrypt_query encrypts; e0 is its error e0 (under the secret seed, at `nonce`); a limb j is the uniform stream
+ *     (domain 9, nonce, 0, j) under a_seed.  a never reaches memory on the receiver.
+ *   hydia_encrypt_queries_seeded           count probes (count x vector_dim, not written), probe i with nonce0 + i, c0_out
+ *     [count][n_q][N]; batches sized from free device memory.
+ *   hydia_encrypt_queries_seeded_device    the same from rows in device memory (hydia_dev_rows above); c0_out is host memory
+ *   hydia_ct_expand_seeded                 on the SENDER: out[i] = the ciphertext (c0[i], a(a_seed, nonce0 + i)), two polynomials on
+ *     n_q limbs at scale 2^scale_bits — an ordinary hydia_ct that every single, *_multi, *_gallery_multi, *_rotated and group entry
+ *     point takes unchanged, each freed on its own.  c0 is not range-checked.
+ *   Errors: no secret key on the encrypting context: HYDIA_ERR_STATE.  nonce0 + count > 2^40, a null pointer, a_seed == seed:
+ *     HYDIA_ERR_ARG.  count == 0: HYDIA_OK and nothing is written.
+ * NOT seeded: the switching key of hydia_db_rekey, hydia_group_keygen, approaches 1 - 4, database enrolment. */
+int hydia_keygen_seeded(hydia_ctx *ctx, const uint8_t seed[32], const uint8_t a_seed[32]);
+int hydia_keygen_rotations_seeded(hydia_ctx *ctx, const uint8_t seed[32], const uint8_t a_seed[32], const int32_t *rots, uint32_t n);
+int hydia_get_key_seed(const hydia_ctx *ctx, uint8_t out[32]);
+size_t hydia_eval_key_seeded_words(const hydia_ctx *ctx);
+int hydia_export_eval_key_seeded(hydia_ctx *ctx, int rot, uint64_t *b_out /* [dnum][n_q+n_p][N] */);
+int hydia_export_public_key_seeded(hydia_ctx *ctx, uint64_t *b_out /* [n_q][N] */);
+int hydia_import_eval_key_seeded(hydia_ctx *ctx, int rot, const uint64_t *b /* [dnum][n_q+n_p][N] */, const uint8_t a_seed[32]);
+int hydia_import_public_key_seeded(hydia_ctx *ctx, const uint64_t *b /* [n_q][N] */, const uint8_t a_seed[32]);
+int hydia_encrypt_query_seeded(hydia_ctx *ctx, const double *query /* vector_dim */, const uint8_t seed[32], const uint8_t a_seed[32],
+                               uint64_t nonce, uint64_t *c0_out /* [n_q][N] host */);
+int hydia_encrypt_queries_seeded(hydia_ctx *ctx, const double *queries /* count x vector_dim */, size_t count, const uint8_t seed[32],
+                                 const uint8_t a_seed[32], uint64_t nonce0, uint64_t *c0_out /* [count][n_q][N] host */);
+int hydia_encrypt_queries_seeded_device(hydia_ctx *ctx, const hydia_dev_rows *rows, const uint8_t seed[32], const uint8_t a_seed[32],
+                                        uint64_t nonce0, uint64_t *c0_out /* [n][n_q][N] host */);
+int hydia_ct_expand_seeded(hydia_ctx *ctx, const uint64_t *c0 /* [count][n_q][N] host */, size_t count, const uint8_t a_seed[32],
+                           uint64_t nonce0, hydia_ct **out /* count handles */);
 /* OpenFHEWrapper::chebyshevCompare (src/openFHE_wrapper.cpp:143-185) on every ciphertext of the batch */
 int hydia_chebyshev_compare(hydia_ctx *ctx, const hydia_ct *in, double delta, size_t sign_depth, hydia_ct **out);
 /* multi-GPU membership tail: sum the batch into one ciphertext, then EvalSum over all slots (:46-47) */

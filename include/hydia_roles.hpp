@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <iostream>
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -109,6 +110,21 @@ class CryptoContextImpl {
         if (!check(group ? hydia_group_keygen(group, seed) : hydia_keygen(h, seed), "key generation")) return KeyPair{};
         return KeyPair{PublicKey{this}, PrivateKey{this}};
     }
+    // KeyGen with every uniform half sampled under a PUBLIC expansion seed (hydia_keygen_seeded; no counterpart in the reference): the
+    // receiver then ships half keys (DiagonalReceiver::exportKeysSeeded).  aSeed32 == nullptr draws the public seed from the OS too,
+    // independently of the secret one.  Not on a sharded context: an error, empty
+    KeyPair KeyGenSeeded(const uint8_t *seed32 = nullptr, const uint8_t *aSeed32 = nullptr) {
+        if (group) {
+            last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: key generation: a seeded key set is generated on the receiver's own context" << std::endl;
+            return KeyPair{};
+        }
+        uint8_t seed[32], aSeed[32];
+        role_seed(seed, seed32);
+        role_seed(aSeed, aSeed32);
+        if (!check(hydia_keygen_seeded(h, seed, aSeed), "key generation")) return KeyPair{};
+        return KeyPair{PublicKey{this}, PrivateKey{this}};
+    }
     // approach 1's key set: secret, public, relinearisation and rotation keys {2^k} u {batch - 2^k} (hydia_base_rotations) — what
     // src/main.cpp:195-206 generates for binaryRotate; hydia_keygen's set would not fit a 2^16 ring
     KeyPair KeyGenBaseline(const uint8_t *seed32 = nullptr) {
@@ -195,6 +211,23 @@ struct DeviceRows {
     hydia_dev_rows d;
     DeviceRows(const void *ptr, hydia_dtype dtype, size_t n, size_t rowStride, void *stream = nullptr) : d{ptr, dtype, n, rowStride, stream} {}
     size_t size() const { return d.n; }
+};
+// seeded queries and keys as they travel (hydia.h, "seeded keys and queries"): the uniform halves are the expansion of the PUBLIC
+// aSeed, so only the other halves are carried.  SeededQuery: c0 [count][n_q][N]; query i was made with nonce0 + i
+struct SeededQuery {
+    std::vector<uint64_t> c0;
+    uint8_t aSeed[32] = {};
+    uint64_t nonce0 = 0;
+    size_t count = 0;
+    size_t nbytes() const { return c0.size() * sizeof(uint64_t) + 32 + sizeof(uint64_t); }
+    explicit operator bool() const { return count > 0 && !c0.empty(); }
+};
+// SeededKeys: the public key's b [n_q][N] and per key id (0 = relinearisation) the b halves [dnum][n_q+n_p][N]
+struct SeededKeys {
+    uint8_t aSeed[32] = {};
+    std::vector<uint64_t> publicKey;
+    std::map<int, std::vector<uint64_t>> evalKeys;
+    explicit operator bool() const { return !publicKey.empty(); }
 };
 inline std::vector<Ciphertext> split_batch(const CryptoContext &cc, hydia_ct *h) {
     std::vector<Ciphertext> v;
@@ -312,6 +345,49 @@ class DiagonalSender : public Sender {
         std::vector<std::vector<Ciphertext>> r;
         for (hydia_ct *h : run_multi(queryCiphers, hydia_index_scenario_gallery_multi, "indexScenarioGalleryMulti")) r.push_back(split_batch(cc, h));
         return r;
+    }
+    // Seeded keys and queries (an extension; hydia.h): the sender regenerates the uniform halves on its GPU from the public seed.
+    // importKeysSeeded takes DiagonalReceiver::exportKeysSeeded's set; expandQuery / expandQueries turn a SeededQuery into ordinary
+    // queryCiphers, one per probe, that every method above takes.  Not on a sharded context: an error, false / empty
+    bool importKeysSeeded(const SeededKeys &keys) {
+        if (cc->group || !keys) {
+            cc->last_status = cc->group ? HYDIA_ERR_STATE : HYDIA_ERR_ARG;
+            std::cerr << "Error: importKeysSeeded: " << (cc->group ? "seeded keys are imported into one context" : "empty key set") << std::endl;
+            return false;
+        }
+        const size_t pk_words = (size_t)cc->info.n_q * cc->info.n, key_words = hydia_eval_key_seeded_words(cc->h);
+        bool sized = keys.publicKey.size() == pk_words;
+        for (auto &kv : keys.evalKeys) sized = sized && kv.second.size() == key_words;
+        if (!sized) {
+            cc->last_status = HYDIA_ERR_ARG;
+            std::cerr << "Error: importKeysSeeded: a half key of another size than this context's" << std::endl;
+            return false;
+        }
+        if (!cc->check(hydia_import_public_key_seeded(cc->h, keys.publicKey.data(), keys.aSeed), "importKeysSeeded")) return false;
+        for (auto &kv : keys.evalKeys)
+            if (!cc->check(hydia_import_eval_key_seeded(cc->h, kv.first, kv.second.data(), keys.aSeed), "importKeysSeeded")) return false;
+        return true;
+    }
+    std::vector<std::vector<Ciphertext>> expandQueries(const SeededQuery &q) {
+        if (cc->group || !q || q.c0.size() != q.count * (size_t)cc->info.n_q * cc->info.n) {
+            cc->last_status = cc->group ? HYDIA_ERR_STATE : HYDIA_ERR_ARG;
+            std::cerr << "Error: expandQueries: " << (cc->group ? "seeded queries are expanded on one context" : "c0 does not hold count polynomials [n_q][N]") << std::endl;
+            return {};
+        }
+        std::vector<hydia_ct *> h(q.count, nullptr);
+        if (!cc->check(hydia_ct_expand_seeded(cc->h, q.c0.data(), q.count, q.aSeed, q.nonce0, h.data()), "expandQueries")) return {};
+        std::vector<std::vector<Ciphertext>> r;
+        for (size_t i = 0; i < q.count; i++) r.push_back(split_batch(cc, h[i]));
+        return r;
+    }
+    std::vector<Ciphertext> expandQuery(const SeededQuery &q) {
+        if (q.count != 1) {
+            cc->last_status = HYDIA_ERR_ARG;
+            std::cerr << "Error: expandQuery takes one probe (expandQueries takes a batch)" << std::endl;
+            return {};
+        }
+        std::vector<std::vector<Ciphertext>> r = expandQueries(q);
+        return r.empty() ? std::vector<Ciphertext>{} : r[0];
     }
     // A plain query (an extension; hydia.h): the sender knows the probe, the database (kinds 5 / 6) stays encrypted and so does every
     // result.  encodeQuery makes exactly the plaintext DiagonalReceiver::encryptQuery encrypts — no seed, no key; the overloads return
@@ -510,6 +586,51 @@ class DiagonalReceiver : public HersReceiver {
         for (size_t i = 0; i < rows.size(); i++) r.push_back(split_batch(cc, h[i]));
         return r;
     }
+    // Seeded secret-key queries (hydia_encrypt_queries_seeded; hydia.h): half the bytes of encryptQuery's ciphertext — c0 and the
+    // public seed c1 is the expansion of.  The error term comes from this receiver's secret sampler key and its next nonces, like
+    // encryptQuery's; the PUBLIC seed is drawn fresh from the OS per call unless aSeed32 is given (a pair (aSeed, nonce) must never
+    // encrypt two queries).  Needs the secret key.  Not on a sharded context: an error, an empty record
+    SeededQuery encryptQueriesSeeded(const std::vector<std::vector<double>> &queries, const uint8_t *aSeed32 = nullptr) {
+        const size_t dim = cc->info.vector_dim;
+        std::vector<double> flat(queries.size() * dim, 0.0);
+        for (size_t i = 0; i < queries.size(); i++)
+            for (size_t j = 0; j < dim && j < queries[i].size(); j++) flat[i * dim + j] = queries[i][j];
+        SeededQuery q;
+        if (!seeded_begin(q, queries.size(), aSeed32, "encryptQueriesSeeded")) return {};
+        if (!cc->check(hydia_encrypt_queries_seeded(cc->h, flat.data(), q.count, seed, q.aSeed, q.nonce0, q.c0.data()), "encryptQueriesSeeded")) return {};
+        nonce += q.count;
+        return q;
+    }
+    SeededQuery encryptQuerySeeded(std::vector<double> query, const uint8_t *aSeed32 = nullptr) {
+        return encryptQueriesSeeded(std::vector<std::vector<double>>{std::move(query)}, aSeed32);
+    }
+    SeededQuery encryptQueriesSeeded(const DeviceRows &rows, const uint8_t *aSeed32 = nullptr) {
+        SeededQuery q;
+        if (!seeded_begin(q, rows.size(), aSeed32, "encryptQueriesSeeded")) return {};
+        if (!cc->check(hydia_encrypt_queries_seeded_device(cc->h, &rows.d, seed, q.aSeed, q.nonce0, q.c0.data()), "encryptQueriesSeeded")) return {};
+        nonce += q.count;
+        return q;
+    }
+    // the seeded key set of CryptoContextImpl::KeyGenSeeded as it travels: the public key's b and the b halves of the relinearisation
+    // key and of every rotation key the context holds (half of what hydia_export_eval_key would ship).  Empty on failure
+    SeededKeys exportKeysSeeded() {
+        SeededKeys k;
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: exportKeysSeeded: a seeded key set lives on the receiver's own context" << std::endl;
+            return {};
+        }
+        if (!cc->check(hydia_get_key_seed(cc->h, k.aSeed), "exportKeysSeeded")) return {};
+        k.publicKey.resize((size_t)cc->info.n_q * cc->info.n);
+        if (!cc->check(hydia_export_public_key_seeded(cc->h, k.publicKey.data()), "exportKeysSeeded")) return {};
+        for (int r = 0; r < (int)cc->info.slots; r++) {
+            if (!hydia_has_eval_key(cc->h, r)) continue;
+            std::vector<uint64_t> &b = k.evalKeys[r];
+            b.resize(hydia_eval_key_seeded_words(cc->h));
+            if (!cc->check(hydia_export_eval_key_seeded(cc->h, r, b.data()), "exportKeysSeeded")) return {};
+        }
+        return k;
+    }
     // The switching key of a re-keyed database (hydia_keygen_switch; no counterpart in the reference): from the OLD receiver's secret
     // (oldSecret, [n_q+n_p][N] as hydia_export_secret_key gives it) to THIS receiver's, for DiagonalEnroller::rekeyDB.  Treat it like an
     // evaluation key.  seed32 == nullptr draws a fresh sampler key from the OS (use a fresh one per switching key).  Empty on failure.
@@ -526,6 +647,21 @@ class DiagonalReceiver : public HersReceiver {
         std::vector<uint64_t> key(hydia_switch_key_words(cc->h));
         if (!cc->check(hydia_keygen_switch(cc->h, oldSecret.data(), s, key.data()), "genSwitchKey")) return {};
         return key;
+    }
+
+  private:
+    // the frame of a SeededQuery of `count` probes: the public seed, this receiver's next nonce, room for c0
+    bool seeded_begin(SeededQuery &q, size_t count, const uint8_t *aSeed32, const char *what) {
+        if (cc->group || count == 0) {
+            cc->last_status = cc->group ? HYDIA_ERR_STATE : HYDIA_ERR_ARG;
+            std::cerr << "Error: " << what << ": " << (cc->group ? "seeded queries are not made on a sharded context" : "no probe") << std::endl;
+            return false;
+        }
+        role_seed(q.aSeed, aSeed32);
+        q.nonce0 = nonce + 1;
+        q.count = count;
+        q.c0.resize(count * (size_t)cc->info.n_q * cc->info.n);
+        return true;
     }
 };
 
