@@ -1114,6 +1114,8 @@ static int check_dev_rows(hydia_ctx *ctx, const hydia_dev_rows *rows, DevRows &o
     REQUIRE(at.device == ctx->cx.device, "rows lie in the memory of another GPU than the context's");
     return HYDIA_OK;
 }
+// (the same checks for wire.cpp's hydia_encrypt_queries_seeded_wire_device; internal, not declared in include/hydia.h)
+int hydia_check_dev_rows(hydia_ctx *ctx, const hydia_dev_rows *rows, DevRows *out) { return check_dev_rows(ctx, rows, *out); }
 #define CHECK_DEV_ROWS(r)                              \
     REQUIRE(ctx && rows, "null argument");             \
     use_device(ctx);                                   \

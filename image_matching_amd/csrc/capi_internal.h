@@ -63,3 +63,5 @@ inline void use_device(const hydia_ctx *ctx) {
     if (ctx) (void)hipSetDevice(ctx->cx.device);
 }
 hydia::Params hydia_to_params(const hydia_params *p);
+// capi.cpp's checks of rows in device memory (pointer, type, stride, GPU, group shard): HYDIA_OK and *out filled, or the code recorded
+extern "C" int hydia_check_dev_rows(hydia_ctx *ctx, const hydia_dev_rows *rows, hydia::DevRows *out);

@@ -178,6 +178,29 @@ void client_import_public_key_seeded(Context &cx, const u64 *b, const uint8_t a_
     cx.sync();
     cx.pk_seeded = false;
 }
+// A key that arrived as a wire message (wire.cpp) and passed its range check: d_src, its unpacked rows in device memory, into its place.
+// a_seed == nullptr: the whole key ([dnum][2][nT][N], the public key [2][nQ][N]); otherwise d_src holds the b halves ([dnum][nT][N],
+// [nQ][N]) and the a halves are expanded as the two imports above expand them.  What follows a key write follows as for them
+void client_install_eval_key(Context &cx, int rot, const u64 *d_src, const uint8_t *a_seed) {
+    const size_t half = (size_t)cx.nT * cx.N * sizeof(u64);
+    u64 *dst = cx.eval_key_storage(rot);
+    if (!a_seed) {
+        HIP_CHECK(hipMemcpyAsync(dst, d_src, 2 * half * (size_t)cx.prm.dnum, hipMemcpyDeviceToDevice, cx.stream));
+    } else {
+        HIP_CHECK(hipMemcpy2DAsync(dst, 2 * half, d_src, half, half, (size_t)cx.prm.dnum, hipMemcpyDeviceToDevice, cx.stream));
+        evk_sample_a(cx, make_key(a_seed), (u64)rot, dst);
+    }
+    cx.sync();
+}
+void client_install_public_key(Context &cx, const u64 *d_src, const uint8_t *a_seed) {
+    if (cx.keys_borrowed) throw StateError("hydia: this context borrows its keys from another context (re-key the owner)");
+    const size_t half = (size_t)cx.nQ * cx.N * sizeof(u64);
+    if (!cx.d_pk) HIP_CHECK(hipMalloc((void **)&cx.d_pk, 2 * half));
+    HIP_CHECK(hipMemcpyAsync(cx.d_pk, d_src, a_seed ? half : 2 * half, hipMemcpyDeviceToDevice, cx.stream));
+    if (a_seed) pk_sample_a(cx, make_key(a_seed), cx.d_pk);
+    cx.sync();
+    cx.pk_seeded = false;
+}
 
 // The switching key of a re-keyed database (Context::db_rekey): from the OLD receiver's secret (old_secret, host memory, [nT][N] in
 // evaluation form as hydia_export_secret_key gives it; its Q limbs are read) to THIS context's secret — gen_evk's key with the
@@ -578,8 +601,11 @@ std::vector<Ct> client_encode_queries_device(Context &cx, const DevRows &rows) {
 
 // Seeded queries: n probes (src: normalised host rows, or rows in device memory that k_rows_widen normalises) -> their c0 halves in
 // host memory, c0_out [n][nQ][N]; probe i takes nonce0 + i.  queries_device's passes — ONE k_query_tile and ONE encrypt_sym_device over
-// what free HBM holds of the encoder's temporaries, one sampled polynomial, its limbs and the output — then one copy out per pass
-static void queries_seeded(Context &cx, const RowSource &src, size_t n, const ChaChaKey &key, const ChaChaKey &akey, u64 nonce0, u64 *c0_out) {
+// what free HBM holds of the encoder's temporaries, one sampled polynomial, its limbs and the output — then one copy out per pass.
+// wire != nullptr: c0_out is the payload of a wire message (wire_format.h) — every pass's c0 goes through k_wire_pack and leaves the
+// GPU packed, wire->off[nQ] words per probe
+static void queries_seeded(Context &cx, const RowSource &src, size_t n, const ChaChaKey &key, const ChaChaKey &akey, u64 nonce0, u64 *c0_out,
+                           const WireRows *wire = nullptr) {
     if (!cx.d_sk) throw StateError("hydia: secret key not loaded (seeded encryption is the secret-key holder's; hydia_encrypt_query takes the public key)");
     const int dim = cx.prm.dim, Nh = cx.slots;
     const size_t elems = (size_t)cx.nQ * cx.N, poly = elems * sizeof(u64);
@@ -591,37 +617,52 @@ static void queries_seeded(Context &cx, const RowSource &src, size_t n, const Ch
     double *d_q = (double *)cx.pool.get(sizeof(double) * pass * dim);
     double *d_slots = (double *)cx.pool.get(sizeof(double) * pass * Nh);
     u64 *d_out = cx.pool.get(pass * poly);
+    const size_t packed = wire ? (size_t)wire->off[cx.nQ] : 0;  // words per probe on the wire
+    u64 *d_packed = wire ? cx.pool.get(pass * packed * sizeof(u64)) : nullptr;
     for (size_t q0 = 0; q0 < n; q0 += pass) {
         const int Q = (int)std::min(pass, n - q0);
         src.stage(cx, q0, (size_t)Q, d_q);
         hc::query_tile(cx.stream, d_q, Q, dim, Nh, d_slots);
         encrypt_sym_device(cx, d_slots, Q, key, akey, nonce0 + q0, d_out);
-        HIP_CHECK(hipMemcpyAsync(c0_out + q0 * elems, d_out, (size_t)Q * poly, hipMemcpyDeviceToHost, cx.stream));
+        if (wire) {
+            cx.timer_begin("k_wire_pack");
+            hc::wire_pack(cx.stream, cx.d_mod, cx.N, d_out, elems, 0, (size_t)Q, 1, cx.nQ, *wire, d_packed);
+            cx.timer_end("k_wire_pack");
+            HIP_CHECK(hipMemcpyAsync(c0_out + q0 * packed, d_packed, (size_t)Q * packed * sizeof(u64), hipMemcpyDeviceToHost, cx.stream));
+        } else {
+            HIP_CHECK(hipMemcpyAsync(c0_out + q0 * elems, d_out, (size_t)Q * poly, hipMemcpyDeviceToHost, cx.stream));
+        }
         cx.sync();  // d_out is written again by the next pass; the caller's rows and c0_out are host memory
     }
+    if (d_packed) cx.pool.put(d_packed);
     cx.pool.put(d_out);
     cx.pool.put((u64 *)d_slots);
     cx.pool.put((u64 *)d_q);
 }
 void client_encrypt_queries_seeded(Context &cx, const double *queries, size_t n, const uint8_t seed[32], const uint8_t a_seed[32], uint64_t nonce0,
-                                   u64 *c0_out) {
+                                   u64 *c0_out, const WireRows *wire) {
     const int dim = cx.prm.dim;
     std::vector<double> qn(queries, queries + n * (size_t)dim);
     for (size_t v = 0; v < n; v++) normalize(qn.data() + v * dim, dim);
     RowSource src;
     src.host = qn.data();
-    queries_seeded(cx, src, n, make_key(seed), make_key(a_seed), nonce0, c0_out);
+    queries_seeded(cx, src, n, make_key(seed), make_key(a_seed), nonce0, c0_out, wire);
 }
 void client_encrypt_queries_seeded_device(Context &cx, const DevRows &rows, const uint8_t seed[32], const uint8_t a_seed[32], uint64_t nonce0,
-                                          u64 *c0_out) {
+                                          u64 *c0_out, const WireRows *wire) {
     RowSource src;
     src.dev = &rows;
     src.normalise = 1;
     wait_for_producer(cx, rows.stream);
-    queries_seeded(cx, src, rows.n, make_key(seed), make_key(a_seed), nonce0, c0_out);
+    queries_seeded(cx, src, rows.n, make_key(seed), make_key(a_seed), nonce0, c0_out, wire);
 }
 // the sender's side: handle i = (c0[i], a) with a limb j = the uniform stream (SYM_A, nonce0 + i, 0, j) under a_seed — the launch of
 // sample_uniform whose thread k_enc_sym repeats — an ordinary fresh ciphertext [1][2][nQ][N] at scale 2^scale_bits
+// (the same launch on its own, for a c0 that was unpacked from a wire message straight into its handle: dst = the handle's c1 [nQ][N])
+void client_sample_query_a(Context &cx, const uint8_t a_seed[32], uint64_t nonce, u64 *dst) {
+    hc::sample_uniform(cx.stream, make_key(a_seed), cx.d_mod, cx.N, HY_STREAM(HY_DOM_SYM_A, nonce, 0, 0), 1ull, 0, dst, (size_t)cx.N, 0,
+                       cx.sel_q(cx.nQ), 1);
+}
 std::vector<Ct> client_expand_seeded(Context &cx, const u64 *c0, size_t n, const uint8_t a_seed[32], uint64_t nonce0) {
     const size_t elems = (size_t)cx.nQ * cx.N;
     const ChaChaKey akey = make_key(a_seed);

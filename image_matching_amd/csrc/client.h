@@ -1,6 +1,7 @@
 // image_matching_amd/csrc/client.h — receiver / enroller / key-generation engines (GPU): sampling, canonical-embedding
 // encode/decode, public-key encryption, decryption, on-GPU enrolment into the HBM-resident diagonal layout.
 #pragma once
+#include "client_kernels.h"
 #include "hydia_core.h"
 
 namespace hydia {
@@ -15,12 +16,20 @@ void client_keygen_rotations(Context &cx, const uint8_t seed[32], const std::vec
 // places, the a halves expanded on the GPU under a_seed by key generation's own sample_uniform launch.  Not range-checked, not marked
 void client_import_eval_key_seeded(Context &cx, int rot, const u64 *b, const uint8_t a_seed[32]);
 void client_import_public_key_seeded(Context &cx, const u64 *b, const uint8_t a_seed[32]);
+// a key from a wire message that passed its range check: d_src = its unpacked rows in DEVICE memory; a_seed == nullptr the whole key,
+// otherwise the b halves, with the a halves expanded as the seeded imports expand them
+void client_install_eval_key(Context &cx, int rot, const u64 *d_src, const uint8_t *a_seed);
+void client_install_public_key(Context &cx, const u64 *d_src, const uint8_t *a_seed);
 // seeded secret-key queries (k_enc_sym): c0 = NTT(e0 + m) - a s of probe i (normalised, tiled, encoded as client_encrypt_query does;
 // e0 under seed, a under the public a_seed, nonce nonce0 + i) into HOST memory c0_out [n][nQ][N].  StateError without a secret key
 void client_encrypt_queries_seeded(Context &cx, const double *queries /* n x vector_dim */, size_t n, const uint8_t seed[32],
-                                   const uint8_t a_seed[32], uint64_t nonce0, u64 *c0_out);
+                                   const uint8_t a_seed[32], uint64_t nonce0, u64 *c0_out, const WireRows *wire = nullptr);
+// (wire != nullptr, here and in the _device twin: c0_out is the payload of a wire message — c0 leaves the GPU packed by k_wire_pack,
+// wire->off[nQ] words per probe)
 // and the sender's expansion: handle i = (c0[i], a(a_seed, nonce0 + i)), an ordinary [1][2][nQ][N] ciphertext at scale 2^scale_bits
 std::vector<Ct> client_expand_seeded(Context &cx, const u64 *c0, size_t n, const uint8_t a_seed[32], uint64_t nonce0);
+// c1 of seeded query `nonce` alone, enqueued on the stream: dst [nQ][N] in device memory (wire.cpp: c0 was unpacked into its handle)
+void client_sample_query_a(Context &cx, const uint8_t a_seed[32], uint64_t nonce, u64 *dst);
 // the switching key of Context::db_rekey: old_secret (host, [nT][N], evaluation form) -> this context's secret, into out (host,
 // [dnum][2][nT][N]); sampler streams of key id HY_EVK_ID_SWITCH.  StateError without a secret; the context's own keys are untouched
 void client_keygen_switch(Context &cx, const u64 *old_secret, const uint8_t seed[32], u64 *out);
@@ -64,7 +73,7 @@ std::vector<Ct> client_encrypt_queries_device(Context &cx, const DevRows &rows, 
 std::vector<Ct> client_encode_queries_device(Context &cx, const DevRows &rows);
 // client_encrypt_queries_seeded from rows in device memory (one k_rows_widen and one k_query_tile per pass); c0_out is host memory
 void client_encrypt_queries_seeded_device(Context &cx, const DevRows &rows, const uint8_t seed[32], const uint8_t a_seed[32], uint64_t nonce0,
-                                          u64 *c0_out);
+                                          u64 *c0_out, const WireRows *wire = nullptr);
 // HERS (approach 4): column-packed enrolment and the vector_dim broadcast query ciphertexts
 void client_hers_enroll(Context &cx, double *db, size_t n, const uint8_t seed[32]);
 Ct client_hers_encrypt_query(Context &cx, const double *query, const uint8_t seed[32], uint64_t nonce0);

@@ -61,3 +61,18 @@ void rows_widen(hipStream_t st, const void *src, int dtype, size_t n, int dim, s
 // slots[q][i] = rows[q][i mod dim] for Q probes (Q <= 65535): the tiling of DiagonalReceiver::encryptQuery
 void query_tile(hipStream_t st, const double *rows, int Q, int dim, int Nh, double *slots);
 }  // namespace hc
+
+// ---- wire_kernels.hip: the wire format's rows (wire_format.h).  off[j] = the 64-bit word at which limb j's packed row starts inside one
+// polynomial's run of rows, off[limbs] = the words of one polynomial: N / 64 granules of w_j words each
+struct WireRows {
+    unsigned off[HY_MAX_MODS + 1];
+};
+namespace hc {
+WireRows wire_rows(const u64 *moduli, int N, int nl);  // limb j <-> moduli[j] (the context's chain: limb j is modulus j of `mod` below)
+// rows [items][npoly][nl] of N u64 residues at src + item * item_stride + poly * poly_stride + limb * N <-> packed rows back to back,
+// dst [items][npoly][R.off[nl]] words.  unpack: *flag := 1 when a residue is >= its modulus (the caller clears it beforehand)
+void wire_pack(hipStream_t st, const ModC *mod, int N, const u64 *src, size_t item_stride, size_t poly_stride, size_t items, int npoly,
+               int nl, const WireRows &R, u64 *dst);
+void wire_unpack_check(hipStream_t st, const ModC *mod, int N, const u64 *src, u64 *dst, size_t item_stride, size_t poly_stride, size_t items,
+                       int npoly, int nl, const WireRows &R, unsigned *flag);
+}  // namespace hc

@@ -36,6 +36,12 @@ class _Info(C.Structure):
         ("delta", C.c_double)]
 
 
+class _WireInfo(C.Structure):  # hydia_wire_info
+    _fields_ = [(n, C.c_uint32) for n in ("type", "log_n", "n_polys", "n_limbs", "rot", "reserved")] + [
+        ("count", C.c_uint64), ("scale", C.c_double), ("a_seed", C.c_uint8 * 32), ("nonce0", C.c_uint64), ("header_bytes", C.c_uint64),
+        ("payload_bytes", C.c_uint64)]
+
+
 def lib_path():
     # HYDIA_LIBPATH: an alternative build of the same library (kernel A/B experiments, tools/ubench)
     return os.environ.get("HYDIA_LIBPATH") or os.path.join(_HERE, "libhydia.so")
@@ -137,6 +143,18 @@ def load_library():
         "hydia_encrypt_queries_seeded": (i32, [vp, vp, sz, vp, vp, u64, vp]),
         "hydia_encrypt_queries_seeded_device": (i32, [vp, C.POINTER(_DevRows), vp, vp, u64, vp]),
         "hydia_ct_expand_seeded": (i32, [vp, vp, sz, vp, u64, vp]),
+        "hydia_wire_peek": (i32, [vp, sz, C.POINTER(_WireInfo)]),
+        "hydia_wire_ct_bytes": (sz, [vp, u64, u32, u32, i32]),
+        "hydia_wire_eval_key_bytes": (sz, [vp, i32]),
+        "hydia_wire_public_key_bytes": (sz, [vp, i32]),
+        "hydia_ct_to_wire": (i32, [vp, vp, vp, sz, C.POINTER(sz)]),
+        "hydia_ct_from_wire": (i32, [vp, vp, sz, vp, sz, C.POINTER(sz)]),
+        "hydia_encrypt_queries_seeded_wire": (i32, [vp, vp, sz, vp, vp, u64, vp, sz, C.POINTER(sz)]),
+        "hydia_encrypt_queries_seeded_wire_device": (i32, [vp, C.POINTER(_DevRows), vp, vp, u64, vp, sz, C.POINTER(sz)]),
+        "hydia_key_to_wire": (i32, [vp, i32, i32, vp, sz, C.POINTER(sz)]),
+        "hydia_key_from_wire": (i32, [vp, vp, sz, C.POINTER(i32)]),
+        "hydia_keys_save": (i32, [vp, C.c_char_p, i32]),
+        "hydia_keys_load": (i32, [vp, C.c_char_p]),
         "hydia_compute_similarity_gallery_multi": (i32, [vp, vp, u32, vp]),
         "hydia_index_scenario_gallery_multi": (i32, [vp, vp, u32, vp]),
         "hydia_membership_scenario_gallery_multi": (i32, [vp, vp, u32, vp]),
@@ -360,8 +378,37 @@ def describe_params(params=None):
     return d, mod[:nt].copy(), roots[:nt].copy()
 
 
+def wire_peek(message):
+    """Host-only (hydia_wire_peek): the context-free validation of a wire message and what its header says — a dict of type, log_n,
+    count, n_polys, n_limbs, rot, scale, a_seed (32 bytes), nonce0, header_bytes, payload_bytes.  A malformed message: HydiaError(-1)
+    naming the field."""
+    raw = np.frombuffer(bytes(message), dtype=np.uint8)
+    info = _WireInfo()
+    _chk(load_library().hydia_wire_peek(_p(raw) if raw.size else None, raw.size, C.byref(info)))
+    d = {k: getattr(info, k) for k, _ in _WireInfo._fields_}
+    d["a_seed"] = bytes(info.a_seed)
+    return d
+
+
+def _wire_out(call):
+    """call(buf, cap, written) -> bytes: the size first (a NULL buffer answers HYDIA_ERR_ARG with the need), then the message"""
+    n = C.c_size_t()
+    code = call(None, 0, C.byref(n))
+    if code != 0 and n.value == 0:
+        _chk(code)
+    if n.value == 0:
+        return b""
+    buf = np.empty(n.value, dtype=np.uint8)
+    _chk(call(_p(buf), buf.size, C.byref(n)))
+    return buf[:n.value].tobytes()
+
+
 class Ciphertext:
     """Handle of a batch of ciphertexts resident in HBM (Ciphertext<DCRTPoly> / vector<Ciphertext<DCRTPoly>>)."""
+
+    def to_wire(self):
+        """the batch as one wire message (hydia_ct_to_wire): packed on the GPU, residues in the bit length of their modulus"""
+        return _wire_out(lambda buf, cap, n: self.cc.L.hydia_ct_to_wire(self.cc.h, self.h, buf, cap, n))
 
     def __init__(self, cc, h):
         self.cc, self.h = cc, h
@@ -563,6 +610,48 @@ class Context:
 
     def has_eval_key(self, rot):
         return bool(self.L.hydia_has_eval_key(self.h, rot))
+
+    # ---- wire messages (include/hydia.h): packed, range-checked, self-describing; the checked path for data from outside
+    def ct_from_wire(self, message):
+        """a type 1 message -> ONE Ciphertext batch; a type 2 message (seeded queries) -> a list of single-ciphertext handles, exactly
+        those hydia_ct_expand_seeded makes.  A malformed or non-canonical message: HydiaError(-1), nothing stays allocated."""
+        raw = np.frombuffer(bytes(message), dtype=np.uint8)
+        info = wire_peek(message)
+        cap = 1 if info["type"] == 1 else info["count"]
+        out = (C.c_void_p * cap)()
+        n = C.c_size_t()
+        _chk(self.L.hydia_ct_from_wire(self.h, _p(raw), raw.size, out, cap, C.byref(n)))
+        cts = [Ciphertext(self, C.c_void_p(out[i])) for i in range(n.value)]
+        return cts[0] if info["type"] == 1 else cts
+
+    def key_to_wire(self, rot, seeded=False):
+        """key `rot` (-1: the public key, 0: relinearisation, r: rotation r) as one wire message; seeded: the b halves and the context's
+        public key seed (HydiaError(-2) for a key hydia_keygen_seeded did not make)"""
+        return _wire_out(lambda buf, cap, n: self.L.hydia_key_to_wire(self.h, rot, int(bool(seeded)), buf, cap, n))
+
+    def key_from_wire(self, message):
+        """installs the key a message carries after its residues passed the range check; returns its id (-1: the public key)"""
+        raw = np.frombuffer(bytes(message), dtype=np.uint8)
+        rot = C.c_int()
+        _chk(self.L.hydia_key_from_wire(self.h, _p(raw) if raw.size else None, raw.size, C.byref(rot)))
+        return rot.value
+
+    def keys_save(self, path, seeded=False):
+        """the public key and every evaluation key the context holds as a key-set file of wire messages"""
+        _chk(self.L.hydia_keys_save(self.h, os.fsencode(path), int(bool(seeded))))
+
+    def keys_load(self, path):
+        """NOT transactional: a refused file (HydiaError(-1) naming the message) leaves the keys of earlier messages installed"""
+        _chk(self.L.hydia_keys_load(self.h, os.fsencode(path)))
+
+    def wire_ct_bytes(self, count, n_polys, n_limbs, seeded=False):
+        return int(self.L.hydia_wire_ct_bytes(self.h, count, n_polys, n_limbs, int(bool(seeded))))
+
+    def wire_eval_key_bytes(self, seeded=False):
+        return int(self.L.hydia_wire_eval_key_bytes(self.h, int(bool(seeded))))
+
+    def wire_public_key_bytes(self, seeded=False):
+        return int(self.L.hydia_wire_public_key_bytes(self.h, int(bool(seeded))))
 
     # ---- ciphertexts
     def import_ct(self, data, scale):
@@ -1054,6 +1143,45 @@ class DiagonalReceiver:
             _chk(L.hydia_encrypt_queries_seeded(self.cc.h, _p(matrix), matrix.shape[0], _p(key), _p(akey), nonce0, _p(c0)))
         return SeededQuery(c0, akey.tobytes(), nonce0)
 
+    # ---- wire messages (include/hydia.h): what crosses to the sender as bytes — packed on the GPU, range-checked on arrival
+    def encryptQueryWire(self, query, seed=None, a_seed=None, nonce=1):
+        """one probe (a host vector, or a 1-D tensor on the context's GPU) -> a type 2 wire message of count 1 (bytes)"""
+        if _is_device_tensor(query):
+            if query.dim() != 1:
+                raise HydiaError(-1, "hydia: encryptQueryWire takes one probe (encryptQueriesWire takes a matrix)")
+            return self.encryptQueriesWire(query, seed, a_seed, nonce)
+        query = np.ascontiguousarray(query, dtype=np.float64)
+        assert query.shape == (self.cc.dim,)
+        return self.encryptQueriesWire(query[None], seed, a_seed, nonce)
+
+    def encryptQueriesWire(self, matrix, seed=None, a_seed=None, nonce0=1):
+        """encryptQueriesSeeded with c0 leaving the GPU packed: ONE type 2 message (bytes) that carries a_seed and nonce0 itself"""
+        if not isinstance(self.cc, Context):
+            raise HydiaError(-2, "hydia: seeded queries are not made on a sharded context")
+        L, h, key, akey = self.cc.L, self.cc.h, _seed(seed), _seed(a_seed)
+        if _is_device_tensor(matrix):
+            d = _dev_rows(self.cc, matrix)
+            return _wire_out(lambda buf, cap, n: L.hydia_encrypt_queries_seeded_wire_device(h, C.byref(d), _p(key), _p(akey), nonce0, buf, cap, n))
+        matrix = np.ascontiguousarray(matrix, dtype=np.float64)
+        assert matrix.ndim == 2 and matrix.shape[1] == self.cc.dim
+        return _wire_out(lambda buf, cap, n: L.hydia_encrypt_queries_seeded_wire(h, _p(matrix), matrix.shape[0], _p(key), _p(akey), nonce0, buf, cap, n))
+
+    def exportKeysWire(self, path, seeded=True, rotations=None):
+        """the key-set file: the public key, then the evaluation keys in ascending id — every key the context holds, or the
+        relinearisation key and `rotations`.  seeded: half keys under the context's public key seed (Context.keygen_seeded)."""
+        cc = self.cc
+        if rotations is None:
+            return cc.keys_save(path, seeded)
+        ids = sorted({0} | {int(r) % cc.slots for r in rotations})
+        with open(path, "wb") as f:
+            f.write(b"HYDKEYS1" + np.array([1, 1 + len(ids)], dtype="<u4").tobytes())
+            for r in [-1] + ids:
+                f.write(cc.key_to_wire(r, seeded))
+
+    def resultFromWire(self, message):
+        """a scenario's result that the sender shipped with resultToWire -> the Ciphertext decryptIndex / decryptMembership take"""
+        return self.cc.ct_from_wire(message)
+
     def exportKeysSeeded(self, rotations=None):
         """the seeded key set of Context.keygen_seeded as SeededKeys: the public key and every evaluation key the context holds (or
         the relinearisation key and `rotations`).  At the default parameters the full set is 6.5 GB of host memory in place of
@@ -1149,6 +1277,26 @@ class DiagonalSender:
         if len(seeded) != 1:
             raise HydiaError(-1, "hydia: expandQuery takes one probe (expandQueries takes a batch)")
         return self.expandQueries(seeded)[0]
+
+    # ---- wire messages (include/hydia.h): the checked path for what arrives from outside
+    def importKeysWire(self, path):
+        """DiagonalReceiver.exportKeysWire's file into this context (hydia_keys_load; not transactional)"""
+        self.cc.keys_load(path)
+
+    def queryFromWire(self, message):
+        """a query message -> what expandQuery / Context.import_ct return, ready for every single, *Multi and *GalleryMulti method: a
+        type 2 message of one probe or a type 1 message gives ONE Ciphertext, a type 2 message of several a list of them"""
+        r = self.cc.ct_from_wire(message)
+        return r[0] if isinstance(r, list) and len(r) == 1 else r
+
+    def queriesFromWire(self, message):
+        """always a list: one Ciphertext per probe of a type 2 message (the batch of a type 1 message as its only element)"""
+        r = self.cc.ct_from_wire(message)
+        return r if isinstance(r, list) else [r]
+
+    def resultToWire(self, result_cipher):
+        """a scenario's output as one wire message (bytes) for DiagonalReceiver.resultFromWire"""
+        return result_cipher.to_wire()
 
     @staticmethod
     def _no_plain(what, *queries):

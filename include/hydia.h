@@ -530,6 +530,80 @@ int hydia_encrypt_queries_seeded_device(hydia_ctx *ctx, const hydia_dev_rows *ro
                                         uint64_t nonce0, uint64_t *c0_out /* [n][n_q][N] host */);
 int hydia_ct_expand_seeded(hydia_ctx *ctx, const uint64_t *c0 /* [count][n_q][N] host */, size_t count, const uint8_t a_seed[32],
                            uint64_t nonce0, hydia_ct **out /* count handles */);
+/* ---- wire messages (an extension; the reference ships OpenFHE's serialised files, serial/multkey.bin, rotkey.bin and one file per
+ * ciphertext — INTEGRATION.md maps them): ONE packed, checked, self-describing format for everything that crosses between receiver,
+ * sender and enroller: ciphertext batches, seeded queries, evaluation keys and the public key, whole or seeded.  Residues travel in the
+ * bit length of their modulus instead of 64 bits; packing happens on the GPU on the way out, unpacking and range-checking on the GPU on
+ * the way in.  THE WIRE ENTRIES ARE THE CHECKED PATH: the raw-limb calls above (hydia_ct_import, hydia_import_eval_key,
+ * hydia_ct_expand_seeded, ...) stay what they are, unchecked, for callers that bind OpenFHE objects directly.
+ * At the default parameters (q_0 and the four special primes 60 bits, six limbs 46 and five 45) a seeded query message is 2 298 216 bytes
+ * against 3 145 728 raw, a seeded evaluation key 9 843 048 against 12 582 912, a whole one 19 685 736 against 25 165 824.
+ * NOT AUTHENTICATED: a message carries no MAC and is not encrypted beyond what a ciphertext is; transport security is the caller's.  What
+ * the library guarantees is that a message it accepts is well-formed and canonical (every residue below its modulus).
+ * FORMAT (little-endian; big-endian hosts are not served).  A message is a 360-byte header followed by the payload, nothing after it.
+ *   header   offset 0 magic "HYDWIRE1" | 8 u32 version = 1 | 12 u32 type | 16 u32 log_n | 20 u32 n_polys | 24 u32 n_limbs | 28 u32 rot |
+ *            32 u64 count | 40 f64 scale | 48 u8 a_seed[32] | 80 u64 nonce0 | 88 u64 payload_bytes | 96 u64 reserved = 0 |
+ *            104 u64 moduli[32]: the moduli of the limbs carried, in order, then zeros
+ *   type     1 ciphertext batch (n_polys 2 or 3, n_limbs 1 .. n_q) | 2 seeded query batch (one polynomial c0 per query on n_q limbs, scale
+ *            2^scale_bits; c1 of query i = the expansion of (a_seed, nonce0 + i)) | 3 evaluation key (count = dnum, n_polys 2 = (b, a),
+ *            n_limbs = n_q + n_p) | 4 seeded evaluation key (n_polys 1: the [d][0] rows) | 5 public key (count 1, n_polys 2, n_limbs n_q) |
+ *            6 seeded public key (b alone)
+ *   rot      types 3 / 4: the key id, 0 = relinearisation, otherwise in [1, slots); every other type 0
+ *   unused   a field a type does not use is zero and is checked: scale (keys), a_seed (types 1, 3, 5), nonce0 (all but 2), moduli past
+ *            n_limbs, reserved
+ *   payload  rows in the order [count][poly][limb], each the N residues of one limb.  w_j = the bit length of q_j (60 and 45 / 46 at the
+ *            default parameters); residue c occupies bits [c w_j, (c + 1) w_j) of the row read as one little-endian bit string; a row is
+ *            N w_j / 8 bytes — N is a multiple of 64, so 64 consecutive residues make exactly w_j 64-bit words — and rows follow one
+ *            another without padding.  payload_bytes = count x n_polys x sum_j N w_j / 8.
+ *   seeded types carry only the half that is not the seed's expansion; the other half is regenerated on import exactly as
+ *            hydia_ct_expand_seeded / hydia_import_eval_key_seeded / hydia_import_public_key_seeded do.
+ *   key-set file   16 bytes (magic "HYDKEYS1", u32 version = 1, u32 number of messages), then the messages back to back: the public key
+ *            first, then the evaluation keys in ascending key id.
+ * VALIDATION happens on the header alone, before anything is allocated or any key or handle is touched; each refusal is HYDIA_ERR_ARG
+ * with a message naming the field: magic, version, an unknown type, len shorter than a header, len != 360 + payload_bytes (neither
+ * truncated nor trailing bytes), payload_bytes other than the shape implies (all size arithmetic is overflow-checked), log_n other than
+ * the context's, count == 0, n_polys, n_limbs outside 1 .. n_q (ciphertexts) or other than n_q + n_p (keys), dnum, rot outside
+ * [0, slots), a listed modulus that is not the context's modulus of that limb, scale not finite or <= 0, nonce0 + count > 2^40, a
+ * non-zero unused field.  Then the packed bytes are uploaded and every residue is checked on the device while it is unpacked: one at or
+ * above its modulus answers HYDIA_ERR_ARG, no handle is returned, no key is changed and nothing stays allocated.
+ *   hydia_wire_peek        the context-free part of the validation, without a GPU (like hydia_params_describe): type, shape, rot, scale,
+ *                          seed, nonce and bytes of the message at (buf, len)
+ *   hydia_wire_*_bytes     the size of a message of that shape on this context; 0 for a shape no message has
+ *   hydia_ct_to_wire       any handle, a hydia_ct_limb_prefix view included -> a type 1 message.  cap too small (or buf NULL):
+ *                          HYDIA_ERR_ARG with *written = the bytes needed; otherwise *written = the bytes written
+ *   hydia_ct_from_wire     type 1 -> ONE batch handle with the message's shape and scale; type 2 -> count single-ciphertext handles,
+ *                          exactly those hydia_ct_expand_seeded makes.  out_cap too small: HYDIA_ERR_ARG with *n_out = the handles needed
+ *   hydia_encrypt_queries_seeded_wire / _wire_device   hydia_encrypt_queries_seeded / _device with c0 leaving the GPU packed, as one type 2
+ *                          message; refusals as theirs (count == 0: HYDIA_OK, *written = 0)
+ *   hydia_key_to_wire      rot = -1 the public key, 0 the relinearisation key, r >= 1 the key of rotation r.  seeded != 0 on a key that is
+ *                          not marked seeded: HYDIA_ERR_STATE, as the seeded exports answer
+ *   hydia_key_from_wire    installs whichever key the message carries (rot_out: its id, -1 the public key), expanding seeded halves.  The
+ *                          rows are unpacked into scratch and installed only after the check passed: a refused message leaves the key
+ *                          installed before, and its seeded mark, untouched.  What follows a key write follows as for hydia_import_eval_key
+ *   hydia_keys_save / hydia_keys_load   the key-set file of every key the context holds, through one pinned staging buffer.  A refused load
+ *                          names the message index; the load is NOT transactional: keys of earlier messages stay installed.
+ * NOT served: hydia_pt handles, the switching key of hydia_db_rekey, hydia_group_*, the database files (they keep their own format). */
+typedef struct {
+    uint32_t type, log_n, n_polys, n_limbs, rot, reserved;
+    uint64_t count;
+    double scale;
+    uint8_t a_seed[32];
+    uint64_t nonce0, header_bytes, payload_bytes;
+} hydia_wire_info;
+int hydia_wire_peek(const void *buf, size_t len, hydia_wire_info *out);
+size_t hydia_wire_ct_bytes(const hydia_ctx *ctx, uint64_t count, uint32_t n_polys, uint32_t n_limbs, int seeded);
+size_t hydia_wire_eval_key_bytes(const hydia_ctx *ctx, int seeded);
+size_t hydia_wire_public_key_bytes(const hydia_ctx *ctx, int seeded);
+int hydia_ct_to_wire(hydia_ctx *ctx, const hydia_ct *ct, void *buf, size_t cap, size_t *written);
+int hydia_ct_from_wire(hydia_ctx *ctx, const void *buf, size_t len, hydia_ct **out, size_t out_cap, size_t *n_out);
+int hydia_encrypt_queries_seeded_wire(hydia_ctx *ctx, const double *queries /* count x vector_dim */, size_t count, const uint8_t seed[32],
+                                      const uint8_t a_seed[32], uint64_t nonce0, void *buf, size_t cap, size_t *written);
+int hydia_encrypt_queries_seeded_wire_device(hydia_ctx *ctx, const hydia_dev_rows *rows, const uint8_t seed[32], const uint8_t a_seed[32],
+                                             uint64_t nonce0, void *buf, size_t cap, size_t *written);
+int hydia_key_to_wire(hydia_ctx *ctx, int rot, int seeded, void *buf, size_t cap, size_t *written);
+int hydia_key_from_wire(hydia_ctx *ctx, const void *buf, size_t len, int *rot_out);
+int hydia_keys_save(hydia_ctx *ctx, const char *path, int seeded);
+int hydia_keys_load(hydia_ctx *ctx, const char *path);
 /* OpenFHEWrapper::chebyshevCompare (src/openFHE_wrapper.cpp:143-185) on every ciphertext of the batch */
 int hydia_chebyshev_compare(hydia_ctx *ctx, const hydia_ct *in, double delta, size_t sign_depth, hydia_ct **out);
 /* multi-GPU membership tail: sum the batch into one ciphertext, then EvalSum over all slots (:46-47) */

@@ -15,8 +15,10 @@
 // Error behaviour mirrors the reference: a message on cerr and carry on (src/sender/sender_diag.cpp:89-91); the
 // status code of the last failing call is kept in CryptoContext::last_status for callers that want to assert.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <iostream>
 #include <map>
@@ -237,6 +239,42 @@ inline std::vector<Ciphertext> split_batch(const CryptoContext &cc, hydia_ct *h)
     return v;
 }
 
+// Wire messages (hydia.h, "wire messages"): what crosses between receiver, sender and enroller as BYTES — residues packed into the bit
+// length of their modulus on the GPU, and on arrival validated, unpacked and range-checked on the GPU.  Not authenticated: transport
+// security is the caller's.  toWire takes the whole of one device batch (what every role method here returns); fromWire gives the
+// batch of a type 1 message.  Approaches 1 - 4 use these two through their handles.  Empty on failure
+inline std::vector<uint8_t> toWire(const CryptoContext &cc, const std::vector<Ciphertext> &ctxts) {
+    if (ctxts.empty() || !ctxts[0] || ctxts[0].batch->count() != ctxts.size()) {
+        cc->last_status = HYDIA_ERR_ARG;
+        std::cerr << "Error: toWire takes the whole of one ciphertext batch" << std::endl;
+        return {};
+    }
+    size_t n = 0;
+    hydia_ct_to_wire(cc->h, ctxts[0].batch->h, nullptr, 0, &n);  // the size: HYDIA_ERR_ARG with n = the need
+    std::vector<uint8_t> buf(n);
+    if (!n || !cc->check(hydia_ct_to_wire(cc->h, ctxts[0].batch->h, buf.data(), buf.size(), &n), "toWire")) return {};
+    return buf;
+}
+// every handle a ciphertext message makes: one batch (type 1), or one single-ciphertext handle per seeded query (type 2)
+inline std::vector<std::vector<Ciphertext>> handlesFromWire(const CryptoContext &cc, const std::vector<uint8_t> &message, const char *what) {
+    hydia_wire_info info;
+    if (!cc->check(hydia_wire_peek(message.data(), message.size(), &info), what)) return {};
+    std::vector<hydia_ct *> h(info.type == 1 ? 1 : (size_t)info.count, nullptr);
+    size_t n = 0;
+    if (!cc->check(hydia_ct_from_wire(cc->h, message.data(), message.size(), h.data(), h.size(), &n), what)) return {};
+    std::vector<std::vector<Ciphertext>> r;
+    for (size_t i = 0; i < n; i++) r.push_back(split_batch(cc, h[i]));
+    return r;
+}
+inline std::vector<Ciphertext> fromWire(const CryptoContext &cc, const std::vector<uint8_t> &message) {
+    std::vector<std::vector<Ciphertext>> r = handlesFromWire(cc, message, "fromWire");
+    if (r.size() != 1) {
+        if (!r.empty()) std::cerr << "Error: fromWire takes a message of one batch or one query (queriesFromWire takes several)" << std::endl;
+        return {};
+    }
+    return r[0];
+}
+
 // the reference's template spelling of the handle types: `using namespace hydia::ofhe;` in place of `using namespace lbcrypto;`
 namespace ofhe {
 struct DCRTPoly {};
@@ -388,6 +426,45 @@ class DiagonalSender : public Sender {
         }
         std::vector<std::vector<Ciphertext>> r = expandQueries(q);
         return r.empty() ? std::vector<Ciphertext>{} : r[0];
+    }
+    // Wire messages (an extension; hydia.h): the checked path for what arrives from outside.  importKeysWire loads
+    // DiagonalReceiver::exportKeysWire's file (not transactional: a refused file leaves the keys of earlier messages installed);
+    // queryFromWire turns a query message into the queryCipher every method above takes (a type 2 message of one probe, or a type 1
+    // batch), queriesFromWire a message of several probes into one queryCipher each; resultToWire ships a scenario's output.  Not on a
+    // sharded context: an error, false / empty
+    bool importKeysWire(const std::string &path) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: importKeysWire: keys are loaded into one context" << std::endl;
+            return false;
+        }
+        return cc->check(hydia_keys_load(cc->h, path.c_str()), "importKeysWire");
+    }
+    std::vector<std::vector<Ciphertext>> queriesFromWire(const std::vector<uint8_t> &message) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: queriesFromWire: messages are unpacked on one context" << std::endl;
+            return {};
+        }
+        return handlesFromWire(cc, message, "queriesFromWire");
+    }
+    std::vector<Ciphertext> queryFromWire(const std::vector<uint8_t> &message) {
+        std::vector<std::vector<Ciphertext>> r = queriesFromWire(message);
+        if (r.size() > 1) {
+            cc->last_status = HYDIA_ERR_ARG;
+            std::cerr << "Error: queryFromWire takes one probe (queriesFromWire takes a batch)" << std::endl;
+            return {};
+        }
+        return r.empty() ? std::vector<Ciphertext>{} : r[0];
+    }
+    std::vector<uint8_t> resultToWire(const std::vector<Ciphertext> &result) { return toWire(cc, result); }
+    std::vector<uint8_t> resultToWire(const Ciphertext &result) {
+        if (!result || result.batch->count() != 1) {
+            cc->last_status = HYDIA_ERR_ARG;
+            std::cerr << "Error: resultToWire takes one ciphertext that is its own batch, or the whole of a batch" << std::endl;
+            return {};
+        }
+        return toWire(cc, std::vector<Ciphertext>{result});
     }
     // A plain query (an extension; hydia.h): the sender knows the probe, the database (kinds 5 / 6) stays encrypted and so does every
     // result.  encodeQuery makes exactly the plaintext DiagonalReceiver::encryptQuery encrypts — no seed, no key; the overloads return
@@ -631,6 +708,55 @@ class DiagonalReceiver : public HersReceiver {
         }
         return k;
     }
+    // Wire messages (hydia.h, "wire messages"): the seeded queries above as ONE type 2 message that carries the public seed and the
+    // nonce itself, c0 leaving the GPU packed; the key-set file (the public key, then the evaluation keys in ascending id: every key
+    // the context holds, or the relinearisation key and `rotations`); a scenario's result back from the sender.  seeded = true ships
+    // half keys and needs CryptoContextImpl::KeyGenSeeded's set.  Empty / false on failure
+    std::vector<uint8_t> encryptQueriesWire(const std::vector<std::vector<double>> &queries, const uint8_t *aSeed32 = nullptr) {
+        const size_t dim = cc->info.vector_dim;
+        std::vector<double> flat(queries.size() * dim, 0.0);
+        for (size_t i = 0; i < queries.size(); i++)
+            for (size_t j = 0; j < dim && j < queries[i].size(); j++) flat[i * dim + j] = queries[i][j];
+        return wire_queries(queries.size(), aSeed32, [&](const uint8_t *a, void *buf, size_t cap, size_t *n) {
+            return hydia_encrypt_queries_seeded_wire(cc->h, flat.data(), queries.size(), seed, a, nonce + 1, buf, cap, n);
+        });
+    }
+    std::vector<uint8_t> encryptQueryWire(std::vector<double> query, const uint8_t *aSeed32 = nullptr) {
+        return encryptQueriesWire(std::vector<std::vector<double>>{std::move(query)}, aSeed32);
+    }
+    std::vector<uint8_t> encryptQueriesWire(const DeviceRows &rows, const uint8_t *aSeed32 = nullptr) {
+        return wire_queries(rows.size(), aSeed32, [&](const uint8_t *a, void *buf, size_t cap, size_t *n) {
+            return hydia_encrypt_queries_seeded_wire_device(cc->h, &rows.d, seed, a, nonce + 1, buf, cap, n);
+        });
+    }
+    bool exportKeysWire(const std::string &path, bool seeded = true, const std::vector<int> &rotations = {}) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: exportKeysWire: a key set lives on the receiver's own context" << std::endl;
+            return false;
+        }
+        if (rotations.empty()) return cc->check(hydia_keys_save(cc->h, path.c_str(), seeded ? 1 : 0), "exportKeysWire");
+        std::map<int, bool> ids{{0, true}};
+        for (int r : rotations) ids[(int)((((long)r % (long)cc->info.slots) + (long)cc->info.slots) % (long)cc->info.slots)] = true;
+        FILE *f = std::fopen(path.c_str(), "wb");
+        if (!f) {
+            cc->last_status = HYDIA_ERR_ARG;
+            std::cerr << "Error: exportKeysWire: cannot open " << path << std::endl;
+            return false;
+        }
+        const uint32_t head[2] = {1u, (uint32_t)ids.size() + 1u};  // the key-set file header: magic, version, number of messages
+        bool ok = std::fwrite("HYDKEYS1", 1, 8, f) == 8 && std::fwrite(head, sizeof head, 1, f) == 1;
+        std::vector<uint8_t> buf(std::max(hydia_wire_eval_key_bytes(cc->h, seeded), hydia_wire_public_key_bytes(cc->h, seeded)));
+        ids[-1] = true;  // (sorts first: the public key)
+        for (auto it = ids.begin(); ok && it != ids.end(); ++it) {
+            size_t n = 0;
+            ok = cc->check(hydia_key_to_wire(cc->h, it->first, seeded ? 1 : 0, buf.data(), buf.size(), &n), "exportKeysWire") &&
+                 std::fwrite(buf.data(), 1, n, f) == n;
+        }
+        std::fclose(f);
+        return ok;
+    }
+    std::vector<Ciphertext> resultFromWire(const std::vector<uint8_t> &message) { return fromWire(cc, message); }
     // The switching key of a re-keyed database (hydia_keygen_switch; no counterpart in the reference): from the OLD receiver's secret
     // (oldSecret, [n_q+n_p][N] as hydia_export_secret_key gives it) to THIS receiver's, for DiagonalEnroller::rekeyDB.  Treat it like an
     // evaluation key.  seed32 == nullptr draws a fresh sampler key from the OS (use a fresh one per switching key).  Empty on failure.
@@ -650,6 +776,28 @@ class DiagonalReceiver : public HersReceiver {
     }
 
   private:
+    // the frame of a query message of `count` probes: the public seed, the size (a NULL buffer answers HYDIA_ERR_ARG with the need),
+    // the message; the probes take this receiver's next `count` nonces
+    template <class Call>
+    std::vector<uint8_t> wire_queries(size_t count, const uint8_t *aSeed32, Call call) {
+        if (cc->group || count == 0) {
+            cc->last_status = cc->group ? HYDIA_ERR_STATE : HYDIA_ERR_ARG;
+            std::cerr << "Error: encryptQueriesWire: " << (cc->group ? "seeded queries are not made on a sharded context" : "no probe") << std::endl;
+            return {};
+        }
+        uint8_t a[32];
+        role_seed(a, aSeed32);
+        size_t n = 0;
+        const int sized = call(a, nullptr, 0, &n);
+        if (n == 0) {
+            cc->check(sized, "encryptQueriesWire");
+            return {};
+        }
+        std::vector<uint8_t> buf(n);
+        if (!cc->check(call(a, buf.data(), buf.size(), &n), "encryptQueriesWire")) return {};
+        nonce += count;
+        return buf;
+    }
     // the frame of a SeededQuery of `count` probes: the public seed, this receiver's next nonce, room for c0
     bool seeded_begin(SeededQuery &q, size_t count, const uint8_t *aSeed32, const char *what) {
         if (cc->group || count == 0) {
