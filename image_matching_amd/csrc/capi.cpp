@@ -9,6 +9,7 @@
 #include <sys/random.h>
 
 #include "capi_internal.h"
+#include "select_kernels.h"
 
 using namespace hydia;
 
@@ -606,30 +607,106 @@ int hydia_decrypt_membership(hydia_ctx *ctx, const hydia_ct *ct, int *result) {
     API_BEGIN
     use_device(ctx);
     REQUIRE(ctx && ct && result, "null argument");
-    std::vector<double> v((size_t)ct->c.X * ctx->cx.slots);
-    client_decrypt(ctx->cx, ct->c, v.data());
-    *result = v[0] >= 1.0 ? 1 : 0;
+    *result = client_decrypt_slot0(ctx->cx, ct->c) >= 1.0 ? 1 : 0;
     return HYDIA_OK;
     API_END
 }
-/* receiver_hers.cpp:37-54 */
+/* receiver_hers.cpp:37-54: hydia_decrypt_matches at threshold 1.0 over all slots, without values */
 int hydia_decrypt_index(hydia_ctx *ctx, const hydia_ct *cts, size_t *out, size_t cap, size_t *n_out) {
     API_BEGIN
     use_device(ctx);
     REQUIRE(ctx && cts && n_out, "null argument");
-    const size_t S = ctx->cx.slots;
-    std::vector<double> v((size_t)cts->c.X * S);
-    client_decrypt(ctx->cx, cts->c, v.data());
-    size_t cnt = 0;
-    for (size_t i = 0; i < (size_t)cts->c.X; i++)
-        for (size_t j = 0; j < S; j++)
-            if (v[i * S + j] >= 1.0) {
-                if (out && cnt < cap) out[cnt] = j + i * S;
-                cnt++;
-            }
-    *n_out = cnt;
+    const Ct *one = &cts->c;
+    client_select(ctx->cx, SelectSource{&one, nullptr, 1, 0}, 1.0, out, nullptr, cap, n_out);
     return HYDIA_OK;
     API_END
+}
+
+// ------------------------------------------------------------------ candidate lists and matches
+// n doubles at p in the memory of the context's GPU (the checks of check_dev_rows): HYDIA_OK, or the code recorded with its message
+static int check_dev_doubles(hydia_ctx *ctx, const double *p, size_t n) {
+    REQUIRE(n >= 1 && n <= HY_SEL_MAX_N, "element count outside 1 .. 2^31 - 1");
+    REQUIRE(p, "null device pointer");
+    REQUIRE((uintptr_t)p % sizeof(double) == 0, "device pointer is not aligned to a double");
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();  // (an address the runtime has never seen: not an error of the device)
+        return fail(HYDIA_ERR_ARG, "hydia: the pointer is not device memory");
+    }
+    REQUIRE(at.type == hipMemoryTypeDevice, "the pointer is not device memory (managed memory is not supported)");
+    REQUIRE(at.device == ctx->cx.device, "the array lies in the memory of another GPU than the context's");
+    return HYDIA_OK;
+}
+// the results of a decrypt entry as a SelectSource: every handle present, n_vectors within every result
+static int check_results(hydia_ctx *ctx, const hydia_ct *const *results, uint32_t n_results, size_t n_vectors, std::vector<const Ct *> &cts) {
+    REQUIRE(results && n_results >= 1, "bad argument");
+    for (uint32_t r = 0; r < n_results; r++) {
+        REQUIRE(results[r], "null result");
+        const size_t all = (size_t)results[r]->c.X * ctx->cx.slots;
+        REQUIRE(all <= HY_SEL_MAX_N, "a result of more than 2^31 - 1 slots");
+        REQUIRE(n_vectors <= all, "n_vectors exceeds the slots of a result");
+        cts.push_back(&results[r]->c);
+    }
+    return HYDIA_OK;
+}
+int hydia_decrypt_device(hydia_ctx *ctx, const hydia_ct *ct, double *dev_out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && ct, "null argument");
+    if (int code = check_dev_doubles(ctx, dev_out, (size_t)ct->c.X * ctx->cx.slots)) return code;
+    client_decrypt_device(ctx->cx, ct->c, dev_out);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_slots_select_device(hydia_ctx *ctx, const double *dev_vals, size_t n, double threshold, size_t *idx_out, double *val_out, size_t cap,
+                              size_t *n_out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && n_out, "null argument");
+    if (int code = check_dev_doubles(ctx, dev_vals, n)) return code;
+    client_select(ctx->cx, SelectSource{nullptr, dev_vals, 1, n}, threshold, idx_out, val_out, cap, n_out);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_slots_topk_device(hydia_ctx *ctx, const double *dev_vals, size_t n, size_t k, size_t *idx_out, double *val_out, size_t *n_out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && idx_out && n_out, "null argument");
+    REQUIRE(k >= 1, "k must be at least 1");
+    if (int code = check_dev_doubles(ctx, dev_vals, n)) return code;
+    client_topk(ctx->cx, SelectSource{nullptr, dev_vals, 1, n}, k, idx_out, val_out, n_out);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_decrypt_matches_multi(hydia_ctx *ctx, const hydia_ct *const *results, uint32_t n_results, size_t n_vectors, double threshold,
+                                size_t *idx_out, double *val_out, size_t cap, size_t *n_out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && n_out, "null argument");
+    std::vector<const Ct *> cts;
+    if (int code = check_results(ctx, results, n_results, n_vectors, cts)) return code;
+    client_select(ctx->cx, SelectSource{cts.data(), nullptr, n_results, n_vectors}, threshold, idx_out, val_out, cap, n_out);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_decrypt_topk_multi(hydia_ctx *ctx, const hydia_ct *const *results, uint32_t n_results, size_t n_vectors, size_t k, size_t *idx_out,
+                             double *val_out, size_t *n_out) {
+    API_BEGIN
+    use_device(ctx);
+    REQUIRE(ctx && idx_out && n_out, "null argument");
+    REQUIRE(k >= 1, "k must be at least 1");
+    std::vector<const Ct *> cts;
+    if (int code = check_results(ctx, results, n_results, n_vectors, cts)) return code;
+    client_topk(ctx->cx, SelectSource{cts.data(), nullptr, n_results, n_vectors}, k, idx_out, val_out, n_out);
+    return HYDIA_OK;
+    API_END
+}
+int hydia_decrypt_matches(hydia_ctx *ctx, const hydia_ct *cts, size_t n_vectors, double threshold, size_t *idx_out, double *val_out, size_t cap,
+                          size_t *n_out) {
+    return hydia_decrypt_matches_multi(ctx, &cts, 1, n_vectors, threshold, idx_out, val_out, cap, n_out);
+}
+int hydia_decrypt_topk(hydia_ctx *ctx, const hydia_ct *cts, size_t n_vectors, size_t k, size_t *idx_out, double *val_out, size_t *n_out) {
+    return hydia_decrypt_topk_multi(ctx, &cts, 1, n_vectors, k, idx_out, val_out, n_out);
 }
 
 // ------------------------------------------------------------------ enroller / database

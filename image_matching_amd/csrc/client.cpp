@@ -16,6 +16,7 @@
 #include "../../include/hydia.h"  // HY_EVK_ID_SWITCH
 #include "client_kernels.h"
 #include "rows_norm.h"
+#include "select_kernels.h"
 
 namespace hydia {
 
@@ -323,23 +324,175 @@ Ct client_encrypt_query(Context &cx, const double *query, const uint8_t seed[32]
     return client_encrypt(cx, batch.data(), 1, seed, nonce);                          // :23
 }
 
-void client_decrypt(Context &cx, const Ct &ct, double *out) {
+// pooled device buffers of one call, back in the pool when it ends (after the stream has been synchronised)
+namespace {
+struct PoolHold {
+    Context &cx;
+    std::vector<u64 *> held;
+    explicit PoolHold(Context &c) : cx(c) {}
+    PoolHold(const PoolHold &) = delete;
+    template <class T>
+    T *get(size_t count) {
+        held.push_back(cx.pool.get(sizeof(T) * count));
+        return (T *)held.back();
+    }
+    ~PoolHold() {
+        for (auto it = held.rbegin(); it != held.rend(); ++it) cx.pool.put(*it);
+    }
+};
+}  // namespace
+// dec_dot, inverse transform and decode of ct, enqueued on the stream: the X * slots doubles land at d_out (device memory)
+static void decrypt_enqueue(Context &cx, const Ct &ct, double *d_out, PoolHold &hold) {
     if (!cx.d_sk) throw StateError("hydia: secret key not loaded");
     ensure_embedding_tables(cx);
     const int N = cx.N, Nh = cx.slots, X = ct.X, nu = ct.nl < 2 ? ct.nl : 2;
-    u64 *t = cx.pool.get(sizeof(u64) * (size_t)X * nu * N);
+    u64 *t = hold.get<u64>((size_t)X * nu * N);
     hc::dec_dot(cx.stream, cx.d_mod, N, ct.npoly, ct.lstride, ct.d, cx.d_sk, t, nu, X);
     const LimbSel s = cx.sel_q(nu);
     cx.ntt_inv(t, t, (size_t)nu * N, (size_t)nu * N, X, s, cx.scale_ninv(s));
-    double2 *work = (double2 *)cx.pool.get(sizeof(double2) * (size_t)X * Nh);
-    double *d_out = (double *)cx.pool.get(sizeof(double) * (size_t)X * Nh);
+    double2 *work = hold.get<double2>((size_t)X * Nh);
     const u64 q0inv = cx.nQ >= 2 ? invmod_u64(cx.q[0] % cx.q[1], cx.q[1]) : 0;
     hc::decode(cx.stream, cx.d_mod, t, nu, N, X, ct.scale, q0inv, work, d_out, cx.d_rot_group, (const double2 *)cx.d_ksi);
-    HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)X * Nh, hipMemcpyDeviceToHost, cx.stream));
+}
+void client_decrypt(Context &cx, const Ct &ct, double *out) {
+    PoolHold hold(cx);
+    const size_t n = (size_t)ct.X * cx.slots;
+    double *d_out = hold.get<double>(n);
+    decrypt_enqueue(cx, ct, d_out, hold);
+    HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * n, hipMemcpyDeviceToHost, cx.stream));
     cx.sync();
-    cx.pool.put((u64 *)d_out);
-    cx.pool.put((u64 *)work);
-    cx.pool.put(t);
+}
+void client_decrypt_device(Context &cx, const Ct &ct, double *dev_out) {
+    PoolHold hold(cx);
+    decrypt_enqueue(cx, ct, dev_out, hold);
+    cx.sync();
+}
+double client_decrypt_slot0(Context &cx, const Ct &ct) {
+    PoolHold hold(cx);
+    double *d_out = hold.get<double>((size_t)ct.X * cx.slots);
+    decrypt_enqueue(cx, ct, d_out, hold);
+    double v = 0;
+    HIP_CHECK(hipMemcpyAsync(&v, d_out, sizeof(double), hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+    return v;
+}
+
+// ---- candidate lists and matches (select_kernels.hip): the selection stage behind the decoder
+static_assert(sizeof(size_t) == sizeof(uint64_t), "the kernels write indices as 64-bit words straight into size_t arrays");
+// the ordered compaction of v[0..n) under p, enqueued: count, scan, scatter (no scatter when nothing can be written)
+static void compact_enqueue(Context &cx, const double *v, size_t n, const SelPred &p, unsigned *tiles, unsigned *total, uint64_t *d_idx, double *d_val) {
+    cx.timer_begin("k_select_count");
+    hc::select_count(cx.stream, v, n, p, tiles);
+    cx.timer_end("k_select_count");
+    cx.timer_begin("k_select_scan");
+    hc::select_scan(cx.stream, tiles, hc::select_tiles(n), total);
+    cx.timer_end("k_select_scan");
+    if (!d_idx) return;
+    cx.timer_begin("k_select_scatter");
+    hc::select_scatter(cx.stream, v, n, p, tiles, d_idx, d_val);
+    cx.timer_end("k_select_scatter");
+}
+// result r of a batch: its decoded slots (decrypted here, or the caller's device array) and how many of them are searched
+static const double *select_source(Context &cx, const SelectSource &src, size_t r, PoolHold &hold, size_t &n) {
+    if (src.dev_vals) {
+        n = src.n;
+        return src.dev_vals;
+    }
+    const Ct &ct = *src.cts[r];
+    const size_t all = (size_t)ct.X * cx.slots;
+    double *d = hold.get<double>(all);
+    decrypt_enqueue(cx, ct, d, hold);
+    n = src.n ? src.n : all;
+    return d;
+}
+void client_select(Context &cx, const SelectSource &src, double threshold, size_t *idx_out, double *val_out, size_t cap, size_t *n_out) {
+    PoolHold hold(cx);
+    const size_t R = src.n_results;
+    if (!idx_out) cap = 0;
+    unsigned *d_total = hold.get<unsigned>(R);
+    std::vector<uint64_t *> d_idx(R, nullptr);
+    std::vector<double *> d_val(R, nullptr);
+    std::vector<size_t> room(R);
+    for (size_t r = 0; r < R; r++) {
+        size_t n;
+        const double *v = select_source(cx, src, r, hold, n);
+        room[r] = std::min(cap, n);
+        if (room[r]) {
+            d_idx[r] = hold.get<uint64_t>(room[r]);
+            if (val_out) d_val[r] = hold.get<double>(room[r]);
+        }
+        const SelPred p{HY_SEL_GE, threshold, (unsigned)room[r], 0, nullptr};
+        compact_enqueue(cx, v, n, p, hold.get<unsigned>(hc::select_tiles(n)), d_total + r, d_idx[r], d_val[r]);
+    }
+    std::vector<unsigned> total(R);
+    HIP_CHECK(hipMemcpyAsync(total.data(), d_total, sizeof(unsigned) * R, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+    // (the stream is idle: only the entries that were written cross to the host)
+    for (size_t r = 0; r < R; r++) {
+        const size_t w = std::min((size_t)total[r], room[r]);
+        if (w) HIP_CHECK(hipMemcpy(idx_out + r * cap, d_idx[r], sizeof(uint64_t) * w, hipMemcpyDeviceToHost));
+        if (w && val_out) HIP_CHECK(hipMemcpy(val_out + r * cap, d_val[r], sizeof(double) * w, hipMemcpyDeviceToHost));
+        n_out[r] = total[r];
+    }
+}
+void client_topk(Context &cx, const SelectSource &src, size_t k, size_t *idx_out, double *val_out, size_t *n_out) {
+    PoolHold hold(cx);
+    const size_t R = src.n_results;
+    std::vector<size_t> kk(R);
+    size_t vs = 0;  // the row stride of the values: the caller's k, or the largest row when the caller wants none (the final sort needs them)
+    for (size_t r = 0; r < R; r++) {
+        const size_t n = src.dev_vals || src.n ? src.n : (size_t)src.cts[r]->X * cx.slots;
+        vs = std::max(vs, kk[r] = std::min(k, n));
+    }
+    std::vector<double> vals;
+    if (val_out) vs = k;
+    else vals.resize(R * vs);
+    double *const vrow = val_out ? val_out : vals.data();
+    for (size_t r = 0; r < R; r++) {
+        size_t n;
+        const double *v = select_source(cx, src, r, hold, n);
+        const size_t kr = kk[r];
+        SelState *state = hold.get<SelState>(1);
+        unsigned *tiles = hold.get<unsigned>(hc::select_tiles(n)), *total = hold.get<unsigned>(1);
+        uint64_t *d_idx = hold.get<uint64_t>(kr);
+        double *d_val = hold.get<double>(kr);
+        HIP_CHECK(hipMemsetAsync(state, 0, sizeof(SelState), cx.stream));
+        for (int pass = 0; pass < 8; pass++) {
+            cx.timer_begin("k_topk_hist");
+            hc::topk_hist(cx.stream, v, n, pass, state);
+            cx.timer_end("k_topk_hist");
+            cx.timer_begin("k_topk_pick");
+            hc::topk_pick(cx.stream, pass, (unsigned)kr, state);
+            cx.timer_end("k_topk_pick");
+        }
+        compact_enqueue(cx, v, n, SelPred{HY_SEL_ABOVE, 0.0, 0, (unsigned)kr, state}, tiles, total, d_idx, d_val);
+        compact_enqueue(cx, v, n, SelPred{HY_SEL_TIE, 0.0, 0, (unsigned)kr, state}, tiles, total, d_idx, d_val);
+        HIP_CHECK(hipMemcpyAsync(idx_out + r * k, d_idx, sizeof(uint64_t) * kr, hipMemcpyDeviceToHost, cx.stream));
+        HIP_CHECK(hipMemcpyAsync(vrow + r * vs, d_val, sizeof(double) * kr, hipMemcpyDeviceToHost, cx.stream));
+    }
+    cx.sync();
+    // the survivors arrive as (keys above the k-th in index order, then ties of the k-th in index order): value descending, index ascending
+    std::vector<std::pair<uint64_t, size_t>> order;
+    std::vector<double> tmp;
+    for (size_t r = 0; r < R; r++) {
+        size_t *ix = idx_out + r * k;
+        double *vv = vrow + r * vs;
+        order.resize(kk[r]);
+        tmp.assign(vv, vv + kk[r]);
+        for (size_t i = 0; i < kk[r]; i++) {
+            uint64_t bits;
+            std::memcpy(&bits, &vv[i], 8);
+            order[i] = {~hy_sel_key(bits), ix[i]};
+        }
+        std::vector<size_t> perm(kk[r]);
+        for (size_t i = 0; i < kk[r]; i++) perm[i] = i;
+        std::sort(perm.begin(), perm.end(), [&](size_t a, size_t b) { return order[a] < order[b]; });
+        for (size_t i = 0; i < kk[r]; i++) {
+            ix[i] = order[perm[i]].second;
+            vv[i] = tmp[perm[i]];
+        }
+        n_out[r] = kk[r];
+    }
 }
 
 // encode X slot vectors that already sit in HBM as plaintexts: the front half of encrypt_device (the encoder at scale 2^scale_bits,

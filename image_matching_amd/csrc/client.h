@@ -39,6 +39,24 @@ void client_encode_plain(Context &cx, const double *slots, int nl, u64 *pt);
 Ct client_encrypt(Context &cx, const double *slots, int count, const uint8_t seed[32], uint64_t nonce0);
 Ct client_encrypt_query(Context &cx, const double *query, const uint8_t seed[32], uint64_t nonce);
 void client_decrypt(Context &cx, const Ct &ct, double *out);
+// the same slots left in DEVICE memory of the context's GPU (dev_out: X * slots doubles); slot 0 of the batch alone
+void client_decrypt_device(Context &cx, const Ct &ct, double *dev_out);
+double client_decrypt_slot0(Context &cx, const Ct &ct);
+// ---- candidate lists and matches (include/hydia.h; select_kernels.hip).  A batch of n_results results, each either a ciphertext batch
+// cts[r] that is decrypted on the way (n: the first n slots are searched, 0 = all X * slots of that result) or, with n_results == 1,
+// the caller's device array dev_vals[0..n).  The C-ABI has checked every argument.  The whole batch is enqueued on the stream, result
+// after result, and read back after ONE synchronisation; only counters and the selected entries cross to the host
+struct SelectSource {
+    const Ct *const *cts;
+    const double *dev_vals;
+    size_t n_results, n;
+};
+// row r of idx_out / val_out (cap entries apart; val_out may be null; idx_out null: count only): the indices i with v[i] >= threshold
+// ascending, with their values; n_out[r] = how many there are, at most cap of them written
+void client_select(Context &cx, const SelectSource &src, double threshold, size_t *idx_out, double *val_out, size_t cap, size_t *n_out);
+// row r (k entries apart; val_out may be null): the min(k, n) largest by (value descending, index ascending), -0.0 tying with +0.0 and
+// NaN below -inf; n_out[r] = min(k, n)
+void client_topk(Context &cx, const SelectSource &src, size_t k, size_t *idx_out, double *val_out, size_t *n_out);
 // first_block: index of this context's first 16384-vector block inside the whole database (a shard of a multi-GPU database
 // encrypts with the nonces the unsharded enrolment would use, so shards hold bit-identical ciphertexts)
 // babies < vector_dim: diagonals pre-rotated for the baby-step / giant-step mat-vec with that many hoisted rotations

@@ -103,6 +103,13 @@ def load_library():
         "hydia_decrypt": (i32, [vp, vp, vp]),
         "hydia_decrypt_membership": (i32, [vp, vp, C.POINTER(i32)]),
         "hydia_decrypt_index": (i32, [vp, vp, vp, sz, C.POINTER(sz)]),
+        "hydia_decrypt_device": (i32, [vp, vp, vp]),
+        "hydia_slots_select_device": (i32, [vp, vp, sz, dbl, vp, vp, sz, vp]),
+        "hydia_slots_topk_device": (i32, [vp, vp, sz, sz, vp, vp, vp]),
+        "hydia_decrypt_matches": (i32, [vp, vp, sz, dbl, vp, vp, sz, vp]),
+        "hydia_decrypt_topk": (i32, [vp, vp, sz, sz, vp, vp, vp]),
+        "hydia_decrypt_matches_multi": (i32, [vp, vp, u32, sz, dbl, vp, vp, sz, vp]),
+        "hydia_decrypt_topk_multi": (i32, [vp, vp, u32, sz, sz, vp, vp, vp]),
         "hydia_db_num_cts": (sz, [vp, sz]),
         "hydia_db_enroll": (i32, [vp, vp, sz, vp]),
         "hydia_db_alloc": (i32, [vp, sz]),
@@ -481,6 +488,7 @@ class Context:
                                                 len(moduli) - n_p, n_p, device, C.byref(h)))
         self.h = h
         self.owned = True
+        self.device = device
         self._read_info()
 
     def _read_info(self):
@@ -498,7 +506,7 @@ class Context:
     def _borrowed(cls, L, params, h):
         """A view of a context owned by a shard group (never destroyed through this object)."""
         self = cls.__new__(cls)
-        self.L, self.params, self.h, self.owned = L, params, C.c_void_p(h), False
+        self.L, self.params, self.h, self.owned, self.device = L, params, C.c_void_p(h), False, None
         self._read_info()
         return self
 
@@ -708,6 +716,47 @@ class Context:
         out = np.zeros((len(ct), self.slots), dtype=np.float64)
         _chk(self.L.hydia_decrypt(self.h, ct.h, _p(out)))
         return out
+
+    # ---- candidate lists and matches (include/hydia.h): the decoded slots stay on the GPU, only what was asked for comes back
+    def decrypt_device(self, ct):
+        """hydia_decrypt_device: the slots of decrypt(ct), bit for bit, as a float64 tensor [count, slots] on the context's GPU.
+        (A process that uses torch beside this library imports torch before it creates a context.)"""
+        import torch
+        if self.device is None:
+            raise HydiaError(-2, "hydia: decrypt_device is not served on a shard of a group")
+        out = torch.empty((len(ct), self.slots), dtype=torch.float64, device="cuda:%d" % self.device)
+        _chk(self.L.hydia_decrypt_device(self.h, ct.h, C.c_void_p(out.data_ptr() or None)))
+        return out
+
+    def _dev_values(self, values):
+        """(pointer, n) of a contiguous float64 tensor, after torch's current stream has finished with it; that the memory lies on
+        the context's GPU is checked by the library (HydiaError(-1))"""
+        import torch
+        if not _is_device_tensor(values) or str(values.dtype) != "torch.float64" or not values.is_contiguous():
+            raise HydiaError(-1, "hydia: the values are a contiguous float64 tensor in the memory of the context's GPU")
+        if values.is_cuda:
+            torch.cuda.current_stream(values.device).synchronize()
+        return C.c_void_p(values.data_ptr() or None), values.numel()
+
+    def slots_select(self, values, threshold, cap=None):
+        """hydia_slots_select_device: (idx, val, total) — the indices i with values[i] >= threshold ascending (at most cap of them,
+        default all), their values, and how many there are"""
+        ptr, n = self._dev_values(values)
+        cap = n if cap is None else int(cap)
+        idx, val, total = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.float64), C.c_size_t()
+        _chk(self.L.hydia_slots_select_device(self.h, ptr, n, float(threshold), _p(idx) if cap else None, _p(val) if cap else None, cap,
+                                              C.byref(total)))
+        w = min(cap, total.value)
+        return idx[:w].astype(np.int64), val[:w], total.value
+
+    def slots_topk(self, values, k):
+        """hydia_slots_topk_device: (idx, val) — the min(k, n) largest by value descending, ties by ascending index, NaN last"""
+        ptr, n = self._dev_values(values)
+        k = int(k)
+        room = max(1, min(k, n))
+        idx, val, got = np.zeros(room, dtype=np.uint64), np.zeros(room, dtype=np.float64), C.c_size_t()
+        _chk(self.L.hydia_slots_topk_device(self.h, ptr, n, k, _p(idx), _p(val), C.byref(got)))
+        return idx[:got.value].astype(np.int64), val[:got.value]
 
     # ---- primitives
     def ntt(self, data, modulus_index, inverse=False):
@@ -1232,6 +1281,48 @@ class DiagonalReceiver:
         _chk(self.cc.L.hydia_decrypt_index(self.cc.h, index_cipher.h, _p(out), cap, C.byref(n)))
         return [int(v) for v in out[:n.value]]
 
+    # ---- candidate lists and matches (include/hydia.h) from computeSimilarity's scores: selected on the GPU behind the decoder.  The
+    # receiver sees every score here, as with Context.decrypt; indexScenario + decryptIndex stays the path that reveals only matches
+    def _handles(self, results):
+        if not isinstance(self.cc, Context):
+            raise HydiaError(-2, "hydia: candidate lists are decrypted on one context")
+        results = list(results)
+        if not results:
+            raise HydiaError(-1, "hydia: an empty list of results")
+        return results, (C.c_void_p * len(results))(*[r.h for r in results])
+
+    def decryptMatchesMulti(self, results, threshold, n_vectors=None, cap=None):
+        """one (idx, val, total) per result: the indices of the slots >= threshold among the first n_vectors (default all), ascending,
+        at most cap of them (default all), with their scores; total counts them all.  One library call and one synchronisation"""
+        results, hs = self._handles(results)
+        R, nv = len(results), int(n_vectors or 0)
+        cap = (nv or max(len(r) for r in results) * self.cc.slots) if cap is None else int(cap)
+        idx, val = np.zeros((R, max(cap, 1)), dtype=np.uint64), np.zeros((R, max(cap, 1)), dtype=np.float64)
+        total = np.zeros(R, dtype=np.uint64)
+        _chk(self.cc.L.hydia_decrypt_matches_multi(self.cc.h, hs, R, nv, float(threshold), _p(idx) if cap else None, _p(val) if cap else None,
+                                                   cap, _p(total)))
+        return [(idx[r, :min(cap, int(total[r]))].astype(np.int64), val[r, :min(cap, int(total[r]))].copy(), int(total[r])) for r in range(R)]
+
+    def decryptTopKMulti(self, results, k, n_vectors=None):
+        """one (idx, val) per result: its min(k, n) best slots among the first n_vectors (default all) by score descending, ties by
+        ascending index.  One library call and one synchronisation"""
+        results, hs = self._handles(results)
+        R, nv, k = len(results), int(n_vectors or 0), int(k)
+        room = max(1, min(k, nv or max(len(r) for r in results) * self.cc.slots))
+        # (rows are k entries apart in the library's layout; a k beyond every result's slots is clamped here, where it changes nothing)
+        kk = min(k, room) if k >= 1 else k
+        idx, val, got = np.zeros((R, room), dtype=np.uint64), np.zeros((R, room), dtype=np.float64), np.zeros(R, dtype=np.uint64)
+        _chk(self.cc.L.hydia_decrypt_topk_multi(self.cc.h, hs, R, nv, kk, _p(idx), _p(val), _p(got)))
+        return [(idx[r, :int(got[r])].astype(np.int64), val[r, :int(got[r])].copy()) for r in range(R)]
+
+    def decryptMatches(self, cts, threshold, n_vectors=None, cap=None):
+        """(idx, val, total) of one result (decryptMatchesMulti of one)"""
+        return self.decryptMatchesMulti([cts], threshold, n_vectors, cap)[0]
+
+    def decryptTopK(self, cts, k, n_vectors=None):
+        """(idx, val) of one result (decryptTopKMulti of one)"""
+        return self.decryptTopKMulti([cts], k, n_vectors)[0]
+
 
 class DiagonalSender:
     """include/sender_diag.h:5-28 — the three virtuals of include/sender.h:28-35."""
@@ -1297,6 +1388,14 @@ class DiagonalSender:
     def resultToWire(self, result_cipher):
         """a scenario's output as one wire message (bytes) for DiagonalReceiver.resultFromWire"""
         return result_cipher.to_wire()
+
+    def scoresToWire(self, scores, limbs=2):
+        """computeSimilarity's scores as one wire message of their first `limbs` limbs (1 or 2) for DiagonalReceiver.resultFromWire:
+        the decoder reads at most the first two limbs, so nothing the receiver decrypts changes with limbs=2, and limbs=1 halves
+        the message again at the precision of q_0 alone"""
+        if limbs not in (1, 2):
+            raise HydiaError(-1, "hydia: scoresToWire ships 1 or 2 limbs")
+        return self.cc.ct_limb_prefix(scores, limbs).to_wire()
 
     @staticmethod
     def _no_plain(what, *queries):

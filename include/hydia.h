@@ -159,6 +159,43 @@ int hydia_decrypt_membership(hydia_ctx *ctx, const hydia_ct *ct, int *result);
  * *n_out receives the number of matches; at most cap are written. */
 int hydia_decrypt_index(hydia_ctx *ctx, const hydia_ct *cts, size_t *out, size_t cap, size_t *n_out);
 
+/* ---- candidate lists and matches (an extension; the reference returns the comparator's booleans or every score).  A selection stage
+ * behind the decoder, on the GPU: the decoded slots stay in device memory and only what was asked for crosses to the host — the k best
+ * entries, or the entries at or above a threshold of the caller's choosing, never all slots.  Exact and deterministic: the same input
+ * gives the same output on every run.
+ * INDICES  index j + i * slots is slot j of ciphertext i: hydia_decrypt_index's rule, the order of hydia_decrypt's output.
+ * MATCHES  (threshold select) the indices i with v[i] >= threshold in ASCENDING order, optionally with their values.  *n_out always
+ *          receives the total count; at most cap entries are written.  The comparison is IEEE: -0.0 >= +0.0 holds, a NaN is never
+ *          selected.  idx_out == NULL counts only.
+ * TOP-K    the k largest values, by VALUE DESCENDING, TIES BY ASCENDING INDEX.  -0.0 ties with +0.0.  A NaN ranks below every number,
+ *          after -inf; NaNs tie with each other by index.  k >= n returns all n; *n_out = min(k, n).
+ * VALUES   bit for bit the doubles hydia_decrypt writes for those slots (val_out may be NULL).
+ * n_vectors  the decrypt entries search the first n_vectors slots only: the padding slots of the last block decode to noise around 0 and
+ *          would otherwise enter a top-k of negative scores.  0 = all count * slots; above that: HYDIA_ERR_ARG.
+ * BATCHES  the *_multi entries take n_results results (each a batch handle of its own count), enqueue them on the context's stream
+ *          result after result and read back after one synchronisation.  Row r of idx_out / val_out starts at r * cap (matches) or
+ *          r * k (top-k); n_out has n_results entries.
+ * DEVICE ARRAYS  hydia_decrypt_device leaves the decoded slots in the caller's device memory; the hydia_slots_* entries select from any
+ *          array of n doubles there.  The memory must be ordinary device memory of the context's GPU, complete (not being written on
+ *          another stream) at the call: host memory, another GPU or managed memory answers HYDIA_ERR_ARG.
+ * REFUSALS (HYDIA_ERR_ARG, outputs untouched): k == 0, n == 0, n above 2^31 - 1, a null n_out, a null handle, a null idx_out for top-k.
+ * TRUST    a receiver that asks for scores sees EVERY score, as with hydia_compute_similarity + hydia_decrypt today: these entries save
+ *          work, they hide nothing.  The fixed-threshold boolean path (hydia_index_scenario, then hydia_decrypt_index) remains the one
+ *          that reveals only matches.
+ * hydia_decrypt_index is hydia_decrypt_matches at threshold 1.0 over all slots without values; hydia_decrypt_membership reads one double. */
+int hydia_decrypt_device(hydia_ctx *ctx, const hydia_ct *ct, double *dev_out /* [count][slots], the context's GPU */);
+int hydia_slots_select_device(hydia_ctx *ctx, const double *dev_vals, size_t n, double threshold, size_t *idx_out,
+                              double *val_out /* may be NULL */, size_t cap, size_t *n_out);
+int hydia_slots_topk_device(hydia_ctx *ctx, const double *dev_vals, size_t n, size_t k, size_t *idx_out, double *val_out /* may be NULL */,
+                            size_t *n_out);
+int hydia_decrypt_matches(hydia_ctx *ctx, const hydia_ct *cts, size_t n_vectors, double threshold, size_t *idx_out, double *val_out,
+                          size_t cap, size_t *n_out);
+int hydia_decrypt_topk(hydia_ctx *ctx, const hydia_ct *cts, size_t n_vectors, size_t k, size_t *idx_out, double *val_out, size_t *n_out);
+int hydia_decrypt_matches_multi(hydia_ctx *ctx, const hydia_ct *const *results, uint32_t n_results, size_t n_vectors, double threshold,
+                                size_t *idx_out /* [n_results][cap] */, double *val_out, size_t cap, size_t *n_out /* [n_results] */);
+int hydia_decrypt_topk_multi(hydia_ctx *ctx, const hydia_ct *const *results, uint32_t n_results, size_t n_vectors, size_t k,
+                             size_t *idx_out /* [n_results][k] */, double *val_out, size_t *n_out /* [n_results] */);
+
 /* ---- enroller: DiagonalEnroller ---- */
 /* number of DB ciphertexts for n vectors (concatenateRows, src/enroller/enroller_diag.cpp:120-122) */
 size_t hydia_db_num_cts(const hydia_ctx *ctx, size_t n_vectors);

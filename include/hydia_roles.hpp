@@ -298,6 +298,39 @@ inline std::vector<double> decryptToVector(CryptoContext cc, Ciphertext ctxt) {
     return std::vector<double>(all.begin() + (size_t)ctxt.index * cc->info.slots,
                                all.begin() + (size_t)(ctxt.index + 1) * cc->info.slots);
 }
+// the reference's three-argument spelling (include/openFHE_wrapper.h): the key handle only says "this context's key"
+inline std::vector<double> decryptToVector(CryptoContext cc, PrivateKey, Ciphertext ctxt) { return decryptToVector(cc, ctxt); }
+// src/openFHE_wrapper.cpp:88-99: the slots of every ciphertext, one after the other (one decryption per distinct device batch)
+inline std::vector<double> decryptVectorToVector(CryptoContext cc, PrivateKey, std::vector<Ciphertext> ctxts) {
+    const size_t S = cc->info.slots;
+    std::vector<double> out(S * ctxts.size()), all;
+    const CtBatch *have = nullptr;
+    for (size_t i = 0; i < ctxts.size(); i++) {
+        if (!ctxts[i]) continue;
+        if (ctxts[i].batch.get() != have) {
+            have = ctxts[i].batch.get();
+            all.assign((size_t)have->count() * S, 0.0);
+            cc->check(hydia_decrypt(cc->h, have->h, all.data()), "decrypt");
+        }
+        std::copy(all.begin() + (size_t)ctxts[i].index * S, all.begin() + (size_t)(ctxts[i].index + 1) * S, out.begin() + i * S);
+    }
+    return out;
+}
+// src/openFHE_wrapper.cpp:74-77: one ciphertext of vec (padded with zeros to the slot count) under a fresh sampler key from the OS
+inline Ciphertext encryptFromVector(CryptoContext cc, PublicKey, std::vector<double> vec) {
+    uint8_t seed[32];
+    role_seed(seed, nullptr);
+    vec.resize(cc->info.slots, 0.0);
+    hydia_ct *out = nullptr;
+    if (!cc->check(hydia_encrypt(cc->h, vec.data(), 1, seed, 0, &out), "encryptFromVector")) return {};
+    return split_batch(cc, out)[0];
+}
+// src/openFHE_wrapper.cpp:143-185 (the comparator runs on the whole batch the ciphertext belongs to; returns the element of ctxt.index)
+inline Ciphertext chebyshevCompare(CryptoContext cc, Ciphertext ctxt, double delta, size_t signDepth) {
+    hydia_ct *out = nullptr;
+    if (!ctxt || !cc->check(hydia_chebyshev_compare(cc->h, ctxt.batch->h, delta, signDepth, &out), "chebyshevCompare")) return {};
+    return split_batch(cc, out)[ctxt.index];
+}
 // src/openFHE_wrapper.cpp:191-218: every dimension-th slot of every ciphertext, packed in order.  The ciphertexts must be the
 // elements 0 .. n-1 of ONE device batch, in order (what every role method here returns); otherwise an error and an empty result
 inline std::vector<Ciphertext> mergeCiphers(CryptoContext cc, std::vector<Ciphertext> &ctxts, size_t dimension) {
@@ -458,6 +491,19 @@ class DiagonalSender : public Sender {
         return r.empty() ? std::vector<Ciphertext>{} : r[0];
     }
     std::vector<uint8_t> resultToWire(const std::vector<Ciphertext> &result) { return toWire(cc, result); }
+    // computeSimilarity's scores as one message of their first `limbs` limbs (1 or 2): the decoder reads at most two, so with 2 the
+    // receiver decrypts the same doubles from a sixth of the bytes; with 1 it decodes from q_0 alone.  For resultFromWire
+    std::vector<uint8_t> scoresToWire(const std::vector<Ciphertext> &scores, uint32_t limbs = 2) {
+        if (scores.empty() || !scores[0] || scores[0].batch->count() != scores.size() || limbs < 1 || limbs > 2) {
+            cc->last_status = HYDIA_ERR_ARG;
+            std::cerr << "Error: scoresToWire takes the whole of one ciphertext batch and 1 or 2 limbs" << std::endl;
+            return {};
+        }
+        hydia_ct *view = nullptr;
+        if (!cc->check(hydia_ct_limb_prefix(cc->h, scores[0].batch->h, limbs, &view), "scoresToWire")) return {};
+        std::vector<uint8_t> message = toWire(cc, split_batch(cc, view));  // (the view is freed with its batch, before `scores`)
+        return message;
+    }
     std::vector<uint8_t> resultToWire(const Ciphertext &result) {
         if (!result || result.batch->count() != 1) {
             cc->last_status = HYDIA_ERR_ARG;
@@ -757,6 +803,54 @@ class DiagonalReceiver : public HersReceiver {
         return ok;
     }
     std::vector<Ciphertext> resultFromWire(const std::vector<uint8_t> &message) { return fromWire(cc, message); }
+    // Candidate lists and matches (an extension; hydia.h) from computeSimilarity's scores, selected on the GPU behind the decoder: only
+    // the entries asked for reach the host.  Index j + i * slots is slot j of ciphertext i, decryptIndex's rule.  nVectors restricts the
+    // search to the first nVectors slots (0: all) and keeps the padding slots of the last block out of a top-k.  The receiver sees
+    // every score here, as with decryptToVector; indexScenario + decryptIndex stays the path that reveals only matches.
+    // A Candidates is empty with total 0 on failure (cc->last_status says why)
+    struct Candidates {
+        std::vector<size_t> index;
+        std::vector<double> value;
+        size_t total = 0;  // matches: how many slots are at or above the threshold (index holds at most cap of them); top-k: index.size()
+    };
+    // the slots >= threshold in ascending index order, at most cap of them (0: all), with their scores
+    Candidates decryptMatches(std::vector<Ciphertext> &scores, double threshold, size_t nVectors = 0, size_t cap = 0) {
+        std::vector<std::vector<Ciphertext>> one{scores};
+        std::vector<Candidates> r = decryptMatchesMulti(one, threshold, nVectors, cap);
+        return r.empty() ? Candidates{} : r[0];
+    }
+    // the k best slots by score descending, ties by ascending index (-0.0 ties with +0.0, a NaN ranks last)
+    Candidates decryptTopK(std::vector<Ciphertext> &scores, size_t k, size_t nVectors = 0) {
+        std::vector<std::vector<Ciphertext>> one{scores};
+        std::vector<Candidates> r = decryptTopKMulti(one, k, nVectors);
+        return r.empty() ? Candidates{} : r[0];
+    }
+    // a batch of results in one library call: enqueued result after result, read back after one synchronisation
+    std::vector<Candidates> decryptMatchesMulti(std::vector<std::vector<Ciphertext>> &results, double threshold, size_t nVectors = 0, size_t cap = 0) {
+        std::vector<const hydia_ct *> h;
+        size_t most = 0;
+        if (!result_handles(results, h, most, "decryptMatchesMulti")) return {};
+        if (cap == 0) cap = nVectors ? nVectors : most;
+        const size_t R = h.size();
+        std::vector<size_t> idx(R * cap), n(R);
+        std::vector<double> val(R * cap);
+        if (!cc->check(hydia_decrypt_matches_multi(cc->h, h.data(), (uint32_t)R, nVectors, threshold, idx.data(), val.data(), cap, n.data()),
+                       "decryptMatchesMulti"))
+            return {};
+        return rows_of(idx, val, n, cap, true);
+    }
+    std::vector<Candidates> decryptTopKMulti(std::vector<std::vector<Ciphertext>> &results, size_t k, size_t nVectors = 0) {
+        std::vector<const hydia_ct *> h;
+        size_t most = 0;
+        if (!result_handles(results, h, most, "decryptTopKMulti")) return {};
+        if (k > most) k = most;  // (rows are k entries apart; no result has more than `most` slots)
+        const size_t R = h.size();
+        std::vector<size_t> idx(R * (k ? k : 1)), n(R);
+        std::vector<double> val(R * (k ? k : 1));
+        if (!cc->check(hydia_decrypt_topk_multi(cc->h, h.data(), (uint32_t)R, nVectors, k, idx.data(), val.data(), n.data()), "decryptTopKMulti"))
+            return {};
+        return rows_of(idx, val, n, k, false);
+    }
     // The switching key of a re-keyed database (hydia_keygen_switch; no counterpart in the reference): from the OLD receiver's secret
     // (oldSecret, [n_q+n_p][N] as hydia_export_secret_key gives it) to THIS receiver's, for DiagonalEnroller::rekeyDB.  Treat it like an
     // evaluation key.  seed32 == nullptr draws a fresh sampler key from the OS (use a fresh one per switching key).  Empty on failure.
@@ -810,6 +904,34 @@ class DiagonalReceiver : public HersReceiver {
         q.count = count;
         q.c0.resize(count * (size_t)cc->info.n_q * cc->info.n);
         return true;
+    }
+    // the batch handle of every result (each the whole of one device batch) and the slots of the largest
+    bool result_handles(const std::vector<std::vector<Ciphertext>> &results, std::vector<const hydia_ct *> &h, size_t &most, const char *what) {
+        bool ok = !cc->group && !results.empty();
+        for (size_t r = 0; ok && r < results.size(); r++) {
+            ok = !results[r].empty() && (bool)results[r][0] && results[r][0].batch->count() == results[r].size();
+            if (ok) {
+                h.push_back(results[r][0].batch->h);
+                most = std::max(most, results[r].size() * (size_t)cc->info.slots);
+            }
+        }
+        if (!ok) {
+            cc->last_status = cc->group ? HYDIA_ERR_STATE : HYDIA_ERR_ARG;
+            std::cerr << "Error: " << what << ": "
+                      << (cc->group ? "candidate lists are decrypted on one context" : "every result is the whole of one ciphertext batch") << std::endl;
+        }
+        return ok;
+    }
+    std::vector<Candidates> rows_of(const std::vector<size_t> &idx, const std::vector<double> &val, const std::vector<size_t> &n, size_t stride,
+                                    bool counted) {
+        std::vector<Candidates> out(n.size());
+        for (size_t r = 0; r < n.size(); r++) {
+            const size_t w = std::min(n[r], stride);
+            out[r].index.assign(idx.begin() + r * stride, idx.begin() + r * stride + w);
+            out[r].value.assign(val.begin() + r * stride, val.begin() + r * stride + w);
+            out[r].total = counted ? n[r] : w;
+        }
+        return out;
     }
 };
 
