@@ -683,6 +683,65 @@ void client_db_update_device(Context &cx, size_t first_vector, const DevRows &ro
     update_blocks(cx, first_vector, src, rows.n, &key, first_block);
 }
 
+// The enroller's half of update_blocks, for a database that lies on ANOTHER machine (hydia_db_delta_make): per touched block the same
+// diag_pack (form `babies`) and encrypt_device under the enrolment's nonces, then k_wire_pack straight from the block buffer and a copy
+// of the packed rows to host memory at payload0 + b * stride for the b-th touched block.  Needs the public key alone; the resident database, if there
+// is one, is neither read nor written.  One block is in flight at a time.
+static void check_delta_nonces(const Context &cx, size_t first_vector, size_t n, size_t first_block) {
+    check_db_nonces(first_block, (first_vector + n + (size_t)cx.slots - 1) / (size_t)cx.slots, cx.prm.dim);
+}
+static void delta_blocks(Context &cx, size_t first_vector, const RowSource &src, size_t n, const ChaChaKey &key, int babies, size_t first_block,
+                         unsigned char *payload0, size_t stride) {
+    const int dim = cx.prm.dim, Nh = cx.slots;
+    const size_t end = first_vector + n, g0 = first_vector / (size_t)Nh, elems = (size_t)cx.nQ * cx.N;
+    const WireRows R = hc::wire_rows(cx.q.data(), cx.N, cx.nQ);
+    const size_t packed = (size_t)dim * 2 * R.off[cx.nQ] * sizeof(u64);
+    double *d_rows = (double *)cx.pool.get(sizeof(double) * (size_t)Nh * dim);
+    double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)dim * Nh);
+    u64 *d_out = cx.pool.get(sizeof(u64) * (size_t)dim * 2 * elems);
+    u64 *d_packed = cx.pool.get(packed);
+    struct Release {
+        Context &cx;
+        u64 *a, *b, *c, *d;
+        ~Release() {
+            cx.pool.put(d);
+            cx.pool.put(c);
+            cx.pool.put(b);
+            cx.pool.put(a);
+        }
+    } release{cx, (u64 *)d_rows, (u64 *)d_slots, d_out, d_packed};
+    for (size_t g = g0; g * (size_t)Nh < end; g++) {
+        const size_t lo = std::max(first_vector, g * (size_t)Nh), hi = std::min(end, (g + 1) * (size_t)Nh);
+        src.stage(cx, lo - first_vector, hi - lo, d_rows);
+        hc::diag_pack(cx.stream, d_rows, (long long)(hi - lo), dim, Nh, d_slots, (babies > 0 && babies < dim) ? babies : 0, (int)(lo - g * (size_t)Nh));
+        encrypt_device(cx, d_slots, dim, key, HY_DB_NONCE_BASE + (first_block + g) * dim, d_out);
+        cx.timer_begin("k_wire_pack");
+        hc::wire_pack(cx.stream, cx.d_mod, cx.N, d_out, 2 * elems, elems, (size_t)dim, 2, cx.nQ, R, d_packed);
+        cx.timer_end("k_wire_pack");
+        HIP_CHECK(hipMemcpyAsync(payload0 + (g - g0) * stride, d_packed, packed, hipMemcpyDeviceToHost, cx.stream));
+        cx.sync();  // the host buffer is the caller's; the block buffers are reused by the next block
+    }
+}
+void client_db_delta_make(Context &cx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32], int babies,
+                          size_t first_block, unsigned char *payload0, size_t stride) {
+    const int dim = cx.prm.dim;
+    check_delta_nonces(cx, first_vector, n, first_block);  // (a refused call leaves the rows as they were)
+    if (normalise)
+        for (size_t v = 0; v < n; v++) normalize(rows + v * dim, dim);
+    RowSource src;
+    src.host = rows;
+    delta_blocks(cx, first_vector, src, n, make_key(seed), babies, first_block, payload0, stride);
+}
+void client_db_delta_make_device(Context &cx, size_t first_vector, const DevRows &rows, int normalise, const uint8_t seed[32], int babies,
+                                 size_t first_block, unsigned char *payload0, size_t stride) {
+    RowSource src;
+    src.dev = &rows;
+    src.normalise = normalise;
+    check_delta_nonces(cx, first_vector, rows.n, first_block);
+    wait_for_producer(cx, rows.stream);
+    delta_blocks(cx, first_vector, src, rows.n, make_key(seed), babies, first_block, payload0, stride);
+}
+
 // In-place update of a resident PLAIN gallery (kind 7 / 8): the update loop with encode_device in place of encrypt_device — no seed,
 // no nonce.  The encoder rounds once per update, and symmetrically: encode(-x) + encode(x) = 0 in every residue, so the negated rows
 // restore an existing block exactly.

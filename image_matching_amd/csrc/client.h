@@ -86,6 +86,12 @@ void client_enroll_device(Context &cx, const DevRows &rows, const uint8_t seed[3
 void client_plain_enroll_device(Context &cx, const DevRows &rows, int babies);
 void client_db_update_device(Context &cx, size_t first_vector, const DevRows &rows, int normalise, const uint8_t seed[32], size_t first_block = 0);
 void client_plain_db_update_device(Context &cx, size_t first_vector, const DevRows &rows, int normalise);
+// a database delta (hydia_db_delta_make): the fresh encryptions E client_db_update would add, block by block, as the packed payloads of
+// CT_BATCH messages in HOST memory — the b-th touched block's at payload0 + b * stride.  Public key only; no database is touched
+void client_db_delta_make(Context &cx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32], int babies,
+                          size_t first_block, unsigned char *payload0, size_t stride);
+void client_db_delta_make_device(Context &cx, size_t first_vector, const DevRows &rows, int normalise, const uint8_t seed[32], int babies,
+                                 size_t first_block, unsigned char *payload0, size_t stride);
 // one handle per probe: query i = client_encrypt_query(row i, seed, nonce0 + i) / client_encode_query(row i), bit for bit
 std::vector<Ct> client_encrypt_queries_device(Context &cx, const DevRows &rows, const uint8_t seed[32], uint64_t nonce0);
 std::vector<Ct> client_encode_queries_device(Context &cx, const DevRows &rows);

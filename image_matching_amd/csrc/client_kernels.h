@@ -75,4 +75,11 @@ void wire_pack(hipStream_t st, const ModC *mod, int N, const u64 *src, size_t it
                int nl, const WireRows &R, u64 *dst);
 void wire_unpack_check(hipStream_t st, const ModC *mod, int N, const u64 *src, u64 *dst, size_t item_stride, size_t poly_stride, size_t items,
                        int npoly, int nl, const WireRows &R, unsigned *flag);
+// the range check of wire_unpack_check alone: packed rows [items][npoly][R.off[nl]] words are read, nothing is written but *flag
+void wire_check(hipStream_t st, const ModC *mod, int N, const u64 *src, size_t items, int npoly, int nl, const WireRows &R, unsigned *flag);
+// one block of a database delta: resident ciphertexts t0 .. t0 + X - 1 += (store: :=) the packed rows [X][2][R.off[nQ]] words at src,
+// mod q_j, in one pass (k_db_accumulate_wire / k_db_store_wire, and their 46-bit forms for the packed limbs of a bits46 layout).  The
+// rows are canonical (wire_check) and L describes a ciphertext database
+void db_wire(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *src, const WireRows &R, void *db, size_t t0, int X, const DbLayout &L,
+             bool store);
 }  // namespace hc

@@ -1,13 +1,17 @@
 // image_matching_amd/csrc/wire_kernels.hip — gfx950 kernels of the wire format (wire_format.h, include/hydia.h "wire messages"): residues
 // packed into the bit length of their modulus on the way out, unpacked and range-checked on the way in.
 //
-// Pure data movement.  The unit of both kernels is the GRANULE: 64 consecutive residues of one limb = exactly w 64-bit words of the
-// packed row (w = the bit length of q_j, wave-uniform, read from ModC at run time — one kernel serves every width).  One wave owns one
+// Further down: the range check alone (k_wire_check) and the kernels that take the packed rows of a database delta straight to the
+// resident database (k_db_accumulate_wire, k_db_store_wire; include/hydia.h "database deltas").
+//
+// Pack and unpack are pure data movement.  The unit of both kernels is the GRANULE: 64 consecutive residues of one limb = exactly
+// w 64-bit words of the packed row (w = the bit length of q_j, wave-uniform, read from ModC at run time — one kernel serves every width).  One wave owns one
 // granule, so no two waves ever write one word and the pack needs no atomics.  Both sides of a granule are coalesced: lane c loads /
 // stores residue c (512 contiguous bytes per wave), lane k < w stores / loads word k (8 w contiguous bytes); the bit gather between
 // the two goes through a 512-byte LDS tile per wave.  A word holds pieces of at most ceil(64 / w) + 1 residues (three for the 45 .. 60
 // bit limbs of this library's chains); the gather loop is general in w.
 #include "client_kernels.h"
+#include "db_accum.h"  // the per-granule arithmetic of an in-place update (host-checkable), shared with k_db_accumulate / k_db_accumulate46
 
 #include <stdexcept>
 
@@ -54,6 +58,110 @@ __global__ __launch_bounds__(256) void k_wire_unpack_check(const ModC *__restric
     if (__syncthreads_or(v >= q) && threadIdx.x == 0) *flag = 1u;
 }
 
+// the range check alone, for a message that is applied only after ALL of it passed (a database delta): same grid, same granule, same
+// flag as k_wire_unpack_check; no destination is written
+__global__ __launch_bounds__(256) void k_wire_check(const ModC *__restrict__ mod, const u64 *__restrict__ src, WireRows R,
+                                                    unsigned *__restrict__ flag) {
+    __shared__ u64 tile[4][64];
+    const int j = blockIdx.y, z = blockIdx.z, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const size_t g = (size_t)blockIdx.x * 4 + wave;
+    const u64 q = mod[j].q;
+    const int w = 64 - __clzll((long long)q);
+    const u64 mask = w == 64 ? ~0ull : (1ull << w) - 1;
+    if (lane < w) tile[wave][lane] = src[(size_t)z * R.off[gridDim.y] + R.off[j] + g * w + lane];
+    __syncthreads();
+    const int k = (lane * w) >> 6, off = (lane * w) & 63;
+    u64 v = tile[wave][k] >> off;
+    if (off + w > 64) v |= tile[wave][k + 1] << (64 - off);
+    v &= mask;
+    if (__syncthreads_or(v >= q) && threadIdx.x == 0) *flag = 1u;
+}
+
+// residue r of a run of whole granules held in LDS from its first word on: bits [r w, (r + 1) w) of the run (the run ends with a
+// residue, so tile[k + 1] exists whenever the field crosses a word)
+__device__ __forceinline__ u64 wire_field(const u64 *tile, int r, int w, u64 mask) {
+    const int bit = r * w, k = bit >> 6, off = bit & 63;
+    u64 v = tile[k] >> off;
+    if (off + w > 64) v |= tile[k + 1] << (64 - off);
+    return v & mask;
+}
+// Packed wire rows of ONE block -> the resident database, in one pass: ciphertexts t0 .. t0 + X - 1 += (STORE: :=) the rows
+// [X][2][nQ] of a CT_BATCH payload, mod q_j.  No unpacked copy of the block in HBM: a workgroup loads the packed words of its PER * 256
+// residues (whole granules, contiguous, coalesced) into LDS, and every thread gathers the residues of the database granule it OWNS —
+// k_db_repack's map, a residue pair (PER = 2; 16 or 12 bytes), or k_db_repack46's, sixteen 46-bit residues = 23 dwords (PER = 16) —
+// and runs db_accum.h's read-add-reduce-write on it (db_offset: either placement).  One thread owns every dword of the database it
+// reads and writes: no atomics.  The residues were range-checked beforehand (k_wire_check): both operands are reduced.
+// grid (ceil(N / (PER 256)), limbs, X * 2); limb j = blockIdx.y + j0
+template <bool STORE, int PER>
+__device__ __forceinline__ void db_wire_body(u64 *tile, const ModC *__restrict__ mod, int N, int nQ, const u64 *__restrict__ src, WireRows R,
+                                             unsigned char *__restrict__ db, const DbLayout &L, size_t t0, int j0) {
+    const int j = blockIdx.y + j0, xp = blockIdx.z, x = xp >> 1, p = xp & 1;
+    const u64 q = mod[j].q;
+    const int w = 64 - __clzll((long long)q);
+    const u64 mask = w == 64 ? ~0ull : (1ull << w) - 1;
+    const size_t c0 = (size_t)blockIdx.x * (PER * 256);                     // first residue of the workgroup (a multiple of 64)
+    const int span = (int)((size_t)N - c0 < (size_t)(PER * 256) ? (size_t)N - c0 : (size_t)(PER * 256));  // its residues (N is a multiple of 512)
+    const u64 *row = src + (size_t)xp * R.off[nQ] + R.off[j] + (c0 >> 6) * w;
+    for (int k = threadIdx.x; k < (span >> 6) * w; k += 256) tile[k] = row[k];
+    __syncthreads();
+    const int r0 = threadIdx.x * PER;
+    if (r0 >= span) return;
+    unsigned char *d = db + db_offset(L, N, t0 + x, p, j, c0 + r0);
+    if (PER == 2) {
+        const u64 ax = wire_field(tile, r0, w, mask), ay = wire_field(tile, r0 + 1, w, mask);
+        const bool pk = L.packed && j > 0;
+        if (!STORE) {
+            db_accumulate_pair(d, pk, ax, ay, q);
+        } else if (pk) {
+            unsigned v[3];
+            db_pack_pair48(ax, ay, v);
+            unsigned *o = reinterpret_cast<unsigned *>(d);
+            o[0] = v[0];
+            o[1] = v[1];
+            o[2] = v[2];
+        } else {
+            reinterpret_cast<u64 *>(d)[0] = ax;
+            reinterpret_cast<u64 *>(d)[1] = ay;
+        }
+    } else {
+        u64 a[16];
+#pragma unroll
+        for (int r = 0; r < 16; r++) a[r] = wire_field(tile, r0 + r, w, mask);
+        unsigned *o = reinterpret_cast<unsigned *>(d);
+        if (!STORE) {
+            db_accumulate_granule46(o, a, q);
+        } else {
+            unsigned v[23];
+            db_pack_granule46(a, v);
+#pragma unroll
+            for (int k = 0; k < 23; k++) o[k] = v[k];
+        }
+    }
+}
+// the 8-byte and 6-byte residues (limb 0, every limb of a 48-bit or unpacked layout): 512 residues = 8 granules <= 512 words per workgroup
+__global__ __launch_bounds__(256) void k_db_accumulate_wire(const ModC *__restrict__ mod, int N, int nQ, const u64 *__restrict__ src, WireRows R,
+                                                            unsigned char *__restrict__ db, DbLayout L, size_t t0) {
+    __shared__ u64 tile[512];
+    db_wire_body<false, 2>(tile, mod, N, nQ, src, R, db, L, t0, 0);
+}
+__global__ __launch_bounds__(256) void k_db_store_wire(const ModC *__restrict__ mod, int N, int nQ, const u64 *__restrict__ src, WireRows R,
+                                                       unsigned char *__restrict__ db, DbLayout L, size_t t0) {
+    __shared__ u64 tile[512];
+    db_wire_body<true, 2>(tile, mod, N, nQ, src, R, db, L, t0, 0);
+}
+// the 46-bit limbs of a bits46 layout (q_j < 2^46, so w <= 46): 4096 residues = 64 granules <= 2944 words per workgroup; limb j =
+// blockIdx.y + 1
+__global__ __launch_bounds__(256) void k_db_accumulate_wire46(const ModC *__restrict__ mod, int N, int nQ, const u64 *__restrict__ src, WireRows R,
+                                                              unsigned char *__restrict__ db, DbLayout L, size_t t0) {
+    __shared__ u64 tile[64 * 46];
+    db_wire_body<false, 16>(tile, mod, N, nQ, src, R, db, L, t0, 1);
+}
+__global__ __launch_bounds__(256) void k_db_store_wire46(const ModC *__restrict__ mod, int N, int nQ, const u64 *__restrict__ src, WireRows R,
+                                                         unsigned char *__restrict__ db, DbLayout L, size_t t0) {
+    __shared__ u64 tile[64 * 46];
+    db_wire_body<true, 16>(tile, mod, N, nQ, src, R, db, L, t0, 1);
+}
+
 }  // namespace
 
 namespace hc {
@@ -83,6 +191,35 @@ void wire_unpack_check(hipStream_t st, const ModC *mod, int N, const u64 *src, u
         const size_t n = items - i0 < per ? items - i0 : per;
         hipLaunchKernelGGL(k_wire_unpack_check, dim3(N / 256, nl, (unsigned)(n * npoly)), dim3(256), 0, st, mod, N,
                            src + i0 * npoly * R.off[nl], R, dst + i0 * item_stride, item_stride, poly_stride, npoly, flag);
+    }
+}
+
+void wire_check(hipStream_t st, const ModC *mod, int N, const u64 *src, size_t items, int npoly, int nl, const WireRows &R, unsigned *flag) {
+    hk::ledger_add("k_wire_check", (double)items * npoly * (double)R.off[nl] * 8);
+    const size_t per = 65535 / (size_t)npoly;
+    for (size_t i0 = 0; i0 < items; i0 += per) {
+        const size_t n = items - i0 < per ? items - i0 : per;
+        hipLaunchKernelGGL(k_wire_check, dim3(N / 256, nl, (unsigned)(n * npoly)), dim3(256), 0, st, mod, src + i0 * npoly * R.off[nl], R, flag);
+    }
+}
+// X <= 32767 ciphertexts of two polynomials on all nQ limbs (one block of a database: X = vector_dim)
+void db_wire(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *src, const WireRows &R, void *db, size_t t0, int X, const DbLayout &L,
+             bool store) {
+    if (L.plain || X < 1 || X > 32767 || N < 512 || N % 512) throw std::runtime_error("hydia: db_wire: bad shape");
+    const bool b46 = L.bits46 && L.packed;
+    if (b46)
+        for (int j = 1; j < nQ; j++)
+            if (R.off[j + 1] - R.off[j] > (unsigned)(N / 64) * 46u) throw std::runtime_error("hydia: db_wire: a limb wider than 46 bits in a 46-bit layout");
+    // resident bytes (read and) written + the packed bytes read
+    hk::ledger_add(store ? "k_db_store_wire" : "k_db_accumulate_wire", (double)X * ((store ? 1.0 : 2.0) * L.ct_bytes + 2.0 * R.off[nQ] * 8));
+    const dim3 g2(N / 512, b46 ? 1 : nQ, X * 2), g16((N + 4095) / 4096, nQ - 1, X * 2);
+    unsigned char *d = (unsigned char *)db;
+    if (store) {
+        hipLaunchKernelGGL(k_db_store_wire, g2, dim3(256), 0, st, mod, N, nQ, src, R, d, L, t0);
+        if (b46 && nQ > 1) hipLaunchKernelGGL(k_db_store_wire46, g16, dim3(256), 0, st, mod, N, nQ, src, R, d, L, t0);
+    } else {
+        hipLaunchKernelGGL(k_db_accumulate_wire, g2, dim3(256), 0, st, mod, N, nQ, src, R, d, L, t0);
+        if (b46 && nQ > 1) hipLaunchKernelGGL(k_db_accumulate_wire46, g16, dim3(256), 0, st, mod, N, nQ, src, R, d, L, t0);
     }
 }
 

@@ -36,6 +36,11 @@ class _Info(C.Structure):
         ("delta", C.c_double)]
 
 
+class _DeltaInfo(C.Structure):  # hydia_db_delta_info
+    _fields_ = [("version", C.c_uint32), ("vector_dim", C.c_uint32)] + [
+        (n, C.c_uint64) for n in ("babies", "first_vector", "n_rows", "first_block", "n_blocks", "total_bytes")]
+
+
 class _WireInfo(C.Structure):  # hydia_wire_info
     _fields_ = [(n, C.c_uint32) for n in ("type", "log_n", "n_polys", "n_limbs", "rot", "reserved")] + [
         ("count", C.c_uint64), ("scale", C.c_double), ("a_seed", C.c_uint8 * 32), ("nonce0", C.c_uint64), ("header_bytes", C.c_uint64),
@@ -162,6 +167,11 @@ def load_library():
         "hydia_key_from_wire": (i32, [vp, vp, sz, C.POINTER(i32)]),
         "hydia_keys_save": (i32, [vp, C.c_char_p, i32]),
         "hydia_keys_load": (i32, [vp, C.c_char_p]),
+        "hydia_db_delta_bytes": (i32, [vp, sz, sz, C.POINTER(sz)]),
+        "hydia_db_delta_peek": (i32, [vp, sz, C.POINTER(_DeltaInfo)]),
+        "hydia_db_delta_make": (i32, [vp, sz, vp, sz, i32, vp, i32, sz, vp, sz, C.POINTER(sz)]),
+        "hydia_db_delta_make_device": (i32, [vp, sz, C.POINTER(_DevRows), i32, vp, i32, sz, vp, sz, C.POINTER(sz)]),
+        "hydia_db_delta_apply": (i32, [vp, vp, sz]),
         "hydia_compute_similarity_gallery_multi": (i32, [vp, vp, u32, vp]),
         "hydia_index_scenario_gallery_multi": (i32, [vp, vp, u32, vp]),
         "hydia_membership_scenario_gallery_multi": (i32, [vp, vp, u32, vp]),
@@ -395,6 +405,15 @@ def wire_peek(message):
     d = {k: getattr(info, k) for k, _ in _WireInfo._fields_}
     d["a_seed"] = bytes(info.a_seed)
     return d
+
+
+def db_delta_peek(message):
+    """Host-only (hydia_db_delta_peek): the context-free validation of a database delta and what its header says — a dict of version,
+    vector_dim, babies, first_vector, n_rows, first_block, n_blocks, total_bytes.  A malformed delta: HydiaError(-1) naming the field."""
+    raw = np.frombuffer(bytes(message), dtype=np.uint8)
+    info = _DeltaInfo()
+    _chk(load_library().hydia_db_delta_peek(_p(raw) if raw.size else None, raw.size, C.byref(info)))
+    return {k: int(getattr(info, k)) for k, _ in _DeltaInfo._fields_}
 
 
 def _wire_out(call):
@@ -918,6 +937,40 @@ class Context:
         assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.ndim == 2 and rows.shape[1] == self.dim
         _chk(self.L.hydia_db_update_shard(self.h, first_vector, _p(rows), rows.shape[0], 1 if normalise else 0, _p(_seed(seed)), first_block))
 
+    # ---- database deltas (include/hydia.h): the enroller's context makes the message, the sender's applies it
+    def db_delta_bytes(self, first_vector, n):
+        """the size of the delta of rows first_vector .. first_vector + n - 1 on this context (host arithmetic only)"""
+        b = C.c_size_t()
+        _chk(self.L.hydia_db_delta_bytes(self.h, first_vector, n, C.byref(b)))
+        return b.value
+
+    def db_delta_peek(self, message):
+        """the module's db_delta_peek (context-free, host only)"""
+        return db_delta_peek(message)
+
+    def db_delta_make(self, first_vector, rows, normalise=True, seed=None, babies=None, first_block=0):
+        """hydia_db_delta_make[_device]: the FRESH encryption of `rows` (k x vector_dim float64, normalised IN PLACE when `normalise`; or
+        a tensor on the context's GPU, never written) that db_update would add at vectors first_vector .., as one message (bytes) for
+        the db_delta_apply of the context that holds the database.  Needs the public key alone.  babies: the form of the TARGET
+        database (None = vector_dim, hoisted).  seed=None draws a fresh key from the OS — a seed must NEVER be used twice on one
+        database (include/hydia.h)."""
+        B = self.dim if babies is None else int(babies)
+        sd = _seed(seed)  # ONE seed for the sizing call and the making call
+        if _is_device_tensor(rows):
+            d = _dev_rows(self, rows)
+            return _wire_out(lambda buf, cap, n: self.L.hydia_db_delta_make_device(self.h, first_vector, C.byref(d), 1 if normalise else 0,
+                                                                                  _p(sd), B, first_block, buf, cap, n))
+        assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.ndim == 2 and rows.shape[1] == self.dim
+        return _wire_out(lambda buf, cap, n: self.L.hydia_db_delta_make(self.h, first_vector, _p(rows), rows.shape[0], 1 if normalise else 0,
+                                                                       _p(sd), B, first_block, buf, cap, n))
+
+    def db_delta_apply(self, message):
+        """hydia_db_delta_apply: add the delta's ciphertexts to the resident kind-5 / kind-6 database (bit for bit what db_update with
+        the maker's arguments leaves), or enrol from it when nothing is resident and it starts at vector 0.  Every header and residue
+        is checked first: a refused delta (HydiaError) changes nothing."""
+        raw = np.frombuffer(bytes(message), dtype=np.uint8)
+        _chk(self.L.hydia_db_delta_apply(self.h, _p(raw) if raw.size else None, raw.size))
+
     # ---- templates already in device memory (include/hydia.h, hydia_dev_rows): `rows` is a tensor on this context's GPU, only read
     def rows_widen_device(self, rows, normalise=True):
         """hydia_rows_widen_device: the rows widened exactly to float64 (and divided by their L2 norm), as a new tensor [n][vector_dim]"""
@@ -1083,6 +1136,34 @@ class DiagonalEnroller:
     def appendDB(self, rows, seed=None):
         """append `rows` (normalised in place) after the last enrolled vector"""
         self.updateRows(self.numVectors, rows, True, seed)
+
+    # ---- database deltas (include/hydia.h): this enroller holds the public key only; the database lies on the sender's machine
+    def _one_context(self):
+        if not isinstance(self.cc, Context):
+            raise HydiaError(-2, "hydia: database deltas are not made on a sharded context (make one per shard context, with its first_block)")
+
+    def updateToWire(self, first_vector, rows, normalise=True, seed=None, babies=None, first_block=0):
+        """updateRows for a database on ANOTHER machine: the update as one delta message (Context.db_delta_make) for
+        DiagonalSender.applyDBWire.  Nothing resident on this context is touched; numVectors follows as in updateRows."""
+        self._one_context()
+        m = self.cc.db_delta_make(first_vector, rows, normalise, seed, babies, first_block)
+        self.numVectors = max(self.numVectors, first_vector + rows.shape[0])
+        return m
+
+    def appendToWire(self, rows, n_resident, seed=None, babies=None, first_block=0):
+        """append `rows` (normalised in place) after the n_resident vectors the sender's database holds"""
+        return self.updateToWire(n_resident, rows, True, seed, babies, first_block)
+
+    def serializeDBToWire(self, database, seed=None, babies=None, first_block=0):
+        """serializeDB for a sender on another machine: yields one delta message per 'slots'-vector block, in order; the first enrols
+        on an empty sender context, every later one appends.  ONE seed for the whole database (None: drawn once from the OS), as
+        an enrolment uses — the blocks differ in their nonces.  `database` is normalised IN PLACE (a tensor is never written)."""
+        self._one_context()
+        n, slots = database.shape[0], self.cc.N // 2
+        sd = bytes(_seed(seed))
+        for lo in range(0, n, slots):
+            yield self.cc.db_delta_make(lo, database[lo:lo + slots], True, sd, babies, first_block)
+        self.numVectors = n
 
     def rekeyDB(self, key):
         """Re-key the enrolled database in place (Context.db_rekey) with the switching key DiagonalReceiver.genSwitchKey of the NEW
@@ -1373,6 +1454,15 @@ class DiagonalSender:
     def importKeysWire(self, path):
         """DiagonalReceiver.exportKeysWire's file into this context (hydia_keys_load; not transactional)"""
         self.cc.keys_load(path)
+
+    def applyDBWire(self, message):
+        """a delta message of DiagonalEnroller.updateToWire / appendToWire / serializeDBToWire into this sender's database
+        (Context.db_delta_apply: checked, transactional); returns the new vector count, which numVectors follows"""
+        if not isinstance(self.cc, Context):
+            raise HydiaError(-2, "hydia: database deltas are not applied on a sharded context (apply one per shard context)")
+        self.cc.db_delta_apply(message)
+        self.numVectors = self.cc.db_stats()[0]
+        return self.numVectors
 
     def queryFromWire(self, message):
         """a query message -> what expandQuery / Context.import_ct return, ready for every single, *Multi and *GalleryMulti method: a

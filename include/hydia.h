@@ -641,6 +641,69 @@ int hydia_key_to_wire(hydia_ctx *ctx, int rot, int seeded, void *buf, size_t cap
 int hydia_key_from_wire(hydia_ctx *ctx, const void *buf, size_t len, int *rot_out);
 int hydia_keys_save(hydia_ctx *ctx, const char *path, int seeded);
 int hydia_keys_load(hydia_ctx *ctx, const char *path);
+/* ---- database deltas (an extension; the reference's enroller writes serial/db_diagonal/index<t>.bin for the sender to read —
+ * INTEGRATION.md maps them): the enroller-to-sender hand-off as a checked message of CIPHERTEXTS.
+ * TRUST MODEL: the enroller holds the templates and the receiver's PUBLIC key and nothing else; the sender holds the encrypted
+ * database and never sees a template.  hydia_db_update needs both on one context.  A delta cuts it in two: hydia_db_delta_make, on the
+ * ENROLLER's context, makes the fresh encryption E of the rows' sparse diagonal image that hydia_db_update would add (public key only:
+ * no secret key, no evaluation key, no database — one that happens to be resident is neither read nor written);
+ * hydia_db_delta_apply, on the SENDER's context, adds E to the resident blocks (database only: no key, no plaintext).  The database
+ * is afterwards BIT FOR BIT what hydia_db_update(first_vector, rows, n, normalise, seed) leaves on it.  With no database resident a
+ * delta at first_vector = 0 ENROLS: the result is bit for bit hydia_db_enroll_shard_ex's on the same rows, seed, first_block and form.
+ * NOT AUTHENTICATED, like every wire message: whoever can hand the sender a delta can change its database; transport security is
+ * the caller's.  What the library guarantees is that a delta it accepts is well-formed and canonical and that a refused one changes
+ * nothing.
+ * SEED: the seed of a delta MUST NEVER HAVE BEEN USED ON THIS DATABASE BEFORE — not by its enrolment, not by an earlier update or
+ * delta.  The nonces are the enrolment's, so a reused seed encrypts a changed plaintext under the same randomness and the difference
+ * of the two ciphertexts reveals the difference of the plaintexts.  Take every delta's seed from hydia_random_seed.
+ * FORMAT (little-endian).  NOT a wire type — a container of its own, like the key-set file: a 64-byte header, then n_blocks ordinary
+ * type 1 (ciphertext batch) wire messages back to back, nothing after the last.
+ *   header   offset 0 magic "HYDDELT1" | 8 u32 version = 1 | 12 u32 vector_dim | 16 u64 babies: the form of the target database,
+ *            vector_dim (hoisted) or a power of two >= 2 dividing it | 24 u64 first_vector | 32 u64 n_rows | 40 u64 first_block
+ *            (recorded for diagnosis: the nonce offset the maker used) | 48 u64 n_blocks | 56 u64 reserved = 0
+ *   message b is block first_vector / slots + b: count = vector_dim, n_polys = 2, n_limbs = n_q, scale = 2^scale_bits; ciphertext i of
+ *            it is E for database ciphertext block * vector_dim + i.
+ * At the default parameters a block's message is 2 353 004 904 bytes against 2 390 753 280 resident (group-sequential, 46-bit);
+ * hydia_db_save would ship the whole database for every change.
+ * VALIDATION reads the container header and the 360-byte headers of the messages only, before anything is allocated or uploaded,
+ * with overflow-checked arithmetic; each refusal is HYDIA_ERR_ARG with a message naming the field: magic, version, reserved,
+ * vector_dim, babies, n_rows == 0, n_blocks other than the blocks first_vector .. first_vector + n_rows - 1 touch, a message that
+ * fails the wire validation against the context or is not of exactly the shape above, a total length that is not exact (truncated, or
+ * bytes after the last message).
+ *   hydia_db_delta_bytes   the size of a delta for rows first_vector .. first_vector + n - 1 on this context (host arithmetic only);
+ *                          n == 0 or a size that overflows: HYDIA_ERR_ARG
+ *   hydia_db_delta_peek    the context-free part of the validation, without a GPU: the header fields and the total bytes
+ *   hydia_db_delta_make    normalise as in hydia_db_update (rows normalised IN PLACE); babies = the form of the target database
+ *                          (hydia_db_babies of the sender's; vector_dim = hoisted); first_block = the nonce offset (0 unless the target
+ *                          is a shard that holds blocks first_block .. of a larger database).  No public key: HYDIA_ERR_STATE.  n == 0,
+ *                          a bad babies, a null argument, first_block + blocks beyond the nonce space, or cap too small (*len = the bytes
+ *                          needed): HYDIA_ERR_ARG with nothing written.  Otherwise *len = the bytes written.  One block is in flight
+ *                          on the device at a time
+ *   hydia_db_delta_make_device   the same from rows in device memory (hydia_dev_rows above); the rows are never written
+ *   hydia_db_delta_apply   a ciphertext database (kind 5 / 6) resident: babies must be hydia_db_babies and first_vector <= n_old
+ *                          (HYDIA_ERR_ARG otherwise); blocks that existed become old + E mod q_j, stored canonical, new blocks become
+ *                          E; growth as in hydia_db_update (the layout may change; no room: HYDIA_ERR_DEVICE); the vector count
+ *                          becomes max(n_old, first_vector + n_rows).  NO database resident: first_vector must be 0 (HYDIA_ERR_STATE
+ *                          otherwise) and the database is created in the form the delta declares.  A plain gallery (kind 7 / 8; the
+ *                          message names hydia_plain_db_update) or kinds 1, 3, 4: HYDIA_ERR_STATE naming the kind.
+ *                          TRANSACTIONAL AGAINST BAD INPUT: every header and every residue of every block is checked (on the device,
+ *                          k_wire_check) before the first byte of the database is written or the database is grown; a residue at or
+ *                          above its modulus anywhere: HYDIA_ERR_ARG, and the database, its layout, form and counts stay exactly as they
+ *                          were.  The packed blocks are uploaded twice, one at a time: device memory beyond the database is one packed
+ *                          block however many the delta holds.  It orders itself against queries in flight as hydia_db_update does.
+ * NOT served: plain galleries and approaches 1 - 4, hydia_group_* (a shard context is served like any other; first_block exists for
+ * it), a streaming file form. */
+typedef struct {
+    uint32_t version, vector_dim;
+    uint64_t babies, first_vector, n_rows, first_block, n_blocks, total_bytes;
+} hydia_db_delta_info;
+int hydia_db_delta_bytes(const hydia_ctx *ctx, size_t first_vector, size_t n, size_t *bytes);
+int hydia_db_delta_peek(const void *buf, size_t len, hydia_db_delta_info *out);
+int hydia_db_delta_make(hydia_ctx *ctx, size_t first_vector, double *rows /* n x vector_dim row-major */, size_t n, int normalise,
+                        const uint8_t seed[32], int babies, size_t first_block, void *buf, size_t cap, size_t *len);
+int hydia_db_delta_make_device(hydia_ctx *ctx, size_t first_vector, const hydia_dev_rows *rows, int normalise, const uint8_t seed[32],
+                               int babies, size_t first_block, void *buf, size_t cap, size_t *len);
+int hydia_db_delta_apply(hydia_ctx *ctx, const void *buf, size_t len);
 /* OpenFHEWrapper::chebyshevCompare (src/openFHE_wrapper.cpp:143-185) on every ciphertext of the batch */
 int hydia_chebyshev_compare(hydia_ctx *ctx, const hydia_ct *in, double delta, size_t sign_depth, hydia_ct **out);
 /* multi-GPU membership tail: sum the batch into one ciphertext, then EvalSum over all slots (:46-47) */

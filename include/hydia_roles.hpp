@@ -490,6 +490,20 @@ class DiagonalSender : public Sender {
         }
         return r.empty() ? std::vector<Ciphertext>{} : r[0];
     }
+    // A delta message of DiagonalEnroller::updateToWire / appendToWire / serializeDBToWire into this sender's database
+    // (hydia_db_delta_apply: every header and residue is checked first, a refused message changes nothing).  Returns the new vector
+    // count, which numVectors follows; 0 on an error.  Not on a sharded context
+    size_t applyDBWire(const std::vector<uint8_t> &message) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: applyDBWire: database deltas are not applied on a sharded context (one per shard context)" << std::endl;
+            return 0;
+        }
+        if (!cc->check(hydia_db_delta_apply(cc->h, message.data(), message.size()), "applyDBWire")) return 0;
+        size_t cts = 0, bytes = 0;
+        if (!cc->check(hydia_db_stats(cc->h, &numVectors, &cts, &bytes), "applyDBWire")) return 0;
+        return numVectors;
+    }
     std::vector<uint8_t> resultToWire(const std::vector<Ciphertext> &result) { return toWire(cc, result); }
     // computeSimilarity's scores as one message of their first `limbs` limbs (1 or 2): the decoder reads at most two, so with 2 the
     // receiver decrypts the same doubles from a sixth of the bytes; with 1 it decodes from q_0 alone.  For resultFromWire
@@ -1031,6 +1045,78 @@ class DiagonalEnroller : public EnrollerBase {
         return true;
     }
     bool appendDB(const DeviceRows &rows, const uint8_t *seed32 = nullptr) { return updateRows(numVectors, rows, true, seed32); }
+    // Database deltas (an extension; hydia.h): updateRows / appendDB / serializeDB for a database that lies on ANOTHER machine.  This
+    // enroller's context holds the public key and nothing else; the message goes to DiagonalSender::applyDBWire, which leaves the
+    // sender's database bit for bit what updateRows with the same arguments would.  babies = the form of the sender's database
+    // (0: vector_dim, the hoisted form); first_block = the nonce offset of a shard's first block.  Nothing resident here is touched;
+    // numVectors follows as in updateRows.  The seed rule is updateRows'.  Not on a sharded context: an error, empty
+    std::vector<uint8_t> updateToWire(size_t first_vector, std::vector<std::vector<double>> &rows, bool normalise = true,
+                                      const uint8_t *seed32 = nullptr, int babies = 0, size_t first_block = 0) {
+        if (!delta_ok("updateToWire")) return {};
+        const size_t dim = cc->info.vector_dim;
+        std::vector<double> flat(rows.size() * dim, 0.0);
+        for (size_t i = 0; i < rows.size(); i++)
+            for (size_t j = 0; j < dim && j < rows[i].size(); j++) flat[i * dim + j] = rows[i][j];
+        uint8_t s[32];
+        role_seed(s, seed32);
+        const int B = babies ? babies : (int)dim;
+        size_t need = 0, len = 0;
+        if (!cc->check(hydia_db_delta_bytes(cc->h, first_vector, rows.size(), &need), "updateToWire")) return {};
+        std::vector<uint8_t> message(need);
+        if (!cc->check(hydia_db_delta_make(cc->h, first_vector, flat.data(), rows.size(), normalise ? 1 : 0, s, B, first_block, message.data(),
+                                           message.size(), &len),
+                       "updateToWire"))
+            return {};
+        message.resize(len);
+        for (size_t i = 0; i < rows.size(); i++)
+            for (size_t j = 0; j < dim && j < rows[i].size(); j++) rows[i][j] = flat[i * dim + j];
+        if (first_vector + rows.size() > numVectors) numVectors = first_vector + rows.size();
+        return message;
+    }
+    std::vector<uint8_t> updateToWire(size_t first_vector, const DeviceRows &rows, bool normalise = true, const uint8_t *seed32 = nullptr,
+                                      int babies = 0, size_t first_block = 0) {
+        if (!delta_ok("updateToWire")) return {};
+        uint8_t s[32];
+        role_seed(s, seed32);
+        const int B = babies ? babies : (int)cc->info.vector_dim;
+        size_t need = 0, len = 0;
+        if (!cc->check(hydia_db_delta_bytes(cc->h, first_vector, rows.size(), &need), "updateToWire")) return {};
+        std::vector<uint8_t> message(need);
+        if (!cc->check(hydia_db_delta_make_device(cc->h, first_vector, &rows.d, normalise ? 1 : 0, s, B, first_block, message.data(), message.size(), &len),
+                       "updateToWire"))
+            return {};
+        message.resize(len);
+        if (first_vector + rows.size() > numVectors) numVectors = first_vector + rows.size();
+        return message;
+    }
+    // append `rows` after the n_resident vectors the sender's database holds
+    std::vector<uint8_t> appendToWire(std::vector<std::vector<double>> &rows, size_t n_resident, const uint8_t *seed32 = nullptr, int babies = 0,
+                                      size_t first_block = 0) {
+        return updateToWire(n_resident, rows, true, seed32, babies, first_block);
+    }
+    std::vector<uint8_t> appendToWire(const DeviceRows &rows, size_t n_resident, const uint8_t *seed32 = nullptr, int babies = 0, size_t first_block = 0) {
+        return updateToWire(n_resident, rows, true, seed32, babies, first_block);
+    }
+    // serializeDB for a sender on another machine: one message per block of `slots` vectors, in order — the first enrols on an empty
+    // sender context, every later one appends.  ONE seed for the whole database, as an enrolment uses (the blocks differ in their
+    // nonces).  A failure: an error, and the messages made so far are dropped
+    std::vector<std::vector<uint8_t>> serializeDBToWire(std::vector<std::vector<double>> &database, const uint8_t *seed32 = nullptr, int babies = 0,
+                                                        size_t first_block = 0) {
+        if (!delta_ok("serializeDBToWire")) return {};
+        uint8_t s[32];
+        role_seed(s, seed32);
+        const size_t slots = cc->info.slots;
+        std::vector<std::vector<uint8_t>> messages;
+        for (size_t lo = 0; lo < database.size(); lo += slots) {
+            const size_t hi = std::min(database.size(), lo + slots);
+            std::vector<std::vector<double>> rows(database.begin() + lo, database.begin() + hi);
+            messages.push_back(updateToWire(lo, rows, true, s, babies, first_block));
+            if (messages.back().empty()) return {};
+            std::copy(rows.begin(), rows.end(), database.begin() + lo);
+        }
+        numVectors = database.size();
+        return messages;
+    }
     // Re-key the enrolled database in place under a new receiver key (hydia_db_rekey; no counterpart in the reference, which re-enrols):
     // every resident ciphertext is key-switched with `key`, the NEW receiver's DiagonalReceiver::genSwitchKey.  Afterwards the caller
     // imports the new receiver's evaluation and public keys; later updateRows / appendDB calls encrypt under the new public key.
@@ -1050,6 +1136,14 @@ class DiagonalEnroller : public EnrollerBase {
     size_t size() const { return numVectors; }
 
   private:
+    bool delta_ok(const char *what) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: " << what << ": database deltas are not made on a sharded context (one per shard context, with its first_block)" << std::endl;
+            return false;
+        }
+        return true;
+    }
     bool device_rows_ok(const char *what, bool count_ok) {
         if (cc->group || !count_ok) {
             cc->last_status = cc->group ? HYDIA_ERR_STATE : HYDIA_ERR_ARG;
