@@ -391,6 +391,8 @@ Context::Context(const Params &p, int dev) : HostParams(p), device(dev) {
     if (const char *e = getenv("HYDIA_TENSOR_BPP")) tensor_bpp = std::max(1, atoi(e));  // (bpp 0 marks a batch launch)
     if (const char *e = getenv("HYDIA_TENSOR_NW")) tensor_nw = atoi(e);
     merge_rescale = getenv("HYDIA_NO_MERGE_RESCALE") == nullptr;
+    ipq_fuse = getenv("HYDIA_NO_IPQ_FUSE") == nullptr;
+    if (const char *e = getenv("HYDIA_IPQ_MIN")) ipq_min = std::max(1, atoi(e));
     fuse_ip = getenv("HYDIA_NO_FUSE_IP") == nullptr;
     fork_products = getenv("HYDIA_NO_FORK") == nullptr;
     fuse_loop_a = getenv("HYDIA_NO_FUSE_LOOPA") == nullptr;

@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "hydia_core.h"
+#include "ntt15_ipq.h"
 
 #include <exception>
 
@@ -663,29 +664,43 @@ void Context::relin_rescale_into(const Ct &c, bool dbl, const Ct *sub, const dou
     const bool fip = fuse_ip;
     modup_digits(c2, c2_xs, X, nl, dig, /*copy_own=*/false, /*p1_only=*/fip, ps, d2buf);
     const LimbSel esel = sel_ext(nl);
-    u64 *acc = pool.get((size_t)XP * nE * N * sizeof(u64));
-    // yu [XP][1 + nP][N]: row 0 = the dropped limb u, rows 1.. = the special-prime limbs, on their way to the coefficient domain
-    const size_t yu_outer = (size_t)(1 + nP) * N;
-    u64 *yu = pool.get((size_t)XP * yu_outer * sizeof(u64));
     // with the fused inner product the special-prime sums never reach acc: the kernel runs the first pass of their inverse
     // transform itself and leaves its raw image in yu (HYDIA_RELIN_SEPARATE_INTT: through acc, as before)
     const bool tail_in_ip = !relin_separate_intt;
     const bool fused_tail = fip && tail_in_ip && prm.logN == 15;
+    const bool cfu = cf_ok() && (q[l] >> 50) == 0;  // the fused kernel carries the dropped limb's centred residue as a double
+    // the sums of limbs 1 .. l-1 are formed in the LAST pass, by the workgroup whose epilogue consumes them: acc shrinks to the row of the
+    // 60-bit limb 0 (k_ntt15_p2_ipq; HYDIA_NO_IPQ_FUSE: one inner-product launch, every sum through acc) — where the inner product would
+    // take the dropped limb, limbs 1 .. l-1 (and no other) run on the FP64 path, and the batch fills the chip (measured: 32 ciphertexts per
+    // launch -1.1 ms per 2^20 query, 4 - 8 no difference, one +0.16 ms — the merged kernel runs its two kinds of rows side by side, two
+    // small dependent launches do not).  Not with four digits or a product subtrahend (ST 11): those forms spill at three waves per SIMD
+    const bool ipq = ipq_fuse && X >= ipq_min && fused_tail && cfu && nd >= 2 && nd <= 3 && !(ps && ps->c) && !tabs.two_ip_launches &&
+                     !tabs.no_drop_in_ip && (tabs.fp_mask & ((1u << l) - 1u)) == ((1u << l) - 2u);
+    u64 *acc = pool.get((size_t)XP * (ipq ? 1 : nE) * N * sizeof(u64));
+    // yu [XP][1 + nP][N]: row 0 = the dropped limb u, rows 1.. = the special-prime limbs, on their way to the coefficient domain
+    const size_t yu_outer = (size_t)(1 + nP) * N;
+    u64 *yu = pool.get((size_t)XP * yu_outer * sizeof(u64));
     const LimbSel qsel_full = sel_q(nl);
     std::vector<u64> pinv(Pinv_mod_q.begin(), Pinv_mod_q.begin() + nl);
     const ScaleSel pinv_sel = scale_of(qsel_full, pinv, false);
     // (round 4) the dropped limb's sums take the same tail inside the merged kernel: (sum P^{-1} + d_l)(x2), inverse pass 2, row 0 of yu
     const DropLimb drop{l, dbl ? 1 : 0, pinv_sel.s[l], pinv_sel.s_sh[l], c.d, ps ? 0 : c.ct_elems(), ps ? 0 : c.poly_elems(), ps};
+    const IpArgs ipa = hk::ntt15_ip_args(nl, nP, nT, alpha, relin_key.d_cell, relin_key.d, c2, c2_xs, acc, yu, yu_outer, 1, false);
     bool drop_done = false;
     timer_begin("ks_inner_product");
-    if (fip)
+    if (ipq) {
+        hk::ntt15_p2_ip_tail(stream, tabs, dig, (size_t)nd * nE * N, nd, X, ipa, drop);
+        drop_done = true;
+    } else if (fip)
         drop_done = hk::ntt15_p2_inner_product(stream, tabs, d_mod, dig, (size_t)nd * nE * N, nd, X, nl, nP, nT, alpha, relin_key.d_cell, relin_key.d,
                                                c2, c2_xs, acc, fused_tail ? yu : nullptr, yu_outer, 1, fused_tail ? &drop : nullptr);
     else
         hk::inner_product(stream, d_mod, N, dig, (size_t)nd * nE * N, nd, relin_key.d_cell, 1, nT, acc, X, esel, c2, c2_xs, alpha, nl);
     timer_end("ks_inner_product");
-    pool.put(dig);
-    if (d2buf) pool.put(d2buf);
+    if (!ipq) {  // (ipq: the last pass reads the digits and d2 again)
+        pool.put(dig);
+        if (d2buf) pool.put(d2buf);
+    }
     if (ps && !(drop_done && fused_tail)) throw std::runtime_error("hydia: fused product outside the merged pipeline (prod_fusable out of step)");
     // limb l of the would-be ModDown output (+ d_l, doubled) replaces row l of the accumulator (nothing else reads that row), so that
     // ONE inverse transform takes rows l .. nE-1 — the dropped limb and the special-prime limbs (pre-multiplied by (P/p_k)^{-1}) —
@@ -701,7 +716,6 @@ void Context::relin_rescale_into(const Ct &c, bool dbl, const Ct *sub, const dou
         tail.mod[1 + k] = nQ + k;
         tail_scale[1 + k] = Phat_inv[k];
     }
-    const bool cfu = cf_ok() && (q[l] >> 50) == 0;  // the fused kernel carries the dropped limb's centred residue as a double
     const bool cf_pre = cfu && cf_small_moddown(XP);  // few workgroups: pass 1' as its own (wider) launch
     if (fused_tail) {
         if (!drop_done)
@@ -739,7 +753,7 @@ void Context::relin_rescale_into(const Ct &c, bool dbl, const Ct *sub, const dou
     stp.out = out_d;
     stp.nl = l;
     stp.in = acc;
-    stp.in_ls = nE;
+    stp.in_ls = ipq ? 1 : nE;
     stp.mul = pinv_sel;
     stp.mul2 = scale_of(qsel, qi, false);
     stp.addend = c.d;
@@ -759,7 +773,13 @@ void Context::relin_rescale_into(const Ct &c, bool dbl, const Ct *sub, const dou
     stp.npoly = 2;
     if (addc)
         for (int j = 0; j < l; j++) stp.addc[j] = double_to_mod(*addc * out_scale, q[j]);
-    if (cfu) hk::ntt15_forward_p2_fused(stream, tabs, w, (size_t)l * N, XP, qsel, stp);
+    if (ipq) {
+        timer_begin("ks_inner_product");  // the inner product's other half (one more interval of the same timer)
+        hk::ntt15_p2_ipq(stream, tabs, dig, (size_t)nd * nE * N, nd, X, ipa, w, (size_t)l * N, stp);
+        timer_end("ks_inner_product");
+        pool.put(dig);
+        if (d2buf) pool.put(d2buf);
+    } else if (cfu) hk::ntt15_forward_p2_fused(stream, tabs, w, (size_t)l * N, XP, qsel, stp);
     else hk::ntt15_forward_fused(stream, tabs, w, w, (size_t)l * N, (size_t)l * N, XP, qsel, ld, stp);
     pool.put(w);
     pool.put(yu);

@@ -330,6 +330,8 @@ struct Context : HostParams {
                           const Ct *csub = nullptr);
     bool prod_fuse_csub = true;  // HYDIA_NO_CSUB_FUSE: Chebyshev steps with a subtrahend keep k_tensor<true>
     bool merge_rescale = true;      // HYDIA_NO_MERGE_RESCALE: run the two steps separately (A/B)
+    bool ipq_fuse = true;           // HYDIA_NO_IPQ_FUSE: the merged pipeline's Q-limb sums through acc (k_ntt15_p2_ip_all + k_ntt15_p2<false, ., 3|9|10|11>; parity variant)
+    int ipq_min = 16;               // HYDIA_IPQ_MIN: fewest ciphertexts per launch that take k_ntt15_p2_ipq (default: where cf_small_moddown ends; the tests say 1)
     Ct clone(const Ct &a);          // compact copy
     void drop_to(Ct &a, int nl);    // O(1): keeps the allocation, lstride unchanged
     int tensor_bpp = 2;             // DB blocks per wave in loop B (HYDIA_TENSOR_BPP; 4 spills past 168 VGPRs)

@@ -19,6 +19,7 @@
 // 16-byte pair loads shared by the TWO polynomials a workgroup transforms together.
 #include "kernels.h"
 #include "ntt_arith.h"
+#include "ntt15_ipq.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -409,14 +410,18 @@ struct IpAcc<FpA> {
     DEV u64 fin(const FpA &ar, const ModC &, int) const { return ar.fin_fwd(s); }
     DEV u64 fin_lazy(const FpA &ar, const ModC &M, int terms) const { return fin(ar, M, terms); }
 };
-template <int ST, class A>
-DEV P2Pre p2_prefetch(const NttStore &st, const A &ar, int xp, int j, unsigned idx, const ModC &M) {
+// REGIN: the `in` operand is not read back — its four residues are in the caller's registers (rin: k_ntt15_p2_ipq)
+template <int ST, class A, bool REGIN = false>
+DEV P2Pre p2_prefetch(const NttStore &st, const A &ar, int xp, int j, unsigned idx, const ModC &M, const u64 *rin = nullptr) {
     constexpr size_t N = 32768;
     P2Pre r;
     r.has_ex = false;
     r.ex0 = r.ex1 = make_ulonglong2(0, 0);
     if (ST == 5) {
         loop_a_inner_product<false>(st.la, ar, M, xp >> 1, xp & 1, j, idx, r.in0, r.in1);
+    } else if (REGIN) {
+        r.in0 = make_ulonglong2(rin[0], rin[1]);
+        r.in1 = make_ulonglong2(rin[2], rin[3]);
     } else {
         const u64 *pi = st.in + ((size_t)xp * st.in_ls + j) * N + idx;
         r.in0 = *reinterpret_cast<const ulonglong2 *>(pi);
@@ -794,10 +799,14 @@ DEV void p2_inverse_BA(const A &ar, const ulonglong2 *__restrict__ tw, u64 (*lds
 // ST 6 = ST 4 for the special-prime limbs with the inverse transform's second pass appended: the two sums of a lane's four
 // coefficients go through phase C' in registers and meet the other lanes' in lds[0], lds[1] (the digits' images there are dead by
 // then: every lane reads and overwrites only its own four slots), phases B', A' follow, the raw image leaves through dinv.
-template <class A, bool INV, int NP, int ST, bool SWZ = false, bool WGS = P2_WGS_DEFAULT>
+// IPQ (k_ntt15_p2_ipq: the two transforms of one workgroup, same limb and chunk, an FP64 limb): 1 = ST 4 whose finished sums stay in the
+// lane's registers, keep[hh][key polynomial][k], instead of going to acc; 2 = a merged epilogue (ST 3, 9, 10, 11) that takes its `in` operand
+// from there — phase C hands a lane the same four coefficients in both — and finds the wave's twiddle table already staged;
+// 3 = ST 4 of ONE limb whose sums go to a compact acc [2X][N] (the 60-bit limb 0, which takes the epilogue as its own step).
+template <class A, bool INV, int NP, int ST, bool SWZ = false, bool WGS = P2_WGS_DEFAULT, int IPQ = 0>
 DEV void p2_body(const A ar, const ulonglong2 *__restrict__ tw, const u64 *const *s, u64 *const *d, u64 (*lds)[P2Lds<SWZ>::SIZE], int t,
                  int B0, const NttStore &stp, const ModC &M, int xp0, int slot, const ulonglong2 *__restrict__ itw = nullptr,
-                 u64 *const *dinv = nullptr, const P2Tab tab = P2Tab{nullptr, nullptr}) {
+                 u64 *const *dinv = nullptr, const P2Tab tab = P2Tab{nullptr, nullptr}, u64 (*keep)[2][4] = nullptr) {
     typedef typename A::T T;
     typedef typename A::TW TW;
     typedef P2Lds<SWZ> LI;
@@ -808,7 +817,7 @@ DEV void p2_body(const A ar, const ulonglong2 *__restrict__ tw, const u64 *const
     const double *wt = nullptr;
     if (std::is_same<A, FpA>::value && !WGS && tab.g && tab.l) {
         double *wl = tab.l + (t >> 6) * 128;
-        p2_stage_twiddles(tab.g, wl, (B0 >> 8) + 2 * (t >> 6), t & 63);
+        if (IPQ != 2) p2_stage_twiddles(tab.g, wl, (B0 >> 8) + 2 * (t >> 6), t & 63);
         wt = wl;
     }
     T v[NP][8];
@@ -871,7 +880,8 @@ DEV void p2_body(const A ar, const ulonglong2 *__restrict__ tw, const u64 *const
 #pragma unroll
             for (int hh = 0; hh < (SPLIT ? 1 : 2); hh++)
 #pragma unroll
-                for (int p = 0; p < NP; p++) pre[hh][p] = p2_prefetch<ST>(stp, ar, xp0 + p, slot, (unsigned)(B0 + p2_elem<WGS>(t, hh)), M);
+                for (int p = 0; p < NP; p++)
+                    pre[hh][p] = p2_prefetch<ST, A, IPQ == 2>(stp, ar, xp0 + p, slot, (unsigned)(B0 + p2_elem<WGS>(t, hh)), M, IPQ == 2 ? keep[hh][p] : nullptr);
             if (ST == 9 || ST == 10 || ST == 11) po.load(stp.prod, xp0 >> 1, slot, (unsigned)(B0 + p2_elem<WGS>(t, 0)));
         }
         // mode 4 / 6: the key rows of the inner product
@@ -915,7 +925,8 @@ DEV void p2_body(const A ar, const ulonglong2 *__restrict__ tw, const u64 *const
             IpAcc<A> ipb[4], ipa[4];
             if (SPLIT && hh == 1) {
 #pragma unroll
-                for (int p = 0; p < NP; p++) pre[0][p] = p2_prefetch<ST>(stp, ar, xp0 + p, slot, (unsigned)(B0 + p2_elem<WGS>(t, 1)), M);
+                for (int p = 0; p < NP; p++)
+                    pre[0][p] = p2_prefetch<ST, A, IPQ == 2>(stp, ar, xp0 + p, slot, (unsigned)(B0 + p2_elem<WGS>(t, 1)), M, IPQ == 2 ? keep[1][p] : nullptr);
                 if (ST == 9 || ST == 10 || ST == 11) po.load(stp.prod, xp0 >> 1, slot, (unsigned)(B0 + p2_elem<WGS>(t, 1)));
             }
 #pragma unroll
@@ -1016,8 +1027,16 @@ DEV void p2_body(const A ar, const ulonglong2 *__restrict__ tw, const u64 *const
                     }
                     continue;
                 }
-                u64 *ob = stp.ip.acc + (((size_t)xp0 * 2) * stp.ip.nE + ip_t) * 32768 + ci;
-                u64 *oa = ob + (size_t)stp.ip.nE * 32768;
+                if (IPQ == 1) {  // the canonical residues acc would hold
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        keep[hh][0][k] = ipb[k].fin(ar, M, NP + 1);
+                        keep[hh][1][k] = ipa[k].fin(ar, M, NP + 1);
+                    }
+                    continue;
+                }
+                u64 *ob = stp.ip.acc + (IPQ == 3 ? (size_t)xp0 * 2 : ((size_t)xp0 * 2) * stp.ip.nE + ip_t) * 32768 + ci;
+                u64 *oa = ob + (size_t)(IPQ == 3 ? 1 : stp.ip.nE) * 32768;
                 *reinterpret_cast<ulonglong2 *>(ob) = make_ulonglong2(ipb[0].fin(ar, M, NP + 1), ipb[1].fin(ar, M, NP + 1));
                 *reinterpret_cast<ulonglong2 *>(ob + 2) = make_ulonglong2(ipb[2].fin(ar, M, NP + 1), ipb[3].fin(ar, M, NP + 1));
                 *reinterpret_cast<ulonglong2 *>(oa) = make_ulonglong2(ipa[0].fin(ar, M, NP + 1), ipa[1].fin(ar, M, NP + 1));
@@ -1134,7 +1153,7 @@ __global__ __launch_bounds__(256) void k_ntt15_p2_wgsync(NttTables T, const u64 
 
 // second pass of the ModUp forward NTTs fused with the key-switching inner product: grid (16, nlimbs*X), x fastest so the
 // workgroups that share a key tile follow each other.  Limb t = t0 + slot; the NP digits are all digits but the limb's own.
-template <int NP, bool OWN, bool TAIL, bool SWZ = false>
+template <int NP, bool OWN, bool TAIL, bool SWZ = false, int IPQ = 0>
 DEV void p2_ip_workgroup(const NttTables &T, const u64 *__restrict__ dig, size_t dxs, int t, int x, const NttStore &stp, int bx,
                          u64 (*lds)[P2Lds<SWZ>::SIZE], double *twl) {
     constexpr int N = 32768;
@@ -1163,9 +1182,9 @@ DEV void p2_ip_workgroup(const NttTables &T, const u64 *__restrict__ dig, size_t
         else p2_body<IntA, false, NP, 6, SWZ>(IntA(M), tw, s, d, lds, threadIdx.x, B0, stp, M, x, t, itw, dinv);
         return;
     }
-    if (fp) p2_body<FpA, false, NP, 4, SWZ>(FpA(M), tw, s, d, lds, threadIdx.x, B0, stp, M, x, t, nullptr, nullptr, P2Tab{(T.twd && !T.no_tw_lds) ? T.twd + (size_t)m * N : nullptr, twl});
-    else if ((T.pm_mask >> m) & 1u) p2_body<IntP, false, NP, 4, SWZ>(IntP(M), tw, s, d, lds, threadIdx.x, B0, stp, M, x, t);
-    else p2_body<IntA, false, NP, 4, SWZ>(IntA(M), tw, s, d, lds, threadIdx.x, B0, stp, M, x, t);
+    if (fp) p2_body<FpA, false, NP, 4, SWZ, P2_WGS_DEFAULT, IPQ>(FpA(M), tw, s, d, lds, threadIdx.x, B0, stp, M, x, t, nullptr, nullptr, P2Tab{(T.twd && !T.no_tw_lds) ? T.twd + (size_t)m * N : nullptr, twl});
+    else if ((T.pm_mask >> m) & 1u) p2_body<IntP, false, NP, 4, SWZ, P2_WGS_DEFAULT, IPQ>(IntP(M), tw, s, d, lds, threadIdx.x, B0, stp, M, x, t);
+    else p2_body<IntA, false, NP, 4, SWZ, P2_WGS_DEFAULT, IPQ>(IntA(M), tw, s, d, lds, threadIdx.x, B0, stp, M, x, t);
 }
 template <int NP, bool OWN, bool TAIL = false>
 __global__ __launch_bounds__(256) void k_ntt15_p2_ip(NttTables T, const u64 *__restrict__ dig, size_t dxs, int X, int t0, NttStore stp) {
@@ -1192,6 +1211,75 @@ __global__ __launch_bounds__(256, ND == 2 ? 4 : 1) void k_ntt15_p2_ip_all(NttTab
     if (pc1 > pc) p2_ip_workgroup<ND, false, true, SWZ>(T, dig, dxs, nl + pc, x, stp, blockIdx.x, lds, &twl[0][0]);
     else if (si - pc == stp.ip.drop_l) p2_ip_workgroup<ND - 1, true, true, SWZ>(T, dig, dxs, si - pc, x, stp, blockIdx.x, lds, &twl[0][0]);  // (ND >= 2 images: enough for the tail)
     else p2_ip_workgroup<ND - 1, true, false, SWZ>(T, dig, dxs, si - pc, x, stp, blockIdx.x, lds, &twl[0][0]);
+}
+
+// The merged relinearise + rescale pipeline with the Q-limb inner product moved into its LAST pass: the sums of limb j < nl - 1 are the
+// `in` operand of the merged ModDown + Rescale epilogue of the same limb, chunk and ciphertext, and nothing transforms them in between,
+// so the workgroup that forms them keeps them in registers and runs the epilogue's transform itself — acc [2X][nE][N], written by
+// k_ntt15_p2_ip_all's Q rows and read back by k_ntt15_p2<false, ., 3|9|10|11>, never exists.  Two ordinary dependent launches:
+//   k_ntt15_p2_ip_tail<ND>  the rows whose sums feed the ModDown conversion (special primes, dropped limb), before it; yu as before
+//   k_ntt15_p2_ipq<ND, ST>  the other Q rows, behind it
+// the special-prime rows (ND digits, inverse tail) and the dropped limb's row (ND - 1 digits, own digit in place, inverse tail) of
+// k_ntt15_p2_ip_all, and the row of limb 0 — a 60-bit limb (IntP), whose fused form would take 180 - 196 registers: its sums go to the
+// compact accumulator stp.ip.acc [2X][N] and its epilogue reads them back.  Groups of xb ciphertexts, inside a group row by row, inside
+// a row x fastest
+template <int ND>
+__global__ __launch_bounds__(256, ND == 2 ? 4 : 1) void k_ntt15_p2_ip_tail(NttTables T, const u64 *__restrict__ dig, size_t dxs, int X, int xb, NttStore stp) {
+    constexpr bool SWZ = ND >= 3;
+    __shared__ u64 lds[ND][P2Lds<SWZ>::SIZE];
+    __shared__ double twl[4][128];
+    const int nl = stp.ip.nl, nP = stp.ip.nE - nl;
+    const int per = (nP + 2) * xb, grp = blockIdx.y / per, r = blockIdx.y - grp * per;
+    const int si = r / xb, x = grp * xb + (r - si * xb);
+    if (si < nP) p2_ip_workgroup<ND, false, true, SWZ>(T, dig, dxs, nl + si, x, stp, blockIdx.x, lds, &twl[0][0]);
+    else if (si == nP) p2_ip_workgroup<ND - 1, true, false, SWZ, 3>(T, dig, dxs, 0, x, stp, blockIdx.x, lds, &twl[0][0]);
+    else p2_ip_workgroup<ND - 1, true, true, SWZ>(T, dig, dxs, stp.ip.drop_l, x, stp, blockIdx.x, lds, &twl[0][0]);
+}
+// One workgroup per (chunk, limb j < nl - 1, ciphertext), x fastest (the workgroups that share a key tile follow each other).  Limbs
+// 1 .. nl - 2, all on the FP64 path (the host checks):
+//   1. pass 2 of the ND - 1 foreign digits and the own-digit term from c2, summed against both key polynomials (p2_body mode 4);
+//   2. the sums finished to the canonical residues acc held, sixteen per lane, kept in registers;
+//   3. pass 2 of the ModDown output's polynomials w[2x], w[2x + 1] of the same limb and chunk through the same LDS images (free by
+//      then: every lane reads and writes only its own wave's blocks), with the merged epilogue ST taking `in` from those registers.
+// Limb 0: step 3 alone, `in` from stp.in [2X][N] (k_ntt15_p2<false, 2, ST>'s workgroup).
+// w: the column-fused conversion's output [2X][wso], limb j at + j N; stp carries the inner product's arguments (ip) AND the epilogue's.
+// (three waves per SIMD: 140 - 165 registers where the epilogue alone takes 109 - 128; held to four, 44 - 148 bytes of scratch per lane.
+// ST 11 and four digits are not instantiated: at three waves they spill 12 bytes per lane, so those products keep k_ntt15_p2_ip_all)
+template <int ND, int ST>
+__global__ __launch_bounds__(256, 3) void k_ntt15_p2_ipq(NttTables T, const u64 *__restrict__ dig, size_t dxs, u64 *__restrict__ w, size_t wso, int X, NttStore stp) {
+    constexpr int N = 32768, NP = ND - 1;
+    static_assert(ND == 2 || ND == 3, "one or two foreign digits: two padded LDS images serve both transforms");
+    constexpr bool SWZ = false, WGS = P2_WGS_DEFAULT;
+    __shared__ u64 lds[2][P2Lds<SWZ>::SIZE];
+    __shared__ double twl[4][128];
+    const int j = blockIdx.y / X, x = blockIdx.y - j * X, m = j, t = threadIdx.x;
+    const ModC M = T.mod[m];
+    const bool fp = (T.fp_mask >> m) & 1u;
+    const ulonglong2 *__restrict__ tw = (fp ? T.twf : T.twp) + (size_t)m * N;
+    const int B0 = blockIdx.x * 2048;
+    const u64 *ws[2];
+    u64 *wd[2];
+#pragma unroll
+    for (int p = 0; p < 2; p++) ws[p] = wd[p] = w + (size_t)(2 * x + p) * wso + (size_t)j * N + B0;
+    if (!fp) {
+        if ((T.pm_mask >> m) & 1u) p2_body<IntP, false, 2, ST, SWZ, WGS>(IntP(M), tw, ws, wd, lds, t, B0, stp, M, 2 * x, j);
+        else p2_body<IntA, false, 2, ST, SWZ, WGS>(IntA(M), tw, ws, wd, lds, t, B0, stp, M, 2 * x, j);
+        return;
+    }
+    const int own_d = j / stp.ip.alpha;
+    const u64 *s[NP];
+    u64 *d[NP];
+#pragma unroll
+    for (int p = 0; p < NP; p++) {
+        const int dgt = p >= own_d ? p + 1 : p;
+        s[p] = dig + (size_t)x * dxs + ((size_t)dgt * stp.ip.nE + j) * N + B0;
+        d[p] = nullptr;
+    }
+    u64 keep[2][2][4];
+    const P2Tab tab{(T.twd && !T.no_tw_lds) ? T.twd + (size_t)m * N : nullptr, &twl[0][0]};
+    p2_body<FpA, false, NP, 4, SWZ, WGS, 1>(FpA(M), tw, s, d, lds, t, B0, stp, M, x, j, nullptr, nullptr, tab, keep);
+    p2_sync<WGS>();
+    p2_body<FpA, false, 2, ST, SWZ, WGS, 2>(FpA(M), tw, ws, wd, lds, t, B0, stp, M, 2 * x, j, nullptr, nullptr, tab, keep);
 }
 
 
@@ -1478,43 +1566,94 @@ __global__ __launch_bounds__(1024) void k_ntt15_1p(NttTables T, const ulonglong2
 
 namespace hk {
 
+static void ip_set_drop(IpArgs &ip, const DropLimb &drop) {
+    ip.drop_l = drop.l;
+    ip.drop_dbl = drop.dbl;
+    ip.drop_mul = drop.mul;
+    ip.drop_mul_sh = drop.mul_sh;
+    ip.drop_add = drop.add;
+    ip.drop_add_x = drop.add_x;
+    ip.drop_add_p = drop.add_p;
+    ip.drop_has_prod = drop.prod ? 1 : 0;
+    if (drop.prod) ip.drop_prod = *drop.prod;
+}
+
+void ntt15_p2_ip_tail(hipStream_t st, const NttTables &T, const u64 *dig, size_t dxs, int nd, int X, const IpArgs &ip, const DropLimb &drop) {
+    NttStore stp{};
+    stp.mode = 4;
+    stp.ip = ip;
+    ip_set_drop(stp.ip, drop);
+    const int nP = ip.nE - ip.nl;
+    char name[64];
+    snprintf(name, sizeof name, "k_ntt15_p2_ip_tail<%d>", nd);
+    // special-prime rows: nd digits in, two raw rows out; the dropped limb's row and limb 0's: nd - 1 digits and the own residues in, two out
+    ledger_add(name, ((nd + 2.0) * nP + 2 * ((nd - 1) + 1 + 2.0)) * X * 262144.0);
+    int xb = T.ip_group;
+    if (xb < 1 || xb > X || X % xb) xb = X;
+    const dim3 grid(16, (nP + 2) * X);
+    if (nd == 2) hipLaunchKernelGGL((k_ntt15_p2_ip_tail<2>), grid, dim3(256), 0, st, T, dig, dxs, X, xb, stp);
+    else hipLaunchKernelGGL((k_ntt15_p2_ip_tail<3>), grid, dim3(256), 0, st, T, dig, dxs, X, xb, stp);
+}
+template <int ST>
+static void launch_p2_ipq(hipStream_t st, const NttTables &T, const u64 *dig, size_t dxs, int nd, int X, u64 *w, size_t wso, const NttStore &sv) {
+    const int rows = sv.ip.nl - 1;
+    char name[64];
+    snprintf(name, sizeof name, "k_ntt15_p2_ipq<%d, %d>", nd, ST);
+    // per polynomial the pass-1 image in, the result out and the epilogue's operands (launch_p2_fwd's prices); limbs 1 .. : WITHOUT `in`,
+    // and per ciphertext nd - 1 digits and the limb's own residues in
+    const double epi = 2.0 * (2.0 + (ST == 3 ? 2.0 : ST == 9 ? 3.0 : 4.0));
+    if (nd < 2 || nd > 3) throw std::runtime_error("hydia: ntt15_p2_ipq takes two or three digits");
+    ledger_add(name, (epi + (rows - 1) * (epi - 2.0 + nd)) * X * 262144.0);
+    const dim3 grid(16, rows * X);
+    if (nd == 2) hipLaunchKernelGGL((k_ntt15_p2_ipq<2, ST>), grid, dim3(256), 0, st, T, dig, dxs, w, wso, X, sv);
+    else hipLaunchKernelGGL((k_ntt15_p2_ipq<3, ST>), grid, dim3(256), 0, st, T, dig, dxs, w, wso, X, sv);
+}
+void ntt15_p2_ipq(hipStream_t st, const NttTables &T, const u64 *dig, size_t dxs, int nd, int X, const IpArgs &ip, u64 *w, size_t wso, const NttStore &epi) {
+    NttStore sv = epi;  // mode 3: ntt15_forward_p2_fused's choice of epilogue
+    sv.ip = ip;
+    sv.ip.drop_l = -1;
+    sv.int_epilogue = T.int_epilogue;
+    if (epi.has_prod && epi.prod.c) throw std::runtime_error("hydia: ntt15_p2_ipq has no epilogue with a product subtrahend");
+    if (epi.has_prod && epi.sub) launch_p2_ipq<10>(st, T, dig, dxs, nd, X, w, wso, sv);
+    else if (epi.has_prod) launch_p2_ipq<9>(st, T, dig, dxs, nd, X, w, wso, sv);
+    else launch_p2_ipq<3>(st, T, dig, dxs, nd, X, w, wso, sv);
+}
+
+IpArgs ntt15_ip_args(int nl, int nP, int nT, int alpha, const u64 *const *keys, const u64 *key, const u64 *c2, size_t c2_xs, u64 *acc, u64 *inv_out,
+                     size_t inv_outer, int inv_row0, bool per_x_keys) {
+    IpArgs ip{};
+    ip.key = key;
+    ip.keys = per_x_keys ? keys : nullptr;  // device array: the key of ciphertext x (giant steps); else `key` serves every x
+    ip.nT = nT;
+    ip.nE = nl + nP;
+    ip.nl = nl;
+    ip.alpha = alpha;
+    ip.own = 1;
+    ip.c2 = c2;
+    ip.c2_xs = c2_xs;
+    ip.acc = acc;
+    ip.inv_out = inv_out;
+    ip.inv_outer = inv_outer;
+    ip.inv_row0 = inv_row0;
+    ip.drop_l = -1;
+    return ip;
+}
+
 bool ntt15_p2_inner_product(hipStream_t st, const NttTables &T, const ModC *mod, const u64 *dig, size_t dxs, int nd, int X, int nl,
                             int nP, int nT, int alpha, const u64 *const *keys, const u64 *key, const u64 *c2, size_t c2_xs, u64 *acc,
                             u64 *inv_out, size_t inv_outer, int inv_row0, const DropLimb *drop, bool per_x_keys) {
     const int nE = nl + nP;
     NttStore stp{};
     stp.mode = 4;
-    stp.ip.key = key;
-    stp.ip.keys = per_x_keys ? keys : nullptr;  // device array: the key of ciphertext x (giant steps); else `key` serves every x
-    stp.ip.nT = nT;
-    stp.ip.nE = nE;
-    stp.ip.nl = nl;
-    stp.ip.alpha = alpha;
-    stp.ip.own = 1;
-    stp.ip.c2 = c2;
-    stp.ip.c2_xs = c2_xs;
-    stp.ip.acc = acc;
-    stp.ip.inv_out = inv_out;
-    stp.ip.inv_outer = inv_outer;
-    stp.ip.inv_row0 = inv_row0;
-    stp.ip.drop_l = -1;
+    stp.ip = ntt15_ip_args(nl, nP, nT, alpha, keys, key, c2, c2_xs, acc, inv_out, inv_outer, inv_row0, per_x_keys);
     // Q limbs: NP = nd - 1 pass-1 digits in (+ the limb's own residues), two accumulator rows out; special-prime limbs: nd digits in, two
     // rows out; the key tiles are shared by all x (L2)
     const double bytes_q = nd >= 2 ? ((nd - 1) + 1 + 2.0) * nl * X * 262144.0 : 0.0, bytes_p = (nd + 2.0) * nP * X * 262144.0;
     const bool merged = inv_out && nd >= 2 && nd <= 4 && !T.two_ip_launches;
     char name[64];
     if (merged) {
-        if (drop && !T.no_drop_in_ip && inv_row0 >= 1 && drop->l == nl - 1) {  // the dropped limb rides the tail (one launch and a round trip of that row less)
-            stp.ip.drop_l = drop->l;
-            stp.ip.drop_dbl = drop->dbl;
-            stp.ip.drop_mul = drop->mul;
-            stp.ip.drop_mul_sh = drop->mul_sh;
-            stp.ip.drop_add = drop->add;
-            stp.ip.drop_add_x = drop->add_x;
-            stp.ip.drop_add_p = drop->add_p;
-            stp.ip.drop_has_prod = drop->prod ? 1 : 0;
-            if (drop->prod) stp.ip.drop_prod = *drop->prod;
-        }
+        if (drop && !T.no_drop_in_ip && inv_row0 >= 1 && drop->l == nl - 1)  // the dropped limb rides the tail (one launch and a round trip of that row less)
+            ip_set_drop(stp.ip, *drop);
         snprintf(name, sizeof name, "k_ntt15_p2_ip_all<%d>", nd);
         ledger_add(name, bytes_q + bytes_p);
         int xb = T.ip_group;  // ciphertexts per interleaving group (HYDIA_IP_GROUP; must divide X)
