@@ -9,7 +9,7 @@ from .hydia import (Context, Ciphertext, DiagonalEnroller, DiagonalReceiver, Dia
                     HersEnroller, HersReceiver, HersSender, BaseEnroller, BaseReceiver, BaseSender, base_rotations,
                     GroteReceiver, GroteSender, grote_row_length, BlindEnroller, BlindReceiver, BlindSender, BLIND_CHUNK_LEN,
                     byte_ledger, default_params, describe_params, compute_required_depth, lib_path, load_library,
-                    params_for_approach, wire_peek, db_delta_peek)
+                    params_for_approach, wire_peek, db_delta_peek, db_delta_seeded_peek)
 from .sharding import (ShardGroup, ShardedDiagonalEnroller, ShardedDiagonalSender, DistDiagonalEnroller,  # noqa: F401
                        DistDiagonalSender, group_babies, shard_blocks, shard_vectors)
 

@@ -252,9 +252,10 @@ static void encrypt_device(Context &cx, const double *d_slots, int X, const ChaC
 // encode + encrypt X slot vectors under the SECRET key with a seeded c1: c0 = NTT(e0 + m) - a s, where e0 is encrypt_device's (the
 // stream (ENC_E0, nonce) under the secret `key`) and a limb j is the uniform stream (SYM_A, nonce, 0, j) under the PUBLIC akey, drawn
 // inside k_enc_sym.  One sampled polynomial and one transform batch where encrypt_device takes three of each.  Writes c0 [X][nQ][N] at
-// c0 and, when c1 != nullptr, a [X][nQ][N] at c1
-static void encrypt_sym_device(Context &cx, const double *d_slots, int X, const ChaChaKey &key, const ChaChaKey &akey, u64 nonce0, u64 *c0,
-                               u64 *c1 = nullptr) {
+// c0 and, when c1 != nullptr, a [X][nQ][N] at c1.  The two streams take nonces of their own: e0 of element x is at nonce0 + x, a at
+// a_nonce0 + x (a query: the same; a database block: the enrolment's nonce and the one its wire message names)
+static void encrypt_sym_device(Context &cx, const double *d_slots, int X, const ChaChaKey &key, const ChaChaKey &akey, u64 nonce0, u64 a_nonce0,
+                               u64 *c0, u64 *c1 = nullptr) {
     if (!cx.d_sk) throw StateError("hydia: secret key not loaded (seeded encryption is the secret-key holder's; hydia_encrypt_query takes the public key)");
     ensure_embedding_tables(cx);
     const int N = cx.N, nQ = cx.nQ, Nh = cx.slots;
@@ -268,7 +269,7 @@ static void encrypt_sym_device(Context &cx, const double *d_slots, int X, const 
     u64 *T0 = cx.pool.get(sizeof(u64) * X * pe);
     hc::small_to_limbs(cx.stream, cx.d_mod, N, e0, coeffs, T0, pe, X, qsel);
     cx.ntt_fwd(T0, pe, X, qsel);
-    hc::enc_sym(cx.stream, akey, cx.d_mod, N, nQ, HY_STREAM(HY_DOM_SYM_A, nonce0, 0, 0), T0, cx.d_sk, c0, c1, X);
+    hc::enc_sym(cx.stream, akey, cx.d_mod, N, nQ, HY_STREAM(HY_DOM_SYM_A, a_nonce0, 0, 0), T0, cx.d_sk, c0, c1, X);
     for (void *p : {(void *)work, (void *)coeffs, (void *)e0, (void *)T0}) cx.pool.put((u64 *)p);
 }
 
@@ -742,6 +743,64 @@ void client_db_delta_make_device(Context &cx, size_t first_vector, const DevRows
     delta_blocks(cx, first_vector, src, rows.n, make_key(seed), babies, first_block, payload0, stride);
 }
 
+// The SEEDED delta of a key-holding enroller (hydia_db_delta_make_seeded): delta_blocks with encrypt_sym_device in place of
+// encrypt_device — per touched block one sampled polynomial (e0 under `key` at the enrolment's nonce, as delta_blocks samples it) and
+// one transform batch; a is drawn inside k_enc_sym under the PUBLIC akey at (first_block + block) * vector_dim, the nonce0 of the block's message, and c1 is never written; k_wire_pack
+// of c0 straight from the block buffer.  Needs the secret key.  One block is in flight at a time.
+static void delta_blocks_seeded(Context &cx, size_t first_vector, const RowSource &src, size_t n, const ChaChaKey &key, const ChaChaKey &akey,
+                                int babies, size_t first_block, unsigned char *payload0, size_t stride) {
+    const int dim = cx.prm.dim, Nh = cx.slots;
+    const size_t end = first_vector + n, g0 = first_vector / (size_t)Nh, elems = (size_t)cx.nQ * cx.N;
+    const WireRows R = hc::wire_rows(cx.q.data(), cx.N, cx.nQ);
+    const size_t packed = (size_t)dim * R.off[cx.nQ] * sizeof(u64);
+    double *d_rows = (double *)cx.pool.get(sizeof(double) * (size_t)Nh * dim);
+    double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)dim * Nh);
+    u64 *d_out = cx.pool.get(sizeof(u64) * (size_t)dim * elems);
+    u64 *d_packed = cx.pool.get(packed);
+    struct Release {
+        Context &cx;
+        u64 *a, *b, *c, *d;
+        ~Release() {
+            cx.pool.put(d);
+            cx.pool.put(c);
+            cx.pool.put(b);
+            cx.pool.put(a);
+        }
+    } release{cx, (u64 *)d_rows, (u64 *)d_slots, d_out, d_packed};
+    for (size_t g = g0; g * (size_t)Nh < end; g++) {
+        const size_t lo = std::max(first_vector, g * (size_t)Nh), hi = std::min(end, (g + 1) * (size_t)Nh);
+        src.stage(cx, lo - first_vector, hi - lo, d_rows);
+        hc::diag_pack(cx.stream, d_rows, (long long)(hi - lo), dim, Nh, d_slots, (babies > 0 && babies < dim) ? babies : 0, (int)(lo - g * (size_t)Nh));
+        encrypt_sym_device(cx, d_slots, dim, key, akey, HY_DB_NONCE_BASE + (first_block + g) * dim, (first_block + g) * dim, d_out);
+        cx.timer_begin("k_wire_pack");
+        hc::wire_pack(cx.stream, cx.d_mod, cx.N, d_out, elems, 0, (size_t)dim, 1, cx.nQ, R, d_packed);
+        cx.timer_end("k_wire_pack");
+        HIP_CHECK(hipMemcpyAsync(payload0 + (g - g0) * stride, d_packed, packed, hipMemcpyDeviceToHost, cx.stream));
+        cx.sync();  // the host buffer is the caller's; the block buffers are reused by the next block
+    }
+}
+void client_db_delta_make_seeded(Context &cx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32],
+                                 const uint8_t a_seed[32], int babies, size_t first_block, unsigned char *payload0, size_t stride) {
+    const int dim = cx.prm.dim;
+    if (!cx.d_sk) throw StateError("hydia: secret key not loaded (a seeded delta is the secret-key holder's; hydia_db_delta_make takes the public key)");
+    check_delta_nonces(cx, first_vector, n, first_block);  // (a refused call leaves the rows as they were)
+    if (normalise)
+        for (size_t v = 0; v < n; v++) normalize(rows + v * dim, dim);
+    RowSource src;
+    src.host = rows;
+    delta_blocks_seeded(cx, first_vector, src, n, make_key(seed), make_key(a_seed), babies, first_block, payload0, stride);
+}
+void client_db_delta_make_seeded_device(Context &cx, size_t first_vector, const DevRows &rows, int normalise, const uint8_t seed[32],
+                                        const uint8_t a_seed[32], int babies, size_t first_block, unsigned char *payload0, size_t stride) {
+    RowSource src;
+    src.dev = &rows;
+    src.normalise = normalise;
+    if (!cx.d_sk) throw StateError("hydia: secret key not loaded (a seeded delta is the secret-key holder's; hydia_db_delta_make takes the public key)");
+    check_delta_nonces(cx, first_vector, rows.n, first_block);
+    wait_for_producer(cx, rows.stream);
+    delta_blocks_seeded(cx, first_vector, src, rows.n, make_key(seed), make_key(a_seed), babies, first_block, payload0, stride);
+}
+
 // In-place update of a resident PLAIN gallery (kind 7 / 8): the update loop with encode_device in place of encrypt_device — no seed,
 // no nonce.  The encoder rounds once per update, and symmetrically: encode(-x) + encode(x) = 0 in every residue, so the negated rows
 // restore an existing block exactly.
@@ -835,7 +894,7 @@ static void queries_seeded(Context &cx, const RowSource &src, size_t n, const Ch
         const int Q = (int)std::min(pass, n - q0);
         src.stage(cx, q0, (size_t)Q, d_q);
         hc::query_tile(cx.stream, d_q, Q, dim, Nh, d_slots);
-        encrypt_sym_device(cx, d_slots, Q, key, akey, nonce0 + q0, d_out);
+        encrypt_sym_device(cx, d_slots, Q, key, akey, nonce0 + q0, nonce0 + q0, d_out);
         if (wire) {
             cx.timer_begin("k_wire_pack");
             hc::wire_pack(cx.stream, cx.d_mod, cx.N, d_out, elems, 0, (size_t)Q, 1, cx.nQ, *wire, d_packed);

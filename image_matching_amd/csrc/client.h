@@ -92,6 +92,13 @@ void client_db_delta_make(Context &cx, size_t first_vector, double *rows, size_t
                           size_t first_block, unsigned char *payload0, size_t stride);
 void client_db_delta_make_device(Context &cx, size_t first_vector, const DevRows &rows, int normalise, const uint8_t seed[32], int babies,
                                  size_t first_block, unsigned char *payload0, size_t stride);
+// a SEEDED database delta (hydia_db_delta_make_seeded): the c0 halves of the secret-key encryptions (c0, a) of the same diagonal images,
+// e0 under `seed` at the enrolment's nonces, a under the public a_seed at (first_block + block) * vector_dim + i, as the packed payloads
+// of SEEDED_QUERY messages in host memory.  Needs the secret key (StateError otherwise); no database is touched
+void client_db_delta_make_seeded(Context &cx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32],
+                                 const uint8_t a_seed[32], int babies, size_t first_block, unsigned char *payload0, size_t stride);
+void client_db_delta_make_seeded_device(Context &cx, size_t first_vector, const DevRows &rows, int normalise, const uint8_t seed[32],
+                                        const uint8_t a_seed[32], int babies, size_t first_block, unsigned char *payload0, size_t stride);
 // one handle per probe: query i = client_encrypt_query(row i, seed, nonce0 + i) / client_encode_query(row i), bit for bit
 std::vector<Ct> client_encrypt_queries_device(Context &cx, const DevRows &rows, const uint8_t seed[32], uint64_t nonce0);
 std::vector<Ct> client_encode_queries_device(Context &cx, const DevRows &rows);

@@ -2,9 +2,8 @@
 #pragma once
 #include "kernels.h"
 
-struct ChaChaKey {
-    unsigned k[8];
-};
+#include "chacha_dev.h"  // ChaChaKey, the ChaCha20 block and the uniform residues drawn from it (after kernels.h: it needs the HIP runtime's attributes)
+
 // stream ids of the deterministic sampler specification (DESIGN.md §"Randomness")
 #define HY_DOM_SK 1ull
 #define HY_DOM_PK_A 2ull
@@ -82,4 +81,9 @@ void wire_check(hipStream_t st, const ModC *mod, int N, const u64 *src, size_t i
 // rows are canonical (wire_check) and L describes a ciphertext database
 void db_wire(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *src, const WireRows &R, void *db, size_t t0, int X, const DbLayout &L,
              bool store);
+// one block of a SEEDED database delta: the same for ciphertexts (c0_x, a_x), c0 from the packed rows [X][R.off[nQ]] words at src and
+// a_x limb j = the uniform stream (SYM_A, nonce0 + x, 0, j) under akey, generated inside the kernel (k_db_accumulate_seeded /
+// k_db_store_seeded and their 46-bit forms).  X <= 65535, nonce0 + X < 2^40
+void db_wire_seeded(hipStream_t st, const ChaChaKey &akey, u64 nonce0, const ModC *mod, int N, int nQ, const u64 *src, const WireRows &R, void *db,
+                    size_t t0, int X, const DbLayout &L, bool store);
 }  // namespace hc

@@ -18,32 +18,6 @@ namespace {
 
 __device__ __constant__ u64 d_gauss_cdt[HYDIA_GAUSS_CDT_LEN] = HYDIA_GAUSS_CDT_VALUES;
 
-DEV unsigned rotl32(unsigned v, int n) { return (v << n) | (v >> (32 - n)); }
-#define CHACHA_QR(a, b, c, d) \
-    a += b; d ^= a; d = rotl32(d, 16); \
-    c += d; b ^= c; b = rotl32(b, 12); \
-    a += b; d ^= a; d = rotl32(d, 8);  \
-    c += d; b ^= c; b = rotl32(b, 7);
-
-// ChaCha20 block with a 64-bit block counter (words 12,13) and a 64-bit stream id (words 14,15)
-DEV void chacha_block(const ChaChaKey &key, u64 stream, u64 block, unsigned out[16]) {
-    unsigned s[16], x[16];
-    s[0] = 0x61707865u; s[1] = 0x3320646eu; s[2] = 0x79622d32u; s[3] = 0x6b206574u;
-#pragma unroll
-    for (int i = 0; i < 8; i++) s[4 + i] = key.k[i];
-    s[12] = (unsigned)block; s[13] = (unsigned)(block >> 32);
-    s[14] = (unsigned)stream; s[15] = (unsigned)(stream >> 32);
-#pragma unroll
-    for (int i = 0; i < 16; i++) x[i] = s[i];
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        CHACHA_QR(x[0], x[4], x[8], x[12]) CHACHA_QR(x[1], x[5], x[9], x[13]) CHACHA_QR(x[2], x[6], x[10], x[14]) CHACHA_QR(x[3], x[7], x[11], x[15])
-        CHACHA_QR(x[0], x[5], x[10], x[15]) CHACHA_QR(x[1], x[6], x[11], x[12]) CHACHA_QR(x[2], x[7], x[8], x[13]) CHACHA_QR(x[3], x[4], x[9], x[14])
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i++) out[i] = x[i] + s[i];
-}
-
 // uniform residues: thread = one ChaCha block = 4 coefficients (128 random bits each, reduced mod q).
 // grid (N/4/256 rounded up, ny, nz): stream = base + y*step_y + z*step_z ; out = dst + y*stride_y + z*stride_z
 __global__ __launch_bounds__(256) void k_sample_uniform(ChaChaKey key, const ModC *__restrict__ mod, int N, u64 sbase,
@@ -53,15 +27,11 @@ __global__ __launch_bounds__(256) void k_sample_uniform(ChaChaKey key, const Mod
     if (blk * 4 >= N) return;
     const int y = blockIdx.y, z = blockIdx.z;
     const ModC M = mod[ysel.mod[y]];
-    unsigned w[16];
-    chacha_block(key, sbase + (u64)y * step_y + (u64)z * step_z, (u64)blk, w);
+    u64 a[4];
+    chacha_uniform4(key, sbase + (u64)y * step_y + (u64)z * step_z, (u64)blk, M, a);
     u64 *o = dst + (size_t)y * stride_y + (size_t)z * stride_z + (size_t)blk * 4;
 #pragma unroll
-    for (int t = 0; t < 4; t++) {
-        const u64 lo = (u64)w[4 * t] | ((u64)w[4 * t + 1] << 32);
-        const u64 hi = (u64)w[4 * t + 2] | ((u64)w[4 * t + 3] << 32);
-        o[t] = reduce128(((u128)hi << 64) | lo, M);
-    }
+    for (int t = 0; t < 4; t++) o[t] = a[t];
 }
 // small signed polynomials: MODE 0 ternary (16 per block), MODE 1 discrete Gaussian sigma 3.19 (8 per block).
 // grid (ceil(N/per/256), X): stream = base + x*step ; out int32 [X][N]
@@ -164,15 +134,8 @@ __global__ __launch_bounds__(256) void k_enc_sym(ChaChaKey akey, const ModC *__r
     if (blk * 4 >= N) return;
     const int j = blockIdx.y, x = blockIdx.z;
     const ModC M = mod[j];
-    unsigned w[16];
-    chacha_block(akey, sbase + (u64)j + ((u64)x << 16), (u64)blk, w);
     u64 a[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-        const u64 lo = (u64)w[4 * t] | ((u64)w[4 * t + 1] << 32);
-        const u64 hi = (u64)w[4 * t + 2] | ((u64)w[4 * t + 3] << 32);
-        a[t] = reduce128(((u128)hi << 64) | lo, M);
-    }
+    chacha_uniform4(akey, sbase + (u64)j + ((u64)x << 16), (u64)blk, M, a);
     const size_t is = (size_t)j * N + (size_t)blk * 4, i = (size_t)x * nQ * N + is;
     const ulonglong2 *tp = (const ulonglong2 *)(t0 + i), *sp = (const ulonglong2 *)(s + is);
     ulonglong2 *op = (ulonglong2 *)(c0 + i);

@@ -2,7 +2,8 @@
 // packed into the bit length of their modulus on the way out, unpacked and range-checked on the way in.
 //
 // Further down: the range check alone (k_wire_check) and the kernels that take the packed rows of a database delta straight to the
-// resident database (k_db_accumulate_wire, k_db_store_wire; include/hydia.h "database deltas").
+// resident database (k_db_accumulate_wire, k_db_store_wire; include/hydia.h "database deltas"), and their seeded forms, which take
+// the c0 halves alone and regenerate a where it is stored (k_db_accumulate_seeded, k_db_store_seeded).
 //
 // Pack and unpack are pure data movement.  The unit of both kernels is the GRANULE: 64 consecutive residues of one limb = exactly
 // w 64-bit words of the packed row (w = the bit length of q_j, wave-uniform, read from ModC at run time — one kernel serves every width).  One wave owns one
@@ -162,6 +163,106 @@ __global__ __launch_bounds__(256) void k_db_store_wire46(const ModC *__restrict_
     db_wire_body<true, 16>(tile, mod, N, nQ, src, R, db, L, t0, 1);
 }
 
+// ---- a SEEDED database delta (include/hydia.h "seeded database deltas"): one block's packed c0 rows [X][R.off[nQ]] words -> BOTH
+// components of resident ciphertexts t0 .. t0 + X - 1 in one pass.  A workgroup takes a tile of PER * 256 residues of limb j of
+// ciphertext x: component 0 += (STORE: :=) the c0 residues gathered from the packed words in LDS, exactly as db_wire_body does, and
+// component 1 += (:=) the matching residues of a, REGENERATED here — stream (SYM_A, nonce0 + x, 0, j) under the public akey, ChaCha
+// block = coefficient / 4, chacha_dev.h's chacha_uniform4, the thread of k_enc_sym and k_sample_uniform — so neither component has a
+// 64-bit image in HBM and a is never read from anywhere.  A thread owns PER consecutive residues of both components: two residue pairs
+// = ONE ChaCha block (PER = 4; 2 x 16 or 2 x 12 bytes, the pairs adjacent in either placement because 4 divides 128), or db_layout.h's
+// 92-byte granule of sixteen 46-bit residues = FOUR blocks (PER = 16).  One thread owns every dword it reads and writes: no atomics.
+// c0 was range-checked beforehand (k_wire_check) and a is reduced by construction: both operands of the add are canonical.
+// grid (ceil(N / (PER 256)), limbs, X); limb j = blockIdx.y + j0
+template <bool STORE>
+__device__ __forceinline__ void db_put_pair(unsigned char *d, bool pk, u64 ax, u64 ay, u64 q) {
+    if (!STORE) {
+        db_accumulate_pair(d, pk, ax, ay, q);
+    } else if (pk) {
+        unsigned v[3];
+        db_pack_pair48(ax, ay, v);
+        unsigned *o = reinterpret_cast<unsigned *>(d);
+        o[0] = v[0];
+        o[1] = v[1];
+        o[2] = v[2];
+    } else {
+        reinterpret_cast<u64 *>(d)[0] = ax;
+        reinterpret_cast<u64 *>(d)[1] = ay;
+    }
+}
+template <bool STORE>
+__device__ __forceinline__ void db_put_granule46(unsigned char *d, const u64 a[16], u64 q) {
+    unsigned *o = reinterpret_cast<unsigned *>(d);
+    if (!STORE) {
+        db_accumulate_granule46(o, a, q);
+    } else {
+        unsigned v[23];
+        db_pack_granule46(a, v);
+#pragma unroll
+        for (int k = 0; k < 23; k++) o[k] = v[k];
+    }
+}
+template <bool STORE, int PER>
+__device__ __forceinline__ void db_seeded_body(u64 *tile, const ChaChaKey &akey, u64 nonce0, const ModC *__restrict__ mod, int N, int nQ,
+                                               const u64 *__restrict__ src, WireRows R, unsigned char *__restrict__ db, const DbLayout &L,
+                                               size_t t0, int j0) {
+    const int j = blockIdx.y + j0, x = blockIdx.z;
+    const ModC M = mod[j];
+    const int w = 64 - __clzll((long long)M.q);
+    const u64 mask = w == 64 ? ~0ull : (1ull << w) - 1;
+    const size_t c0 = (size_t)blockIdx.x * (PER * 256);                     // first residue of the workgroup (a multiple of 64)
+    const int span = (int)((size_t)N - c0 < (size_t)(PER * 256) ? (size_t)N - c0 : (size_t)(PER * 256));  // its residues (N is a multiple of 512)
+    const u64 *row = src + (size_t)x * R.off[nQ] + R.off[j] + (c0 >> 6) * w;
+    for (int k = threadIdx.x; k < (span >> 6) * w; k += 256) tile[k] = row[k];
+    __syncthreads();
+    const int r0 = threadIdx.x * PER;
+    if (r0 >= span) return;
+    const u64 stream = HY_STREAM(HY_DOM_SYM_A, nonce0 + (u64)x, 0, j), blk0 = (u64)((c0 + r0) >> 2);
+    unsigned char *d0 = db + db_offset(L, N, t0 + x, 0, j, c0 + r0), *d1 = db + db_offset(L, N, t0 + x, 1, j, c0 + r0);
+    u64 v[PER];
+#pragma unroll
+    for (int r = 0; r < PER; r++) v[r] = wire_field(tile, r0 + r, w, mask);
+    if constexpr (PER == 4) {
+        const bool pk = L.packed && j > 0;
+        const int pair_bytes = pk ? 12 : 16;
+        db_put_pair<STORE>(d0, pk, v[0], v[1], M.q);
+        db_put_pair<STORE>(d0 + pair_bytes, pk, v[2], v[3], M.q);
+        chacha_uniform4(akey, stream, blk0, M, v);
+        db_put_pair<STORE>(d1, pk, v[0], v[1], M.q);
+        db_put_pair<STORE>(d1 + pair_bytes, pk, v[2], v[3], M.q);
+    } else {
+        db_put_granule46<STORE>(d0, v, M.q);
+#pragma unroll
+        for (int b = 0; b < PER / 4; b++) chacha_uniform4(akey, stream, blk0 + b, M, v + 4 * b);
+        db_put_granule46<STORE>(d1, v, M.q);
+    }
+}
+// the 8-byte and 6-byte residues (limb 0, every limb of a 48-bit or unpacked layout): 1024 residues = 16 granules <= 1024 words per workgroup
+__global__ __launch_bounds__(256) void k_db_accumulate_seeded(ChaChaKey akey, u64 nonce0, const ModC *__restrict__ mod, int N, int nQ,
+                                                              const u64 *__restrict__ src, WireRows R, unsigned char *__restrict__ db,
+                                                              DbLayout L, size_t t0) {
+    __shared__ u64 tile[1024];
+    db_seeded_body<false, 4>(tile, akey, nonce0, mod, N, nQ, src, R, db, L, t0, 0);
+}
+__global__ __launch_bounds__(256) void k_db_store_seeded(ChaChaKey akey, u64 nonce0, const ModC *__restrict__ mod, int N, int nQ,
+                                                         const u64 *__restrict__ src, WireRows R, unsigned char *__restrict__ db, DbLayout L,
+                                                         size_t t0) {
+    __shared__ u64 tile[1024];
+    db_seeded_body<true, 4>(tile, akey, nonce0, mod, N, nQ, src, R, db, L, t0, 0);
+}
+// the 46-bit limbs of a bits46 layout (w <= 46): 4096 residues = 64 granules <= 2944 words per workgroup; limb j = blockIdx.y + 1
+__global__ __launch_bounds__(256) void k_db_accumulate_seeded46(ChaChaKey akey, u64 nonce0, const ModC *__restrict__ mod, int N, int nQ,
+                                                                const u64 *__restrict__ src, WireRows R, unsigned char *__restrict__ db,
+                                                                DbLayout L, size_t t0) {
+    __shared__ u64 tile[64 * 46];
+    db_seeded_body<false, 16>(tile, akey, nonce0, mod, N, nQ, src, R, db, L, t0, 1);
+}
+__global__ __launch_bounds__(256) void k_db_store_seeded46(ChaChaKey akey, u64 nonce0, const ModC *__restrict__ mod, int N, int nQ,
+                                                           const u64 *__restrict__ src, WireRows R, unsigned char *__restrict__ db,
+                                                           DbLayout L, size_t t0) {
+    __shared__ u64 tile[64 * 46];
+    db_seeded_body<true, 16>(tile, akey, nonce0, mod, N, nQ, src, R, db, L, t0, 1);
+}
+
 }  // namespace
 
 namespace hc {
@@ -220,6 +321,28 @@ void db_wire(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *src, con
     } else {
         hipLaunchKernelGGL(k_db_accumulate_wire, g2, dim3(256), 0, st, mod, N, nQ, src, R, d, L, t0);
         if (b46 && nQ > 1) hipLaunchKernelGGL(k_db_accumulate_wire46, g16, dim3(256), 0, st, mod, N, nQ, src, R, d, L, t0);
+    }
+}
+
+// X <= 65535 ciphertexts: c0 from the packed rows [X][R.off[nQ]] words at src, a from (akey, nonce0 + x)
+void db_wire_seeded(hipStream_t st, const ChaChaKey &akey, u64 nonce0, const ModC *mod, int N, int nQ, const u64 *src, const WireRows &R, void *db,
+                    size_t t0, int X, const DbLayout &L, bool store) {
+    if (L.plain || X < 1 || X > 65535 || N < 512 || N % 512 || nonce0 + (u64)X >= (1ull << 40))
+        throw std::runtime_error("hydia: db_wire_seeded: bad shape");
+    const bool b46 = L.bits46 && L.packed;
+    if (b46)
+        for (int j = 1; j < nQ; j++)
+            if (R.off[j + 1] - R.off[j] > (unsigned)(N / 64) * 46u) throw std::runtime_error("hydia: db_wire_seeded: a limb wider than 46 bits in a 46-bit layout");
+    // resident bytes (read and) written + the packed bytes read; a costs no memory traffic
+    hk::ledger_add(store ? "k_db_store_seeded" : "k_db_accumulate_seeded", (double)X * ((store ? 1.0 : 2.0) * L.ct_bytes + 1.0 * R.off[nQ] * 8));
+    const dim3 g4((N + 1023) / 1024, b46 ? 1 : nQ, X), g16((N + 4095) / 4096, nQ - 1, X);
+    unsigned char *d = (unsigned char *)db;
+    if (store) {
+        hipLaunchKernelGGL(k_db_store_seeded, g4, dim3(256), 0, st, akey, nonce0, mod, N, nQ, src, R, d, L, t0);
+        if (b46 && nQ > 1) hipLaunchKernelGGL(k_db_store_seeded46, g16, dim3(256), 0, st, akey, nonce0, mod, N, nQ, src, R, d, L, t0);
+    } else {
+        hipLaunchKernelGGL(k_db_accumulate_seeded, g4, dim3(256), 0, st, akey, nonce0, mod, N, nQ, src, R, d, L, t0);
+        if (b46 && nQ > 1) hipLaunchKernelGGL(k_db_accumulate_seeded46, g16, dim3(256), 0, st, akey, nonce0, mod, N, nQ, src, R, d, L, t0);
     }
 }
 

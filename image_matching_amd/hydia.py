@@ -172,6 +172,11 @@ def load_library():
         "hydia_db_delta_make": (i32, [vp, sz, vp, sz, i32, vp, i32, sz, vp, sz, C.POINTER(sz)]),
         "hydia_db_delta_make_device": (i32, [vp, sz, C.POINTER(_DevRows), i32, vp, i32, sz, vp, sz, C.POINTER(sz)]),
         "hydia_db_delta_apply": (i32, [vp, vp, sz]),
+        "hydia_db_delta_seeded_bytes": (i32, [vp, sz, sz, C.POINTER(sz)]),
+        "hydia_db_delta_seeded_peek": (i32, [vp, sz, C.POINTER(_DeltaInfo)]),
+        "hydia_db_delta_make_seeded": (i32, [vp, sz, vp, sz, i32, vp, vp, i32, sz, vp, sz, C.POINTER(sz)]),
+        "hydia_db_delta_make_seeded_device": (i32, [vp, sz, C.POINTER(_DevRows), i32, vp, vp, i32, sz, vp, sz, C.POINTER(sz)]),
+        "hydia_db_delta_apply_seeded": (i32, [vp, vp, sz]),
         "hydia_compute_similarity_gallery_multi": (i32, [vp, vp, u32, vp]),
         "hydia_index_scenario_gallery_multi": (i32, [vp, vp, u32, vp]),
         "hydia_membership_scenario_gallery_multi": (i32, [vp, vp, u32, vp]),
@@ -414,6 +419,24 @@ def db_delta_peek(message):
     info = _DeltaInfo()
     _chk(load_library().hydia_db_delta_peek(_p(raw) if raw.size else None, raw.size, C.byref(info)))
     return {k: int(getattr(info, k)) for k, _ in _DeltaInfo._fields_}
+
+
+def db_delta_seeded_peek(message):
+    """Host-only (hydia_db_delta_seeded_peek): db_delta_peek for a SEEDED database delta (magic HYDDELS1, type 2 messages); the same
+    dict.  A malformed delta, an unseeded one included: HydiaError(-1) naming the field."""
+    raw = np.frombuffer(bytes(message), dtype=np.uint8)
+    info = _DeltaInfo()
+    _chk(load_library().hydia_db_delta_seeded_peek(_p(raw) if raw.size else None, raw.size, C.byref(info)))
+    return {k: int(getattr(info, k)) for k, _ in _DeltaInfo._fields_}
+
+
+def _public_seed(x):
+    """a PUBLIC expansion seed: None = a fresh hydia_random_seed, otherwise as _seed"""
+    if x is not None:
+        return _seed(x)
+    out = np.zeros(32, dtype=np.uint8)
+    _chk(load_library().hydia_random_seed(_p(out)))
+    return out
 
 
 def _wire_out(call):
@@ -971,6 +994,38 @@ class Context:
         raw = np.frombuffer(bytes(message), dtype=np.uint8)
         _chk(self.L.hydia_db_delta_apply(self.h, _p(raw) if raw.size else None, raw.size))
 
+    # ---- seeded database deltas (include/hydia.h): the maker holds the SECRET key; only the c0 halves travel
+    def db_delta_seeded_bytes(self, first_vector, n):
+        """the size of the seeded delta of rows first_vector .. first_vector + n - 1 on this context (host arithmetic only)"""
+        b = C.c_size_t()
+        _chk(self.L.hydia_db_delta_seeded_bytes(self.h, first_vector, n, C.byref(b)))
+        return b.value
+
+    def db_delta_seeded_peek(self, message):
+        """the module's db_delta_seeded_peek (context-free, host only)"""
+        return db_delta_seeded_peek(message)
+
+    def db_delta_make_seeded(self, first_vector, rows, normalise=True, seed=None, a_seed=None, babies=None, first_block=0):
+        """hydia_db_delta_make_seeded[_device]: db_delta_make on a context that holds the SECRET key — the c0 halves alone, half the
+        bytes, for db_delta_apply_seeded.  seed (secret, the noise) as in db_delta_make; a_seed (PUBLIC, travels in the message):
+        None = a fresh hydia_random_seed — it must never have served a query under this key or another delta on that database, and
+        must differ from seed (include/hydia.h)."""
+        B = self.dim if babies is None else int(babies)
+        sd, ad = _seed(seed), _public_seed(a_seed)  # ONE pair for the sizing call and the making call
+        if _is_device_tensor(rows):
+            d = _dev_rows(self, rows)
+            return _wire_out(lambda buf, cap, n: self.L.hydia_db_delta_make_seeded_device(self.h, first_vector, C.byref(d), 1 if normalise else 0,
+                                                                                         _p(sd), _p(ad), B, first_block, buf, cap, n))
+        assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.ndim == 2 and rows.shape[1] == self.dim
+        return _wire_out(lambda buf, cap, n: self.L.hydia_db_delta_make_seeded(self.h, first_vector, _p(rows), rows.shape[0], 1 if normalise else 0,
+                                                                              _p(sd), _p(ad), B, first_block, buf, cap, n))
+
+    def db_delta_apply_seeded(self, message):
+        """hydia_db_delta_apply_seeded: db_delta_apply for a seeded delta — c0 from the message, a regenerated on the GPU straight into
+        the resident layout.  Needs no key.  Every header and c0 residue is checked first: a refused delta (HydiaError) changes nothing."""
+        raw = np.frombuffer(bytes(message), dtype=np.uint8)
+        _chk(self.L.hydia_db_delta_apply_seeded(self.h, _p(raw) if raw.size else None, raw.size))
+
     # ---- templates already in device memory (include/hydia.h, hydia_dev_rows): `rows` is a tensor on this context's GPU, only read
     def rows_widen_device(self, rows, normalise=True):
         """hydia_rows_widen_device: the rows widened exactly to float64 (and divided by their L2 norm), as a new tensor [n][vector_dim]"""
@@ -1163,6 +1218,29 @@ class DiagonalEnroller:
         sd = bytes(_seed(seed))
         for lo in range(0, n, slots):
             yield self.cc.db_delta_make(lo, database[lo:lo + slots], True, sd, babies, first_block)
+        self.numVectors = n
+
+    # ---- seeded database deltas (include/hydia.h): this enroller is the owner — it holds the SECRET key; half the bytes travel
+    def updateToWireSeeded(self, first_vector, rows, normalise=True, seed=None, a_seed=None, babies=None, first_block=0):
+        """updateToWire on a key-holding context: one SEEDED delta message (Context.db_delta_make_seeded) for
+        DiagonalSender.applyDBWireSeeded.  a_seed=None draws a fresh hydia_random_seed."""
+        self._one_context()
+        m = self.cc.db_delta_make_seeded(first_vector, rows, normalise, seed, a_seed, babies, first_block)
+        self.numVectors = max(self.numVectors, first_vector + rows.shape[0])
+        return m
+
+    def appendToWireSeeded(self, rows, n_resident, seed=None, a_seed=None, babies=None, first_block=0):
+        """append `rows` (normalised in place) after the n_resident vectors the sender's database holds, as a seeded delta"""
+        return self.updateToWireSeeded(n_resident, rows, True, seed, a_seed, babies, first_block)
+
+    def serializeDBToWireSeeded(self, database, seed=None, a_seed=None, babies=None, first_block=0):
+        """serializeDBToWire as seeded deltas: one message per 'slots'-vector block, in order.  ONE seed and ONE a_seed for the whole
+        database (None: each drawn once), as an enrolment uses one seed — the blocks differ in their nonces."""
+        self._one_context()
+        n, slots = database.shape[0], self.cc.N // 2
+        sd, ad = bytes(_seed(seed)), bytes(_public_seed(a_seed))
+        for lo in range(0, n, slots):
+            yield self.cc.db_delta_make_seeded(lo, database[lo:lo + slots], True, sd, ad, babies, first_block)
         self.numVectors = n
 
     def rekeyDB(self, key):
@@ -1461,6 +1539,15 @@ class DiagonalSender:
         if not isinstance(self.cc, Context):
             raise HydiaError(-2, "hydia: database deltas are not applied on a sharded context (apply one per shard context)")
         self.cc.db_delta_apply(message)
+        self.numVectors = self.cc.db_stats()[0]
+        return self.numVectors
+
+    def applyDBWireSeeded(self, message):
+        """a SEEDED delta message of DiagonalEnroller.updateToWireSeeded / appendToWireSeeded / serializeDBToWireSeeded into this
+        sender's database (Context.db_delta_apply_seeded: checked, transactional, no key needed); returns the new vector count"""
+        if not isinstance(self.cc, Context):
+            raise HydiaError(-2, "hydia: database deltas are not applied on a sharded context (apply one per shard context)")
+        self.cc.db_delta_apply_seeded(message)
         self.numVectors = self.cc.db_stats()[0]
         return self.numVectors
 

@@ -550,7 +550,8 @@ int hydia_encode_queries_device(hydia_ctx *ctx, const hydia_dev_rows *rows, hydi
  *     point takes unchanged, each freed on its own.  c0 is not range-checked.
  *   Errors: no secret key on the encrypting context: HYDIA_ERR_STATE.  nonce0 + count > 2^40, a null pointer, a_seed == seed:
  *     HYDIA_ERR_ARG.  count == 0: HYDIA_OK and nothing is written.
- * NOT seeded: the switching key of hydia_db_rekey, hydia_group_keygen, approaches 1 - 4, database enrolment. */
+ * NOT seeded: the switching key of hydia_db_rekey, hydia_group_keygen, approaches 1 - 4, a LOCAL database enrolment or update
+ * (hydia_db_enroll*, hydia_db_update).  An enrolment or update that is SHIPPED to a sender is: "seeded database deltas" below. */
 int hydia_keygen_seeded(hydia_ctx *ctx, const uint8_t seed[32], const uint8_t a_seed[32]);
 int hydia_keygen_rotations_seeded(hydia_ctx *ctx, const uint8_t seed[32], const uint8_t a_seed[32], const int32_t *rots, uint32_t n);
 int hydia_get_key_seed(const hydia_ctx *ctx, uint8_t out[32]);
@@ -704,6 +705,59 @@ int hydia_db_delta_make(hydia_ctx *ctx, size_t first_vector, double *rows /* n x
 int hydia_db_delta_make_device(hydia_ctx *ctx, size_t first_vector, const hydia_dev_rows *rows, int normalise, const uint8_t seed[32],
                                int babies, size_t first_block, void *buf, size_t cap, size_t *len);
 int hydia_db_delta_apply(hydia_ctx *ctx, const void *buf, size_t len);
+/* ---- seeded database deltas (an extension): the delta of an enroller that holds the SECRET key — half the bytes.
+ * Under the secret key c1 of a fresh encryption is the uniform polynomial a, the expansion of a 32-byte public seed, so only c0 travels:
+ * at the default parameters a block's message is 1 176 502 632 bytes against 2 353 004 904, 0.50 of the unseeded delta.  The maker
+ * samples one polynomial and runs one transform batch per ciphertext where hydia_db_delta_make takes three of each; the sender
+ * regenerates a on its GPU straight into the resident layout (k_db_accumulate_seeded / k_db_store_seeded: no 64-bit image of either
+ * component in device memory).
+ * TRUST MODEL: the ENROLLER's context now holds the SECRET key and the templates — this is for an owner who is both enroller and
+ * receiver and has its own gallery matched on someone else's GPU.  An enroller that holds only the receiver's public key keeps
+ * hydia_db_delta_make.  The SENDER still never sees a template and needs no key at all to apply.
+ * SEEDS: two, and they must differ.  `seed` is secret and addresses the noise e0 at the enrolment's nonces; its rule stays the one of
+ * hydia_db_update and "database deltas" above: never used on this database before.  `a_seed` is PUBLIC and travels in every message.
+ * For one secret key a pair (a_seed, nonce) MUST NEVER ENCRYPT TWO PLAINTEXTS, and database ciphertexts and seeded queries share
+ * stream domain 9: a delta's a_seed must never have been used for a QUERY under that key, and never for ANOTHER DELTA on that database
+ * (nor for its enrolment).  Take every one from hydia_random_seed.
+ * NOT AUTHENTICATED, like every delta.  Noise: one fresh Gaussian e0 — lower than the public-key path's e0 + e1 s + u e_pk; the noise of
+ * a key switch is not involved.
+ * FORMAT (little-endian): a container of its own next to "HYDDELT1", NOT a wire type (hydia_wire_peek keeps refusing type 7 and up).
+ *   header   the 64 bytes of a delta header, same fields at the same offsets, under magic "HYDDELS1", version 1
+ *   then n_blocks ordinary type 2 (seeded query batch) wire messages back to back, nothing after the last.  Message b is block
+ *            first_vector / slots + b: count = vector_dim, n_polys = 1, n_limbs = n_q, scale = 2^scale_bits, a_seed = the delta's,
+ *            nonce0 = (first_block + block) * vector_dim.  Ciphertext i of it is E = (c0_i, a(a_seed, nonce0 + i)), expanded exactly as
+ *            hydia_ct_expand_seeded expands a query: hydia_ct_from_wire of one block's message yields the block's ciphertexts.
+ * VALIDATION as for a delta (container header and the 360-byte message headers only, overflow-checked, HYDIA_ERR_ARG naming the
+ * field), and beyond it: type is 2, n_polys is 1, every message carries one a_seed, nonce0 of message b is (first_block + block) *
+ * vector_dim, nonce0 + count is below 2^40.  The two containers refuse each other by the magic: hydia_db_delta_apply_seeded and
+ * hydia_db_delta_seeded_peek name hydia_db_delta_apply for a "HYDDELT1" buffer; hydia_db_delta_apply / hydia_db_delta_peek refuse
+ * a "HYDDELS1" buffer as a bad magic.
+ *   hydia_db_delta_seeded_bytes   the size for rows first_vector .. first_vector + n - 1 on this context (host arithmetic only)
+ *   hydia_db_delta_seeded_peek    the context-free part of the validation, without a GPU
+ *   hydia_db_delta_make_seeded    arguments as hydia_db_delta_make, plus a_seed.  Per touched block: the update's diag_pack, ONE
+ *                          secret-key encryption pass (e0 under seed at the enrolment's nonce, a under a_seed; c1 is never written)
+ *                          and k_wire_pack of c0; one block in flight on the device at a time.  No secret key: HYDIA_ERR_STATE.
+ *                          a_seed == seed, n == 0, a bad babies, a null argument, nonces beyond 2^40, or cap too small (*len = the
+ *                          bytes needed): HYDIA_ERR_ARG with nothing written
+ *   hydia_db_delta_make_seeded_device   the same from rows in device memory; the rows are never written
+ *   hydia_db_delta_apply_seeded   targets, growth and refusals as hydia_db_delta_apply (kinds 5 and 6; nothing resident: first_vector
+ *                          must be 0; a plain gallery and kinds 1, 3, 4: HYDIA_ERR_STATE naming the kind; babies must be
+ *                          hydia_db_babies).  Needs no key.  TRANSACTIONAL AGAINST BAD INPUT: every header and every c0 residue of
+ *                          every block is range-checked (k_wire_check) before the database is grown or a byte is written; a is
+ *                          canonical by construction.  The packed c0 blocks are uploaded twice, one at a time: device memory beyond
+ *                          the database is one packed HALF block.  Ordered against queries in flight as hydia_db_update is.
+ * The result is bit for bit what hydia_db_delta_apply of the type 1 messages holding the expanded ciphertexts leaves.
+ * NOT served: a local hydia_db_update / hydia_db_enroll under the secret key, plain galleries, approaches 1 - 4, hydia_group_*, a
+ * streaming file form. */
+int hydia_db_delta_seeded_bytes(const hydia_ctx *ctx, size_t first_vector, size_t n, size_t *bytes);
+int hydia_db_delta_seeded_peek(const void *buf, size_t len, hydia_db_delta_info *out);
+int hydia_db_delta_make_seeded(hydia_ctx *ctx, size_t first_vector, double *rows /* n x vector_dim row-major */, size_t n, int normalise,
+                               const uint8_t seed[32], const uint8_t a_seed[32], int babies, size_t first_block, void *buf, size_t cap,
+                               size_t *len);
+int hydia_db_delta_make_seeded_device(hydia_ctx *ctx, size_t first_vector, const hydia_dev_rows *rows, int normalise,
+                                      const uint8_t seed[32], const uint8_t a_seed[32], int babies, size_t first_block, void *buf,
+                                      size_t cap, size_t *len);
+int hydia_db_delta_apply_seeded(hydia_ctx *ctx, const void *buf, size_t len);
 /* OpenFHEWrapper::chebyshevCompare (src/openFHE_wrapper.cpp:143-185) on every ciphertext of the batch */
 int hydia_chebyshev_compare(hydia_ctx *ctx, const hydia_ct *in, double delta, size_t sign_depth, hydia_ct **out);
 /* multi-GPU membership tail: sum the batch into one ciphertext, then EvalSum over all slots (:46-47) */

@@ -504,6 +504,19 @@ class DiagonalSender : public Sender {
         if (!cc->check(hydia_db_stats(cc->h, &numVectors, &cts, &bytes), "applyDBWire")) return 0;
         return numVectors;
     }
+    // The same for a SEEDED delta of DiagonalEnroller::updateToWireSeeded / appendToWireSeeded / serializeDBToWireSeeded
+    // (hydia_db_delta_apply_seeded: c0 from the message, a regenerated on the GPU; no key needed)
+    size_t applyDBWireSeeded(const std::vector<uint8_t> &message) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: applyDBWireSeeded: database deltas are not applied on a sharded context (one per shard context)" << std::endl;
+            return 0;
+        }
+        if (!cc->check(hydia_db_delta_apply_seeded(cc->h, message.data(), message.size()), "applyDBWireSeeded")) return 0;
+        size_t cts = 0, bytes = 0;
+        if (!cc->check(hydia_db_stats(cc->h, &numVectors, &cts, &bytes), "applyDBWireSeeded")) return 0;
+        return numVectors;
+    }
     std::vector<uint8_t> resultToWire(const std::vector<Ciphertext> &result) { return toWire(cc, result); }
     // computeSimilarity's scores as one message of their first `limbs` limbs (1 or 2): the decoder reads at most two, so with 2 the
     // receiver decrypts the same doubles from a sixth of the bytes; with 1 it decodes from q_0 alone.  For resultFromWire
@@ -1111,6 +1124,80 @@ class DiagonalEnroller : public EnrollerBase {
             const size_t hi = std::min(database.size(), lo + slots);
             std::vector<std::vector<double>> rows(database.begin() + lo, database.begin() + hi);
             messages.push_back(updateToWire(lo, rows, true, s, babies, first_block));
+            if (messages.back().empty()) return {};
+            std::copy(rows.begin(), rows.end(), database.begin() + lo);
+        }
+        numVectors = database.size();
+        return messages;
+    }
+    // Seeded database deltas (an extension; hydia.h): the ToWire methods for an enroller whose context holds the SECRET key — an owner
+    // who is also the receiver.  Only the c0 halves travel: half the bytes; the message goes to DiagonalSender::applyDBWireSeeded.
+    // seed32 (secret, the noise): updateRows' rule.  a_seed32 (PUBLIC, travels in the message; nullptr: a fresh hydia_random_seed) must
+    // never have served a query under this key or another delta on that database, and must differ from seed32
+    std::vector<uint8_t> updateToWireSeeded(size_t first_vector, std::vector<std::vector<double>> &rows, bool normalise = true,
+                                            const uint8_t *seed32 = nullptr, const uint8_t *a_seed32 = nullptr, int babies = 0,
+                                            size_t first_block = 0) {
+        if (!delta_ok("updateToWireSeeded")) return {};
+        const size_t dim = cc->info.vector_dim;
+        std::vector<double> flat(rows.size() * dim, 0.0);
+        for (size_t i = 0; i < rows.size(); i++)
+            for (size_t j = 0; j < dim && j < rows[i].size(); j++) flat[i * dim + j] = rows[i][j];
+        uint8_t s[32], a[32];
+        role_seed(s, seed32);
+        role_seed(a, a_seed32);
+        const int B = babies ? babies : (int)dim;
+        size_t need = 0, len = 0;
+        if (!cc->check(hydia_db_delta_seeded_bytes(cc->h, first_vector, rows.size(), &need), "updateToWireSeeded")) return {};
+        std::vector<uint8_t> message(need);
+        if (!cc->check(hydia_db_delta_make_seeded(cc->h, first_vector, flat.data(), rows.size(), normalise ? 1 : 0, s, a, B, first_block,
+                                                  message.data(), message.size(), &len),
+                       "updateToWireSeeded"))
+            return {};
+        message.resize(len);
+        for (size_t i = 0; i < rows.size(); i++)
+            for (size_t j = 0; j < dim && j < rows[i].size(); j++) rows[i][j] = flat[i * dim + j];
+        if (first_vector + rows.size() > numVectors) numVectors = first_vector + rows.size();
+        return message;
+    }
+    std::vector<uint8_t> updateToWireSeeded(size_t first_vector, const DeviceRows &rows, bool normalise = true, const uint8_t *seed32 = nullptr,
+                                            const uint8_t *a_seed32 = nullptr, int babies = 0, size_t first_block = 0) {
+        if (!delta_ok("updateToWireSeeded")) return {};
+        uint8_t s[32], a[32];
+        role_seed(s, seed32);
+        role_seed(a, a_seed32);
+        const int B = babies ? babies : (int)cc->info.vector_dim;
+        size_t need = 0, len = 0;
+        if (!cc->check(hydia_db_delta_seeded_bytes(cc->h, first_vector, rows.size(), &need), "updateToWireSeeded")) return {};
+        std::vector<uint8_t> message(need);
+        if (!cc->check(hydia_db_delta_make_seeded_device(cc->h, first_vector, &rows.d, normalise ? 1 : 0, s, a, B, first_block, message.data(),
+                                                         message.size(), &len),
+                       "updateToWireSeeded"))
+            return {};
+        message.resize(len);
+        if (first_vector + rows.size() > numVectors) numVectors = first_vector + rows.size();
+        return message;
+    }
+    std::vector<uint8_t> appendToWireSeeded(std::vector<std::vector<double>> &rows, size_t n_resident, const uint8_t *seed32 = nullptr,
+                                            const uint8_t *a_seed32 = nullptr, int babies = 0, size_t first_block = 0) {
+        return updateToWireSeeded(n_resident, rows, true, seed32, a_seed32, babies, first_block);
+    }
+    std::vector<uint8_t> appendToWireSeeded(const DeviceRows &rows, size_t n_resident, const uint8_t *seed32 = nullptr,
+                                            const uint8_t *a_seed32 = nullptr, int babies = 0, size_t first_block = 0) {
+        return updateToWireSeeded(n_resident, rows, true, seed32, a_seed32, babies, first_block);
+    }
+    // one message per block, in order; ONE seed and ONE a_seed for the whole database (the blocks differ in their nonces)
+    std::vector<std::vector<uint8_t>> serializeDBToWireSeeded(std::vector<std::vector<double>> &database, const uint8_t *seed32 = nullptr,
+                                                              const uint8_t *a_seed32 = nullptr, int babies = 0, size_t first_block = 0) {
+        if (!delta_ok("serializeDBToWireSeeded")) return {};
+        uint8_t s[32], a[32];
+        role_seed(s, seed32);
+        role_seed(a, a_seed32);
+        const size_t slots = cc->info.slots;
+        std::vector<std::vector<uint8_t>> messages;
+        for (size_t lo = 0; lo < database.size(); lo += slots) {
+            const size_t hi = std::min(database.size(), lo + slots);
+            std::vector<std::vector<double>> rows(database.begin() + lo, database.begin() + hi);
+            messages.push_back(updateToWireSeeded(lo, rows, true, s, a, babies, first_block));
             if (messages.back().empty()) return {};
             std::copy(rows.begin(), rows.end(), database.begin() + lo);
         }

@@ -8,6 +8,12 @@ memory, as a caller's); every call ends in a device synchronise.  Spread: min / 
            alternating over --repeats child processes each
   kernels  hydia_kernel_time and the byte ledger of k_wire_check, k_db_accumulate_wire and k_db_store_wire (a delta that appends a block)
            beside a device-to-device copy of as many bytes
+  --seeded the seeded delta (include/hydia.h "seeded database deltas") beside the whole one, on this tree's library alone:
+           seeded   hydia_db_delta_make_seeded / _apply_seeded and hydia_db_delta_make / _apply of the same block, alternating in ONE
+                    process over --repeats repeats (medians of --calls calls each), and the bytes of both messages
+           kernels_seeded   hydia_kernel_time and the byte ledger of k_wire_check, k_db_accumulate_seeded and k_db_store_seeded (a seeded
+                    delta that adds to the last block and creates the next one), beside the whole delta's kernels in the same process and
+                    a device-to-device copy of as many bytes
 The seeds repeat from call to call: a measurement, never a deployment (include/hydia.h, SEED).  Every leg is a child process of its own
 (one library per process).  One JSON line per child."""
 import argparse
@@ -132,12 +138,93 @@ def leg_kernels(args):
     return out
 
 
-LEGS = {"update": leg_update, "delta": leg_delta, "kernels": leg_kernels}
+def leg_seeded(args):
+    im, cc, rows, seed = setup(args)  # (keygen_rotations: the secret key is on the context)
+    a_seed = np.frombuffer((10).to_bytes(32, "little"), dtype=np.uint8).copy()
+    first = (args.blocks // 2) * cc.slots
+    need_w, need_s = cc.db_delta_bytes(first, rows.shape[0]), cc.db_delta_seeded_bytes(first, rows.shape[0])
+    buf_w, buf_s, ln_w, ln_s = np.empty(need_w, dtype=np.uint8), np.empty(need_s, dtype=np.uint8), C.c_size_t(), C.c_size_t()
+
+    def make_s():
+        assert cc.L.hydia_db_delta_make_seeded(cc.h, first, p(rows), rows.shape[0], 1, p(seed), p(a_seed), cc.dim, 0, p(buf_s), buf_s.size, C.byref(ln_s)) == 0
+
+    def apply_s():
+        assert cc.L.hydia_db_delta_apply_seeded(cc.h, p(buf_s), ln_s.value) == 0
+
+    def make_w():
+        assert cc.L.hydia_db_delta_make(cc.h, first, p(rows), rows.shape[0], 1, p(seed), cc.dim, 0, p(buf_w), buf_w.size, C.byref(ln_w)) == 0
+
+    def apply_w():
+        assert cc.L.hydia_db_delta_apply(cc.h, p(buf_w), ln_w.value) == 0
+    out = {"leg": "seeded", "blocks": args.blocks, "rows": rows.shape[0], "delta_bytes": need_w, "seeded_delta_bytes": need_s,
+           "ratio": round(need_s / need_w, 4), "group": cc.db_group(), "residue_bits": cc.db_residue_bits(), "repeats": []}
+    for _ in range(args.repeats):  # seeded and whole alternate inside every repeat
+        out["repeats"].append({"make_seeded_ms": timed(make_s, args.calls), "make_ms": timed(make_w, args.calls),
+                               "apply_seeded_ms": timed(apply_s, args.calls), "apply_ms": timed(apply_w, args.calls)})
+    for k in ("make_seeded_ms", "make_ms", "apply_seeded_ms", "apply_ms"):
+        out[k + "_medians"] = [r[k]["median"] for r in out["repeats"]]
+    cc.close()
+    return out
+
+
+def leg_kernels_seeded(args):
+    import torch  # (before the context: torch finds no device once the library has opened it)
+    torch.zeros(1, device="cuda")
+    im, cc, rows, seed = setup(args)
+    a_seed = np.frombuffer((10).to_bytes(32, "little"), dtype=np.uint8).copy()
+    first = args.blocks * cc.slots - 100  # the last 100 slots of the last block and a new block: one accumulate, one store per delta
+    need_w, need_s = cc.db_delta_bytes(first, rows.shape[0]), cc.db_delta_seeded_bytes(first, rows.shape[0])
+    buf, ln = np.empty(need_w, dtype=np.uint8), C.c_size_t()
+    out = {"leg": "kernels_seeded", "blocks": args.blocks}
+    names = {"seeded": ["k_wire_check", "k_db_accumulate_seeded", "k_db_store_seeded", "k_wire_pack"],
+             "whole": ["k_wire_check", "k_db_accumulate_wire", "k_db_store_wire", "k_wire_pack"]}
+    for kind in ("seeded", "whole"):
+        im.byte_ledger(1)
+        cc.kernel_time_reset()
+        for k in range(args.calls):
+            fv = first + (k + (args.calls if kind == "whole" else 0)) * cc.slots
+            if kind == "seeded":
+                assert cc.L.hydia_db_delta_make_seeded(cc.h, fv, p(rows), rows.shape[0], 1, p(seed), p(a_seed), cc.dim, 0, p(buf), buf.size, C.byref(ln)) == 0
+                assert cc.L.hydia_db_delta_apply_seeded(cc.h, p(buf), ln.value) == 0
+            else:
+                assert cc.L.hydia_db_delta_make(cc.h, fv, p(rows), rows.shape[0], 1, p(seed), cc.dim, 0, p(buf), buf.size, C.byref(ln)) == 0
+                assert cc.L.hydia_db_delta_apply(cc.h, p(buf), ln.value) == 0
+        ledger = im.byte_ledger(0)
+        out[kind] = {}
+        for name in names[kind]:
+            ms, launches = cc.kernel_time(name)
+            n, nbytes = ledger.get(name, (0, 0.0))
+            per = ms / max(launches, 1)
+            out[kind][name] = {"ms_per_launch": round(per, 4), "launches": launches, "ledger_bytes_per_launch": int(nbytes / max(n, 1)),
+                               "tb_per_s": round(nbytes / max(n, 1) / (per * 1e-3) / 1e12, 3) if per > 0 and n else None}
+    stats = cc.db_stats()
+    out["blocks_after"], out["group_after"], out["seeded_delta_bytes"], out["delta_bytes"] = stats[1] // cc.dim, cc.db_group(), need_s, need_w
+    cc.close()
+    # a device copy that reads and writes what each seeded apply kernel reads and writes of one block, and one of what the check reads
+    for name in ("k_db_accumulate_seeded", "k_db_store_seeded", "k_wire_check"):
+        nbytes = out["seeded"][name]["ledger_bytes_per_launch"]
+        half = max(nbytes // 2, 8)
+        src, dst = torch.empty(half, dtype=torch.uint8, device="cuda"), torch.empty(half, dtype=torch.uint8, device="cuda")
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        copies = []
+        for _ in range(args.calls + 1):
+            a.record()
+            dst.copy_(src)
+            b.record()
+            b.synchronize()
+            copies.append(a.elapsed_time(b))
+        ms = spread(copies[1:])
+        out["device_copy_of_%s_bytes" % name] = {"bytes_moved": 2 * half, "ms": ms, "tb_per_s": round(2 * half / (ms["median"] * 1e-3) / 1e12, 3)}
+        del src, dst
+    return out
+
+
+LEGS = {"update": leg_update, "delta": leg_delta, "kernels": leg_kernels, "seeded": leg_seeded, "kernels_seeded": leg_kernels_seeded}
 
 
 def child(args, leg, root):
     cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--log-n", str(args.log_n), "--dim", str(args.dim), "--blocks", str(args.blocks),
-           "--calls", str(args.calls)] + (["--root", root] if root else [])
+           "--calls", str(args.calls), "--repeats", str(args.repeats)] + (["--root", root] if root else [])
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1100)
     if r.returncode != 0:
         raise SystemExit("leg %s failed (%d): %s" % (leg, r.returncode, r.stderr[-2000:]))
@@ -158,10 +245,15 @@ def main():
     ap.add_argument("--root", default=None, help="(a child's) checkout to import image_matching_amd from")
     ap.add_argument("--leg", choices=sorted(LEGS), default=None)
     ap.add_argument("--only", default="delta,update,kernels")
+    ap.add_argument("--seeded", action="store_true", help="the seeded delta beside the whole one (legs seeded and kernels_seeded) instead")
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.root) if args.root else ROOT)
     if args.leg:
         print(json.dumps(LEGS[args.leg](args)), flush=True)
+        return
+    if args.seeded:
+        child(args, "seeded", None)
+        child(args, "kernels_seeded", None)
         return
     only = args.only.split(",")
     if "delta" in only:
