@@ -632,34 +632,41 @@ void client_enroll_device(Context &cx, const DevRows &rows, const uint8_t seed[3
     enroll_blocks(cx, src, rows.n, &key, first_block, babies);
 }
 
+// The walk over the blocks that source rows placed at vectors first_vector .. first_vector + n - 1 touch, shared by an in-place update
+// and a delta: per touched block g the rows are staged and packed into the block's vector_dim slot images (diag_pack with the form
+// `babies` and the rows' first slot), then block(g, d_slots) encrypts or encodes them and places the result.
+template <class Block>
+static void walk_touched_blocks(Context &cx, size_t first_vector, const RowSource &src, size_t n, int babies, Block block) {
+    const int dim = cx.prm.dim;
+    const size_t Nh = (size_t)cx.slots, end = first_vector + n;
+    PoolBuf rows(cx.pool, sizeof(double) * Nh * dim), slots(cx.pool, sizeof(double) * (size_t)dim * Nh);
+    double *d_rows = (double *)rows.p, *d_slots = (double *)slots.p;
+    for (size_t g = first_vector / Nh; g * Nh < end; g++) {
+        const size_t lo = std::max(first_vector, g * Nh), hi = std::min(end, (g + 1) * Nh);
+        src.stage(cx, lo - first_vector, hi - lo, d_rows);
+        hc::diag_pack(cx.stream, d_rows, (long long)(hi - lo), dim, (int)Nh, d_slots, (babies > 0 && babies < dim) ? babies : 0, (int)(lo - g * Nh));
+        block(g, d_slots);
+    }
+}
 // The block loop of an in-place update of a resident diagonal database (kind 5 / 6, key != nullptr) or plain gallery (kind 7 / 8,
 // key == nullptr): the sparse diagonal image of the n source rows at vectors first_vector .. first_vector + n - 1, freshly ENCRYPTED
-// with the enrolment's nonces or ENCODED, is added to the blocks they touch.  Per touched block: diag_pack with the rows' first slot,
-// encrypt_device / encode_device, then db_accumulate for a block that existed or db_store for a new one — a new block is bit-identical
-// to that block of an enrolment of the same rows (with the same seed).  Form and kind stay.
+// with the enrolment's nonces or ENCODED, is added to the blocks they touch.  Per touched block: the walk above, encrypt_device /
+// encode_device, then db_accumulate for a block that existed or db_store for a new one — a new block is bit-identical to that block of
+// an enrolment of the same rows (with the same seed).  Form and kind stay.
 static void update_blocks(Context &cx, size_t first_vector, const RowSource &src, size_t n, const ChaChaKey *key, size_t first_block) {
-    const int dim = cx.prm.dim, Nh = cx.slots, babies = cx.db_babies;
+    const int dim = cx.prm.dim, Nh = cx.slots;
     const size_t G_old = cx.db_cts / dim, out_elems = (size_t)(key ? 2 : 1) * cx.nQ * cx.N;
     const size_t n_new = std::max(cx.db_vectors, first_vector + n), G_new = (n_new + (size_t)Nh - 1) / (size_t)Nh;
     if (key) check_db_nonces(first_block, G_new, dim);
     cx.db_grow(n_new, G_new * (size_t)dim);  // (throws before anything is touched when a larger database does not fit)
-    double *d_rows = (double *)cx.pool.get(sizeof(double) * (size_t)Nh * dim);
-    double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)dim * Nh);
-    u64 *d_out = cx.pool.get(sizeof(u64) * (size_t)dim * out_elems);
-    const size_t end = first_vector + n;
-    for (size_t g = first_vector / (size_t)Nh; g * (size_t)Nh < end; g++) {
-        const size_t lo = std::max(first_vector, g * (size_t)Nh), hi = std::min(end, (g + 1) * (size_t)Nh);
-        src.stage(cx, lo - first_vector, hi - lo, d_rows);
-        hc::diag_pack(cx.stream, d_rows, (long long)(hi - lo), dim, Nh, d_slots, (babies > 0 && babies < dim) ? babies : 0, (int)(lo - g * (size_t)Nh));
-        if (key) encrypt_device(cx, d_slots, dim, *key, HY_DB_NONCE_BASE + (first_block + g) * dim, d_out);
-        else encode_device(cx, d_slots, dim, d_out);
-        if (g < G_old) cx.db_accumulate(g * dim, d_out, dim);
-        else cx.db_store(g * dim, d_out, dim);
-    }
+    PoolBuf out(cx.pool, sizeof(u64) * (size_t)dim * out_elems);
+    walk_touched_blocks(cx, first_vector, src, n, cx.db_babies, [&](size_t g, const double *d_slots) {
+        if (key) encrypt_device(cx, d_slots, dim, *key, HY_DB_NONCE_BASE + (first_block + g) * dim, out.p);
+        else encode_device(cx, d_slots, dim, out.p);
+        if (g < G_old) cx.db_accumulate(g * dim, out.p, dim);
+        else cx.db_store(g * dim, out.p, dim);
+    });
     cx.sync();
-    cx.pool.put(d_out);
-    cx.pool.put((u64 *)d_slots);
-    cx.pool.put((u64 *)d_rows);
 }
 // In-place update of a resident diagonal database (kind 5 / 6): a FRESH encryption of the sparse diagonal image of `rows` at vectors
 // first_vector .. first_vector + n - 1 is added to the blocks they touch (append: first_vector = the vector count — the padding slots
@@ -684,121 +691,65 @@ void client_db_update_device(Context &cx, size_t first_vector, const DevRows &ro
     update_blocks(cx, first_vector, src, rows.n, &key, first_block);
 }
 
-// The enroller's half of update_blocks, for a database that lies on ANOTHER machine (hydia_db_delta_make): per touched block the same
-// diag_pack (form `babies`) and encrypt_device under the enrolment's nonces, then k_wire_pack straight from the block buffer and a copy
-// of the packed rows to host memory at payload0 + b * stride for the b-th touched block.  Needs the public key alone; the resident database, if there
-// is one, is neither read nor written.  One block is in flight at a time.
-static void check_delta_nonces(const Context &cx, size_t first_vector, size_t n, size_t first_block) {
-    check_db_nonces(first_block, (first_vector + n + (size_t)cx.slots - 1) / (size_t)cx.slots, cx.prm.dim);
-}
-static void delta_blocks(Context &cx, size_t first_vector, const RowSource &src, size_t n, const ChaChaKey &key, int babies, size_t first_block,
-                         unsigned char *payload0, size_t stride) {
-    const int dim = cx.prm.dim, Nh = cx.slots;
-    const size_t end = first_vector + n, g0 = first_vector / (size_t)Nh, elems = (size_t)cx.nQ * cx.N;
+// The enroller's half of update_blocks, for a database that lies on ANOTHER machine (hydia_db_delta_make[_seeded]): per touched block
+// the same walk (form `babies`) and an encryption under the enrolment's nonces, then k_wire_pack straight from the block buffer and a
+// copy of the packed rows to host memory at payload0 + b * stride for the b-th touched block.  The resident database, if there is one,
+// is neither read nor written.  One block is in flight at a time.
+//   akey == nullptr: encrypt_device, both polynomials packed.  Needs the public key alone.
+//   akey != nullptr (the SEEDED delta of a key-holding enroller): encrypt_sym_device — one sampled polynomial (e0 under `key` at the same
+//   nonce) and one transform batch; a is drawn inside k_enc_sym under the PUBLIC akey at (first_block + block) * vector_dim, the nonce0
+//   of the block's message, and c1 is never written; c0 alone is packed.  Needs the secret key.
+static void delta_blocks(Context &cx, size_t first_vector, const RowSource &src, size_t n, const ChaChaKey &key, const ChaChaKey *akey, int babies,
+                         size_t first_block, unsigned char *payload0, size_t stride) {
+    const int dim = cx.prm.dim, npoly = akey ? 1 : 2;
+    const size_t g0 = first_vector / (size_t)cx.slots, elems = (size_t)cx.nQ * cx.N;
     const WireRows R = hc::wire_rows(cx.q.data(), cx.N, cx.nQ);
-    const size_t packed = (size_t)dim * 2 * R.off[cx.nQ] * sizeof(u64);
-    double *d_rows = (double *)cx.pool.get(sizeof(double) * (size_t)Nh * dim);
-    double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)dim * Nh);
-    u64 *d_out = cx.pool.get(sizeof(u64) * (size_t)dim * 2 * elems);
-    u64 *d_packed = cx.pool.get(packed);
-    struct Release {
-        Context &cx;
-        u64 *a, *b, *c, *d;
-        ~Release() {
-            cx.pool.put(d);
-            cx.pool.put(c);
-            cx.pool.put(b);
-            cx.pool.put(a);
-        }
-    } release{cx, (u64 *)d_rows, (u64 *)d_slots, d_out, d_packed};
-    for (size_t g = g0; g * (size_t)Nh < end; g++) {
-        const size_t lo = std::max(first_vector, g * (size_t)Nh), hi = std::min(end, (g + 1) * (size_t)Nh);
-        src.stage(cx, lo - first_vector, hi - lo, d_rows);
-        hc::diag_pack(cx.stream, d_rows, (long long)(hi - lo), dim, Nh, d_slots, (babies > 0 && babies < dim) ? babies : 0, (int)(lo - g * (size_t)Nh));
-        encrypt_device(cx, d_slots, dim, key, HY_DB_NONCE_BASE + (first_block + g) * dim, d_out);
+    const size_t packed_bytes = (size_t)dim * npoly * R.off[cx.nQ] * sizeof(u64);
+    PoolBuf out(cx.pool, sizeof(u64) * (size_t)dim * npoly * elems), packed(cx.pool, packed_bytes);
+    walk_touched_blocks(cx, first_vector, src, n, babies, [&](size_t g, const double *d_slots) {
+        const u64 block0 = (first_block + g) * dim;
+        if (akey) encrypt_sym_device(cx, d_slots, dim, key, *akey, HY_DB_NONCE_BASE + block0, block0, out.p);
+        else encrypt_device(cx, d_slots, dim, key, HY_DB_NONCE_BASE + block0, out.p);
         cx.timer_begin("k_wire_pack");
-        hc::wire_pack(cx.stream, cx.d_mod, cx.N, d_out, 2 * elems, elems, (size_t)dim, 2, cx.nQ, R, d_packed);
+        hc::wire_pack(cx.stream, cx.d_mod, cx.N, out.p, npoly * elems, akey ? 0 : elems, (size_t)dim, npoly, cx.nQ, R, packed.p);
         cx.timer_end("k_wire_pack");
-        HIP_CHECK(hipMemcpyAsync(payload0 + (g - g0) * stride, d_packed, packed, hipMemcpyDeviceToHost, cx.stream));
+        HIP_CHECK(hipMemcpyAsync(payload0 + (g - g0) * stride, packed.p, packed_bytes, hipMemcpyDeviceToHost, cx.stream));
         cx.sync();  // the host buffer is the caller's; the block buffers are reused by the next block
+    });
+}
+// what the four front-ends share: the nonce space (a refused call leaves host rows as they were), the rows (host_rows normalised IN
+// PLACE, or dev_rows by the kernel that stages them), the walk
+static void delta_make(Context &cx, size_t first_vector, double *host_rows, const DevRows *dev_rows, size_t n, int normalise, const uint8_t seed[32],
+                       const uint8_t *a_seed, int babies, size_t first_block, unsigned char *payload0, size_t stride) {
+    const int dim = cx.prm.dim;
+    check_db_nonces(first_block, (first_vector + n + (size_t)cx.slots - 1) / (size_t)cx.slots, dim);
+    RowSource src;
+    src.host = host_rows;
+    src.dev = dev_rows;
+    if (dev_rows) {
+        src.normalise = normalise;
+        wait_for_producer(cx, dev_rows->stream);
+    } else if (normalise) {
+        for (size_t v = 0; v < n; v++) normalize(host_rows + v * dim, dim);
     }
+    const ChaChaKey akey = a_seed ? make_key(a_seed) : ChaChaKey{};
+    delta_blocks(cx, first_vector, src, n, make_key(seed), a_seed ? &akey : nullptr, babies, first_block, payload0, stride);
 }
 void client_db_delta_make(Context &cx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32], int babies,
                           size_t first_block, unsigned char *payload0, size_t stride) {
-    const int dim = cx.prm.dim;
-    check_delta_nonces(cx, first_vector, n, first_block);  // (a refused call leaves the rows as they were)
-    if (normalise)
-        for (size_t v = 0; v < n; v++) normalize(rows + v * dim, dim);
-    RowSource src;
-    src.host = rows;
-    delta_blocks(cx, first_vector, src, n, make_key(seed), babies, first_block, payload0, stride);
+    delta_make(cx, first_vector, rows, nullptr, n, normalise, seed, nullptr, babies, first_block, payload0, stride);
 }
 void client_db_delta_make_device(Context &cx, size_t first_vector, const DevRows &rows, int normalise, const uint8_t seed[32], int babies,
                                  size_t first_block, unsigned char *payload0, size_t stride) {
-    RowSource src;
-    src.dev = &rows;
-    src.normalise = normalise;
-    check_delta_nonces(cx, first_vector, rows.n, first_block);
-    wait_for_producer(cx, rows.stream);
-    delta_blocks(cx, first_vector, src, rows.n, make_key(seed), babies, first_block, payload0, stride);
-}
-
-// The SEEDED delta of a key-holding enroller (hydia_db_delta_make_seeded): delta_blocks with encrypt_sym_device in place of
-// encrypt_device — per touched block one sampled polynomial (e0 under `key` at the enrolment's nonce, as delta_blocks samples it) and
-// one transform batch; a is drawn inside k_enc_sym under the PUBLIC akey at (first_block + block) * vector_dim, the nonce0 of the block's message, and c1 is never written; k_wire_pack
-// of c0 straight from the block buffer.  Needs the secret key.  One block is in flight at a time.
-static void delta_blocks_seeded(Context &cx, size_t first_vector, const RowSource &src, size_t n, const ChaChaKey &key, const ChaChaKey &akey,
-                                int babies, size_t first_block, unsigned char *payload0, size_t stride) {
-    const int dim = cx.prm.dim, Nh = cx.slots;
-    const size_t end = first_vector + n, g0 = first_vector / (size_t)Nh, elems = (size_t)cx.nQ * cx.N;
-    const WireRows R = hc::wire_rows(cx.q.data(), cx.N, cx.nQ);
-    const size_t packed = (size_t)dim * R.off[cx.nQ] * sizeof(u64);
-    double *d_rows = (double *)cx.pool.get(sizeof(double) * (size_t)Nh * dim);
-    double *d_slots = (double *)cx.pool.get(sizeof(double) * (size_t)dim * Nh);
-    u64 *d_out = cx.pool.get(sizeof(u64) * (size_t)dim * elems);
-    u64 *d_packed = cx.pool.get(packed);
-    struct Release {
-        Context &cx;
-        u64 *a, *b, *c, *d;
-        ~Release() {
-            cx.pool.put(d);
-            cx.pool.put(c);
-            cx.pool.put(b);
-            cx.pool.put(a);
-        }
-    } release{cx, (u64 *)d_rows, (u64 *)d_slots, d_out, d_packed};
-    for (size_t g = g0; g * (size_t)Nh < end; g++) {
-        const size_t lo = std::max(first_vector, g * (size_t)Nh), hi = std::min(end, (g + 1) * (size_t)Nh);
-        src.stage(cx, lo - first_vector, hi - lo, d_rows);
-        hc::diag_pack(cx.stream, d_rows, (long long)(hi - lo), dim, Nh, d_slots, (babies > 0 && babies < dim) ? babies : 0, (int)(lo - g * (size_t)Nh));
-        encrypt_sym_device(cx, d_slots, dim, key, akey, HY_DB_NONCE_BASE + (first_block + g) * dim, (first_block + g) * dim, d_out);
-        cx.timer_begin("k_wire_pack");
-        hc::wire_pack(cx.stream, cx.d_mod, cx.N, d_out, elems, 0, (size_t)dim, 1, cx.nQ, R, d_packed);
-        cx.timer_end("k_wire_pack");
-        HIP_CHECK(hipMemcpyAsync(payload0 + (g - g0) * stride, d_packed, packed, hipMemcpyDeviceToHost, cx.stream));
-        cx.sync();  // the host buffer is the caller's; the block buffers are reused by the next block
-    }
+    delta_make(cx, first_vector, nullptr, &rows, rows.n, normalise, seed, nullptr, babies, first_block, payload0, stride);
 }
 void client_db_delta_make_seeded(Context &cx, size_t first_vector, double *rows, size_t n, int normalise, const uint8_t seed[32],
                                  const uint8_t a_seed[32], int babies, size_t first_block, unsigned char *payload0, size_t stride) {
-    const int dim = cx.prm.dim;
-    if (!cx.d_sk) throw StateError("hydia: secret key not loaded (a seeded delta is the secret-key holder's; hydia_db_delta_make takes the public key)");
-    check_delta_nonces(cx, first_vector, n, first_block);  // (a refused call leaves the rows as they were)
-    if (normalise)
-        for (size_t v = 0; v < n; v++) normalize(rows + v * dim, dim);
-    RowSource src;
-    src.host = rows;
-    delta_blocks_seeded(cx, first_vector, src, n, make_key(seed), make_key(a_seed), babies, first_block, payload0, stride);
+    delta_make(cx, first_vector, rows, nullptr, n, normalise, seed, a_seed, babies, first_block, payload0, stride);
 }
 void client_db_delta_make_seeded_device(Context &cx, size_t first_vector, const DevRows &rows, int normalise, const uint8_t seed[32],
                                         const uint8_t a_seed[32], int babies, size_t first_block, unsigned char *payload0, size_t stride) {
-    RowSource src;
-    src.dev = &rows;
-    src.normalise = normalise;
-    if (!cx.d_sk) throw StateError("hydia: secret key not loaded (a seeded delta is the secret-key holder's; hydia_db_delta_make takes the public key)");
-    check_delta_nonces(cx, first_vector, rows.n, first_block);
-    wait_for_producer(cx, rows.stream);
-    delta_blocks_seeded(cx, first_vector, src, rows.n, make_key(seed), make_key(a_seed), babies, first_block, payload0, stride);
+    delta_make(cx, first_vector, nullptr, &rows, rows.n, normalise, seed, a_seed, babies, first_block, payload0, stride);
 }
 
 // In-place update of a resident PLAIN gallery (kind 7 / 8): the update loop with encode_device in place of encrypt_device — no seed,

@@ -61,6 +61,15 @@ class Pool {
     std::map<int, std::multimap<size_t, u64 *>> free_;    // per lane
     std::map<u64 *, std::pair<size_t, int>> size_;         // block -> (bytes, owning lane)
 };
+// a pool block that goes back when its scope ends, a throw included
+struct PoolBuf {
+    Pool &pool;
+    u64 *p;
+    PoolBuf(Pool &pl, size_t bytes) : pool(pl), p(pl.get(bytes)) {}
+    PoolBuf(const PoolBuf &) = delete;
+    PoolBuf &operator=(const PoolBuf &) = delete;
+    ~PoolBuf() { pool.put(p); }
+};
 
 struct Context;
 

@@ -22,12 +22,6 @@ const uint64_t *moduli_of(const Context &cx) { return reinterpret_cast<const uin
 W::Expect expect_of(const Context &cx) {
     return W::Expect{(uint32_t)cx.prm.logN, (uint32_t)cx.nQ, (uint32_t)cx.nP, (uint32_t)cx.prm.dnum, moduli_of(cx), cx.delta};
 }
-struct PoolBuf {
-    Context &cx;
-    u64 *p;
-    PoolBuf(Context &c, size_t bytes) : cx(c), p(c.pool.get(bytes)) {}
-    ~PoolBuf() { cx.pool.put(p); }
-};
 struct PinnedBuf {
     void *p = nullptr;
     explicit PinnedBuf(size_t n) { HIP_CHECK(hipHostMalloc(&p, n, hipHostMallocDefault)); }
@@ -43,7 +37,7 @@ struct FileCloser {
 void pack_to_host(Context &cx, const u64 *src, size_t item_stride, size_t poly_stride, size_t items, int npoly, int nl, unsigned char *payload) {
     const WireRows R = hc::wire_rows(cx.q.data(), cx.N, nl);
     const size_t bytes = items * (size_t)npoly * R.off[nl] * sizeof(u64);
-    PoolBuf d(cx, bytes);
+    PoolBuf d(cx.pool, bytes);
     cx.timer_begin("k_wire_pack");
     hc::wire_pack(cx.stream, cx.d_mod, cx.N, src, item_stride, poly_stride, items, npoly, nl, R, d.p);
     cx.timer_end("k_wire_pack");
@@ -56,7 +50,7 @@ struct Unpacker {
     WireRows R;
     int nl;
     PoolBuf d, f;
-    Unpacker(Context &c, const unsigned char *payload, size_t bytes, int nl_) : cx(c), R(hc::wire_rows(c.q.data(), c.N, nl_)), nl(nl_), d(c, bytes), f(c, 8) {
+    Unpacker(Context &c, const unsigned char *payload, size_t bytes, int nl_) : cx(c), R(hc::wire_rows(c.q.data(), c.N, nl_)), nl(nl_), d(c.pool, bytes), f(c.pool, 8) {
         HIP_CHECK(hipMemsetAsync(f.p, 0, 8, cx.stream));
         HIP_CHECK(hipMemcpyAsync(d.p, payload, bytes, hipMemcpyHostToDevice, cx.stream));
     }
@@ -124,7 +118,7 @@ int key_from_wire(hydia_ctx *ctx, const W::Header &h, const unsigned char *paylo
     const int nl = (int)h.n_limbs, npoly = (int)h.n_polys;
     const size_t row = (size_t)nl * cx.N;
     {
-        PoolBuf tmp(cx, (size_t)h.count * npoly * row * sizeof(u64));  // pool scratch: the key installed before stays untouched until the check passed
+        PoolBuf tmp(cx.pool, (size_t)h.count * npoly * row * sizeof(u64));  // pool scratch: the key installed before stays untouched until the check passed
         Unpacker up(cx, payload, (size_t)h.payload_bytes, nl);
         up.rows(0, h.count, npoly, tmp.p, npoly * row, row);
         if (!up.canonical()) return fail(HYDIA_ERR_ARG, NOT_CANONICAL);

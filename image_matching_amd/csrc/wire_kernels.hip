@@ -15,6 +15,7 @@
 #include "db_accum.h"  // the per-granule arithmetic of an in-place update (host-checkable), shared with k_db_accumulate / k_db_accumulate46
 
 #include <stdexcept>
+#include <string>
 
 namespace {
 
@@ -38,6 +39,14 @@ __global__ __launch_bounds__(256) void k_wire_pack(const ModC *__restrict__ mod,
         dst[(size_t)z * R.off[gridDim.y] + R.off[j] + g * w + lane] = word;
     }
 }
+// residue r of a run of whole granules held in LDS from its first word on: bits [r w, (r + 1) w) of the run (the run ends with a
+// residue, so tile[k + 1] exists whenever the field crosses a word)
+__device__ __forceinline__ u64 wire_field(const u64 *tile, int r, int w, u64 mask) {
+    const int bit = r * w, k = bit >> 6, off = bit & 63;
+    u64 v = tile[k] >> off;
+    if (off + w > 64) v |= tile[k + 1] << (64 - off);
+    return v & mask;
+}
 // the inverse, and the range check: *flag := 1 when any residue is at or above its modulus (never cleared here), in the style of
 // k_db_check_canonical.  Same grid
 __global__ __launch_bounds__(256) void k_wire_unpack_check(const ModC *__restrict__ mod, int N, const u64 *__restrict__ src, WireRows R,
@@ -51,10 +60,7 @@ __global__ __launch_bounds__(256) void k_wire_unpack_check(const ModC *__restric
     const u64 mask = w == 64 ? ~0ull : (1ull << w) - 1;
     if (lane < w) tile[wave][lane] = src[(size_t)z * R.off[gridDim.y] + R.off[j] + g * w + lane];
     __syncthreads();
-    const int k = (lane * w) >> 6, off = (lane * w) & 63;
-    u64 v = tile[wave][k] >> off;
-    if (off + w > 64) v |= tile[wave][k + 1] << (64 - off);  // (off > 0 here; the last residue ends with word w - 1)
-    v &= mask;
+    const u64 v = wire_field(tile[wave], lane, w, mask);
     dst[(size_t)(z / npoly) * item_stride + (size_t)(z % npoly) * poly_stride + (size_t)j * N + g * 64 + lane] = v;
     if (__syncthreads_or(v >= q) && threadIdx.x == 0) *flag = 1u;
 }
@@ -71,21 +77,52 @@ __global__ __launch_bounds__(256) void k_wire_check(const ModC *__restrict__ mod
     const u64 mask = w == 64 ? ~0ull : (1ull << w) - 1;
     if (lane < w) tile[wave][lane] = src[(size_t)z * R.off[gridDim.y] + R.off[j] + g * w + lane];
     __syncthreads();
-    const int k = (lane * w) >> 6, off = (lane * w) & 63;
-    u64 v = tile[wave][k] >> off;
-    if (off + w > 64) v |= tile[wave][k + 1] << (64 - off);
-    v &= mask;
+    const u64 v = wire_field(tile[wave], lane, w, mask);
     if (__syncthreads_or(v >= q) && threadIdx.x == 0) *flag = 1u;
 }
 
-// residue r of a run of whole granules held in LDS from its first word on: bits [r w, (r + 1) w) of the run (the run ends with a
-// residue, so tile[k + 1] exists whenever the field crosses a word)
-__device__ __forceinline__ u64 wire_field(const u64 *tile, int r, int w, u64 mask) {
-    const int bit = r * w, k = bit >> 6, off = bit & 63;
-    u64 v = tile[k] >> off;
-    if (off + w > 64) v |= tile[k + 1] << (64 - off);
-    return v & mask;
+// ---- what the block bodies of a delta and of a seeded delta share
+// the residues a thread owns += (STORE: :=) into the resident database: a residue pair (16 bytes, or pk: 12), or db_layout.h's 92-byte
+// granule of sixteen 46-bit residues
+template <bool STORE>
+__device__ __forceinline__ void db_put_pair(unsigned char *d, bool pk, u64 ax, u64 ay, u64 q) {
+    if (!STORE) {
+        db_accumulate_pair(d, pk, ax, ay, q);
+    } else if (pk) {
+        unsigned v[3];
+        db_pack_pair48(ax, ay, v);
+        unsigned *o = reinterpret_cast<unsigned *>(d);
+        o[0] = v[0];
+        o[1] = v[1];
+        o[2] = v[2];
+    } else {
+        reinterpret_cast<u64 *>(d)[0] = ax;
+        reinterpret_cast<u64 *>(d)[1] = ay;
+    }
 }
+template <bool STORE>
+__device__ __forceinline__ void db_put_granule46(unsigned char *d, const u64 a[16], u64 q) {
+    unsigned *o = reinterpret_cast<unsigned *>(d);
+    if (!STORE) {
+        db_accumulate_granule46(o, a, q);
+    } else {
+        unsigned v[23];
+        db_pack_granule46(a, v);
+#pragma unroll
+        for (int k = 0; k < 23; k++) o[k] = v[k];
+    }
+}
+// the workgroup's PER * 256 residues of one limb's packed row, from residue c0 (a multiple of 64) on: whole granules, contiguous and
+// coalesced, into LDS; returns how many residues that is (N is a multiple of 512)
+template <int PER>
+__device__ __forceinline__ int db_load_tile(u64 *tile, const u64 *__restrict__ row, int N, size_t c0, int w) {
+    const int span = (int)((size_t)N - c0 < (size_t)(PER * 256) ? (size_t)N - c0 : (size_t)(PER * 256));
+    row += (c0 >> 6) * w;
+    for (int k = threadIdx.x; k < (span >> 6) * w; k += 256) tile[k] = row[k];
+    __syncthreads();
+    return span;
+}
+
 // Packed wire rows of ONE block -> the resident database, in one pass: ciphertexts t0 .. t0 + X - 1 += (STORE: :=) the rows
 // [X][2][nQ] of a CT_BATCH payload, mod q_j.  No unpacked copy of the block in HBM: a workgroup loads the packed words of its PER * 256
 // residues (whole granules, contiguous, coalesced) into LDS, and every thread gathers the residues of the database granule it OWNS —
@@ -100,44 +137,15 @@ __device__ __forceinline__ void db_wire_body(u64 *tile, const ModC *__restrict__
     const u64 q = mod[j].q;
     const int w = 64 - __clzll((long long)q);
     const u64 mask = w == 64 ? ~0ull : (1ull << w) - 1;
-    const size_t c0 = (size_t)blockIdx.x * (PER * 256);                     // first residue of the workgroup (a multiple of 64)
-    const int span = (int)((size_t)N - c0 < (size_t)(PER * 256) ? (size_t)N - c0 : (size_t)(PER * 256));  // its residues (N is a multiple of 512)
-    const u64 *row = src + (size_t)xp * R.off[nQ] + R.off[j] + (c0 >> 6) * w;
-    for (int k = threadIdx.x; k < (span >> 6) * w; k += 256) tile[k] = row[k];
-    __syncthreads();
-    const int r0 = threadIdx.x * PER;
+    const size_t c0 = (size_t)blockIdx.x * (PER * 256);  // first residue of the workgroup
+    const int span = db_load_tile<PER>(tile, src + (size_t)xp * R.off[nQ] + R.off[j], N, c0, w), r0 = threadIdx.x * PER;
     if (r0 >= span) return;
     unsigned char *d = db + db_offset(L, N, t0 + x, p, j, c0 + r0);
-    if (PER == 2) {
-        const u64 ax = wire_field(tile, r0, w, mask), ay = wire_field(tile, r0 + 1, w, mask);
-        const bool pk = L.packed && j > 0;
-        if (!STORE) {
-            db_accumulate_pair(d, pk, ax, ay, q);
-        } else if (pk) {
-            unsigned v[3];
-            db_pack_pair48(ax, ay, v);
-            unsigned *o = reinterpret_cast<unsigned *>(d);
-            o[0] = v[0];
-            o[1] = v[1];
-            o[2] = v[2];
-        } else {
-            reinterpret_cast<u64 *>(d)[0] = ax;
-            reinterpret_cast<u64 *>(d)[1] = ay;
-        }
-    } else {
-        u64 a[16];
+    u64 v[PER];
 #pragma unroll
-        for (int r = 0; r < 16; r++) a[r] = wire_field(tile, r0 + r, w, mask);
-        unsigned *o = reinterpret_cast<unsigned *>(d);
-        if (!STORE) {
-            db_accumulate_granule46(o, a, q);
-        } else {
-            unsigned v[23];
-            db_pack_granule46(a, v);
-#pragma unroll
-            for (int k = 0; k < 23; k++) o[k] = v[k];
-        }
-    }
+    for (int r = 0; r < PER; r++) v[r] = wire_field(tile, r0 + r, w, mask);
+    if constexpr (PER == 2) db_put_pair<STORE>(d, L.packed && j > 0, v[0], v[1], q);
+    else db_put_granule46<STORE>(d, v, q);
 }
 // the 8-byte and 6-byte residues (limb 0, every limb of a 48-bit or unpacked layout): 512 residues = 8 granules <= 512 words per workgroup
 __global__ __launch_bounds__(256) void k_db_accumulate_wire(const ModC *__restrict__ mod, int N, int nQ, const u64 *__restrict__ src, WireRows R,
@@ -173,34 +181,6 @@ __global__ __launch_bounds__(256) void k_db_store_wire46(const ModC *__restrict_
 // 92-byte granule of sixteen 46-bit residues = FOUR blocks (PER = 16).  One thread owns every dword it reads and writes: no atomics.
 // c0 was range-checked beforehand (k_wire_check) and a is reduced by construction: both operands of the add are canonical.
 // grid (ceil(N / (PER 256)), limbs, X); limb j = blockIdx.y + j0
-template <bool STORE>
-__device__ __forceinline__ void db_put_pair(unsigned char *d, bool pk, u64 ax, u64 ay, u64 q) {
-    if (!STORE) {
-        db_accumulate_pair(d, pk, ax, ay, q);
-    } else if (pk) {
-        unsigned v[3];
-        db_pack_pair48(ax, ay, v);
-        unsigned *o = reinterpret_cast<unsigned *>(d);
-        o[0] = v[0];
-        o[1] = v[1];
-        o[2] = v[2];
-    } else {
-        reinterpret_cast<u64 *>(d)[0] = ax;
-        reinterpret_cast<u64 *>(d)[1] = ay;
-    }
-}
-template <bool STORE>
-__device__ __forceinline__ void db_put_granule46(unsigned char *d, const u64 a[16], u64 q) {
-    unsigned *o = reinterpret_cast<unsigned *>(d);
-    if (!STORE) {
-        db_accumulate_granule46(o, a, q);
-    } else {
-        unsigned v[23];
-        db_pack_granule46(a, v);
-#pragma unroll
-        for (int k = 0; k < 23; k++) o[k] = v[k];
-    }
-}
 template <bool STORE, int PER>
 __device__ __forceinline__ void db_seeded_body(u64 *tile, const ChaChaKey &akey, u64 nonce0, const ModC *__restrict__ mod, int N, int nQ,
                                                const u64 *__restrict__ src, WireRows R, unsigned char *__restrict__ db, const DbLayout &L,
@@ -209,12 +189,8 @@ __device__ __forceinline__ void db_seeded_body(u64 *tile, const ChaChaKey &akey,
     const ModC M = mod[j];
     const int w = 64 - __clzll((long long)M.q);
     const u64 mask = w == 64 ? ~0ull : (1ull << w) - 1;
-    const size_t c0 = (size_t)blockIdx.x * (PER * 256);                     // first residue of the workgroup (a multiple of 64)
-    const int span = (int)((size_t)N - c0 < (size_t)(PER * 256) ? (size_t)N - c0 : (size_t)(PER * 256));  // its residues (N is a multiple of 512)
-    const u64 *row = src + (size_t)x * R.off[nQ] + R.off[j] + (c0 >> 6) * w;
-    for (int k = threadIdx.x; k < (span >> 6) * w; k += 256) tile[k] = row[k];
-    __syncthreads();
-    const int r0 = threadIdx.x * PER;
+    const size_t c0 = (size_t)blockIdx.x * (PER * 256);  // first residue of the workgroup
+    const int span = db_load_tile<PER>(tile, src + (size_t)x * R.off[nQ] + R.off[j], N, c0, w), r0 = threadIdx.x * PER;
     if (r0 >= span) return;
     const u64 stream = HY_STREAM(HY_DOM_SYM_A, nonce0 + (u64)x, 0, j), blk0 = (u64)((c0 + r0) >> 2);
     unsigned char *d0 = db + db_offset(L, N, t0 + x, 0, j, c0 + r0), *d1 = db + db_offset(L, N, t0 + x, 1, j, c0 + r0);
@@ -303,14 +279,22 @@ void wire_check(hipStream_t st, const ModC *mod, int N, const u64 *src, size_t i
         hipLaunchKernelGGL(k_wire_check, dim3(N / 256, nl, (unsigned)(n * npoly)), dim3(256), 0, st, mod, src + i0 * npoly * R.off[nl], R, flag);
     }
 }
-// X <= 32767 ciphertexts of two polynomials on all nQ limbs (one block of a database: X = vector_dim)
-void db_wire(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *src, const WireRows &R, void *db, size_t t0, int X, const DbLayout &L,
-             bool store) {
-    if (L.plain || X < 1 || X > 32767 || N < 512 || N % 512) throw std::runtime_error("hydia: db_wire: bad shape");
+// what both delta launchers require of a block: a ciphertext layout, at least one ciphertext and no more than the launch's grid takes
+// (fits, the caller's bound), whole 512-residue tiles, and in a 46-bit layout no packed limb wider than 46 bits.  Returns whether the
+// 46-bit kernels serve limbs 1 .. nQ - 1
+static bool db_wire_shape(const char *who, bool fits, int N, int nQ, const WireRows &R, int X, const DbLayout &L) {
+    if (L.plain || X < 1 || !fits || N < 512 || N % 512) throw std::runtime_error(std::string("hydia: ") + who + ": bad shape");
     const bool b46 = L.bits46 && L.packed;
     if (b46)
         for (int j = 1; j < nQ; j++)
-            if (R.off[j + 1] - R.off[j] > (unsigned)(N / 64) * 46u) throw std::runtime_error("hydia: db_wire: a limb wider than 46 bits in a 46-bit layout");
+            if (R.off[j + 1] - R.off[j] > (unsigned)(N / 64) * 46u)
+                throw std::runtime_error(std::string("hydia: ") + who + ": a limb wider than 46 bits in a 46-bit layout");
+    return b46;
+}
+// X <= 32767 ciphertexts of two polynomials on all nQ limbs (one block of a database: X = vector_dim)
+void db_wire(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *src, const WireRows &R, void *db, size_t t0, int X, const DbLayout &L,
+             bool store) {
+    const bool b46 = db_wire_shape("db_wire", X <= 32767, N, nQ, R, X, L);
     // resident bytes (read and) written + the packed bytes read
     hk::ledger_add(store ? "k_db_store_wire" : "k_db_accumulate_wire", (double)X * ((store ? 1.0 : 2.0) * L.ct_bytes + 2.0 * R.off[nQ] * 8));
     const dim3 g2(N / 512, b46 ? 1 : nQ, X * 2), g16((N + 4095) / 4096, nQ - 1, X * 2);
@@ -327,12 +311,7 @@ void db_wire(hipStream_t st, const ModC *mod, int N, int nQ, const u64 *src, con
 // X <= 65535 ciphertexts: c0 from the packed rows [X][R.off[nQ]] words at src, a from (akey, nonce0 + x)
 void db_wire_seeded(hipStream_t st, const ChaChaKey &akey, u64 nonce0, const ModC *mod, int N, int nQ, const u64 *src, const WireRows &R, void *db,
                     size_t t0, int X, const DbLayout &L, bool store) {
-    if (L.plain || X < 1 || X > 65535 || N < 512 || N % 512 || nonce0 + (u64)X >= (1ull << 40))
-        throw std::runtime_error("hydia: db_wire_seeded: bad shape");
-    const bool b46 = L.bits46 && L.packed;
-    if (b46)
-        for (int j = 1; j < nQ; j++)
-            if (R.off[j + 1] - R.off[j] > (unsigned)(N / 64) * 46u) throw std::runtime_error("hydia: db_wire_seeded: a limb wider than 46 bits in a 46-bit layout");
+    const bool b46 = db_wire_shape("db_wire_seeded", X <= 65535 && nonce0 + (u64)X < (1ull << 40), N, nQ, R, X, L);
     // resident bytes (read and) written + the packed bytes read; a costs no memory traffic
     hk::ledger_add(store ? "k_db_store_seeded" : "k_db_accumulate_seeded", (double)X * ((store ? 1.0 : 2.0) * L.ct_bytes + 1.0 * R.off[nQ] * 8));
     const dim3 g4((N + 1023) / 1024, b46 ? 1 : nQ, X), g16((N + 4095) / 4096, nQ - 1, X);

@@ -412,22 +412,23 @@ def wire_peek(message):
     return d
 
 
+def _delta_peek(message, peek):
+    raw = np.frombuffer(bytes(message), dtype=np.uint8)
+    info = _DeltaInfo()
+    _chk(peek(_p(raw) if raw.size else None, raw.size, C.byref(info)))
+    return {k: int(getattr(info, k)) for k, _ in _DeltaInfo._fields_}
+
+
 def db_delta_peek(message):
     """Host-only (hydia_db_delta_peek): the context-free validation of a database delta and what its header says — a dict of version,
     vector_dim, babies, first_vector, n_rows, first_block, n_blocks, total_bytes.  A malformed delta: HydiaError(-1) naming the field."""
-    raw = np.frombuffer(bytes(message), dtype=np.uint8)
-    info = _DeltaInfo()
-    _chk(load_library().hydia_db_delta_peek(_p(raw) if raw.size else None, raw.size, C.byref(info)))
-    return {k: int(getattr(info, k)) for k, _ in _DeltaInfo._fields_}
+    return _delta_peek(message, load_library().hydia_db_delta_peek)
 
 
 def db_delta_seeded_peek(message):
     """Host-only (hydia_db_delta_seeded_peek): db_delta_peek for a SEEDED database delta (magic HYDDELS1, type 2 messages); the same
     dict.  A malformed delta, an unseeded one included: HydiaError(-1) naming the field."""
-    raw = np.frombuffer(bytes(message), dtype=np.uint8)
-    info = _DeltaInfo()
-    _chk(load_library().hydia_db_delta_seeded_peek(_p(raw) if raw.size else None, raw.size, C.byref(info)))
-    return {k: int(getattr(info, k)) for k, _ in _DeltaInfo._fields_}
+    return _delta_peek(message, load_library().hydia_db_delta_seeded_peek)
 
 
 def _public_seed(x):
@@ -960,12 +961,32 @@ class Context:
         assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.ndim == 2 and rows.shape[1] == self.dim
         _chk(self.L.hydia_db_update_shard(self.h, first_vector, _p(rows), rows.shape[0], 1 if normalise else 0, _p(_seed(seed)), first_block))
 
-    # ---- database deltas (include/hydia.h): the enroller's context makes the message, the sender's applies it
+    # ---- database deltas and seeded database deltas (include/hydia.h): the enroller's context makes the message, the sender's applies
+    # it.  Seeded: the maker holds the SECRET key; only the c0 halves travel
+    def _delta_bytes(self, entry, first_vector, n):
+        b = C.c_size_t()
+        _chk(entry(self.h, first_vector, n, C.byref(b)))
+        return b.value
+
+    def _delta_make(self, host_entry, device_entry, first_vector, rows, normalise, seeds, babies, first_block):
+        """seeds: the seed arrays the entries take — ONE set for the sizing call and the making call"""
+        B = self.dim if babies is None else int(babies)
+        if _is_device_tensor(rows):
+            d = _dev_rows(self, rows)
+            call, src = device_entry, (C.byref(d),)
+        else:
+            assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.ndim == 2 and rows.shape[1] == self.dim
+            call, src = host_entry, (_p(rows), rows.shape[0])
+        sp = [_p(x) for x in seeds]
+        return _wire_out(lambda buf, cap, n: call(self.h, first_vector, *src, 1 if normalise else 0, *sp, B, first_block, buf, cap, n))
+
+    def _delta_apply(self, entry, message):
+        raw = np.frombuffer(bytes(message), dtype=np.uint8)
+        _chk(entry(self.h, _p(raw) if raw.size else None, raw.size))
+
     def db_delta_bytes(self, first_vector, n):
         """the size of the delta of rows first_vector .. first_vector + n - 1 on this context (host arithmetic only)"""
-        b = C.c_size_t()
-        _chk(self.L.hydia_db_delta_bytes(self.h, first_vector, n, C.byref(b)))
-        return b.value
+        return self._delta_bytes(self.L.hydia_db_delta_bytes, first_vector, n)
 
     def db_delta_peek(self, message):
         """the module's db_delta_peek (context-free, host only)"""
@@ -977,29 +998,18 @@ class Context:
         the db_delta_apply of the context that holds the database.  Needs the public key alone.  babies: the form of the TARGET
         database (None = vector_dim, hoisted).  seed=None draws a fresh key from the OS — a seed must NEVER be used twice on one
         database (include/hydia.h)."""
-        B = self.dim if babies is None else int(babies)
-        sd = _seed(seed)  # ONE seed for the sizing call and the making call
-        if _is_device_tensor(rows):
-            d = _dev_rows(self, rows)
-            return _wire_out(lambda buf, cap, n: self.L.hydia_db_delta_make_device(self.h, first_vector, C.byref(d), 1 if normalise else 0,
-                                                                                  _p(sd), B, first_block, buf, cap, n))
-        assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.ndim == 2 and rows.shape[1] == self.dim
-        return _wire_out(lambda buf, cap, n: self.L.hydia_db_delta_make(self.h, first_vector, _p(rows), rows.shape[0], 1 if normalise else 0,
-                                                                       _p(sd), B, first_block, buf, cap, n))
+        return self._delta_make(self.L.hydia_db_delta_make, self.L.hydia_db_delta_make_device, first_vector, rows, normalise, [_seed(seed)],
+                                babies, first_block)
 
     def db_delta_apply(self, message):
         """hydia_db_delta_apply: add the delta's ciphertexts to the resident kind-5 / kind-6 database (bit for bit what db_update with
         the maker's arguments leaves), or enrol from it when nothing is resident and it starts at vector 0.  Every header and residue
         is checked first: a refused delta (HydiaError) changes nothing."""
-        raw = np.frombuffer(bytes(message), dtype=np.uint8)
-        _chk(self.L.hydia_db_delta_apply(self.h, _p(raw) if raw.size else None, raw.size))
+        self._delta_apply(self.L.hydia_db_delta_apply, message)
 
-    # ---- seeded database deltas (include/hydia.h): the maker holds the SECRET key; only the c0 halves travel
     def db_delta_seeded_bytes(self, first_vector, n):
         """the size of the seeded delta of rows first_vector .. first_vector + n - 1 on this context (host arithmetic only)"""
-        b = C.c_size_t()
-        _chk(self.L.hydia_db_delta_seeded_bytes(self.h, first_vector, n, C.byref(b)))
-        return b.value
+        return self._delta_bytes(self.L.hydia_db_delta_seeded_bytes, first_vector, n)
 
     def db_delta_seeded_peek(self, message):
         """the module's db_delta_seeded_peek (context-free, host only)"""
@@ -1010,21 +1020,13 @@ class Context:
         bytes, for db_delta_apply_seeded.  seed (secret, the noise) as in db_delta_make; a_seed (PUBLIC, travels in the message):
         None = a fresh hydia_random_seed — it must never have served a query under this key or another delta on that database, and
         must differ from seed (include/hydia.h)."""
-        B = self.dim if babies is None else int(babies)
-        sd, ad = _seed(seed), _public_seed(a_seed)  # ONE pair for the sizing call and the making call
-        if _is_device_tensor(rows):
-            d = _dev_rows(self, rows)
-            return _wire_out(lambda buf, cap, n: self.L.hydia_db_delta_make_seeded_device(self.h, first_vector, C.byref(d), 1 if normalise else 0,
-                                                                                         _p(sd), _p(ad), B, first_block, buf, cap, n))
-        assert rows.dtype == np.float64 and rows.flags.c_contiguous and rows.ndim == 2 and rows.shape[1] == self.dim
-        return _wire_out(lambda buf, cap, n: self.L.hydia_db_delta_make_seeded(self.h, first_vector, _p(rows), rows.shape[0], 1 if normalise else 0,
-                                                                              _p(sd), _p(ad), B, first_block, buf, cap, n))
+        return self._delta_make(self.L.hydia_db_delta_make_seeded, self.L.hydia_db_delta_make_seeded_device, first_vector, rows, normalise,
+                                [_seed(seed), _public_seed(a_seed)], babies, first_block)
 
     def db_delta_apply_seeded(self, message):
         """hydia_db_delta_apply_seeded: db_delta_apply for a seeded delta — c0 from the message, a regenerated on the GPU straight into
         the resident layout.  Needs no key.  Every header and c0 residue is checked first: a refused delta (HydiaError) changes nothing."""
-        raw = np.frombuffer(bytes(message), dtype=np.uint8)
-        _chk(self.L.hydia_db_delta_apply_seeded(self.h, _p(raw) if raw.size else None, raw.size))
+        self._delta_apply(self.L.hydia_db_delta_apply_seeded, message)
 
     # ---- templates already in device memory (include/hydia.h, hydia_dev_rows): `rows` is a tensor on this context's GPU, only read
     def rows_widen_device(self, rows, normalise=True):
@@ -1197,13 +1199,26 @@ class DiagonalEnroller:
         if not isinstance(self.cc, Context):
             raise HydiaError(-2, "hydia: database deltas are not made on a sharded context (make one per shard context, with its first_block)")
 
+    def _delta_to_wire(self, make, first_vector, rows, *args):
+        """make: the name of the Context method (looked up only once the context is known to be one)"""
+        self._one_context()
+        m = getattr(self.cc, make)(first_vector, rows, *args)
+        self.numVectors = max(self.numVectors, first_vector + rows.shape[0])
+        return m
+
+    def _db_to_wire(self, make, database, seeds, babies, first_block):
+        """seeds: (draw, given) per seed the maker takes — each drawn ONCE here, for every block"""
+        self._one_context()
+        n, slots = database.shape[0], self.cc.N // 2
+        drawn = [bytes(draw(given)) for draw, given in seeds]
+        for lo in range(0, n, slots):
+            yield getattr(self.cc, make)(lo, database[lo:lo + slots], True, *drawn, babies, first_block)
+        self.numVectors = n
+
     def updateToWire(self, first_vector, rows, normalise=True, seed=None, babies=None, first_block=0):
         """updateRows for a database on ANOTHER machine: the update as one delta message (Context.db_delta_make) for
         DiagonalSender.applyDBWire.  Nothing resident on this context is touched; numVectors follows as in updateRows."""
-        self._one_context()
-        m = self.cc.db_delta_make(first_vector, rows, normalise, seed, babies, first_block)
-        self.numVectors = max(self.numVectors, first_vector + rows.shape[0])
-        return m
+        return self._delta_to_wire("db_delta_make", first_vector, rows, normalise, seed, babies, first_block)
 
     def appendToWire(self, rows, n_resident, seed=None, babies=None, first_block=0):
         """append `rows` (normalised in place) after the n_resident vectors the sender's database holds"""
@@ -1213,21 +1228,13 @@ class DiagonalEnroller:
         """serializeDB for a sender on another machine: yields one delta message per 'slots'-vector block, in order; the first enrols
         on an empty sender context, every later one appends.  ONE seed for the whole database (None: drawn once from the OS), as
         an enrolment uses — the blocks differ in their nonces.  `database` is normalised IN PLACE (a tensor is never written)."""
-        self._one_context()
-        n, slots = database.shape[0], self.cc.N // 2
-        sd = bytes(_seed(seed))
-        for lo in range(0, n, slots):
-            yield self.cc.db_delta_make(lo, database[lo:lo + slots], True, sd, babies, first_block)
-        self.numVectors = n
+        return self._db_to_wire("db_delta_make", database, [(_seed, seed)], babies, first_block)
 
     # ---- seeded database deltas (include/hydia.h): this enroller is the owner — it holds the SECRET key; half the bytes travel
     def updateToWireSeeded(self, first_vector, rows, normalise=True, seed=None, a_seed=None, babies=None, first_block=0):
         """updateToWire on a key-holding context: one SEEDED delta message (Context.db_delta_make_seeded) for
         DiagonalSender.applyDBWireSeeded.  a_seed=None draws a fresh hydia_random_seed."""
-        self._one_context()
-        m = self.cc.db_delta_make_seeded(first_vector, rows, normalise, seed, a_seed, babies, first_block)
-        self.numVectors = max(self.numVectors, first_vector + rows.shape[0])
-        return m
+        return self._delta_to_wire("db_delta_make_seeded", first_vector, rows, normalise, seed, a_seed, babies, first_block)
 
     def appendToWireSeeded(self, rows, n_resident, seed=None, a_seed=None, babies=None, first_block=0):
         """append `rows` (normalised in place) after the n_resident vectors the sender's database holds, as a seeded delta"""
@@ -1236,12 +1243,7 @@ class DiagonalEnroller:
     def serializeDBToWireSeeded(self, database, seed=None, a_seed=None, babies=None, first_block=0):
         """serializeDBToWire as seeded deltas: one message per 'slots'-vector block, in order.  ONE seed and ONE a_seed for the whole
         database (None: each drawn once), as an enrolment uses one seed — the blocks differ in their nonces."""
-        self._one_context()
-        n, slots = database.shape[0], self.cc.N // 2
-        sd, ad = bytes(_seed(seed)), bytes(_public_seed(a_seed))
-        for lo in range(0, n, slots):
-            yield self.cc.db_delta_make_seeded(lo, database[lo:lo + slots], True, sd, ad, babies, first_block)
-        self.numVectors = n
+        return self._db_to_wire("db_delta_make_seeded", database, [(_seed, seed), (_public_seed, a_seed)], babies, first_block)
 
     def rekeyDB(self, key):
         """Re-key the enrolled database in place (Context.db_rekey) with the switching key DiagonalReceiver.genSwitchKey of the NEW
@@ -1533,23 +1535,22 @@ class DiagonalSender:
         """DiagonalReceiver.exportKeysWire's file into this context (hydia_keys_load; not transactional)"""
         self.cc.keys_load(path)
 
+    def _apply_db_wire(self, apply, message):
+        if not isinstance(self.cc, Context):
+            raise HydiaError(-2, "hydia: database deltas are not applied on a sharded context (apply one per shard context)")
+        getattr(self.cc, apply)(message)
+        self.numVectors = self.cc.db_stats()[0]
+        return self.numVectors
+
     def applyDBWire(self, message):
         """a delta message of DiagonalEnroller.updateToWire / appendToWire / serializeDBToWire into this sender's database
         (Context.db_delta_apply: checked, transactional); returns the new vector count, which numVectors follows"""
-        if not isinstance(self.cc, Context):
-            raise HydiaError(-2, "hydia: database deltas are not applied on a sharded context (apply one per shard context)")
-        self.cc.db_delta_apply(message)
-        self.numVectors = self.cc.db_stats()[0]
-        return self.numVectors
+        return self._apply_db_wire("db_delta_apply", message)
 
     def applyDBWireSeeded(self, message):
         """a SEEDED delta message of DiagonalEnroller.updateToWireSeeded / appendToWireSeeded / serializeDBToWireSeeded into this
         sender's database (Context.db_delta_apply_seeded: checked, transactional, no key needed); returns the new vector count"""
-        if not isinstance(self.cc, Context):
-            raise HydiaError(-2, "hydia: database deltas are not applied on a sharded context (apply one per shard context)")
-        self.cc.db_delta_apply_seeded(message)
-        self.numVectors = self.cc.db_stats()[0]
-        return self.numVectors
+        return self._apply_db_wire("db_delta_apply_seeded", message)
 
     def queryFromWire(self, message):
         """a query message -> what expandQuery / Context.import_ct return, ready for every single, *Multi and *GalleryMulti method: a

@@ -493,30 +493,10 @@ class DiagonalSender : public Sender {
     // A delta message of DiagonalEnroller::updateToWire / appendToWire / serializeDBToWire into this sender's database
     // (hydia_db_delta_apply: every header and residue is checked first, a refused message changes nothing).  Returns the new vector
     // count, which numVectors follows; 0 on an error.  Not on a sharded context
-    size_t applyDBWire(const std::vector<uint8_t> &message) {
-        if (cc->group) {
-            cc->last_status = HYDIA_ERR_STATE;
-            std::cerr << "Error: applyDBWire: database deltas are not applied on a sharded context (one per shard context)" << std::endl;
-            return 0;
-        }
-        if (!cc->check(hydia_db_delta_apply(cc->h, message.data(), message.size()), "applyDBWire")) return 0;
-        size_t cts = 0, bytes = 0;
-        if (!cc->check(hydia_db_stats(cc->h, &numVectors, &cts, &bytes), "applyDBWire")) return 0;
-        return numVectors;
-    }
+    size_t applyDBWire(const std::vector<uint8_t> &message) { return apply_db_wire("applyDBWire", false, message); }
     // The same for a SEEDED delta of DiagonalEnroller::updateToWireSeeded / appendToWireSeeded / serializeDBToWireSeeded
     // (hydia_db_delta_apply_seeded: c0 from the message, a regenerated on the GPU; no key needed)
-    size_t applyDBWireSeeded(const std::vector<uint8_t> &message) {
-        if (cc->group) {
-            cc->last_status = HYDIA_ERR_STATE;
-            std::cerr << "Error: applyDBWireSeeded: database deltas are not applied on a sharded context (one per shard context)" << std::endl;
-            return 0;
-        }
-        if (!cc->check(hydia_db_delta_apply_seeded(cc->h, message.data(), message.size()), "applyDBWireSeeded")) return 0;
-        size_t cts = 0, bytes = 0;
-        if (!cc->check(hydia_db_stats(cc->h, &numVectors, &cts, &bytes), "applyDBWireSeeded")) return 0;
-        return numVectors;
-    }
+    size_t applyDBWireSeeded(const std::vector<uint8_t> &message) { return apply_db_wire("applyDBWireSeeded", true, message); }
     std::vector<uint8_t> resultToWire(const std::vector<Ciphertext> &result) { return toWire(cc, result); }
     // computeSimilarity's scores as one message of their first `limbs` limbs (1 or 2): the decoder reads at most two, so with 2 the
     // receiver decrypts the same doubles from a sixth of the bytes; with 1 it decodes from q_0 alone.  For resultFromWire
@@ -597,6 +577,17 @@ class DiagonalSender : public Sender {
     }
 
   private:
+    size_t apply_db_wire(const char *what, bool seeded, const std::vector<uint8_t> &message) {
+        if (cc->group) {
+            cc->last_status = HYDIA_ERR_STATE;
+            std::cerr << "Error: " << what << ": database deltas are not applied on a sharded context (one per shard context)" << std::endl;
+            return 0;
+        }
+        if (!cc->check((seeded ? hydia_db_delta_apply_seeded : hydia_db_delta_apply)(cc->h, message.data(), message.size()), what)) return 0;
+        size_t cts = 0, bytes = 0;
+        if (!cc->check(hydia_db_stats(cc->h, &numVectors, &cts, &bytes), what)) return 0;
+        return numVectors;
+    }
     // the C call of every batch method: one result handle per query, or nothing after an error (reported by check)
     template <class H>
     std::vector<hydia_ct *> batch_call(const std::vector<const H *> &in, int (*multi)(hydia_ctx *, const H *const *, uint32_t, hydia_ct **),
@@ -1065,42 +1056,11 @@ class DiagonalEnroller : public EnrollerBase {
     // numVectors follows as in updateRows.  The seed rule is updateRows'.  Not on a sharded context: an error, empty
     std::vector<uint8_t> updateToWire(size_t first_vector, std::vector<std::vector<double>> &rows, bool normalise = true,
                                       const uint8_t *seed32 = nullptr, int babies = 0, size_t first_block = 0) {
-        if (!delta_ok("updateToWire")) return {};
-        const size_t dim = cc->info.vector_dim;
-        std::vector<double> flat(rows.size() * dim, 0.0);
-        for (size_t i = 0; i < rows.size(); i++)
-            for (size_t j = 0; j < dim && j < rows[i].size(); j++) flat[i * dim + j] = rows[i][j];
-        uint8_t s[32];
-        role_seed(s, seed32);
-        const int B = babies ? babies : (int)dim;
-        size_t need = 0, len = 0;
-        if (!cc->check(hydia_db_delta_bytes(cc->h, first_vector, rows.size(), &need), "updateToWire")) return {};
-        std::vector<uint8_t> message(need);
-        if (!cc->check(hydia_db_delta_make(cc->h, first_vector, flat.data(), rows.size(), normalise ? 1 : 0, s, B, first_block, message.data(),
-                                           message.size(), &len),
-                       "updateToWire"))
-            return {};
-        message.resize(len);
-        for (size_t i = 0; i < rows.size(); i++)
-            for (size_t j = 0; j < dim && j < rows[i].size(); j++) rows[i][j] = flat[i * dim + j];
-        if (first_vector + rows.size() > numVectors) numVectors = first_vector + rows.size();
-        return message;
+        return rows_to_wire("updateToWire", false, first_vector, rows, normalise, seed32, nullptr, babies, first_block);
     }
     std::vector<uint8_t> updateToWire(size_t first_vector, const DeviceRows &rows, bool normalise = true, const uint8_t *seed32 = nullptr,
                                       int babies = 0, size_t first_block = 0) {
-        if (!delta_ok("updateToWire")) return {};
-        uint8_t s[32];
-        role_seed(s, seed32);
-        const int B = babies ? babies : (int)cc->info.vector_dim;
-        size_t need = 0, len = 0;
-        if (!cc->check(hydia_db_delta_bytes(cc->h, first_vector, rows.size(), &need), "updateToWire")) return {};
-        std::vector<uint8_t> message(need);
-        if (!cc->check(hydia_db_delta_make_device(cc->h, first_vector, &rows.d, normalise ? 1 : 0, s, B, first_block, message.data(), message.size(), &len),
-                       "updateToWire"))
-            return {};
-        message.resize(len);
-        if (first_vector + rows.size() > numVectors) numVectors = first_vector + rows.size();
-        return message;
+        return delta_to_wire("updateToWire", false, first_vector, nullptr, &rows.d, rows.size(), normalise, seed32, nullptr, babies, first_block);
     }
     // append `rows` after the n_resident vectors the sender's database holds
     std::vector<uint8_t> appendToWire(std::vector<std::vector<double>> &rows, size_t n_resident, const uint8_t *seed32 = nullptr, int babies = 0,
@@ -1115,20 +1075,7 @@ class DiagonalEnroller : public EnrollerBase {
     // nonces).  A failure: an error, and the messages made so far are dropped
     std::vector<std::vector<uint8_t>> serializeDBToWire(std::vector<std::vector<double>> &database, const uint8_t *seed32 = nullptr, int babies = 0,
                                                         size_t first_block = 0) {
-        if (!delta_ok("serializeDBToWire")) return {};
-        uint8_t s[32];
-        role_seed(s, seed32);
-        const size_t slots = cc->info.slots;
-        std::vector<std::vector<uint8_t>> messages;
-        for (size_t lo = 0; lo < database.size(); lo += slots) {
-            const size_t hi = std::min(database.size(), lo + slots);
-            std::vector<std::vector<double>> rows(database.begin() + lo, database.begin() + hi);
-            messages.push_back(updateToWire(lo, rows, true, s, babies, first_block));
-            if (messages.back().empty()) return {};
-            std::copy(rows.begin(), rows.end(), database.begin() + lo);
-        }
-        numVectors = database.size();
-        return messages;
+        return db_to_wire("serializeDBToWire", false, database, seed32, nullptr, babies, first_block);
     }
     // Seeded database deltas (an extension; hydia.h): the ToWire methods for an enroller whose context holds the SECRET key — an owner
     // who is also the receiver.  Only the c0 halves travel: half the bytes; the message goes to DiagonalSender::applyDBWireSeeded.
@@ -1137,45 +1084,11 @@ class DiagonalEnroller : public EnrollerBase {
     std::vector<uint8_t> updateToWireSeeded(size_t first_vector, std::vector<std::vector<double>> &rows, bool normalise = true,
                                             const uint8_t *seed32 = nullptr, const uint8_t *a_seed32 = nullptr, int babies = 0,
                                             size_t first_block = 0) {
-        if (!delta_ok("updateToWireSeeded")) return {};
-        const size_t dim = cc->info.vector_dim;
-        std::vector<double> flat(rows.size() * dim, 0.0);
-        for (size_t i = 0; i < rows.size(); i++)
-            for (size_t j = 0; j < dim && j < rows[i].size(); j++) flat[i * dim + j] = rows[i][j];
-        uint8_t s[32], a[32];
-        role_seed(s, seed32);
-        role_seed(a, a_seed32);
-        const int B = babies ? babies : (int)dim;
-        size_t need = 0, len = 0;
-        if (!cc->check(hydia_db_delta_seeded_bytes(cc->h, first_vector, rows.size(), &need), "updateToWireSeeded")) return {};
-        std::vector<uint8_t> message(need);
-        if (!cc->check(hydia_db_delta_make_seeded(cc->h, first_vector, flat.data(), rows.size(), normalise ? 1 : 0, s, a, B, first_block,
-                                                  message.data(), message.size(), &len),
-                       "updateToWireSeeded"))
-            return {};
-        message.resize(len);
-        for (size_t i = 0; i < rows.size(); i++)
-            for (size_t j = 0; j < dim && j < rows[i].size(); j++) rows[i][j] = flat[i * dim + j];
-        if (first_vector + rows.size() > numVectors) numVectors = first_vector + rows.size();
-        return message;
+        return rows_to_wire("updateToWireSeeded", true, first_vector, rows, normalise, seed32, a_seed32, babies, first_block);
     }
     std::vector<uint8_t> updateToWireSeeded(size_t first_vector, const DeviceRows &rows, bool normalise = true, const uint8_t *seed32 = nullptr,
                                             const uint8_t *a_seed32 = nullptr, int babies = 0, size_t first_block = 0) {
-        if (!delta_ok("updateToWireSeeded")) return {};
-        uint8_t s[32], a[32];
-        role_seed(s, seed32);
-        role_seed(a, a_seed32);
-        const int B = babies ? babies : (int)cc->info.vector_dim;
-        size_t need = 0, len = 0;
-        if (!cc->check(hydia_db_delta_seeded_bytes(cc->h, first_vector, rows.size(), &need), "updateToWireSeeded")) return {};
-        std::vector<uint8_t> message(need);
-        if (!cc->check(hydia_db_delta_make_seeded_device(cc->h, first_vector, &rows.d, normalise ? 1 : 0, s, a, B, first_block, message.data(),
-                                                         message.size(), &len),
-                       "updateToWireSeeded"))
-            return {};
-        message.resize(len);
-        if (first_vector + rows.size() > numVectors) numVectors = first_vector + rows.size();
-        return message;
+        return delta_to_wire("updateToWireSeeded", true, first_vector, nullptr, &rows.d, rows.size(), normalise, seed32, a_seed32, babies, first_block);
     }
     std::vector<uint8_t> appendToWireSeeded(std::vector<std::vector<double>> &rows, size_t n_resident, const uint8_t *seed32 = nullptr,
                                             const uint8_t *a_seed32 = nullptr, int babies = 0, size_t first_block = 0) {
@@ -1188,21 +1101,7 @@ class DiagonalEnroller : public EnrollerBase {
     // one message per block, in order; ONE seed and ONE a_seed for the whole database (the blocks differ in their nonces)
     std::vector<std::vector<uint8_t>> serializeDBToWireSeeded(std::vector<std::vector<double>> &database, const uint8_t *seed32 = nullptr,
                                                               const uint8_t *a_seed32 = nullptr, int babies = 0, size_t first_block = 0) {
-        if (!delta_ok("serializeDBToWireSeeded")) return {};
-        uint8_t s[32], a[32];
-        role_seed(s, seed32);
-        role_seed(a, a_seed32);
-        const size_t slots = cc->info.slots;
-        std::vector<std::vector<uint8_t>> messages;
-        for (size_t lo = 0; lo < database.size(); lo += slots) {
-            const size_t hi = std::min(database.size(), lo + slots);
-            std::vector<std::vector<double>> rows(database.begin() + lo, database.begin() + hi);
-            messages.push_back(updateToWireSeeded(lo, rows, true, s, a, babies, first_block));
-            if (messages.back().empty()) return {};
-            std::copy(rows.begin(), rows.end(), database.begin() + lo);
-        }
-        numVectors = database.size();
-        return messages;
+        return db_to_wire("serializeDBToWireSeeded", true, database, seed32, a_seed32, babies, first_block);
     }
     // Re-key the enrolled database in place under a new receiver key (hydia_db_rekey; no counterpart in the reference, which re-enrols):
     // every resident ciphertext is key-switched with `key`, the NEW receiver's DiagonalReceiver::genSwitchKey.  Afterwards the caller
@@ -1230,6 +1129,64 @@ class DiagonalEnroller : public EnrollerBase {
             return false;
         }
         return true;
+    }
+    // one delta message, whole (hydia_db_delta_make[_device]) or seeded (hydia_db_delta_make_seeded[_device]: the public a_seed is
+    // a_seed32 or freshly drawn), of n rows in host memory (flat) or in device memory (dev)
+    std::vector<uint8_t> delta_to_wire(const char *what, bool seeded, size_t first_vector, double *flat, const hydia_dev_rows *dev, size_t n,
+                                       bool normalise, const uint8_t *seed32, const uint8_t *a_seed32, int babies, size_t first_block) {
+        if (!delta_ok(what)) return {};
+        uint8_t s[32], a[32];
+        role_seed(s, seed32);
+        if (seeded) role_seed(a, a_seed32);
+        const int B = babies ? babies : (int)cc->info.vector_dim, norm = normalise ? 1 : 0;
+        size_t need = 0, len = 0;
+        if (!cc->check(seeded ? hydia_db_delta_seeded_bytes(cc->h, first_vector, n, &need) : hydia_db_delta_bytes(cc->h, first_vector, n, &need), what))
+            return {};
+        std::vector<uint8_t> message(need);
+        uint8_t *buf = message.data();
+        int status;
+        if (seeded)
+            status = dev ? hydia_db_delta_make_seeded_device(cc->h, first_vector, dev, norm, s, a, B, first_block, buf, need, &len)
+                         : hydia_db_delta_make_seeded(cc->h, first_vector, flat, n, norm, s, a, B, first_block, buf, need, &len);
+        else
+            status = dev ? hydia_db_delta_make_device(cc->h, first_vector, dev, norm, s, B, first_block, buf, need, &len)
+                         : hydia_db_delta_make(cc->h, first_vector, flat, n, norm, s, B, first_block, buf, need, &len);
+        if (!cc->check(status, what)) return {};
+        message.resize(len);
+        if (first_vector + n > numVectors) numVectors = first_vector + n;
+        return message;
+    }
+    // the same from host rows, which are padded to vector_dim on the way in and take the normalised values on the way out
+    std::vector<uint8_t> rows_to_wire(const char *what, bool seeded, size_t first_vector, std::vector<std::vector<double>> &rows, bool normalise,
+                                      const uint8_t *seed32, const uint8_t *a_seed32, int babies, size_t first_block) {
+        const size_t dim = cc->info.vector_dim;
+        std::vector<double> flat(rows.size() * dim, 0.0);
+        for (size_t i = 0; i < rows.size(); i++)
+            for (size_t j = 0; j < dim && j < rows[i].size(); j++) flat[i * dim + j] = rows[i][j];
+        std::vector<uint8_t> message = delta_to_wire(what, seeded, first_vector, flat.data(), nullptr, rows.size(), normalise, seed32, a_seed32, babies, first_block);
+        if (message.empty()) return {};
+        for (size_t i = 0; i < rows.size(); i++)
+            for (size_t j = 0; j < dim && j < rows[i].size(); j++) rows[i][j] = flat[i * dim + j];
+        return message;
+    }
+    // one message per block of `slots` vectors, in order, under ONE seed (and ONE a_seed) for the whole database
+    std::vector<std::vector<uint8_t>> db_to_wire(const char *what, bool seeded, std::vector<std::vector<double>> &database, const uint8_t *seed32,
+                                                 const uint8_t *a_seed32, int babies, size_t first_block) {
+        if (!delta_ok(what)) return {};
+        uint8_t s[32], a[32];
+        role_seed(s, seed32);
+        if (seeded) role_seed(a, a_seed32);
+        const size_t slots = cc->info.slots;
+        std::vector<std::vector<uint8_t>> messages;
+        for (size_t lo = 0; lo < database.size(); lo += slots) {
+            const size_t hi = std::min(database.size(), lo + slots);
+            std::vector<std::vector<double>> rows(database.begin() + lo, database.begin() + hi);
+            messages.push_back(rows_to_wire(seeded ? "updateToWireSeeded" : "updateToWire", seeded, lo, rows, true, s, seeded ? a : nullptr, babies, first_block));
+            if (messages.back().empty()) return {};
+            std::copy(rows.begin(), rows.end(), database.begin() + lo);
+        }
+        numVectors = database.size();
+        return messages;
     }
     bool device_rows_ok(const char *what, bool count_ok) {
         if (cc->group || !count_ok) {
